@@ -42,6 +42,7 @@ PEAK_FP32_VALU_TFLOPS = 157.3  # MI355X_MICROARCH.md: peak FP32 vector (FMA = 2 
 PEAK_HBM_GBPS = 8000.0
 PEAK_F16_MFMA_TFLOPS = 2500.0   # MI355X_MICROARCH.md: dense bf16/f16 MFMA peak
 PEAK_I8_MFMA_TOPS = 5000.0      # dense int8 MFMA (2 x K of fp16)
+DUMP_BYTES = 60 << 20          # --dump-outputs: all arrays together (3/4 for the main workload, 1/4 for strong_u8)
 
 
 def pmc_traffic(i8):
@@ -77,6 +78,45 @@ def result_checksum(result):
     if qt is not None:
         c = zlib.crc32(np.ascontiguousarray(qt, dtype=np.int32).tobytes(), c)
     return int(c)
+
+
+def output_arrays(result, budget_bytes, seed=0):
+    """What a caller of the timed path received from one step -- offsets int64[P + 1], qt int32[M, 2] (query row, train row),
+    dist float32[M]; qt / dist are None where the path does not hand them over -- as float32 / float64 copies, taken at once (the
+    step's arrays may be views of buffers the next matching call reuses).  Integers become float32 where every value is exact in
+    it, float64 otherwise.  Where the offsets would take more than a quarter of `budget_bytes`, or the match rows more than what
+    the offsets left, a seeded sample of their rows is kept instead -- the same rows for the same length -- with the row numbers
+    beside it as <name>_rows.  -> {name: array}"""
+    offs, qt, dist = result[0], result[1], result[2]
+    rng = np.random.default_rng(seed)
+    out = {}
+
+    def float_type(a):
+        if a.dtype.kind == "f":
+            return a.dtype
+        exact32 = a.size == 0 or (int(a.min()) > -2 ** 24 and int(a.max()) < 2 ** 24)
+        return np.dtype(np.float32 if exact32 else np.float64)
+
+    def put(names, arrs, budget):
+        arrs = [np.asarray(a) for a in arrs]
+        types = [float_type(a) for a in arrs]
+        row_bytes = sum(t.itemsize * int(np.prod(a.shape[1:])) for a, t in zip(arrs, types))
+        n = len(arrs[0])
+        used = 0
+        if n * row_bytes > budget:   # (drawn with replacement, then unique: no permutation of n is built)
+            rows = np.unique(rng.integers(0, n, max(1, int(budget // (row_bytes + 8)))))
+            out[names[0] + "_rows"] = rows.astype(np.float64)
+            used += rows.size * 8
+            arrs = [a[rows] for a in arrs]
+        for name, a, t in zip(names, arrs, types):
+            out[name] = a.astype(t)
+            used += out[name].nbytes
+        return used
+
+    used = put(["offsets"], [offs], budget_bytes // 4)
+    if qt is not None:
+        put(["qt", "dist"] if dist is not None else ["qt"], [qt, dist] if dist is not None else [qt], budget_bytes - used)
+    return out
 
 
 def opencv_found():
@@ -322,7 +362,13 @@ def main():
     ap.add_argument("--no-e2e", action="store_true", help="skip the cold end-to-end run of the ComputeMatches executable (end_to_end)")
     ap.add_argument("--no-solo", action="store_true",
                     help="skip the 4 extra steps with the pipeline off that measure the sweeps alone (roofline.solo); for kernel traces")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32 / float64, "
+                         "%d MB at most; a seeded sample of the rows of a larger job): offsets, qt, dist of the main workload, "
+                         "u8_offsets, u8_qt, u8_dist of strong_u8" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.u8_steps is None:
         args.u8_steps = 1 if args.u8_images >= 1329 else 2
 
@@ -397,9 +443,10 @@ def main():
     elif args.f16_only:
         ctx.set_prefilter(2)
 
-    def run_job(imgs, pairs, steps, warmup, collect=None, sustained_steps=0, solo_pass=True, **match_kw):
+    def run_job(imgs, pairs, steps, warmup, collect=None, sustained_steps=0, solo_pass=True, dump_bytes=0, **match_kw):
         """Upload, W untimed + K timed steps; -> (seconds of the K steps: max over ranks, result of the last step,
-        upload seconds, per-rank [compute_ms, exchange_ms] means)."""
+        upload seconds, per-rank [compute_ms, exchange_ms] means).  dump_bytes > 0: run_job.outputs holds the arrays the last
+        timed step handed its caller on rank 0 (output_arrays)."""
         n_rows = np.array([len(x) for x in imgs], np.int64)
         ctx.clear_images()
         t_up = time.perf_counter()
@@ -446,9 +493,9 @@ def main():
             if not multi:
                 # one rank: the step ends with the lists in the library's page-locked host buffers ("view": no second copy)
                 t = time.perf_counter()
-                offs, qt, _ = ctx.match_pairs(pairs, fetch="view", **match_kw)
+                offs, qt, d = ctx.match_pairs(pairs, fetch="view", **match_kw)
                 sm.last = {"compute_ms": (time.perf_counter() - t) * 1e3, "exchange_ms": 0.0}
-                return offs, qt, None
+                return offs, qt, d
             return sm.match_to_writer(pairs, n_rows, dst=0, with_dist=False)
 
         result = None
@@ -464,6 +511,8 @@ def main():
                 collect(ctx.profile())
         barrier()
         dt = time.perf_counter() - t0
+        # copied here, outside the timed region: the steps below reuse the buffers the last timed step's arrays may view
+        run_job.outputs = output_arrays(result, dump_bytes) if dump_bytes > 0 and rank == 0 else None
         sustained = None
         if sustained_steps > 0:   # after the timed region: the same step, long enough for the power / thermal state to settle
             t1 = time.perf_counter()
@@ -529,7 +578,10 @@ def main():
             acc[k] += p[k]
         last_prof.update(p)
 
-    dt, result, upload_s, per_rank, n_rows = run_job(imgs, pairs, args.steps, args.warmup, collect, args.sustained_steps, **main_kw)
+    dump_bytes = DUMP_BYTES if args.dump_outputs else 0
+    dt, result, upload_s, per_rank, n_rows = run_job(imgs, pairs, args.steps, args.warmup, collect, args.sustained_steps,
+                                                     dump_bytes=dump_bytes * 3 // 4, **main_kw)
+    outputs = dict(run_job.outputs or {})
     sustained = run_job.sustained
     solo = run_job.solo
     stream_main = run_job.stream_stats
@@ -696,7 +748,8 @@ def main():
         # One warm-up step (buffers sized, plan hints learnt), then the timed ones; the sweeps-alone pass only on small subsets
         # (three more steps of the full job would be half a minute)
         u_dt, u_res, u_upload_s, u_per_rank, u_rows = run_job(u_imgs, u_pairs, args.u8_steps, 1, u_collect, solo_pass=n_img <= 256,
-                                                              max_distance=1e9)
+                                                              dump_bytes=dump_bytes // 4, max_distance=1e9)
+        outputs.update(("u8_" + k, v) for k, v in (run_job.outputs or {}).items())
         u_solo = run_job.solo
         u_total = int((u_rows[u_pairs[:, 0]] * u_rows[u_pairs[:, 1]]).sum())
         i8 = u_acc["sweep1_i8_launches"] > 0
@@ -741,6 +794,11 @@ def main():
         cb = out.get("cpu_baseline", {})
         # (against the FASTER of the port's orders: the ratio is a lower bound)
         out["end_to_end"] = end_to_end_ratios(e2e, max(cb.get("value") or 0.0, cb.get("fast_order_value") or 0.0) or None, cb.get("single_thread_value"))
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": {k: list(a.shape) for k, a in outputs.items()}}
     if rank == 0:
         print(json.dumps(out), flush=True)
     ctx.close()

@@ -45,6 +45,14 @@ def _free_port():
     return p
 
 
+def _barrier():
+    """The ranks here are CPU-only: dist.barrier() first asks torch for the machine's accelerator, which starts the GPU runtime in
+    every rank of a GPU box, so they wait for each other through an all_reduce of a CPU tensor over gloo instead."""
+    import torch
+    import torch.distributed as dist
+    dist.all_reduce(torch.zeros(1))
+
+
 SIZES = [90, 120, 60, 100, 2, 75, 110]
 SKEWED = [4, 5, 4, 6, 300, 310, 4, 5, 6]   # one pair outweighs total / world: middle ranks get EMPTY ranges
 
@@ -87,7 +95,7 @@ def _worker(rank, world, port, out_dir, sizes=SIZES):
             assert (wd is None) if not with_dist else np.array_equal(wd.view(np.int32), d.view(np.int32))
         else:
             assert wqt is None and wd is None
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
@@ -148,7 +156,7 @@ def _subgroup_worker(rank, world, port, out_dir):
             np.save(os.path.join(out_dir, "sub.npy"), qt)
         else:
             assert qt is None
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
@@ -204,7 +212,7 @@ def _batches_worker(rank, world, port, out_dir):
     all_counts = rng.poisson(409, len(pairs4)).astype(np.int64)
     best = 1e9
     for rep in range(5):
-        dist.barrier()
+        _barrier()
         t0 = time.perf_counter()
         parts = partition_pairs(pairs4, n_rows4, world)
         bounds = range_bounds(parts, len(pairs4))
@@ -219,7 +227,7 @@ def _batches_worker(rank, world, port, out_dir):
         assert offs[-1] == all_counts.sum() and abs(int(offs[-1]) - 3.6e8) < 2e7
     if rank == 0:
         np.save(os.path.join(out_dir, "host_ms.npy"), np.array([best * 1e3]))
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
@@ -274,11 +282,11 @@ def _pipelined_worker(rank, world, port, out_dir):
     out = {}
     for mode in (False, True):
         got = []
-        dist.barrier()
+        _barrier()
         t0 = time.perf_counter()
         counts = sm.match_to_writer_batches(pairs, n_rows, batch_pairs=batch, dst=0, with_dist=True, pipelined=mode,
                                             sink=lambda b0, offs, qt, d: got.append((b0, np.array(offs), np.array(qt), np.array(d))))
-        dist.barrier()
+        _barrier()
         out[mode] = (time.perf_counter() - t0, counts, got, dict(sm.last))
     sharding.gather_to_writer = real
     serial, piped = out[False], out[True]
@@ -291,7 +299,7 @@ def _pipelined_worker(rank, world, port, out_dir):
     assert serial[3]["exchange_wait_ms"] >= 0.9 * B * 25.0
     if rank == 0:
         np.save(os.path.join(out_dir, "walls.npy"), np.array([serial[0], piped[0], piped[3]["exchange_wait_ms"], piped[3]["exchange_ms"], B]))
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
