@@ -209,7 +209,7 @@ def test_golden_byte_fixture_through_the_integer_cores(gpu_ctx):
 
 
 def test_norm_spread_beyond_the_digit_range_takes_the_fp16_kernels(gpu_ctx):
-    """The digit k-step carries H0 - h within [-504 064, 507 903]: an image holding an all-128 row (h = 0) next to an
+    """The digit k-step carries H0 - h within [-243 968, 245 759]: an image holding an all-128 row (h = 0) next to an
     all-0 row (h = 2^20) cannot be centred, is stored as a float image and matched on the fp16 cores -- same lists."""
     u = synth.u8_images(2, [500, 450], seed=9, dup_frac=0.3, as_float=False)
     wide = u[0].copy()
