@@ -12,9 +12,15 @@
 // Solver: normalised 8-point.  The null vector of the 9 x 9 moment matrix M = A^T A comes from two
 // steps of inverse iteration on M + eps I (Cholesky, no pivoting, no data-dependent indexing -- the
 // smallest eigenvalue of M is ~0, the shift makes the factorisation exist, the eigen-gap makes one
-// step converge to ~1e-10); rank 2 is enforced by removing the smallest right singular direction
-// (3 x 3 cyclic Jacobi, fixed sweep count).
+// step converge to ~1e-10); the consensus refit, whose smallest eigenvalue is the residual and may sit
+// close to the next one, first brackets it by bisection and then iterates with that shift (solve);
+// rank 2 is enforced by removing the smallest right singular direction (3 x 3 cyclic Jacobi, fixed
+// sweep count).
 #pragma once
+
+#if !defined(__HIPCC__)
+#include <cmath>
+#endif
 
 #if defined(__HIPCC__)
 #define MSFM_FHD __host__ __device__ inline
@@ -26,7 +32,9 @@
 
 namespace msfm_fmat {
 
-constexpr int kFmatRefitSteps = 12;  // inverse-iteration steps of the least-squares refit
+constexpr int kFmatRefitSteps = 4;     // inverse-iteration steps of the least-squares refit before the bisection
+constexpr int kFmatBisectSteps = 48;   // bisection steps bracketing the refit's smallest eigenvalue
+constexpr int kFmatPolishSteps = 3;    // shifted inverse-iteration steps after the bisection
 
 struct Norm2D {
     double cx, cy, s;
@@ -88,52 +96,46 @@ MSFM_FHD void jacobi_rot(double& app, double& aqq, double& apq, double& apr, dou
     vp2 = p2; vq2 = q2;
 }
 
-// F (row-major 3 x 3, unit Frobenius norm, x2^T F x1 = 0) from the moment matrix of normalised points.
-// M is destroyed.  `steps` inverse-iteration steps: 2 for an 8-point sample (exact null space), more for a
-// least-squares refit whose smallest eigenvalue is the residual.  Returns false for degenerate input.
-MSFM_FHD bool solve(double M[45], const Norm2D& t1, const Norm2D& t2, double F[9], int steps) {
-    double trace = 0.0;
-MSFM_UNROLL
-    for (int a = 0; a < 9; ++a) trace += M[tri(a, a)];
-    if (!(trace > 0.0) || !(trace < 1e300)) return false;
-    const double eps = trace * 1e-13;
-MSFM_UNROLL
-    for (int a = 0; a < 9; ++a) M[tri(a, a)] += eps;
-    // Cholesky M = U^T U in place (U upper triangular, packed)
+// Cholesky factor U (packed upper triangle, M - shift I = U^T U) of the packed symmetric 9 x 9 matrix M; false if
+// M - shift I is not (numerically) positive definite
+MSFM_FHD bool cholesky(const double M[45], double shift, double U[45]) {
 MSFM_UNROLL
     for (int k = 0; k < 9; ++k) {
-        double d = M[tri(k, k)];
+        double d = M[tri(k, k)] - shift;
 MSFM_UNROLL
-        for (int j = 0; j < k; ++j) d -= M[tri(j, k)] * M[tri(j, k)];
+        for (int j = 0; j < k; ++j) d -= U[tri(j, k)] * U[tri(j, k)];
         if (!(d > 0.0)) return false;
         d = sqrt(d);
-        M[tri(k, k)] = d;
+        U[tri(k, k)] = d;
 MSFM_UNROLL
         for (int b = k + 1; b < 9; ++b) {
             double v = M[tri(k, b)];
 MSFM_UNROLL
-            for (int j = 0; j < k; ++j) v -= M[tri(j, k)] * M[tri(j, b)];
-            M[tri(k, b)] = v / d;
+            for (int j = 0; j < k; ++j) v -= U[tri(j, k)] * U[tri(j, b)];
+            U[tri(k, b)] = v / d;
         }
     }
-    // inverse iteration from a fixed generic start vector
-    double x[9] = {0.31, -0.17, 0.43, 0.29, -0.37, 0.23, -0.41, 0.19, 0.47};
+    return true;
+}
+
+// `steps` steps of inverse iteration x <- (U^T U)^-1 x / |.|
+MSFM_FHD bool inverse_iteration(const double U[45], double x[9], int steps) {
     for (int step = 0; step < steps; ++step) {
         // U^T y = x
 MSFM_UNROLL
         for (int k = 0; k < 9; ++k) {
             double v = x[k];
 MSFM_UNROLL
-            for (int j = 0; j < k; ++j) v -= M[tri(j, k)] * x[j];
-            x[k] = v / M[tri(k, k)];
+            for (int j = 0; j < k; ++j) v -= U[tri(j, k)] * x[j];
+            x[k] = v / U[tri(k, k)];
         }
         // U z = y
 MSFM_UNROLL
         for (int k = 8; k >= 0; --k) {
             double v = x[k];
 MSFM_UNROLL
-            for (int j = k + 1; j < 9; ++j) v -= M[tri(k, j)] * x[j];
-            x[k] = v / M[tri(k, k)];
+            for (int j = k + 1; j < 9; ++j) v -= U[tri(k, j)] * x[j];
+            x[k] = v / U[tri(k, k)];
         }
         double nn = 0.0;
 MSFM_UNROLL
@@ -142,6 +144,45 @@ MSFM_UNROLL
         nn = 1.0 / sqrt(nn);
 MSFM_UNROLL
         for (int k = 0; k < 9; ++k) x[k] *= nn;
+    }
+    return true;
+}
+
+// F (row-major 3 x 3, unit Frobenius norm, x2^T F x1 = 0) from the moment matrix of normalised points.
+// `steps` inverse-iteration steps on M + eps I: 2 for an 8-point sample (exact null space).  A
+// least-squares refit (refine = true) cannot rely on an eigen-gap -- near-planar and small-baseline consensus sets
+// have lambda8 / lambda9 close to 1, where plain inverse iteration stalls -- so it then brackets the smallest
+// eigenvalue by bisection (M - sigma I has a Cholesky factor iff sigma < lambda9) between -eps and the Rayleigh
+// quotient of the iterate, and polishes with inverse iteration shifted to the lower end of the bracket, whose
+// convergence factor (lambda9 - sigma) / (lambda8 - sigma) is then ~ 2^-kFmatBisectSteps.  Returns false for
+// degenerate input.
+MSFM_FHD bool solve(double M[45], const Norm2D& t1, const Norm2D& t2, double F[9], int steps, bool refine = false) {
+    double trace = 0.0;
+MSFM_UNROLL
+    for (int a = 0; a < 9; ++a) trace += M[tri(a, a)];
+    if (!(trace > 0.0) || !(trace < 1e300)) return false;
+    const double eps = trace * 1e-13;
+    double U[45];
+    if (!cholesky(M, -eps, U)) return false;
+    // inverse iteration from a fixed generic start vector
+    double x[9] = {0.31, -0.17, 0.43, 0.29, -0.37, 0.23, -0.41, 0.19, 0.47};
+    if (!inverse_iteration(U, x, steps)) return false;
+    if (refine) {
+        double rho = 0.0;   // Rayleigh quotient x^T M x >= lambda9
+MSFM_UNROLL
+        for (int a = 0; a < 9; ++a) {
+            double v = 0.0;
+MSFM_UNROLL
+            for (int b = 0; b < 9; ++b) v += M[a <= b ? tri(a, b) : tri(b, a)] * x[b];
+            rho += x[a] * v;
+        }
+        double lo = -eps, hi = rho;
+        for (int k = 0; k < kFmatBisectSteps; ++k) {
+            const double mid = 0.5 * (lo + hi);
+            if (cholesky(M, mid, U)) lo = mid;
+            else hi = mid;
+        }
+        if (!cholesky(M, lo, U) || !inverse_iteration(U, x, kFmatPolishSteps)) return false;
     }
     // rank 2: G = Fn^T Fn, remove the eigen-direction of its smallest eigenvalue
     double g00 = 0, g01 = 0, g02 = 0, g11 = 0, g12 = 0, g22 = 0;

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void vf_mask_compact_kernel(
             for (int i = 0; i < n; ++i)
                 if (flags[base + i]) moment_add(M, t1, t2, x1[base + i], y1[base + i], x2[base + i], y2[base + i]);
             double F2[9];
-            s_ok = solve(M, t1, t2, F2, kFmatRefitSteps) ? 1 : 0;
+            s_ok = solve(M, t1, t2, F2, kFmatRefitSteps, true) ? 1 : 0;
             for (int k = 0; k < 9; ++k) sF[k] = F2[k];
         }
         __syncthreads();

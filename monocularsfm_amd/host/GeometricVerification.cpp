@@ -61,7 +61,7 @@ std::vector<unsigned char> FundamentalRansacMask(const std::vector<Point2f>& pts
         const size_t k = (size_t)in[(size_t)i];
         moment_add(M, t1, t2, x1[k], y1[k], x2[k], y2[k]);
     }
-    if (solve(M, t1, t2, F, kFmatRefitSteps)) {
+    if (solve(M, t1, t2, F, kFmatRefitSteps, true)) {
         std::vector<unsigned char> cur((size_t)n);
         const int count = count_inliers(F, cur.data());
         if (count >= best_count) best.swap(cur);

@@ -8,6 +8,7 @@
 #include "GeometricVerification.h"
 #include "MatchEmission.h"
 #include "YamlConfig.h"
+#include "../csrc/msfm_fmat.h"
 
 using namespace MonocularSfM;
 
@@ -206,6 +207,66 @@ int host_fundamental_ransac(const float* p1, const float* p2, int n, unsigned ch
     const std::vector<unsigned char> m = FundamentalRansacMask(a, b);
     for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
     return (int)m.size();
+}
+
+// the same with every RANSAC parameter explicit
+int host_fundamental_ransac_ex(const float* p1, const float* p2, int n, double threshold, double confidence, int max_iters,
+                               unsigned long long seed, unsigned char* mask) {
+    std::vector<Point2f> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[(size_t)i] = Point2f{p1[2 * i], p1[2 * i + 1]};
+        b[(size_t)i] = Point2f{p2[2 * i], p2[2 * i + 1]};
+    }
+    const std::vector<unsigned char> m = FundamentalRansacMask(a, b, threshold, confidence, max_iters, seed);
+    for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
+    return (int)m.size();
+}
+
+// ---- the pieces of msfm_fmat.h, one by one (tests/test_fmat_reference.py compares them with oracle/fmat_ref.py) ------
+void host_fmat_sample8(unsigned long long seed, int it, int n, int* idx) { msfm_fmat::sample8(seed, it, n, idx); }
+
+int host_fmat_hypothesis(const float* x1, const float* y1, const float* x2, const float* y2, int n, unsigned long long seed,
+                         int it, double* F) {
+    return msfm_fmat::hypothesis(x1, y1, x2, y2, n, seed, it, F) ? 1 : 0;
+}
+
+// the consensus refit of FundamentalRansacMask: normaliser over the masked points, moments in index order, solve
+int host_fmat_refit(const float* x1, const float* y1, const float* x2, const float* y2, int n, const unsigned char* mask,
+                    double* F) {
+    using namespace msfm_fmat;
+    std::vector<int> in;
+    for (int i = 0; i < n; ++i)
+        if (mask[i]) in.push_back(i);
+    const int m = (int)in.size();
+    if (m == 0) return 0;
+    const Norm2D t1 = normalizer(x1, y1, m, [&](int i) { return in[(size_t)i]; });
+    const Norm2D t2 = normalizer(x2, y2, m, [&](int i) { return in[(size_t)i]; });
+    double M[45] = {0};
+    for (int k : in) moment_add(M, t1, t2, x1[k], y1[k], x2[k], y2[k]);
+    return solve(M, t1, t2, F, kFmatRefitSteps, true) ? 1 : 0;
+}
+
+double host_fmat_epipolar_error(const double* F, float ax, float ay, float bx, float by) {
+    return msfm_fmat::epipolar_error(F, ax, ay, bx, by);
+}
+
+double host_fmat_det_log(double x) { return msfm_fmat::det_log(x); }
+
+int host_fmat_replay(const int* counts, int n_counts, int n, int max_iters, double confidence, int* best_count) {
+    return msfm_fmat::replay_adaptive(n, max_iters, confidence, [&](int it) { return it < n_counts ? counts[it] : 0; },
+                                      best_count);
+}
+
+// inlier count of every hypothesis 0 .. max_iters-1 (0 where the solve fails), as the device computes them
+void host_fmat_counts(const float* x1, const float* y1, const float* x2, const float* y2, int n, unsigned long long seed,
+                      int max_iters, double thr2, int* out_counts) {
+    for (int it = 0; it < max_iters; ++it) {
+        double F[9];
+        int c = 0;
+        if (msfm_fmat::hypothesis(x1, y1, x2, y2, n, seed, it, F))
+            for (int i = 0; i < n; ++i) c += msfm_fmat::epipolar_error(F, x1[i], y1[i], x2[i], y2[i]) <= thr2 ? 1 : 0;
+        out_counts[it] = c;
+    }
 }
 
 }  // extern "C"
