@@ -13,7 +13,7 @@ struct Batch {
     int max_npad = 0;
     int64_t desc_pairs = 0;
     int64_t algo_bytes = 0;
-    bool route_i8 = false;           // every prefiltered pair joins two byte images and sweep 2 is the compacted one: both sweeps on the integer cores (prepare_batch_images)
+    MsfmRoute route;                 // what its prefiltered pairs run on (prepare_batch_images)
     // host tables of copies that are still in flight when the issuing function returns (they live as long as the sub-batch)
     std::vector<CandList> dense_lists;
     std::vector<VerifyPair> verify_pairs;
@@ -114,24 +114,24 @@ int fill_pair(msfm_ctx* ctx, int id1, int id2, PairDesc& pd, PfPair& pp) {
     return MSFM_OK;
 }
 
-// Which forms of its images does this sub-batch read?  Decided here, before anything is launched:
-//   * route_i8 -- match lists with ratio <= 0.95 (the compacted sweep 2), every prefiltered pair joins two byte images: both sweeps on the
-//     integer matrix cores, the candidates' exact S from the sweep itself (pf_exact_candidates_kernel<4>): only the 176-byte rows are read;
+// The sub-batch's route (msfm_route, msfm_hostutil.h), and which forms of its images it reads -- decided here, before anything is launched:
+//   * kRouteI8: only the 176-byte rows (the candidates' exact S comes from the sweep itself, pf_exact_candidates_kernel<4>);
 //   * otherwise the float forms (permuted fp32 rows, fp16 operand rows) -- derived on demand for byte images;
 //   * brute-force pairs (not fp16-safe, MSFM_PREFILTER=0, a candidate-list overflow) also read the panels.
 // Then every pair's pointers are refreshed (fill_pair ran before the forms existed).
 int prepare_batch_images(msfm_ctx* ctx, Batch& b, const PruneParams& prune) {
     const size_t P = b.pairs.size();
-    const bool compact = prune.prune != 0 && prune.ratio > 0.f && prune.ratio <= 0.95f;
-    bool i8 = compact && ctx->prefilter == 1;
-    for (size_t p = 0; p < P && i8; ++p)
-        if (b.pairs[p].valid && b.pf[p].use) i8 = ctx->images[(size_t)b.id1[p]].is_u8 && ctx->images[(size_t)b.id2[p]].is_u8;
-    b.route_i8 = i8;
+    std::vector<MsfmRoutePair> rp(P);
+    for (size_t p = 0; p < P; ++p) {
+        const Image &ia = ctx->images[(size_t)b.id1[p]], &ib = ctx->images[(size_t)b.id2[p]];
+        rp[p] = MsfmRoutePair{b.pairs[p].valid != 0, b.pf[p].use != 0, ia.is_u8, ib.is_u8, ia.q8 != nullptr, ib.q8 != nullptr, b.pairs[p].n1, b.pairs[p].n2};
+    }
+    b.route = msfm_route(ctx->route_knobs(), prune.prune, prune.ratio, rp);
     std::vector<int> wide, panel;
     for (size_t p = 0; p < P; ++p) {
         if (!b.pairs[p].valid) continue;
         const bool brute = !b.pf[p].use || b.pairs[p].path == 0;
-        if (brute || !i8) {
+        if (brute || b.route.kind != kRouteI8) {
             wide.push_back(b.id1[p]);
             wide.push_back(b.id2[p]);
         }
@@ -433,9 +433,7 @@ struct PrefilterLaunch {
     PruneParams prune;
     size_t P = 0;
     HostClock hc;
-    // routes of the sub-batch (choose_routes)
-    bool compact = false, i8 = false, q8 = false, q8_mixed = false, fine_twins = false, q8_direct = false, q8_refine = false;
-    std::vector<char> twin;
+    const MsfmRoute& route;          // the sub-batch's route (prepare_batch_images); apply_route applies it
     std::vector<PfPair> pfq, pf16;
     long long dense_cand = 0;
     // work items and buffers (build_and_upload)
@@ -460,139 +458,67 @@ struct PrefilterLaunch {
     PlanCounts pc = {};
     PlanOut po = {};
 
-    PrefilterLaunch(msfm_ctx* c, Batch& batch, size_t ev, PruneParams pr) : ctx(c), b(batch), ev_base(ev), prune(pr) {}
+    PrefilterLaunch(msfm_ctx* c, Batch& batch, size_t ev, PruneParams pr) : ctx(c), b(batch), ev_base(ev), prune(pr), route(batch.route) {}
 
-    // ---- stage 1: which matrix cores sweep what (byte stores, route Q, mixed sub-batches), the pairs' tables of each sweep
-    int choose_routes() {
+    // ---- stage 1: the pairs' tables of each sweep for the sub-batch's route (byte stores, route Q, mixed sub-batches)
+    int apply_route() {
         P = b.pairs.size();
         hc = HostClock();
         SC.pf_pending = PfPending{};
         assign_partials(b, 1, 4 * ctx->cu_count);
-        // Sweep 2 on the compacted live rows, or on everything again?  Decided per batch, before any result exists: the Lowe
-        // test is what kills rows (~94 % at ratio 0.8 on SIFT-like data); with a ratio near or above 1 almost every row stays
-        // alive and the compacted sweep (both directions separately) would multiply up to twice what the dense one does.
-        compact = prune.prune != 0 && prune.ratio > 0.f && prune.ratio <= 0.95f;
-        // Byte stores: both sweeps on the integer matrix cores (msfm_sweep_i8.hip.h) when every prefiltered pair of the batch
-        // joins two byte images (a store is bytes throughout or not at all; a mixed batch takes the fp16 kernels)
-        i8 = compact && b.route_i8;   // (prepare_batch_images: the images' float forms may not even exist on this route)
-        if (i8)
-            for (size_t p = 0; p < P; ++p) {
-                if (!b.pairs[p].valid || !b.pf[p].use) continue;
-                const Image& ia = ctx->images[b.id1[p]];
-                const Image& ib = ctx->images[b.id2[p]];
-                PfPair& pp = b.pf[p];
-                pp.i8 = 1;
-                pp.a_h = reinterpret_cast<const _Float16*>(ia.i8);   // 176-byte rows behind the same pointers
-                pp.b_h = reinterpret_cast<const _Float16*>(ib.i8);
-                pp.a_nrm = ia.nrm_i8;
-                pp.b_nrm = ib.nrm_i8;
-                pp.a_nrm_max = ia.nrm_i8_max;
-                pp.b_nrm_max = ib.nrm_i8_max;
-                pp.a_c = pp.b_c = 0.f;
-                pp.a_h0 = ia.h0_i8;
-                pp.b_h0 = ib.h0_i8;
-                pp.a_n2 = ia.n2_i8;
-                pp.b_n2 = ib.n2_i8;
-            }
-        SC.pf_pending.i8 = i8;
-        // Route Q (msfm_q8.hip.h): float images with byte twins -- sweep 1 on the twins (integer matrix cores); coarse twins: an fp16
-        // sweep 1' on the rows that survive.  A pair takes it when both its images have twins; a sub-batch in which only SOME pairs do runs
-        // two first sweeps (fine twins: q8_mixed below) or keeps the fp16 route for all of them (coarse twins).
-        q8 = compact && !i8 && ctx->prefilter == 1 && ctx->q8_route;
-        long long q8_rows = 0, q8_pairs = 0, twin_pairs = 0, twin_rows = 0;
-        twin.clear();
-        if (q8) {
-            twin.assign(P, 0);
-            for (size_t p = 0; p < P; ++p)
-                if (b.pairs[p].valid && b.pf[p].use) {
-                    q8_rows += b.pairs[p].n1 + b.pairs[p].n2;
-                    q8_pairs += 1;
-                    if (ctx->images[b.id1[p]].q8 != nullptr && ctx->images[b.id2[p]].q8 != nullptr) {
-                        twin[p] = 1;
-                        twin_pairs += 1;
-                        twin_rows += b.pairs[p].n1 + b.pairs[p].n2;
-                    }
-                }
-    }
-    // (two plans and three sweeps only pay on real images: batches of small ones -- the pre-emptive filter's 100-row
-    // subsets -- keep the fp16 route; MSFM_Q8=2 lifts the limit, for the tests)
-    fine_twins = ctx->q8_direct == 2 || (ctx->q8_direct == 1 && ctx->q8_level <= kQ8DirectMaxLevel);
-    q8_mixed = false;   // some pairs join images without twins: THEIR sweep 1 runs on the fp16 cores, the twins' on the integer cores
-    if (q8 && twin_pairs < q8_pairs) {
-        // (fine twins only: the coarse route's plan A / sweep 1' cover whole sub-batches; and only when a quarter of the work or more has twins)
-        q8_mixed = fine_twins && twin_pairs > 0 && 4 * twin_rows >= q8_rows;
-        if (!q8_mixed) q8 = false;
-    }
-    if (q8 && ctx->q8_route < 2 && (twin_pairs == 0 || twin_rows < 2 * 1024 * twin_pairs)) q8 = q8_mixed = false;
-    pfq.clear(), pf16.clear();
-    if (q8) {
-        pfq = b.pf;
+        SC.prof.demoted_pairs += route.demoted_pairs;
+        SC.pf_pending.refine = route.kind == kRouteQ8Refine;
+        dense_cand = 0;
         for (size_t p = 0; p < P; ++p) {
-            if (!b.pairs[p].valid || !b.pf[p].use) continue;
-            if (!twin[p]) {   // (mixed sub-batch: not a pair of the twins' sweep)
-                pfq[p].use = 0;
-                continue;
+            b.pf[p].tu_off = b.pairs[p].kf_off;
+            b.pf[p].tv_off = b.pairs[p].kr_off;  // same combined index space as the kNN arrays
+            b.pf[p].cand_off = 0;
+            b.pf[p].cand_cap = 0;
+            if (!route.compact() && b.pairs[p].valid && b.pf[p].use) {
+                b.pf[p].cand_off = dense_cand;
+                b.pf[p].cand_cap = 16 * (b.pairs[p].n1 + b.pairs[p].n2) + 2048;
+                dense_cand += b.pf[p].cand_cap;
+                SC.pf_pending.dense_swept += (long long)b.pairs[p].n1pad * b.pairs[p].n2;
             }
-            const Image& ia = ctx->images[b.id1[p]];
-            const Image& ib = ctx->images[b.id2[p]];
-            PfPair& pp = pfq[p];
+        }
+        // The integer first sweeps read byte rows behind the fp16 pointers: byte stores their own (both sweeps; the images' float forms
+        // may not even exist), route Q (msfm_q8.hip.h) the twins, in a table of its own in which only the pairs with twins are in use.
+        pfq.clear(), pf16.clear();
+        if (route.q8()) pfq = b.pf;
+        for (size_t p = 0; p < P && (route.kind == kRouteI8 || route.q8()); ++p) {
+            if (!b.pairs[p].valid || !b.pf[p].use) continue;
+            PfPair& pp = route.q8() ? pfq[p] : b.pf[p];
+            pp.use = route.q8() ? route.twin[p] : 1;   // (mixed sub-batch: the pairs without twins are not in the twins' sweep)
+            if (!pp.use) continue;
+            const Image &ia = ctx->images[b.id1[p]], &ib = ctx->images[b.id2[p]];
             pp.i8 = 1;
-            pp.a_h = reinterpret_cast<const _Float16*>(ia.q8);
-            pp.b_h = reinterpret_cast<const _Float16*>(ib.q8);
-            pp.a_nrm = ia.nrm_q8;
-            pp.b_nrm = ib.nrm_q8;
-            pp.a_c = ia.err_q8_max;     // (the twin pair carries the images' largest quantisation errors here)
-            pp.b_c = ib.err_q8_max;
-            pp.a_h0 = ia.h0_q8;
-            pp.b_h0 = ib.h0_q8;
-            pp.a_err = ia.err_q8;
-            pp.b_err = ib.err_q8;
+            if (route.q8()) {
+                pp.a_h = reinterpret_cast<const _Float16*>(ia.q8);
+                pp.b_h = reinterpret_cast<const _Float16*>(ib.q8);
+                pp.a_nrm = ia.nrm_q8, pp.b_nrm = ib.nrm_q8;
+                pp.a_c = ia.err_q8_max, pp.b_c = ib.err_q8_max;   // (the twin pair carries the images' largest quantisation errors here)
+                pp.a_h0 = ia.h0_q8, pp.b_h0 = ib.h0_q8;
+                pp.a_err = ia.err_q8, pp.b_err = ib.err_q8;
+            } else {
+                pp.a_h = reinterpret_cast<const _Float16*>(ia.i8);
+                pp.b_h = reinterpret_cast<const _Float16*>(ib.i8);
+                pp.a_nrm = ia.nrm_i8, pp.b_nrm = ib.nrm_i8;
+                pp.a_nrm_max = ia.nrm_i8_max, pp.b_nrm_max = ib.nrm_i8_max;
+                pp.a_c = pp.b_c = 0.f;
+                pp.a_h0 = ia.h0_i8, pp.b_h0 = ib.h0_i8;
+                pp.a_n2 = ia.n2_i8, pp.b_n2 = ib.n2_i8;
+            }
         }
-    }
-    // The route is chosen per sub-batch: one pair that cannot take an integer route sends all of them to the fp16 kernels (same
-    // results, ~1.6 x the sweep time).  Counted, so that a mixed store shows up in the profile instead of only in the clock.
-    if (compact && ctx->prefilter == 1 && !i8 && !q8)   // (a mixed sub-batch of fine twins keeps the twins' pairs on the integer cores: q8_mixed)
-        for (size_t p = 0; p < P; ++p) {
-            if (!b.pairs[p].valid || !b.pf[p].use) continue;
-            const Image& ia = ctx->images[b.id1[p]];
-            const Image& ib = ctx->images[b.id2[p]];
-            const bool twins = ctx->q8_route && ia.q8 && ib.q8 && (ctx->q8_route == 2 || b.pairs[p].n1 + b.pairs[p].n2 >= 2048);
-            if ((ia.is_u8 && ib.is_u8) || twins) SC.prof.demoted_pairs += 1;
+        if (route.kind == kRouteQ8Mixed) {   // the table of the fp16 first sweep and its thresholds: the pairs WITHOUT twins
+            pf16 = b.pf;
+            // The column partials share one buffer: the fp16 sweep stores 8-byte entries at ELEMENT cp_off, the integer sweep 4-byte entries
+            // at the same element numbers -- in a homogeneous sub-batch either is consistent, mixed they would overlap.  The twins' pairs
+            // count their offset in 4-byte entries of their own 8-byte region.  (Only the integer sweep and the prune kernel read it; the
+            // batch is rebuilt before a re-run.)
+            for (size_t p = 0; p < P; ++p)
+                if (route.twin[p]) pf16[p].use = 0, b.pairs[p].cp_off *= 2;
         }
-    // fine twins: their sweep's bounds are the thresholds of sweep 2; coarse ones (a store with values near 1): an fp16 sweep 1'
-    // of the live rows refines them first
-    q8_direct = q8 && fine_twins;
-    q8_refine = q8 && !q8_direct;
-    SC.pf_pending.q8 = q8_refine;   // (a plan A and a sweep 1' to account for at the end of the batch)
-    dense_cand = 0;
-    for (size_t p = 0; p < P; ++p) {
-        b.pf[p].tu_off = b.pairs[p].kf_off;
-        b.pf[p].tv_off = b.pairs[p].kr_off;  // same combined index space as the kNN arrays
-        b.pf[p].cand_off = 0;
-        b.pf[p].cand_cap = 0;
-        if (!compact && b.pairs[p].valid && b.pf[p].use) {
-            b.pf[p].cand_off = dense_cand;
-            b.pf[p].cand_cap = 16 * (b.pairs[p].n1 + b.pairs[p].n2) + 2048;
-            dense_cand += b.pf[p].cand_cap;
-            SC.pf_pending.dense_swept += (long long)b.pairs[p].n1pad * b.pairs[p].n2;
-        }
-    }
-    for (size_t p = 0; p < P && q8; ++p) {
-        pfq[p].tu_off = b.pf[p].tu_off;
-        pfq[p].tv_off = b.pf[p].tv_off;
-    }
-    if (q8_mixed) {   // the table of the fp16 first sweep and its thresholds: the pairs WITHOUT twins (after the offsets above are final)
-        pf16 = b.pf;
-        for (size_t p = 0; p < P; ++p)
-            if (twin[p]) pf16[p].use = 0;
-        // The column partials share one buffer: the fp16 sweep stores 8-byte entries at ELEMENT cp_off, the integer sweep 4-byte entries
-        // at the same element numbers -- in a homogeneous sub-batch either is consistent, mixed they would overlap.  The twins' pairs
-        // count their offset in 4-byte entries of their own 8-byte region.  (Only the integer sweep and the prune kernel read it; the
-        // batch is rebuilt before a re-run.)
-        for (size_t p = 0; p < P; ++p)
-            if (twin[p]) b.pairs[p].cp_off *= 2;
-    }
-    return MSFM_OK;
+        return MSFM_OK;
     }
 
     // ---- stage 2: work items, the buffers of sweep 1 and of the reduce, every clear in one launch, the tables in one copy
@@ -601,9 +527,9 @@ struct PrefilterLaunch {
         per16 = 0;
         build_items(b, 1);
         if (b.n_items == 0) return MSFM_OK;   // (nothing on this path: run() stops here)
-        if (q8_mixed) {   // the fp16 first sweep's own item list: the pairs without twins
+        if (route.kind == kRouteQ8Mixed) {   // the fp16 first sweep's own item list: the pairs without twins
             std::vector<char> only(P, 0);
-            for (size_t p = 0; p < P; ++p) only[p] = (b.pairs[p].valid && b.pf[p].use && !twin[p]) ? 1 : 0;
+            for (size_t p = 0; p < P; ++p) only[p] = (b.pairs[p].valid && b.pf[p].use && !route.twin[p]) ? 1 : 0;
             build_items(b, 1, &only, &item_base16, &per16);
     }
     kn = std::max<long long>(1, b.kf_elems + b.kr_elems);
@@ -611,7 +537,7 @@ struct PrefilterLaunch {
     HIPCHK(ctx, SC.d_rp_s1.ensure(std::max<long long>(1, b.rp_elems) * 4));
     // column partials of sweep 1: one float2 (the two largest of four row-class maxima) per 512-row A block and column; the integer
     // sweeps pack theirs into 4 bytes (msfm_cp_pack) -- a mixed sub-batch keeps the 8-byte stride for both
-    HIPCHK(ctx, SC.d_cp_s0.ensure(std::max<long long>(1, b.cp_elems) * ((i8 || (q8_direct && !q8_mixed)) ? 4 : 8)));   // (coarse twins: q8_scatter_kernel writes float2 entries)
+    HIPCHK(ctx, SC.d_cp_s0.ensure(std::max<long long>(1, b.cp_elems) * ((route.kind == kRouteI8 || route.kind == kRouteQ8Direct) ? 4 : 8)));   // (coarse twins: q8_scatter_kernel writes float2 entries)
     HIPCHK(ctx, SC.d_tu.ensure(kn * 4));
     HIPCHK(ctx, SC.d_colmask.ensure(kn * 4));
     HIPCHK(ctx, SC.d_best.ensure(kn * 8));
@@ -621,13 +547,14 @@ struct PrefilterLaunch {
     // of the exact re-check
     HIPCHK(ctx, SC.d_totals.ensure(128));
     FillBatch fills;
-    if (!compact) {   // (compacted sweep 2: pf_assign_kernel initialises the live slots only)
+    if (!route.compact()) {   // (compacted sweep 2: pf_assign_kernel initialises the live slots only)
         fills.add(SC.d_best.p, (size_t)kn * 8, 0xff);
         fills.add(SC.d_second.p, (size_t)kn * 8, 0xff);
     }
     fills.add(SC.d_totals.p, 128, 0);
     fills.add(SC.d_overflow.p, P, 0);   // (which pairs own an overflowed list: pf_overflow_kernel at the end of the chain)
-    const int rc = upload_pair_tables(ctx, b, 1, q8 ? &pfq : nullptr, fills, q8_mixed ? &pf16 : nullptr, q8_mixed ? &item_base16 : nullptr, per16);
+    const int rc = upload_pair_tables(ctx, b, 1, route.q8() ? &pfq : nullptr, fills, route.kind == kRouteQ8Mixed ? &pf16 : nullptr,
+                                        route.kind == kRouteQ8Mixed ? &item_base16 : nullptr, per16);
     if (rc != MSFM_OK) return rc;
     return MSFM_OK;
     }
@@ -655,9 +582,9 @@ struct PrefilterLaunch {
             if (&other != ctx->cur && other.sweep2_recorded && other.seq + 2 <= SC.seq)
                 HIPCHK(ctx, hipStreamWaitEvent(SC.stream, other.sweep2_done, 0));
         HIPCHK(ctx, hipEventRecord(e0, SC.stream));
-        if (i8 || q8)
+        if (route.kind == kRouteI8 || route.q8())
             hipLaunchKernelGGL(sweep_i8_kernel<1>, dim3(std::min<unsigned>(sweep_grid, (unsigned)b.n_items)), dim3(kI8Threads), kI8LdsBytes, SC.stream, dp,
-                               q8 ? (const PfPair*)SC.d_pfq.as<PfPair>() : dpf,
+                               route.q8() ? (const PfPair*)SC.d_pfq.as<PfPair>() : dpf,
                                SC.d_items.as<WorkItem>(), SC.d_rp_s0.as<float>(), SC.d_rp_s1.as<float>(), SC.d_cp_s0.as<float>(),
                                (const float*)nullptr, (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)b.n_items, (int*)nullptr,
                                (int*)nullptr);
@@ -667,7 +594,7 @@ struct PrefilterLaunch {
                                SC.d_cp_s0.as<float>(), (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                                (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)b.n_items, (int*)nullptr);
         HIPCHK(ctx, hipGetLastError());
-        if (q8_mixed && per16) {   // the pairs without twins: their own item list (the twins' sweep skipped them: not in use in ITS table)
+        if (route.kind == kRouteQ8Mixed && per16) {   // the pairs without twins: their own item list (the twins' sweep skipped them: not in use in ITS table)
             hipLaunchKernelGGL(sweep_kernel<1>, dim3(std::min<unsigned>(sweep_grid, (unsigned)(per16 * 8))), block, kPfLdsBytes, SC.stream, dp,
                                (const PfPair*)SC.d_pf16.as<PfPair>(), SC.d_items16.as<WorkItem>(), SC.d_rp_s0.as<float>(), SC.d_rp_s1.as<float>(),
                                SC.d_cp_s0.as<float>(), (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
@@ -681,10 +608,10 @@ struct PrefilterLaunch {
     SC.sweep1_recorded = true;
     ctx->last_sweep1 = ctx->cur;
     SC.prof.approx_kernel_launches += 1;
-    if (i8 || q8) SC.prof.sweep1_i8_launches += 1;
-    if (q8) SC.prof.sweep1_q8_launches += 1;
+    if (route.kind == kRouteI8 || route.q8()) SC.prof.sweep1_i8_launches += 1;
+    if (route.q8()) SC.prof.sweep1_q8_launches += 1;
     mgrid = dim3((unsigned)((b.max_npad + 255) / 256), (unsigned)P);
-    if (!compact) {
+    if (!route.compact()) {
         hipLaunchKernelGGL(pf_thresholds_kernel, mgrid, dim3(256), 0, SC.stream, dp, dpf, SC.d_rp_s0.as<float>(),
                            SC.d_rp_s1.as<float>(), SC.d_cp_s0.as<float>(), (unsigned*)nullptr, tuv, tuv, prune, PlanCounts{}, 0);
         HIPCHK(ctx, hipGetLastError());
@@ -699,21 +626,22 @@ struct PrefilterLaunch {
     int plan_buffers() {
         // ---- static plan tables (the GPU is busy with sweep 1 meanwhile), buffers from the prediction ----------
         cp = CompactPlan{};
-        build_compact_plan(ctx, b, cp, q8_refine);
+        const bool refine = route.kind == kRouteQ8Refine;
+        build_compact_plan(ctx, b, cp, refine);
         G = cp.groups.size(), M = cp.member_pair.size();
         n_lists = G;
         long long max_ranges = 1;
         for (const PlanGroup& g : cp.groups) max_ranges = std::max<long long>(max_ranges, g.ranges);
         // Capacities: msfm_plan_room (msfm_hostutil.h) -- a prediction relative to the rows this sub-batch could compact at most; existing
         // buffers are kept while they hold it.
-        const long long ub = q8_refine ? cp.rows_ub_all_bits : cp.rows_ub;
+        const long long ub = refine ? cp.rows_ub_all_bits : cp.rows_ub;
         long long rows_have = (long long)std::min(std::min(SC.d_cmp_tu.cap / 4, SC.d_live_idx.cap / 4), std::min(SC.d_row_pair.cap / 4, SC.d_row_src.cap / 8));
-        if (i8) rows_have = std::min<long long>(rows_have, (long long)(SC.d_cmp_n2.cap / 4));
-        if (q8_refine) rows_have = std::min<long long>(rows_have, (long long)std::min(SC.d_cmp_s0.cap / 4, SC.d_cmp_s1.cap / 4));
+        if (route.kind == kRouteI8) rows_have = std::min<long long>(rows_have, (long long)(SC.d_cmp_n2.cap / 4));
+        if (refine) rows_have = std::min<long long>(rows_have, (long long)std::min(SC.d_cmp_s0.cap / 4, SC.d_cmp_s1.cap / 4));
         long long cand_have = (long long)(SC.d_cand.cap / sizeof(int2));
-        if (i8) cand_have = std::min<long long>(cand_have, (long long)(SC.d_cand_val.cap / 4));
+        if (route.kind == kRouteI8) cand_have = std::min<long long>(cand_have, (long long)(SC.d_cand_val.cap / 4));
         const long long items_have = (long long)(SC.d_vitems.cap / sizeof(WorkItem)) / 8 * 8;
-        const MsfmPlanRoom room = msfm_plan_room(ub, q8_refine ? cp.rows_ub_all_bits * 5 / 32 : cp.rows_ub * 5 / 16, (long long)G, max_ranges, kPfWgRows,
+        const MsfmPlanRoom room = msfm_plan_room(ub, refine ? cp.rows_ub_all_bits * 5 / 32 : cp.rows_ub * 5 / 16, (long long)G, max_ranges, kPfWgRows,
                                                  ctx->hint_rows_ub, ctx->cmp_rows_hint, ctx->cand_hint, ctx->items_hint, rows_have, cand_have, items_have);
         rows_cap = room.rows, cand_cap = room.cand, items_cap = room.items;
         SC.pf_pending.rows_ub = ub;
@@ -731,7 +659,7 @@ struct PrefilterLaunch {
         HIPCHK(ctx, SC.d_row_pair.ensure((size_t)rows_cap * 4));
         HIPCHK(ctx, SC.d_row_src.ensure((size_t)rows_cap * 8));
         HIPCHK(ctx, SC.d_cand.ensure((size_t)cand_cap * sizeof(int2)));
-        if (i8) {
+        if (route.kind == kRouteI8) {
             HIPCHK(ctx, SC.d_cand_val.ensure((size_t)cand_cap * 4));
             HIPCHK(ctx, SC.d_cmp_n2.ensure((size_t)rows_cap * 4));
         }
@@ -778,7 +706,7 @@ struct PrefilterLaunch {
         po.cand_cap = cand_cap;
         po.items_cap = items_cap;
         po.cmp_tu = SC.d_cmp_tu.as<float>();
-        po.cmp_n2 = i8 ? SC.d_cmp_n2.as<int>() : nullptr;
+        po.cmp_n2 = route.kind == kRouteI8 ? SC.d_cmp_n2.as<int>() : nullptr;
         return MSFM_OK;
     }
 
@@ -804,9 +732,9 @@ struct PrefilterLaunch {
                            SC.stream, dp, dpf, dpp, (const float*)tuv,
                            (const unsigned*)colmask, (const long long*)SC.d_mrow.as<long long>(), SC.d_cnt.as<int>(),
                            SC.d_live_idx.as<int>(), SC.d_row_pair.as<int>(), SC.d_cmp_tu.as<float>(),
-                           SC.d_row_src.as<const _Float16*>(), i8 ? kI8RowBytes / 2 : kPfRowHalfs,
+                           SC.d_row_src.as<const _Float16*>(), route.kind == kRouteI8 ? kI8RowBytes / 2 : kPfRowHalfs,
                            SC.d_best.as<unsigned long long>(), SC.d_second.as<unsigned long long>(), norms_only,
-                           i8 ? SC.d_cmp_n2.as<int>() : (int*)nullptr);
+                           route.kind == kRouteI8 ? SC.d_cmp_n2.as<int>() : (int*)nullptr);
         HIPCHK(ctx, hipGetLastError());
         DBGSYNC(ctx, "pf_assign_kernel");
         return MSFM_OK;
@@ -814,15 +742,13 @@ struct PrefilterLaunch {
 
     // ---- stage 4b (route Q): live / dead from the twins' sweep; coarse twins: plan A, the fp16 sweep 1' of the live rows, scatter
     int launch_route_q() {
-        if (q8) {
-            // ---- route Q: live / dead (fine twins: and the thresholds, the block masks, the counts of the plan) from the twins' sweep
-            hipLaunchKernelGGL(pf_prune_q8_kernel, mgrid, dim3(256), 0, SC.stream, dp, dpf, (const PfPair*)SC.d_pfq.as<PfPair>(),
-                               (const float*)SC.d_rp_s0.as<float>(), (const float*)SC.d_rp_s1.as<float>(), (const float*)SC.d_cp_s0.as<float>(),
-                               colmask, tuv, prune, pc, ctx->q8_level / 255.f, q8_direct ? 1 : 0);
-            HIPCHK(ctx, hipGetLastError());
-            DBGSYNC(ctx, "pf_prune_q8_kernel");
-        }
-        if (q8_refine) {
+        // ---- route Q: live / dead (fine twins: and the thresholds, the block masks, the counts of the plan) from the twins' sweep
+        hipLaunchKernelGGL(pf_prune_q8_kernel, mgrid, dim3(256), 0, SC.stream, dp, dpf, (const PfPair*)SC.d_pfq.as<PfPair>(),
+                           (const float*)SC.d_rp_s0.as<float>(), (const float*)SC.d_rp_s1.as<float>(), (const float*)SC.d_cp_s0.as<float>(),
+                           colmask, tuv, prune, pc, ctx->q8_level / 255.f, route.kind == kRouteQ8Refine ? 0 : 1);
+        HIPCHK(ctx, hipGetLastError());
+        DBGSYNC(ctx, "pf_prune_q8_kernel");
+        if (route.kind == kRouteQ8Refine) {
             // ---- coarse twins: plan A, fp16 sweep 1' on the live rows, scatter ------------------------------------------------
             HIPCHK(ctx, hipMemsetAsync(SC.d_summary_a.p, 0, sizeof(PlanSummary), SC.stream));
             int rc = launch_plan(SC.d_summary_a.as<PlanSummary>(), 1);
@@ -868,18 +794,17 @@ struct PrefilterLaunch {
     // ---- stage 4c: thresholds + live counts, the plan, the compacted sweep 2
     int launch_compact_sweep2() {
         // thresholds + live counts per member / group (the plan tables above are uploaded by now; sweep 1 is still running)
-        if (!q8_direct)
-            hipLaunchKernelGGL(pf_thresholds_kernel, mgrid, dim3(256), 0, SC.stream, dp, dpf, SC.d_rp_s0.as<float>(),
-                               SC.d_rp_s1.as<float>(), SC.d_cp_s0.as<float>(), colmask, tuv, tuv, prune, pc, q8 ? 1 : 0);
-        else if (q8_mixed)   // (the pairs of the fp16 sweep 1: thresholds and plan counts the usual way; the prune kernel did the twins')
-            hipLaunchKernelGGL(pf_thresholds_kernel, mgrid, dim3(256), 0, SC.stream, dp, (const PfPair*)SC.d_pf16.as<PfPair>(), SC.d_rp_s0.as<float>(),
-                               SC.d_rp_s1.as<float>(), SC.d_cp_s0.as<float>(), colmask, tuv, tuv, prune, pc, 0);
+        // (fine twins: the prune kernel did it; in a mixed sub-batch for the twins' pairs -- the pairs of the fp16 sweep 1 the usual way)
+        if (route.kind != kRouteQ8Direct)
+            hipLaunchKernelGGL(pf_thresholds_kernel, mgrid, dim3(256), 0, SC.stream, dp, route.kind == kRouteQ8Mixed ? (const PfPair*)SC.d_pf16.as<PfPair>() : dpf,
+                               SC.d_rp_s0.as<float>(), SC.d_rp_s1.as<float>(), SC.d_cp_s0.as<float>(), colmask, tuv, tuv, prune, pc,
+                               route.kind == kRouteQ8Refine ? 1 : 0);
         HIPCHK(ctx, hipGetLastError());
         DBGSYNC(ctx, "pf_thresholds_kernel");
         const int rc = launch_plan(SC.d_summary.as<PlanSummary>(), 0);
         if (rc != MSFM_OK) return rc;
         HIPCHK(ctx, hipEventRecord(e2, SC.stream));
-        if (i8)
+        if (route.kind == kRouteI8)
             hipLaunchKernelGGL(sweep_i8_kernel<3>, dim3(sweep_grid), dim3(kI8Threads), kI8LdsBytes3, SC.stream,
                                (const PairDesc*)SC.d_vpairs.as<PairDesc>(), (const PfPair*)SC.d_vpf.as<PfPair>(),
                                (const WorkItem*)SC.d_vitems.as<WorkItem>(), (float*)nullptr, (float*)nullptr, (float*)nullptr,
@@ -949,7 +874,7 @@ struct PrefilterLaunch {
                            (const int2*)SC.d_cand.as<int2>(), SC.d_best.as<unsigned long long>(), SC.d_second.as<unsigned long long>(), \
                            (int)n_lists, SC.d_totals.as<int>() + 16, (const int*)SC.d_cand_val.as<int>(), 0)
             // byte pairs on the integer route: the sweep handed over exact integers -- no rows are read, the named order does not matter
-            if (i8 && compact) MSFM_LAUNCH_EXACT(4);
+            if (route.kind == kRouteI8) MSFM_LAUNCH_EXACT(4);
             else if (ctx->order == MSFM_ORDER_SSE4X4) MSFM_LAUNCH_EXACT(0);
             else if (ctx->order == MSFM_ORDER_AVX2_FMA) MSFM_LAUNCH_EXACT(1);
             else MSFM_LAUNCH_EXACT(3);
@@ -982,15 +907,15 @@ struct PrefilterLaunch {
     }
 
     int run() {
-        int rc = choose_routes();
+        int rc = apply_route();
         if (rc != MSFM_OK) return rc;
         rc = build_and_upload();
         if (rc != MSFM_OK || b.n_items == 0) return rc;
         rc = launch_sweep1();
         if (rc != MSFM_OK) return rc;
-        if (compact) {
+        if (route.compact()) {
             rc = plan_buffers();
-            if (rc == MSFM_OK && q8) rc = launch_route_q();
+            if (rc == MSFM_OK && route.q8()) rc = launch_route_q();
             if (rc == MSFM_OK) rc = launch_compact_sweep2();
         } else {
             rc = launch_dense_sweep2();
@@ -1033,7 +958,7 @@ int finish_prefilter(msfm_ctx* ctx, Batch& b, std::vector<char>& force_exact, bo
         ctx->items_hint = sm.items_needed;
         ctx->cand_hint = sm.cand_elems;
         ctx->hint_rows_ub = pe.rows_ub;
-        if (pe.q8) {   // plan A (every live column in every block group) is the larger one
+        if (pe.refine) {   // plan A (every live column in every block group) is the larger one
             PlanSummary sa;
             std::memcpy(&sa, hs + sizeof(PlanSummary), sizeof(PlanSummary));
             ctx->cmp_rows_hint = std::max(ctx->cmp_rows_hint, sa.cmp_rows);
@@ -1219,7 +1144,7 @@ int queue_tail_copies(msfm_ctx* ctx, size_t P) {
     if (SC.d_sens.p) segs.s[2] = ExportSeg{SC.d_sens.as<char>(), h + 8 + (P + 1) * 8, (unsigned)(P * 4)};
     if (SC.pf_pending.active) {
         if (SC.pf_pending.compact) segs.s[3] = ExportSeg{SC.d_summary.as<char>(), hs, (unsigned)sizeof(PlanSummary)};
-        if (SC.pf_pending.q8) segs.s[6] = ExportSeg{SC.d_summary_a.as<char>(), hs + sizeof(PlanSummary), (unsigned)sizeof(PlanSummary)};
+        if (SC.pf_pending.refine) segs.s[6] = ExportSeg{SC.d_summary_a.as<char>(), hs + sizeof(PlanSummary), (unsigned)sizeof(PlanSummary)};
         segs.s[4] = ExportSeg{SC.d_totals.as<char>(), hs + kHsTotals, 16};
         segs.s[5] = ExportSeg{SC.d_overflow.as<char>(), hs + kHsOverflow, (unsigned)P};
     }

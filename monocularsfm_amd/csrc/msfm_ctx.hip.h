@@ -539,7 +539,7 @@ constexpr long long kMinPipelineCost = 15000000000LL;
 // any before -- and the explicit wait is what makes replacing a buffer safe that kernels queued earlier still read; steady
 // state allocates nothing).
 struct PfPending {                // what the end-of-batch synchronisation has to look at
-    bool active = false, compact = false, i8 = false, q8 = false;
+    bool active = false, compact = false, refine = false;   // refine: route Q with coarse twins -- a plan A and a sweep 1' to collect
     size_t n_lists = 0, P = 0;
     long long rows_cap = 0, cand_cap = 0, items_cap = 0;
     long long rows_ub = 0;            // the rows this sub-batch could compact at most: what its needs are relative to (the next prediction)
@@ -660,6 +660,7 @@ struct msfm_ctx {
     float q8_level = 0.f;             // m: largest value of the twinned images so far, rounded up to a multiple of 1/16 (msfm_q8.hip.h)
     int q8_direct = 1;                // thresholds for sweep 2 straight from the twins' sweep when they are fine enough (MSFM_Q8_DIRECT=0: never, 2: always)
     int q8_route = 1;                 // float images in [0, 1] get byte twins and their first sweep on the integer cores (MSFM_Q8=0: off)
+    MsfmRouteKnobs route_knobs() const { return MsfmRouteKnobs{prefilter, q8_route, q8_direct, q8_level}; }   // (msfm_route)
     DeferredFrees deferred;           // device buffers replaced while sub-batches were in flight: freed when the call has drained
     long long cmp_rows_hint = 0;      // compacted rows the previous batch needed (sizes the next batch's buffers) ...
     long long hint_rows_ub = 0;       // ... of the rows it could compact at most: the prediction scales with that, and is void beyond a factor 2

@@ -1,6 +1,7 @@
 // msfm_hostutil.h -- small pure functions shared by device and host code, compilable on their own (tests/test_hostutil.py builds a
 // g++ driver around them): the 4-byte packing of the integer sweeps' column partials, the cost marks of a call's sub-batches, the
-// scratch memory one image pair of a sub-batch needs, the fold of a candidate's key into a slot's (best, second).
+// scratch memory one image pair of a sub-batch needs, the matching route of a sub-batch, the fold of a candidate's key into a slot's
+// (best, second).
 #pragma once
 #include <vector>
 
@@ -81,6 +82,89 @@ inline long long msfm_pair_scratch_bytes(int n1, int n2, int n1pad, int n2pad, i
     // only knows live / dead -- twice the compacted rows of the direct route)
     const long long cmp_rows = ((long long)n1 + (long long)n2 * bits) / (route == 4 ? 8 : 16) + 1024;
     return common + partials + (route == 3 ? 120LL : 84LL) * cmp_rows;
+}
+
+// ---- The matching route of a sub-batch: the ONE statement of the policy (every route gives the same bits).  msfm_route
+// runs once per sub-batch (prepare_batch_images), MatchJob::build cuts a call by msfm_scratch_route before any sub-batch exists.
+// with twins at least this fine the twins' sweep yields thresholds tight enough to collect candidates with directly
+// (~4.5 per live row on RootSIFT-like data against 2.5 after an fp16 sweep 1'; 12 at m = 1): no sweep 1' (msfm_q8.hip.h)
+constexpr float kQ8DirectMaxLevel = 0.625f;
+struct MsfmRouteKnobs { int prefilter, q8_route, q8_direct; float q8_level; };   // the context's (msfm_ctx.hip.h; q8_level 0: no twins yet)
+// Sweep 2 on the compacted live rows, or on everything again?  The Lowe test kills ~94 % of the rows at ratio 0.8 on SIFT-like data; near
+// or above 1 almost every row stays alive, and the compacted sweep (both directions separately) would do up to twice the dense one's work.
+inline bool msfm_compact_sweep2(int prune, float ratio) { return prune != 0 && ratio > 0.f && ratio <= 0.95f; }
+// route Q at all: twins are read on the integer-core prefilter only
+inline bool msfm_twin_route_on(const MsfmRouteKnobs& k) { return k.prefilter == 1 && k.q8_route != 0; }
+// fine twins: their sweep's bounds are the thresholds of sweep 2; coarse ones (a store with values near 1): an fp16 sweep 1' first
+inline bool msfm_fine_twins(const MsfmRouteKnobs& k) { return k.q8_direct == 2 || (k.q8_direct == 1 && k.q8_level <= kQ8DirectMaxLevel); }
+// both images byte stores (a store is bytes throughout or not at all)
+inline bool msfm_byte_pair(bool a_is_u8, bool b_is_u8) { return a_is_u8 && b_is_u8; }
+
+// Route of a sub-batch's prefiltered pairs (brute-force pairs run beside any of them):
+enum MsfmRouteKind {
+    kRouteDense,      // prune off or ratio > 0.95 (the kNN-level API): fp16 sweep 1, thresholds, dense sweep 2
+    kRouteFp16,       // fp16 sweep 1, compacted sweep 2
+    kRouteI8,         // every pair joins two byte images: both sweeps on the integer cores, exact S from the sweep itself
+    kRouteQ8Direct,   // route Q, fine twins on every pair: the twins' sweep 1 on the integer cores gives sweep 2 its thresholds
+    kRouteQ8Mixed,    // route Q, fine twins on some pairs: the twins' sweep 1 for them, the fp16 sweep 1 for the others
+    kRouteQ8Refine,   // route Q, coarse twins on every pair: the twins' sweep 1, plan A, fp16 sweep 1' of the live rows
+};
+struct MsfmRoute {
+    MsfmRouteKind kind = kRouteDense;
+    std::vector<char> twin;          // per pair: swept on its twins (route Q; the others of a mixed sub-batch take the fp16 sweep 1)
+    long long demoted_pairs = 0;     // pairs that could take an integer route alone but go to the fp16 cores with the rest
+    bool compact() const { return kind != kRouteDense; }
+    bool q8() const { return kind >= kRouteQ8Direct; }
+};
+struct MsfmRoutePair { bool valid, use, a_is_u8, b_is_u8, a_twin, b_twin; int n1, n2; };   // (a pair counts when valid and in use)
+
+inline MsfmRoute msfm_route(const MsfmRouteKnobs& k, int prune, float ratio, const std::vector<MsfmRoutePair>& pairs) {
+    MsfmRoute r;
+    r.twin.assign(pairs.size(), 0);
+    if (!msfm_compact_sweep2(prune, ratio)) return r;
+    r.kind = kRouteFp16;
+    if (k.prefilter != 1) return r;
+    long long rows = 0, n_pairs = 0, twin_pairs = 0, twin_rows = 0;
+    bool bytes = true;
+    for (const MsfmRoutePair& q : pairs) {
+        if (!q.valid || !q.use) continue;
+        bytes = bytes && msfm_byte_pair(q.a_is_u8, q.b_is_u8);
+        rows += q.n1 + q.n2;
+        n_pairs += 1;
+        if (q.a_twin && q.b_twin) twin_pairs += 1, twin_rows += q.n1 + q.n2;
+    }
+    if (bytes) {   // (also a sub-batch without prefiltered pairs: nothing is swept)
+        r.kind = kRouteI8;
+        return r;
+    }
+    // Route Q: a pair takes it when both its images have twins; a sub-batch in which only SOME pairs do runs two first sweeps (fine twins,
+    // a quarter of the rows or more with twins) or keeps the fp16 route for all (coarse twins: plan A and sweep 1' cover whole sub-batches).
+    // Two plans and three sweeps only pay on real images: small ones -- the pre-emptive filter's 100-row subsets -- need q8_route == 2.
+    const bool fine = msfm_fine_twins(k), mixed = twin_pairs < n_pairs;
+    bool q8 = msfm_twin_route_on(k) && (!mixed || (fine && twin_pairs > 0 && 4 * twin_rows >= rows));
+    if (q8 && k.q8_route < 2 && (twin_pairs == 0 || twin_rows < 2 * 1024 * twin_pairs)) q8 = false;
+    if (q8) {
+        r.kind = mixed ? kRouteQ8Mixed : (fine ? kRouteQ8Direct : kRouteQ8Refine);
+        for (std::size_t p = 0; p < pairs.size(); ++p) r.twin[p] = pairs[p].valid && pairs[p].use && pairs[p].a_twin && pairs[p].b_twin;
+        return r;
+    }
+    // One pair that cannot take an integer route sends all of them to the fp16 kernels (~1.6 x the sweep time): counted, so that a mixed
+    // store shows up in the profile.  (Each pair's own n1 + n2 >= 2048 here, while the decision above takes the mean over the twin pairs.)
+    for (const MsfmRoutePair& q : pairs)
+        if (q.valid && q.use && (msfm_byte_pair(q.a_is_u8, q.b_is_u8) ||
+                                 (k.q8_route && q.a_twin && q.b_twin && (k.q8_route == 2 || q.n1 + q.n2 >= 2048))))
+            r.demoted_pairs += 1;
+    return r;
+}
+
+// What msfm_pair_scratch_bytes charges one pair for (route code 0 - 4), before the sub-batch -- and with it its route -- exists.
+inline int msfm_scratch_route(const MsfmRouteKnobs& k, int prune, float ratio, bool use, bool a_is_u8, bool b_is_u8) {
+    if (!use || k.prefilter == 0) return 0;
+    if (!msfm_compact_sweep2(prune, ratio)) return 2;
+    if (k.prefilter == 1 && msfm_byte_pair(a_is_u8, b_is_u8)) return 3;
+    // (every prefiltered non-byte pair counts as route 4 when the context's twins are coarse, even a pair without twins)
+    if (msfm_twin_route_on(k) && k.q8_level > 0.f && !msfm_fine_twins(k)) return 4;
+    return 1;
 }
 
 // Room for the device-side plan of sweep 2 (compacted rows, candidate entries, work items) of a sub-batch that could compact `ub` rows at

@@ -31,9 +31,8 @@ struct MatchJob {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     int kSets = kInFlight;
     long long kScratchBytes = 1;
-    int scratch_route = 1;
+    MsfmRouteKnobs knobs = {};   // the context's route knobs at the start of the call: what its pairs are charged for (msfm_scratch_route)
     int kMaxPairsPerBatch = kDefaultMaxPairsPerBatch;
-    bool coarse_twins = false;   // float stores whose twins need the fp16 sweep 1' (plan A: more compacted rows per pair)
     std::vector<long long> marks;
     long long cost_done = 0;   // cost of the sub-batches built so far (a re-built sub-batch starts from its own begin: see build)
     bool need_fix = false;
@@ -137,11 +136,8 @@ struct MatchJob {
         ctx->budget_for_limit = ctx->scratch_bytes;
     }
     kScratchBytes = std::max<long long>(1, budget / kSets);
-    // which buffers a pair needs (msfm_pair_scratch_bytes): 0 brute force, 1 matrix cores + compacted sweep 2 (3: on the integer cores), 2 + dense sweep 2
-    scratch_route = !ctx->prefilter ? 0 : ((prune.ratio > 0.f && prune.ratio <= 0.95f) ? 1 : 2);
+    knobs = ctx->route_knobs();
     kMaxPairsPerBatch = ctx->max_pairs_per_batch;
-    coarse_twins = ctx->prefilter == 1 && ctx->q8_route && ctx->q8_level > 0.f &&
-                   !(ctx->q8_direct == 2 || (ctx->q8_direct == 1 && ctx->q8_level <= kQ8DirectMaxLevel));
     // cumulative-cost marks of the parts (empty: no cost cut): msfm_pipeline_marks (msfm_hostutil.h) -- shrinking parts
     marks.clear();
     if (ctx->pipeline > 1 && n_pairs > 1) {
@@ -187,16 +183,12 @@ struct MatchJob {
             PfPair pp;
             int rc = fill_pair(ctx, pairs[2 * end], pairs[2 * end + 1], pd, pp);
             if (rc != MSFM_OK) return rc;
-            if (verify) {
-                const Image& ia = ctx->images[pairs[2 * end]];
-                const Image& ib = ctx->images[pairs[2 * end + 1]];
-                if (ia.nk < ia.n || ib.nk < ib.n)
-                    return fail(ctx, MSFM_E_STATE, "geometric verification needs msfm_upload_keypoints for image " +
-                                                       std::to_string(ia.nk < ia.n ? pairs[2 * end] : pairs[2 * end + 1]));
-            }
-            const bool bytes_pair = ctx->prefilter == 1 && ctx->images[(size_t)pairs[2 * end]].is_u8 && ctx->images[(size_t)pairs[2 * end + 1]].is_u8;
-            const long long need = pd.valid ? msfm_pair_scratch_bytes(pd.n1, pd.n2, pd.n1pad, pd.n2pad, pd.a_blocks, pd.a_blocks256,
-                                                                     !pp.use ? 0 : (scratch_route == 1 && bytes_pair ? 3 : (scratch_route == 1 && coarse_twins ? 4 : scratch_route))) : 0;
+            const Image &ia = ctx->images[pairs[2 * end]], &ib = ctx->images[pairs[2 * end + 1]];
+            if (verify && (ia.nk < ia.n || ib.nk < ib.n))
+                return fail(ctx, MSFM_E_STATE, "geometric verification needs msfm_upload_keypoints for image " +
+                                                   std::to_string(ia.nk < ia.n ? pairs[2 * end] : pairs[2 * end + 1]));
+            const int route = msfm_scratch_route(knobs, prune.prune, prune.ratio, pp.use != 0, ia.is_u8, ib.is_u8);
+            const long long need = pd.valid ? msfm_pair_scratch_bytes(pd.n1, pd.n2, pd.n1pad, pd.n2pad, pd.a_blocks, pd.a_blocks256, route) : 0;
             const long long c = pd.valid ? (long long)pd.n1 * pd.n2 : 0;
             if (end > begin && est + need > kScratchBytes) break;
             if (end > begin && !marks.empty() && cost_begin + cost + c / 2 > mark) break;

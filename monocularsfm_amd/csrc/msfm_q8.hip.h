@@ -43,9 +43,7 @@
 // twin built under a smaller m is rebuilt at the start of the next matching call (msfm_store_host.hip.h: rebuild_stale_twins -> build_twins, from the resident fp32 rows).  The
 // real number the bounds are stated with is the float `inv` ~ 1 / s itself: the twin is a^ = q * inv EXACTLY.
 constexpr float kQ8LevelStep = 1.f / 16.f;
-// with twins at least this fine the twins' sweep yields thresholds tight enough to collect candidates with directly
-// (~4.5 per live row on RootSIFT-like data against 2.5 after an fp16 sweep 1'; 12 at m = 1): no sweep 1'
-constexpr float kQ8DirectMaxLevel = 0.625f;
+// (which twins are fine enough to skip sweep 1': msfm_fine_twins, msfm_hostutil.h)
 
 // live / dead from the integer sweep on the twins.  Rows: rp_s0 / rp_s1 hold S~min and an upper bound of the second
 // smallest S~ (floats holding integers); columns: per 512-row block the two largest accumulator maxima (-S~/2).

@@ -298,7 +298,7 @@ int finalize_store(msfm_ctx* ctx) {
             if (k > 15) im.pf_safe = false;
             else im.c = std::ldexp(1.f, k);
         }
-        want_twin[j] = (!im.no_twin && ctx->q8_route && mx[4] == 0) ? 1 : 0;   // every value in [0, 1] (a float image of 0 / 1 entries is both)
+        want_twin[j] = (!im.no_twin && ctx->q8_route && mx[4] == 0) ? 1 : 0;   // values in [0, 1] (0 / 1 images too); q8_route alone, even if prefilter != 1
         if (want_twin[j])
             ctx->q8_level = std::max(ctx->q8_level, std::max(kQ8LevelStep, std::ceil(im.abs_max / kQ8LevelStep) * kQ8LevelStep));
         want_float[j] = (!im.is_u8 || want_twin[j]) ? 1 : 0;
@@ -377,7 +377,7 @@ int finalize_store(msfm_ctx* ctx) {
 
 // twins built before a later upload raised the context's level (msfm_q8.hip.h): rebuilt from the resident fp32 rows
 int rebuild_stale_twins(msfm_ctx* ctx, const int32_t* ids, int n_ids) {
-    if (!ctx->q8_route || ctx->prefilter != 1) return MSFM_OK;
+    if (!msfm_twin_route_on(ctx->route_knobs())) return MSFM_OK;   // (q8_route on and prefilter == 1, unlike the building of twins)
     std::vector<int> stale;
     for (int k = 0; k < n_ids; ++k) {
         const int id = ids[k];
