@@ -300,6 +300,60 @@ int msfm_knn2_pair(msfm_ctx* ctx, int id1, int id2,
                    int32_t* fwd_idx0, float* fwd_d0, float* fwd_d1,
                    int32_t* rev_idx0, float* rev_d0, float* rev_d1);
 
+/* ---- vocabulary retrieval: the pairs of matching mode 2 -------------------------------------
+ * The reference's configuration reserves SIFTmatch.match_type 2 for "vocabulary tree match" (not implemented there).  Here it is a FLAT
+ * visual vocabulary: every row's word is found by exhaustive search on the integer matrix cores, so every row gets its EXACT nearest
+ * word (a tree would only approximate it).  Pairs are the images that a tf-idf comparison of their word histograms says overlap.
+ * Everything up to the scores is integer arithmetic (a numpy reference reproduces it bit for bit: tests/retrieval_ref.py).
+ *   quantised row q (128 x u8), per image: an image whose values are all integers in 0..255 (u8 or f32 uploads) uses q = x; an image
+ *     whose values all lie in [0, 1] (RootSIFT, L2- or L1-root) uses q = (u8) rintf(x * 255.0f) (fp32 multiply, round half to even);
+ *     any other image fails the call with MSFM_E_INVALID (msfm_last_error names it).  (The store's byte twins of float images use a
+ *     store-wide level instead of 255: a different quantisation, not used here.)
+ *   nearest word of a row: argmin_w sum (q - c_w)^2, exact in int32; the lower w wins a tie.  With q' = q - 128, c' = c - 128 this is
+ *     argmin_w |c'_w|^2 - 2 q'.c'_w: one v_mfma_i32_32x32x32_i8 dot product and a constant per word.
+ *   training sample: the call's images by ascending id, rows concatenated, R rows; s = max(1, R / M); the rows at 0, s, 2s, ... (at most
+ *     M of them, Ms in all).  V' = min(V, max(1, Ms / 8)) words; word k starts as sample row (k Ms) / V' (64-bit integers).
+ *   k-means: at most T Lloyd iterations on the sample, integer sums and counts; a word with cnt > 0 rows becomes
+ *     c = floor((2 sum + cnt) / (2 cnt)) per dimension, a word without rows keeps its centroid; an iteration that changes no centroid ends
+ *     the training early (the result is the same).
+ *   scores: c_iw = rows of image i with word w, n_w = images of the call containing w, idf_w = ln(N / n_w), v_iw = c_iw idf_w,
+ *     s_ij = v_i.v_j / (|v_i| |v_j|), 0 for a zero norm -- that is the fp64 definition.  The device evaluates a_iw = fl32(v_iw / |v_i|)
+ *     (idf and |v_i| in fp64) and s_ij = one fp32 fmaf chain over w ascending: the same bits on every call and in any id order,
+ *     s_ij == s_ji bit for bit, and |s_dev - s| <= (m + 4) 2^-23 with m = min(nnz(v_i), nnz(v_j)).
+ *   selection: image i takes the first K images j != i with s_ij > 0, by device score, highest first, the lower id on equal scores; the
+ *     pairs are the union of (max(i, j), min(i, j)) -- brute mode's orientation --, by first id, then second id, ascending.
+ * Errors: no vocabulary, or a streaming series open: MSFM_E_STATE; an id that is not resident, twice in the list, an unsupported image,
+ * n > MSFM_MAX_IMAGES, K outside 1..1024: MSFM_E_INVALID.  The context stays usable after any of them; a pending store build is done
+ * first.  Only the vocabulary stays resident (V' x 144 B); the scratch of a call (words of every row, the n x V' histograms, the n x n
+ * scores) is freed when it returns. */
+typedef struct msfm_retrieval_params {
+    int num_words;      /* V, 0 = 16384 (at most 65536) */
+    int train_iters;    /* T, 0 = 8 */
+    int64_t train_rows; /* M, 0 = 64 V (at most 2^24: the sums stay in 32 bits) */
+} msfm_retrieval_params;
+/* Device time of the phases of the last msfm_train_vocabulary / msfm_retrieve_pairs calls (HIP events on the library's stream). */
+typedef struct msfm_retrieval_profile {
+    double train_ms;         /* sample gather + every Lloyd iteration */
+    int train_iterations;    /* iterations run (an unchanged iteration ends the training) */
+    double assign_ms;        /* the nearest word of every row of the retrieval call (ret_assign_kernel) */
+    double score_ms;         /* histograms, idf, norms, S = A A^T */
+    double topk_ms;          /* per-image top-K */
+    int64_t rows;            /* rows assigned by the retrieval call */
+    int num_words;           /* V' of the resident vocabulary */
+} msfm_retrieval_profile;
+/* Trains the vocabulary on the images `ids` (any order) and keeps it resident.  out_words (nullable): V' x 128 bytes c. */
+int msfm_train_vocabulary(msfm_ctx* ctx, const int32_t* ids, int n, const msfm_retrieval_params* params, uint8_t* out_words,
+                          int* out_num_words);
+/* A caller's vocabulary (n_words x 128 bytes c, 1 <= n_words <= 65536) instead of training. */
+int msfm_set_vocabulary(msfm_ctx* ctx, const uint8_t* words, int n_words);
+/* The word of every row of one image (parity / debug): out_word = rows(image_id) int32. */
+int msfm_image_words(msfm_ctx* ctx, int image_id, int32_t* out_word);
+/* The retrieved pairs of the images `ids`: out_pairs (capacity n * num_nearest pairs) = (id1 > id2) int32 pairs in brute mode's order,
+ * out_scores (nullable) their s, out_score_matrix (nullable, n x n in the order of `ids`, debug) every s_ij (0 on the diagonal). */
+int msfm_retrieve_pairs(msfm_ctx* ctx, const int32_t* ids, int n, int num_nearest, int32_t* out_pairs, float* out_scores,
+                        int* out_n_pairs, float* out_score_matrix);
+int msfm_get_retrieval_profile(const msfm_ctx* ctx, msfm_retrieval_profile* out);
+
 /* ---- host-side helpers (no device work) ------------------------------------------------- */
 /* FeatureUtils::ExtractTopScaleDescriptors' row selection (FeatureUtils.cpp:68-96):
  * kpts = n x 4 float (x, y, size, angle); writes min(k, n) indices, k > n => identity.

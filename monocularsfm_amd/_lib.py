@@ -27,6 +27,7 @@ EXPORTS = [
     "msfm_version", "msfm_upload_keypoints", "msfm_match_pairs_verified", "msfm_subset_image", "msfm_view_matches", "msfm_set_limits", "msfm_fetch_matches_device",
     "msfm_fetch_order_certificate", "msfm_set_pipeline", "msfm_device_count", "msfm_finalize_store", "msfm_store_info",
     "msfm_match_pairs_begin", "msfm_match_pairs_next", "msfm_read_device", "msfm_memory_info", "msfm_match_pairs_end",
+    "msfm_train_vocabulary", "msfm_set_vocabulary", "msfm_image_words", "msfm_retrieve_pairs", "msfm_get_retrieval_profile",
 ]
 
 
@@ -62,6 +63,15 @@ class Chunk(C.Structure):
 
 class Memory(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("device_free", "device_total", "store", "inbox", "scratch", "results_device", "page_locked_host")]
+
+
+class RetrievalParams(C.Structure):
+    _fields_ = [("num_words", C.c_int), ("train_iters", C.c_int), ("train_rows", C.c_int64)]
+
+
+class RetrievalProfile(C.Structure):
+    _fields_ = [("train_ms", C.c_double), ("train_iterations", C.c_int), ("assign_ms", C.c_double), ("score_ms", C.c_double),
+                ("topk_ms", C.c_double), ("rows", C.c_int64), ("num_words", C.c_int)]
 
 
 class MsfmError(RuntimeError):
@@ -127,6 +137,15 @@ def load():
     try:   # (the A/B tools also load older builds of the library: tools/ab.py)
         L.msfm_device_count.argtypes = []
         L.msfm_device_count.restype = C.c_int
+    except AttributeError:
+        pass
+    try:   # vocabulary retrieval (matching mode 2); older builds loaded by the A/B tools lack it
+        u8p = C.POINTER(C.c_uint8)
+        L.msfm_train_vocabulary.argtypes = [vp, ip, C.c_int, C.POINTER(RetrievalParams), u8p, C.POINTER(C.c_int)]
+        L.msfm_set_vocabulary.argtypes = [vp, u8p, C.c_int]
+        L.msfm_image_words.argtypes = [vp, C.c_int, ip]
+        L.msfm_retrieve_pairs.argtypes = [vp, ip, C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int), fp]
+        L.msfm_get_retrieval_profile.argtypes = [vp, C.POINTER(RetrievalProfile)]
     except AttributeError:
         pass
     for name in EXPORTS:
@@ -256,6 +275,47 @@ class Context:
         b, r, p = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._L.msfm_store_info(self._h, C.byref(b), C.byref(r), C.byref(p)))
         return {"device_bytes": b.value, "rows": r.value, "pending_images": p.value}
+
+    # ---- vocabulary retrieval (matching mode 2; include/msfm_match.h) ----
+    def train_vocabulary(self, ids, num_words=0, train_iters=0, train_rows=0):
+        """Train the flat vocabulary on the images `ids` and keep it resident -> the words (V' x 128 uint8)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        prm = RetrievalParams(int(num_words), int(train_iters), int(train_rows))
+        cap = int(num_words) if num_words else 16384
+        out = np.zeros((cap, DIM), np.uint8)
+        nw = C.c_int()
+        self._chk(self._L.msfm_train_vocabulary(self._h, _ip(ids), len(ids), C.byref(prm), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nw)))
+        return out[:nw.value].copy()
+
+    def set_vocabulary(self, words):
+        words = np.ascontiguousarray(words, dtype=np.uint8).reshape(-1, DIM)
+        self._chk(self._L.msfm_set_vocabulary(self._h, words.ctypes.data_as(C.POINTER(C.c_uint8)), len(words)))
+
+    def image_words(self, image_id):
+        """The nearest word of every row of one resident image (int32)."""
+        out = np.zeros(max(1, self.image_rows(image_id)), np.int32)
+        self._chk(self._L.msfm_image_words(self._h, int(image_id), _ip(out)))
+        return out[:self.image_rows(image_id)]
+
+    def retrieve_pairs(self, ids, num_nearest=50, score_matrix=False):
+        """-> (pairs P x 2 int32 (id1 > id2, brute mode's order), scores P float32[, n x n scores in the order of ids])."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        n = len(ids)
+        pairs = np.zeros((max(1, n * int(num_nearest)), 2), np.int32)
+        scores = np.zeros(len(pairs), np.float32)
+        mat = np.zeros((n, n), np.float32) if score_matrix else None
+        cnt = C.c_int()
+        self._chk(self._L.msfm_retrieve_pairs(self._h, _ip(ids), n, int(num_nearest), _ip(pairs), _fp(scores), C.byref(cnt),
+                                              _fp(mat) if mat is not None else None))
+        k = cnt.value
+        if score_matrix:
+            return pairs[:k].copy(), scores[:k].copy(), mat
+        return pairs[:k].copy(), scores[:k].copy()
+
+    def retrieval_profile(self):
+        p = RetrievalProfile()
+        self._chk(self._L.msfm_get_retrieval_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in RetrievalProfile._fields_}
 
     def match_pair(self, id1, id2, ratio=0.8, cross_check=True, max_distance=0.7):
         n1 = max(self.image_rows(id1), 1)

@@ -410,6 +410,8 @@ struct Image {
     float err_q8_max = 0.f;
     int h0_q8 = 0;
     float q8_level = 0.f;     // the context's twin level m (scale 255 / m) this twin was built with
+    // vocabulary retrieval (msfm_retrieval.hip.h): every value an integer in [0, 255] (q = x), every value in [0, 1] (q = rint(255 x))
+    bool ret_int = false, ret_unit = false;
     // keypoint coordinates (x, y) for the geometric verification; nk = -1: not uploaded
     float2* kxy = nullptr;
     int nk = -1;
@@ -677,6 +679,11 @@ struct msfm_ctx {
     std::vector<hipEvent_t> ev_pool;
     MatchJob* job = nullptr;          // the matching call in progress (one at a time; the streaming form keeps it between calls)
     bool series_open = false;         // a streaming series (msfm_match_pairs_begin .. _next) has sub-batches in flight: the store must not change
+    // vocabulary retrieval (msfm_retrieval_host.hip.h): the resident words q' = c - 128, padded with zero rows to a multiple of 64, and
+    // their constants; ret_v = 0: no vocabulary
+    DevBuf ret_words, ret_cn;
+    int ret_v = 0;
+    msfm_retrieval_profile ret_prof = {};
 };
 
 #define SC (*ctx->cur)

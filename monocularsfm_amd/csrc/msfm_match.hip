@@ -12,6 +12,7 @@
 #include "msfm_kernels.hip.h"
 #include "msfm_prefilter.hip.h"
 #include "msfm_verify.hip.h"
+#include "msfm_retrieval.hip.h"
 
 #include <sys/mman.h>
 
@@ -190,7 +191,7 @@ void msfm_destroy(msfm_ctx* ctx) {
     hc.lap("destroy: store");
     for (Scratch& sc : ctx->sc) sc.release_all();
     hc.lap("destroy: scratch sets");
-    DevBuf* bufs[] = {&ctx->d_jobs, &ctx->d_store_maxima, &ctx->d_zero_row};
+    DevBuf* bufs[] = {&ctx->d_jobs, &ctx->d_store_maxima, &ctx->d_zero_row, &ctx->ret_words, &ctx->ret_cn};
     for (DevBuf* b : bufs) b->release();
     for (OutSeg& s : ctx->out_segs) {
         s.qt.release();
@@ -708,6 +709,67 @@ int msfm_pair_from_id(int32_t pair_id, int* out_id1, int* out_id2) {
     if (!out_id1 || !out_id2 || pair_id < 0) return MSFM_E_INVALID;
     *out_id2 = pair_id % MSFM_MAX_IMAGES;
     *out_id1 = (pair_id - *out_id2) / MSFM_MAX_IMAGES;
+    return MSFM_OK;
+    MSFM_API_END
+}
+
+}  // extern "C"
+
+// ---- vocabulary retrieval (matching mode 2) ---------------------------------------------------------------------------------------
+#include "msfm_retrieval_host.hip.h"
+
+extern "C" {
+
+int msfm_train_vocabulary(msfm_ctx* ctx, const int32_t* ids, int n, const msfm_retrieval_params* params, uint8_t* out_words,
+                          int* out_num_words) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return ret_drained(ctx, train_impl(ctx, ids, n, params, out_words, out_num_words));
+    MSFM_API_END
+}
+
+int msfm_set_vocabulary(msfm_ctx* ctx, const uint8_t* words, int n_words) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (!words || n_words < 1 || n_words > kRetMaxWords) return fail(ctx, MSFM_E_INVALID, "msfm_set_vocabulary: bad vocabulary");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = ret_alloc_vocab(ctx, n_words);
+    if (rc != MSFM_OK) return ret_drained(ctx, rc);
+    std::vector<unsigned char> q((size_t)n_words * kDim);
+    for (size_t k = 0; k < q.size(); ++k) q[k] = words[k] ^ 0x80;   // c' = c - 128
+    HIPCHK(ctx, hipStreamSynchronize(store_stream(ctx)));
+    HIPCHK(ctx, hipMemcpy(ctx->ret_words.p, q.data(), q.size(), hipMemcpyHostToDevice));
+    ctx->ret_v = n_words;
+    rc = ret_norms(ctx);
+    if (rc != MSFM_OK) {
+        ctx->ret_v = 0;
+        return ret_drained(ctx, rc);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(store_stream(ctx)));
+    ctx->ret_prof.num_words = n_words;
+    return MSFM_OK;
+    MSFM_API_END
+}
+
+int msfm_image_words(msfm_ctx* ctx, int image_id, int32_t* out_word) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return ret_drained(ctx, image_words_impl(ctx, image_id, out_word));
+    MSFM_API_END
+}
+
+int msfm_retrieve_pairs(msfm_ctx* ctx, const int32_t* ids, int n, int num_nearest, int32_t* out_pairs, float* out_scores, int* out_n_pairs,
+                        float* out_score_matrix) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return ret_drained(ctx, retrieve_impl(ctx, ids, n, num_nearest, out_pairs, out_scores, out_n_pairs, out_score_matrix));
+    MSFM_API_END
+}
+
+int msfm_get_retrieval_profile(const msfm_ctx* ctx, msfm_retrieval_profile* out) {
+    MSFM_API_BEGIN(nullptr)
+    if (!ctx || !out) return MSFM_E_INVALID;
+    *out = ctx->ret_prof;
     return MSFM_OK;
     MSFM_API_END
 }

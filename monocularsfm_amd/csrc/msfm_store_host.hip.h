@@ -276,6 +276,8 @@ int finalize_store(msfm_ctx* ctx) {
         const unsigned* mx = ctx->h_store_maxima.as<unsigned>() + 16 * j;
         im.nrm_max = bits_to_float(mx[0]);
         im.abs_max = bits_to_float(mx[1]);
+        im.ret_int = mx[6] == 0;
+        im.ret_unit = mx[4] == 0;
         // A FLOAT upload whose every value is an integer in [0, 255] (raw OpenCV SIFT stored as CV_32F, the reference's
         // Database::WriteDescriptors format before RootSIFT) is the same store as a byte upload: every partial sum of (a - b)^2 stays
         // below 2^24, S is an exact integer under any accumulation order, the image rides the integer matrix cores.

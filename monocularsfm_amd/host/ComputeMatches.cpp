@@ -55,8 +55,9 @@ int main(int argc, char** argv) {
     fs.Get("SIFTmatch.distance_ratio", &distance_ratio);
     fs.Get("SIFTmatch.cross_check", &cross_check);
 
-    if (!(match_type == 0 || match_type == 1)) {  // assert(match_type == 0 || match_type == 1)
-        std::cerr << "ComputeMatches: SIFTmatch.match_type must be 0 (sequential) or 1 (brute)" << std::endl;
+    // (the reference asserts 0 or 1; 2 is the vocabulary mode its configuration reserves, implemented here)
+    if (!(match_type == 0 || match_type == 1 || match_type == 2)) {
+        std::cerr << "ComputeMatches: SIFTmatch.match_type must be 0 (sequential), 1 (brute) or 2 (vocabulary)" << std::endl;
         std::abort();
     }
 
@@ -69,6 +70,17 @@ int main(int argc, char** argv) {
             matcher.reset(new SequentialFeatureMatcher(database_path, 3, 10240, max_distance, distance_ratio, cross_check));
         else
             matcher.reset(new SequentialFeatureMatcher(database_path));
+    } else if (match_type == 2) {
+        // read only in mode 2: K, and the vocabulary's size and training iterations (0: the library's defaults)
+        int num_nearest_images = 50, vocab_num_words = 0, vocab_train_iters = 0;
+        fs.Get("SIFTmatch.num_nearest_images", &num_nearest_images);
+        fs.Get("SIFTmatch.vocab_num_words", &vocab_num_words);
+        fs.Get("SIFTmatch.vocab_train_iters", &vocab_train_iters);
+        if (use_yaml)
+            matcher.reset(new VocabularyTreeFeatureMatcher(database_path, num_nearest_images, vocab_num_words, vocab_train_iters, 100, 10240,
+                                                           max_distance, distance_ratio, cross_check));
+        else
+            matcher.reset(new VocabularyTreeFeatureMatcher(database_path, num_nearest_images, vocab_num_words, vocab_train_iters));
     } else {
         if (use_yaml)
             matcher.reset(new BruteFeatureMatcher(database_path, 100, true, 100, 4, 10240, max_distance, distance_ratio, cross_check));

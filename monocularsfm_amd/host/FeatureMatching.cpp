@@ -30,6 +30,7 @@
 #include "MatchEmission.h"
 #include "Pipeline.h"
 #include "Timer.h"
+#include "../csrc/msfm_retrieval.h"
 
 namespace MonocularSfM {
 
@@ -672,6 +673,45 @@ void BruteFeatureMatcher::RunMatching() {
         if (is_preemtive_) PreemptivelyFilterGroups(&groups);
         MatchImagePairGroups(groups);
     }
+    CloseDatabaseAndDevice();
+}
+
+void VocabularyTreeFeatureMatcher::RunMatching() {
+    OpenDatabaseAndDevice();
+    PreloadAllImages();
+    const std::vector<Database::Image> images = database_->ReadAllImages();
+    std::vector<std::vector<std::pair<image_t, image_t>>> groups;
+    if (images.size() >= 2) {
+        // image ids as brute mode forms them: 0 .. N-1
+        std::vector<int32_t> ids;
+        for (size_t i = 0; i < images.size(); ++i) {
+            if (!bulk_loaded_) EnsureResident((image_t)i);
+            ids.push_back((int32_t)i);
+        }
+        Timer timer;
+        timer.Start();
+        msfm_retrieval_params prm = {vocab_num_words_, vocab_train_iters_, 0};
+        int num_words = 0;
+        MSFM_CALL(ctx_, msfm_train_vocabulary(ctx_, ids.data(), (int)ids.size(), &prm, nullptr, &num_words));
+        const int k = std::min(num_nearest_images_, 1024);
+        std::vector<int32_t> flat(2 * ids.size() * (size_t)std::max(k, 1));
+        int n_pairs = 0;
+        MSFM_CALL(ctx_, msfm_retrieve_pairs(ctx_, ids.data(), (int)ids.size(), k, flat.data(), nullptr, &n_pairs, nullptr));
+        std::vector<std::pair<int, int>> pairs((size_t)n_pairs);
+        for (int t = 0; t < n_pairs; ++t) pairs[(size_t)t] = std::make_pair(flat[2 * (size_t)t], flat[2 * (size_t)t + 1]);
+        std::printf("Vocabulary retrieval: %zu images, %d words, %d nearest, %d pairs, %.3f s\n", ids.size(), num_words, k, n_pairs,
+                    timer.ElapsedSeconds());
+        std::fflush(stdout);
+        // brute mode's groups over the retrieved pairs: row i ascending, j < i ascending, a flush every max_pairs_size_ pairs and at
+        // the end of every row
+        size_t at = 0;
+        for (size_t end : msfm_ret_group_ends(pairs, max_pairs_size_)) {
+            std::vector<std::pair<image_t, image_t>> g;
+            for (; at < end; ++at) g.emplace_back((image_t)pairs[at].first, (image_t)pairs[at].second);
+            groups.push_back(std::move(g));
+        }
+    }
+    if (!groups.empty()) MatchImagePairGroups(groups);
     CloseDatabaseAndDevice();
 }
 

@@ -115,4 +115,27 @@ private:
     int preemtive_min_num_matches_;
 };
 
+// Matching mode 2 (SIFTmatch.match_type 2, which the reference reserves for "vocabulary tree match" and does not implement): a flat
+// visual vocabulary trained on the run's images picks, for every image, its num_nearest_images most similar images
+// (msfm_train_vocabulary / msfm_retrieve_pairs on the first device); the union of those pairs is matched in brute mode's orientation,
+// order and groups.  Retrieval replaces the pre-emptive filter, which is not applied.
+class VocabularyTreeFeatureMatcher : public FeatureMatcher {
+public:
+    VocabularyTreeFeatureMatcher(const std::string& database_path, const int& num_nearest_images = 50, const int& vocab_num_words = 0,
+                                 const int& vocab_train_iters = 0, const int& max_pairs_size = 100, const int& max_num_matches = 10240,
+                                 const double& max_distance = 0.7, const double& distance_ratio = 0.8, const bool& cross_check = true)
+        : FeatureMatcher(database_path, max_num_matches, max_distance, distance_ratio, cross_check),
+          num_nearest_images_(num_nearest_images),
+          vocab_num_words_(vocab_num_words),
+          vocab_train_iters_(vocab_train_iters),
+          max_pairs_size_(max_pairs_size) {}
+    void RunMatching() override;
+
+private:
+    int num_nearest_images_;
+    int vocab_num_words_;     // 0: the library's default (16384)
+    int vocab_train_iters_;   // 0: the library's default (8)
+    int max_pairs_size_;
+};
+
 }  // namespace MonocularSfM

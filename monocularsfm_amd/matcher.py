@@ -197,3 +197,37 @@ class BruteFeatureMatcher(FeatureMatcher):
                                           max_distance=float("inf"), fetch=False)
         counts = np.diff(offs)
         return [p for p, c in zip(image_pairs, counts) if c >= self.preemtive_min_num_matches_]
+
+
+class VocabularyTreeFeatureMatcher(FeatureMatcher):
+    """Matching mode 2 (the reference reserves it for "vocabulary tree match"): a flat vocabulary trained on the run's images picks each
+    image's num_nearest_images most similar images (Context.train_vocabulary / retrieve_pairs); the union of those pairs is matched in
+    brute mode's orientation, order and groups (a flush every max_pairs_size pairs and at the end of each row).  No pre-emptive filter."""
+
+    def __init__(self, database_path, num_nearest_images=50, vocab_num_words=0, vocab_train_iters=0, max_pairs_size=100, **kw):
+        super().__init__(database_path, **kw)
+        self.num_nearest_images_ = num_nearest_images
+        self.vocab_num_words_ = vocab_num_words
+        self.vocab_train_iters_ = vocab_train_iters
+        self.max_pairs_size_ = max_pairs_size
+
+    def RunMatching(self):
+        self.database_ = Database(self.database_path_)
+        n = len(self.database_.ReadAllImages())
+        if n >= 2:
+            ids = list(range(n))
+            for i in ids:
+                self._ensure_resident(i)
+            t0 = time.perf_counter()
+            words = self.ctx.train_vocabulary(ids, num_words=self.vocab_num_words_, train_iters=self.vocab_train_iters_)
+            k = min(int(self.num_nearest_images_), 1024)
+            pairs, _ = self.ctx.retrieve_pairs(ids, k)
+            self._out("Vocabulary retrieval: %d images, %d words, %d nearest, %d pairs, %.3f s\n"
+                      % (n, len(words), k, len(pairs), time.perf_counter() - t0))
+            group = []
+            for t, (i, j) in enumerate(pairs.tolist()):
+                group.append((i, j))
+                if len(group) == self.max_pairs_size_ or t + 1 == len(pairs) or pairs[t + 1][0] != i:
+                    self.MatchImagePairs(group)
+                    group = []
+        self.database_.Close()
