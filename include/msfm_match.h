@@ -287,6 +287,24 @@ typedef struct msfm_verify_params {
     unsigned long long seed;     /* sampling stream, the same for every pair */
 } msfm_verify_params;
 int msfm_upload_keypoints(msfm_ctx* ctx, int image_id, const float* kpts, int n, int stride_floats);
+
+/* ---- verification model --------------------------------------------------------------------
+ * MSFM_VERIFY_FUNDAMENTAL (the default) is FeatureUtils::FilterMatches as above.  MSFM_VERIFY_ESSENTIAL verifies with the camera
+ * instead (the reference's TODO at src/Feature/FeatureMatching.cpp:59; its reconstruction runs cv::findEssentialMat on the same
+ * camera): 5-point essential-matrix RANSAC on normalised, undistorted coordinates, Sampson error <= (threshold / ((fx + fy) / 2))^2,
+ * the same adaptive stopping rule with sample size 5, no refit; < 5 matches or a consensus below 5 keeps none.  Bit-identical to the
+ * host twin EssentialRansacMask (csrc/msfm_emat.h).  One camera for every image; per context; honoured by msfm_match_pairs_verified
+ * and msfm_match_pairs_begin(.., geometric_verification = 1, ..).  MSFM_E_INVALID: unknown model, NULL camera for model 1,
+ * fx / fy <= 0 or any parameter non-finite; MSFM_E_STATE while a streaming series is open.
+ * msfm_get_verification_stats: hypotheses solved and rounds of kVeRound = 32 hypotheses run (the largest over the pairs) by the
+ * last verified call / series under model 1 (0 under model 0). */
+#define MSFM_VERIFY_FUNDAMENTAL 0
+#define MSFM_VERIFY_ESSENTIAL 1
+typedef struct msfm_camera {
+    double fx, fy, cx, cy, k1, k2, p1, p2;
+} msfm_camera;
+int msfm_set_verification_model(msfm_ctx* ctx, int model, const msfm_camera* camera);
+int msfm_get_verification_stats(const msfm_ctx* ctx, int64_t* hypotheses_solved, int* rounds);
 int msfm_match_pairs_verified(msfm_ctx* ctx, const int32_t* pairs, int n_pairs,
                               const msfm_match_params* params, const msfm_verify_params* verify,
                               int64_t* out_offsets);

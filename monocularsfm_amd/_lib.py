@@ -28,11 +28,17 @@ EXPORTS = [
     "msfm_fetch_order_certificate", "msfm_set_pipeline", "msfm_device_count", "msfm_finalize_store", "msfm_store_info",
     "msfm_match_pairs_begin", "msfm_match_pairs_next", "msfm_read_device", "msfm_memory_info", "msfm_match_pairs_end",
     "msfm_train_vocabulary", "msfm_set_vocabulary", "msfm_image_words", "msfm_retrieve_pairs", "msfm_get_retrieval_profile",
+    "msfm_set_verification_model", "msfm_get_verification_stats",
 ]
+VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL = 0, 1
 
 
 class MatchParams(C.Structure):
     _fields_ = [("ratio", C.c_float), ("cross_check", C.c_int), ("max_distance", C.c_double)]
+
+
+class Camera(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")]
 
 
 class VerifyParams(C.Structure):
@@ -148,6 +154,8 @@ def load():
         L.msfm_get_retrieval_profile.argtypes = [vp, C.POINTER(RetrievalProfile)]
     except AttributeError:
         pass
+    L.msfm_set_verification_model.argtypes = [vp, C.c_int, C.POINTER(Camera)]
+    L.msfm_get_verification_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if the library lacks a declared symbol
     _lib = L
@@ -437,6 +445,23 @@ class Context:
         d = np.empty(max(M, 1), np.float32)
         self._chk(self._L.msfm_fetch_matches(self._h, _ip(qt), _fp(d)))
         return offs, qt[:M], d[:M]
+
+    def set_verification_model(self, model, camera=None):
+        """Model of the geometric verification of match_pairs_verified and the verified streaming form: VERIFY_FUNDAMENTAL (0,
+        the default: FeatureUtils::FilterMatches) or VERIFY_ESSENTIAL (1: 5-point essential-matrix RANSAC with `camera`, a dict
+        or sequence fx, fy, cx, cy[, k1, k2, p1, p2] -- missing distortion coefficients are 0)."""
+        cam = None
+        if camera is not None:
+            keys = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")
+            vals = [camera.get(k, 0.0) for k in keys] if isinstance(camera, dict) else list(camera) + [0.0] * (8 - len(camera))
+            cam = Camera(*[float(v) for v in vals[:8]])
+        self._chk(self._L.msfm_set_verification_model(self._h, int(model), C.byref(cam) if cam is not None else None))
+
+    def verification_stats(self):
+        """(hypotheses solved, rounds run) of the last verified call / series under VERIFY_ESSENTIAL."""
+        solved, rounds = C.c_int64(), C.c_int()
+        self._chk(self._L.msfm_get_verification_stats(self._h, C.byref(solved), C.byref(rounds)))
+        return int(solved.value), int(rounds.value)
 
     def knn2_pair(self, id1, id2):
         n1, n2 = self.image_rows(id1), self.image_rows(id2)

@@ -580,6 +580,8 @@ struct Scratch {
     // geometric verification
     DevBuf d_vf_pairs, d_vf_x1, d_vf_y1, d_vf_x2, d_vf_y2, d_vf_hyp, d_vf_best_it, d_vf_best_count, d_vf_flags,
         d_st2_qt, d_st2_d, d_counts2;
+    // calibrated verification (msfm_verify_e.hip.h): normalised coordinates of the staged matches (fp64), per-pair state, counters
+    DevBuf d_ve_x1, d_ve_y1, d_ve_x2, d_ve_y2, d_ve_state, d_ve_stats;
     msfm_profile prof = {};           // this sub-batch's share; joins the call's profile when the sub-batch is accepted
     hipEvent_t sweep1_done = nullptr; // recorded behind sweep 1: the other stream's next sweep 1 waits for it
     bool sweep1_recorded = false;
@@ -593,7 +595,7 @@ struct Scratch {
                           &d_vpairs, &d_vpf, &d_vitems, &d_lists, &d_colmask, &d_gtot, &d_grow0, &d_cnt, &d_mrow, &d_summary, &d_overflow,
                           &d_totals, &d_vf_pairs,
                           &d_vf_x1, &d_vf_y1, &d_vf_x2, &d_vf_y2, &d_vf_hyp, &d_vf_best_it, &d_vf_best_count, &d_vf_flags, &d_st2_qt,
-                          &d_st2_d, &d_counts2, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
+                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_ve_state, &d_ve_stats, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
         for (DevBuf* b : bufs) fn(*b, arg);
     }
     long long device_bytes() {
@@ -684,6 +686,11 @@ struct msfm_ctx {
     DevBuf ret_words, ret_cn;
     int ret_v = 0;
     msfm_retrieval_profile ret_prof = {};
+    // geometric verification model (msfm_set_verification_model): 0 fundamental matrix, 1 essential matrix with `camera`
+    int verify_model = MSFM_VERIFY_FUNDAMENTAL;
+    msfm_emat::Camera camera = {};
+    long long ve_solved = 0;          // of the last verified call / series: hypotheses solved, rounds run (model 1)
+    int ve_rounds = 0;
 };
 
 #define SC (*ctx->cur)

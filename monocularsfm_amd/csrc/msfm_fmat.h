@@ -327,17 +327,30 @@ MSFM_FHD double det_log(double x) {
     return 2.0 * sum + (double)e * 0.6931471805599453;
 }
 
-template <typename CountFn>
-MSFM_FHD int replay_adaptive(int n, int max_iters, double confidence, CountFn count_at, int* best_count_out) {
+// kSample is the minimal sample size (8 here, 5 for the essential matrix, msfm_emat.h): need = log(1 - conf) / log(1 - w^kSample),
+// and a winner needs >= kSample inliers.  avail: the loop may only read counts [0, avail) -- the staged device form scores
+// hypotheses round by round; *decided (if given) is false when the loop needed a count beyond avail (the result is then not final).
+template <int kSample = 8, typename CountFn>
+MSFM_FHD int replay_adaptive(int n, int max_iters, double confidence, CountFn count_at, int* best_count_out,
+                             int avail = 0x7fffffff, bool* decided = nullptr) {
+    static_assert(kSample == 8 || kSample == 5, "sample sizes of the F and E solvers");
     int best = 0, best_it = -1, iters = max_iters;
+    if (decided) *decided = true;
     for (int it = 0; it < iters; ++it) {
+        if (it >= avail) {
+            if (decided) *decided = false;
+            break;
+        }
         const int c = count_at(it);
         if (c > best) {
             best = c;
             best_it = it;
             const double w = (double)c / n;
-            const double w2 = w * w, w4 = w2 * w2, w8 = w4 * w4;
-            double q = 1.0 - w8;
+            const double w2 = w * w, w4 = w2 * w2;
+            double wk;
+            if constexpr (kSample == 8) wk = w4 * w4;
+            else wk = w4 * w;
+            double q = 1.0 - wk;
             if (q < 1e-300) q = 1e-300;
             const double need = det_log(1.0 - confidence) / det_log(q);
             if (need > 0.0 && need < (double)iters) {  // q == 1 (tiny consensus) gives -inf / NaN: no bound
@@ -348,7 +361,7 @@ MSFM_FHD int replay_adaptive(int n, int max_iters, double confidence, CountFn co
         }
     }
     *best_count_out = best;
-    return best >= 8 ? best_it : -1;
+    return best >= kSample ? best_it : -1;
 }
 
 }  // namespace msfm_fmat

@@ -53,6 +53,8 @@ struct MatchJob {
         if (vp) {
             verify_store = *vp;
             verify = &verify_store;
+            c->ve_solved = 0;
+            c->ve_rounds = 0;
         }
         for (SubBatch& w : sb) w = SubBatch{};
         next_begin = 0;
@@ -244,7 +246,13 @@ struct MatchJob {
         const int* d_counts = SC.d_counts.as<int>();
         const int2* d_st_qt = SC.d_st_qt.as<int2>();
         const float* d_st_d = SC.d_st_d.as<float>();
-        if (verify) {
+        if (verify && ctx->verify_model == MSFM_VERIFY_ESSENTIAL) {
+            rc = issue_essential(b, begin, oe, ev_base);
+            if (rc != MSFM_OK) return rc;
+            d_counts = SC.d_counts2.as<int>();
+            d_st_qt = SC.d_st2_qt.as<int2>();
+            d_st_d = SC.d_st2_d.as<float>();
+        } else if (verify) {
             // FeatureUtils::FilterMatches on the staged lists: all hypotheses of all pairs at once
             VerifyParams vprm = {verify->threshold * verify->threshold, verify->confidence, verify->max_iters, 0, verify->seed};
             std::vector<VerifyPair>& vpairs = b.verify_pairs;   // (lives as long as the sub-batch: the copy below may still be in flight)
@@ -302,6 +310,69 @@ struct MatchJob {
         rc = queue_tail_copies(ctx, P);
         if (rc != MSFM_OK) return rc;
         w.active = true;
+        return MSFM_OK;
+    }
+
+    // the calibrated verification (msfm_verify_e.hip.h), staged: the rounds are launched back to back (no host wait); an undecided
+    // pair's round kernel returns at once when ve_decide_kernel has marked it.  The lists go to the second staging buffer.
+    int issue_essential(Batch& b, int begin, long long oe, size_t ev_base) {
+        const size_t P = b.pairs.size();
+        const double f = (ctx->camera.fx + ctx->camera.fy) * 0.5, tn = verify->threshold / f;
+        VerifyEParams eprm = {tn * tn, verify->confidence, verify->max_iters, 0, verify->seed};
+        std::vector<VerifyPair>& vpairs = b.verify_pairs;   // (lives as long as the sub-batch: the copy below may still be in flight)
+        vpairs.resize(P);
+        for (size_t p = 0; p < P; ++p)
+            vpairs[p] = VerifyPair{ctx->images[pairs[2 * (begin + (int)p)]].kxy, ctx->images[pairs[2 * (begin + (int)p) + 1]].kxy};
+        HIPCHK(ctx, SC.d_vf_pairs.ensure(P * sizeof(VerifyPair)));
+        HIPCHK(ctx, SC.d_ve_x1.ensure(oe * 8));
+        HIPCHK(ctx, SC.d_ve_y1.ensure(oe * 8));
+        HIPCHK(ctx, SC.d_ve_x2.ensure(oe * 8));
+        HIPCHK(ctx, SC.d_ve_y2.ensure(oe * 8));
+        HIPCHK(ctx, SC.d_vf_hyp.ensure(P * (size_t)eprm.max_iters * 4));
+        HIPCHK(ctx, SC.d_vf_best_it.ensure(P * 4));
+        HIPCHK(ctx, SC.d_vf_best_count.ensure(P * 4));
+        HIPCHK(ctx, SC.d_ve_state.ensure((3 * P + 2) * 4));   // state[P] | two pair lists [P] | their two counts
+        HIPCHK(ctx, SC.d_ve_stats.ensure(sizeof(VerifyEStats)));
+        HIPCHK(ctx, SC.d_st2_qt.ensure(oe * sizeof(int2)));
+        HIPCHK(ctx, SC.d_st2_d.ensure(oe * 4));
+        HIPCHK(ctx, SC.d_counts2.ensure(P * 4));
+        HIPCHK(ctx, hipMemcpyAsync(SC.d_vf_pairs.p, vpairs.data(), P * sizeof(VerifyPair), hipMemcpyHostToDevice, SC.stream));
+        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_state.p, 0, (3 * P + 2) * 4, SC.stream));
+        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_stats.p, 0, sizeof(VerifyEStats), SC.stream));
+        hipEvent_t v0 = get_event(ctx, ev_base + 6), v1 = get_event(ctx, ev_base + 7);
+        if (!v0 || !v1) return fail(ctx, MSFM_E_DEVICE, "hipEventCreate failed");
+        HIPCHK(ctx, hipEventRecord(v0, SC.stream));
+        const PairDesc* dp = SC.d_pairs.as<PairDesc>();
+        const int* d_counts = SC.d_counts.as<int>();
+        double *x1 = SC.d_ve_x1.as<double>(), *y1 = SC.d_ve_y1.as<double>(), *x2 = SC.d_ve_x2.as<double>(), *y2 = SC.d_ve_y2.as<double>();
+        hipLaunchKernelGGL(ve_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, SC.d_vf_pairs.as<VerifyPair>(), d_counts,
+                           (const int2*)SC.d_st_qt.as<int2>(), ctx->camera, x1, y1, x2, y2);
+        HIPCHK(ctx, hipGetLastError());
+        VerifyEStats* stats = SC.d_ve_stats.as<VerifyEStats>();
+        int* state = SC.d_ve_state.as<int>();
+        int* list = state + P;
+        const int rounds = (eprm.max_iters + kVeRound - 1) / kVeRound;
+        const unsigned grid = (unsigned)std::min<size_t>(P, (size_t)kVeGroupsPerCU * (size_t)std::max(1, ctx->cu_count));
+        for (int r = -1; r < rounds; ++r) {
+            if (r >= 0) {
+                eprm.round = r;
+                hipLaunchKernelGGL(ve_round_kernel, dim3(grid), dim3(kVeRound), 0, SC.stream, dp, d_counts, (const double*)x1,
+                                   (const double*)y1, (const double*)x2, (const double*)y2, list, (int)P, SC.d_vf_hyp.as<int>(), eprm,
+                                   stats);
+                HIPCHK(ctx, hipGetLastError());
+            }
+            eprm.round = r;
+            hipLaunchKernelGGL(ve_decide_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts,
+                               (const int*)SC.d_vf_hyp.as<int>(), (int)P, eprm, state, list, SC.d_vf_best_it.as<int>(),
+                               SC.d_vf_best_count.as<int>(), stats);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(ve_mask_compact_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts,
+                           (const int2*)SC.d_st_qt.as<int2>(), (const float*)SC.d_st_d.as<float>(), (const double*)x1, (const double*)y1,
+                           (const double*)x2, (const double*)y2, (const int*)SC.d_vf_best_it.as<int>(), eprm, SC.d_st2_qt.as<int2>(),
+                           SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(v1, SC.stream));
         return MSFM_OK;
     }
 
@@ -391,6 +462,13 @@ struct MatchJob {
             float vms = 0.f;
             HIPCHK(ctx, hipEventElapsedTime(&vms, ctx->ev_pool[w.ev_base + 6], ctx->ev_pool[w.ev_base + 7]));
             SC.prof.verify_ms += vms;
+            if (ctx->verify_model == MSFM_VERIFY_ESSENTIAL) {   // (the stream has been synchronised above)
+                VerifyEStats st = {};
+                HIPCHK(ctx, hipMemcpyAsync(&st, SC.d_ve_stats.p, sizeof(st), hipMemcpyDeviceToHost, SC.stream));
+                HIPCHK(ctx, hipStreamSynchronize(SC.stream));   // (on this set's stream: the other sets' sub-batches stay in flight)
+                ctx->ve_solved += (long long)st.solved;
+                ctx->ve_rounds = std::max(ctx->ve_rounds, st.rounds);
+            }
         }
         SC.prof.sub_batches += 1;
         add_profile(ctx->prof, SC.prof);

@@ -12,6 +12,7 @@
 #include "msfm_kernels.hip.h"
 #include "msfm_prefilter.hip.h"
 #include "msfm_verify.hip.h"
+#include "msfm_verify_e.hip.h"
 #include "msfm_retrieval.hip.h"
 
 #include <sys/mman.h>
@@ -399,6 +400,36 @@ int msfm_match_pairs_verified(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, 
     if (!(v.threshold >= 0.0) || !(v.confidence > 0.0) || !(v.confidence < 1.0) || v.max_iters < 1 || v.max_iters > (1 << 16))
         return fail(ctx, MSFM_E_INVALID, "bad verification parameters");
     return drained(ctx, match_pairs_impl(ctx, pairs, n_pairs, params, &v, out_offsets));
+    MSFM_API_END
+}
+
+int msfm_set_verification_model(msfm_ctx* ctx, int model, const msfm_camera* camera) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "a streaming series is open");
+    if (model == MSFM_VERIFY_FUNDAMENTAL) {
+        ctx->verify_model = model;
+        return MSFM_OK;
+    }
+    if (model != MSFM_VERIFY_ESSENTIAL) return fail(ctx, MSFM_E_INVALID, "unknown verification model");
+    if (!camera) return fail(ctx, MSFM_E_INVALID, "the essential-matrix model needs a camera");
+    const msfm_camera c = *camera;
+    const double all[8] = {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+    for (double v : all)
+        if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, "camera parameters must be finite");
+    if (!(c.fx > 0.0) || !(c.fy > 0.0)) return fail(ctx, MSFM_E_INVALID, "fx and fy must be positive");
+    ctx->verify_model = model;
+    ctx->camera = msfm_emat::Camera{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+    return MSFM_OK;
+    MSFM_API_END
+}
+
+int msfm_get_verification_stats(const msfm_ctx* ctx, int64_t* hypotheses_solved, int* rounds) {
+    MSFM_API_BEGIN(nullptr)
+    if (!ctx) return MSFM_E_INVALID;
+    if (hypotheses_solved) *hypotheses_solved = ctx->ve_solved;
+    if (rounds) *rounds = ctx->ve_rounds;
+    return MSFM_OK;
     MSFM_API_END
 }
 

@@ -8,6 +8,7 @@
 // into using the YAML values instead.
 #include <cassert>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -15,6 +16,7 @@
 #include <string>
 
 #include "FeatureMatching.h"
+#include "GeometricVerification.h"
 #include "Timer.h"
 #include "YamlConfig.h"
 
@@ -61,6 +63,38 @@ int main(int argc, char** argv) {
         std::abort();
     }
 
+    // SIFTmatch.verification_model : 0 (default: the reference's F-matrix check) | 1 (essential matrix with the camera of
+    // Reconstruction.Camera.*, the keys the reference's reconstruction reads from the same file; distortion defaults to 0)
+    int verification_model = 0;
+    fs.Get("SIFTmatch.verification_model", &verification_model);
+    if (!(verification_model == 0 || verification_model == 1)) {
+        std::cerr << "ComputeMatches: SIFTmatch.verification_model must be 0 (fundamental matrix) or 1 (essential matrix)" << std::endl;
+        return EXIT_FAILURE;
+    }
+    CameraIntrinsics camera = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (verification_model == 1) {
+        for (const char* k : {"fx", "fy", "cx", "cy"})
+            if (!fs.Has(std::string("Reconstruction.Camera.") + k)) {
+                std::cerr << "ComputeMatches: SIFTmatch.verification_model : 1 needs Reconstruction.Camera." << k << std::endl;
+                return EXIT_FAILURE;
+            }
+        fs.Get("Reconstruction.Camera.fx", &camera.fx);
+        fs.Get("Reconstruction.Camera.fy", &camera.fy);
+        fs.Get("Reconstruction.Camera.cx", &camera.cx);
+        fs.Get("Reconstruction.Camera.cy", &camera.cy);
+        fs.Get("Reconstruction.Camera.k1", &camera.k1);
+        fs.Get("Reconstruction.Camera.k2", &camera.k2);
+        fs.Get("Reconstruction.Camera.p1", &camera.p1);
+        fs.Get("Reconstruction.Camera.p2", &camera.p2);
+        const double all[8] = {camera.fx, camera.fy, camera.cx, camera.cy, camera.k1, camera.k2, camera.p1, camera.p2};
+        bool ok = camera.fx > 0 && camera.fy > 0;
+        for (double v : all) ok = ok && std::isfinite(v);
+        if (!ok) {
+            std::cerr << "ComputeMatches: Reconstruction.Camera.* must be finite, with fx, fy > 0" << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     const char* honour = std::getenv("MSFM_HONOUR_YAML_MATCH_PARAMS");
     const bool use_yaml = honour && honour[0] == '1';
 
@@ -87,6 +121,8 @@ int main(int argc, char** argv) {
         else
             matcher.reset(new BruteFeatureMatcher(database_path));
     }
+
+    if (verification_model == 1) matcher->SetEssentialVerification(camera);
 
     Timer timer;
     timer.Start();

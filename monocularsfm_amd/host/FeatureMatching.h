@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "Database.h"
+#include "GeometricVerification.h"
 #include "Types.h"
 #include "msfm_match.h"
 
@@ -38,6 +39,12 @@ public:
     // on the device by default (msfm_match_pairs_verified), by the host twin with MSFM_GEOMETRIC_VERIFICATION=host
     // (GeometricVerification.h; the two give identical lists).
     void SetGeometricVerification(bool on) { geometric_verification_ = on; }
+    // SIFTmatch.verification_model : 1 -- the essential matrix with the reference's camera instead of F, on every device
+    // context (msfm_set_verification_model) or in the host twin (FilterMatchesEssential).  Call before RunMatching.
+    void SetEssentialVerification(const CameraIntrinsics& camera) {
+        essential_ = true;
+        camera_ = camera;
+    }
 
 protected:
     void OpenDatabaseAndDevice();
@@ -56,6 +63,8 @@ protected:
     bool cross_check_;
     bool geometric_verification_ = true;
     bool verification_on_host_ = false;  // MSFM_GEOMETRIC_VERIFICATION=host
+    bool essential_ = false;             // SetEssentialVerification
+    CameraIntrinsics camera_ = {};
     Database* database_ = nullptr;
     // One context per GPU: MSFM_DEVICE (default 0), MSFM_DEVICES="0,1,..." or "all".  The whole descriptor store is replicated on
     // each; the pairs of a run are dealt to the devices in small cost-balanced blocks, round-robin, so that every device's results

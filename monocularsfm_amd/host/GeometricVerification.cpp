@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "../csrc/msfm_emat.h"
 #include "../csrc/msfm_fmat.h"
 
 namespace MonocularSfM {
@@ -69,6 +70,66 @@ std::vector<unsigned char> FundamentalRansacMask(const std::vector<Point2f>& pts
     return best;
 }
 
+// A literal sequential loop: hypothesis it is solved and scored when the loop reaches it; its count is the largest over its
+// solutions.  The winning solution (the lowest index among equal counts) gives the mask.
+std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                               const CameraIntrinsics& camera, double threshold, double confidence,
+                                               int max_iters, unsigned long long seed) {
+    using namespace msfm_emat;
+    const int n = (int)pts1.size();
+    if (n < 5) return {};
+    const Camera cam{camera.fx, camera.fy, camera.cx, camera.cy, camera.k1, camera.k2, camera.p1, camera.p2};
+    std::vector<double> x1((size_t)n), y1((size_t)n), x2((size_t)n), y2((size_t)n);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        undistort(cam, (double)pts1[i].x, (double)pts1[i].y, &x1[i], &y1[i]);
+        undistort(cam, (double)pts2[i].x, (double)pts2[i].y, &x2[i], &y2[i]);
+    }
+    const double f = (camera.fx + camera.fy) * 0.5, t = threshold / f, thr2 = t * t;
+    std::vector<double> ws((size_t)kWork);
+    // best solution of hypothesis it: (count, solution index); the solutions stay in ws
+    auto score = [&](int it, int* sol) {
+        const int ns = hypothesis<1>(x1.data(), y1.data(), x2.data(), y2.data(), n, seed, it, ws.data());
+        int best = 0, bs = -1;
+        for (int s = 0; s < ns; ++s) {
+            const double* E = ws.data() + kWsSol + 9 * s;
+            int c = 0;
+            for (int i = 0; i < n; ++i) c += sampson(E, x1[(size_t)i], y1[(size_t)i], x2[(size_t)i], y2[(size_t)i]) <= thr2 ? 1 : 0;
+            if (bs < 0 || c > best) {
+                best = c;
+                bs = s;
+            }
+        }
+        *sol = bs;
+        return best;
+    };
+    int best_count = 0, best_it = -1, iters = max_iters;
+    for (int it = 0; it < iters; ++it) {
+        int sol;
+        const int c = score(it, &sol);
+        if (c > best_count) {
+            best_count = c;
+            best_it = it;
+            const double w = (double)c / n;
+            const double w2 = w * w, w4 = w2 * w2;
+            double q = 1.0 - w4 * w;
+            if (q < 1e-300) q = 1e-300;
+            const double need = msfm_fmat::det_log(1.0 - confidence) / msfm_fmat::det_log(q);
+            if (need > 0.0 && need < (double)iters) {
+                int ni = (int)need;
+                if ((double)ni < need) ni += 1;
+                iters = ni > it + 1 ? ni : it + 1;
+            }
+        }
+    }
+    if (best_count < 5 || best_it < 0) return {};
+    int sol;
+    score(best_it, &sol);
+    std::vector<unsigned char> mask((size_t)n, 0);
+    const double* E = ws.data() + kWsSol + 9 * sol;
+    for (int i = 0; i < n; ++i) mask[(size_t)i] = sampson(E, x1[(size_t)i], y1[(size_t)i], x2[(size_t)i], y2[(size_t)i]) <= thr2 ? 1 : 0;
+    return mask;
+}
+
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
                    const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches) {
     if (kpts1.empty() || matches.empty()) return;  // FeatureUtils.cpp:181-184
@@ -80,6 +141,22 @@ void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoin
         b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
     }
     const std::vector<unsigned char> mask = FundamentalRansacMask(a, b, 3.0, 0.99);
+    for (size_t i = 0; i < mask.size(); ++i)
+        if (mask[i]) prune_matches->push_back(matches[i]);
+}
+
+void FilterMatchesEssential(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
+                            const std::vector<DMatch>& matches, const CameraIntrinsics& camera,
+                            std::vector<DMatch>* prune_matches) {
+    if (kpts1.empty() || matches.empty()) return;
+    std::vector<Point2f> a, b;
+    a.reserve(matches.size());
+    b.reserve(matches.size());
+    for (const DMatch& m : matches) {
+        a.push_back(Point2f{kpts1[(size_t)m.queryIdx].x, kpts1[(size_t)m.queryIdx].y});
+        b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
+    }
+    const std::vector<unsigned char> mask = EssentialRansacMask(a, b, camera, 3.0, 0.99);
     for (size_t i = 0; i < mask.size(); ++i)
         if (mask[i]) prune_matches->push_back(matches[i]);
 }

@@ -23,8 +23,26 @@ std::vector<unsigned char> FundamentalRansacMask(const std::vector<Point2f>& pts
                                                  double threshold = 3.0, double confidence = 0.99,
                                                  int max_iters = 1000, unsigned long long seed = 0x5eed5eedULL);
 
+struct CameraIntrinsics {   // pinhole + Brown distortion (the reference's Reconstruction.Camera.* keys)
+    double fx, fy, cx, cy, k1, k2, p1, p2;
+};
+
+// The calibrated alternative (msfm_emat.h): RANSAC over 5-point essential matrices in normalised coordinates, Sampson
+// error <= (threshold / ((fx + fy) / 2))^2, the replayed adaptive stopping rule with sample size 5, no refit.
+// < 5 points or a best consensus below 5 -> empty mask (the caller keeps nothing); otherwise a mask of n entries.
+// Host twin of the staged device RANSAC (csrc/msfm_verify_e.hip.h): the same bits.
+std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                               const CameraIntrinsics& camera, double threshold = 3.0,
+                                               double confidence = 0.99, int max_iters = 1000,
+                                               unsigned long long seed = 0x5eed5eedULL);
+
 // FeatureUtils::GetAlignedPointsFromMatches + FilterMatches
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
                    const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches);
+
+// The same hand-off with EssentialRansacMask (SIFTmatch.verification_model : 1) and the reference's constants
+void FilterMatchesEssential(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
+                            const std::vector<DMatch>& matches, const CameraIntrinsics& camera,
+                            std::vector<DMatch>* prune_matches);
 
 }  // namespace MonocularSfM

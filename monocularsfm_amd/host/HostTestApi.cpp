@@ -1,4 +1,4 @@
-// HostTestApi.cpp -- C-linkage shims over the host-only pieces (YAML reader, Database, F-RANSAC)
+// HostTestApi.cpp -- C-linkage shims over the host-only pieces (YAML reader, Database, F- and E-RANSAC)
 // so that the CPU test-suite can exercise them through ctypes without a GPU.
 #include <cstring>
 #include <string>
@@ -8,6 +8,7 @@
 #include "GeometricVerification.h"
 #include "MatchEmission.h"
 #include "YamlConfig.h"
+#include "../csrc/msfm_emat.h"
 #include "../csrc/msfm_fmat.h"
 
 using namespace MonocularSfM;
@@ -267,6 +268,80 @@ void host_fmat_counts(const float* x1, const float* y1, const float* x2, const f
             for (int i = 0; i < n; ++i) c += msfm_fmat::epipolar_error(F, x1[i], y1[i], x2[i], y2[i]) <= thr2 ? 1 : 0;
         out_counts[it] = c;
     }
+}
+
+// ---- the pieces of msfm_emat.h (tests/test_emat_reference.py compares them with tests/emat_ref.py) -------------------------
+// cam: fx fy cx cy k1 k2 p1 p2
+void host_emat_undistort(const double* cam, const double* uv, int n, double* xy) {
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    for (int i = 0; i < n; ++i) msfm_emat::undistort(c, uv[2 * i], uv[2 * i + 1], &xy[2 * i], &xy[2 * i + 1]);
+}
+
+void host_emat_sample5(unsigned long long seed, int it, int n, int* idx) { msfm_emat::sample5(seed, it, n, idx); }
+
+// q1, q2: 5 x 2 normalised points; E: room for 10 x 9; roots: room for 10.  Returns the number of solutions.
+int host_emat_five_point(const double* q1, const double* q2, double* E, double* roots) {
+    double ws[msfm_emat::kWork];
+    double a[5], b[5], c[5], d[5];
+    for (int k = 0; k < 5; ++k) {
+        a[k] = q1[2 * k];
+        b[k] = q1[2 * k + 1];
+        c[k] = q2[2 * k];
+        d[k] = q2[2 * k + 1];
+    }
+    const int ns = msfm_emat::five_point<1>(a, b, c, d, ws);
+    for (int s = 0; s < ns; ++s) {
+        for (int k = 0; k < 9; ++k) E[9 * s + k] = ws[msfm_emat::kWsSol + 9 * s + k];
+        roots[s] = ws[msfm_emat::kWsRoots + s];
+    }
+    return ns;
+}
+
+double host_emat_sampson(const double* E, double x1, double y1, double x2, double y2) {
+    return msfm_emat::sampson(E, x1, y1, x2, y2);
+}
+
+// replay_adaptive<5> over counts [0, avail); *decided = 0 when it needed more
+int host_emat_replay(const int* counts, int avail, int n, int max_iters, double confidence, int* best_count, int* decided) {
+    bool dec = true;
+    const int r = msfm_fmat::replay_adaptive<5>(n, max_iters, confidence, [&](int it) { return counts[it]; }, best_count, avail, &dec);
+    *decided = dec ? 1 : 0;
+    return r;
+}
+
+// count of every hypothesis 0 .. max_iters-1 (largest over its solutions) and the solution that reaches it (-1: none);
+// x1..y2 normalised
+void host_emat_counts(const double* x1, const double* y1, const double* x2, const double* y2, int n, unsigned long long seed,
+                      int max_iters, double thr2, int* out_counts, int* out_sol) {
+    std::vector<double> ws((size_t)msfm_emat::kWork);
+    for (int it = 0; it < max_iters; ++it) {
+        const int ns = msfm_emat::hypothesis<1>(x1, y1, x2, y2, n, seed, it, ws.data());
+        int best = 0, bs = -1;
+        for (int s = 0; s < ns; ++s) {
+            int c = 0;
+            for (int i = 0; i < n; ++i) c += msfm_emat::sampson(ws.data() + msfm_emat::kWsSol + 9 * s, x1[i], y1[i], x2[i], y2[i]) <= thr2 ? 1 : 0;
+            if (bs < 0 || c > best) {
+                best = c;
+                bs = s;
+            }
+        }
+        out_counts[it] = best;
+        out_sol[it] = bs;
+    }
+}
+
+// EssentialRansacMask on pixel coordinates p1, p2 (n x 2); returns the mask length (0: nothing kept)
+int host_essential_ransac(const float* p1, const float* p2, int n, const double* cam, double threshold, double confidence,
+                          int max_iters, unsigned long long seed, unsigned char* mask) {
+    std::vector<Point2f> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[(size_t)i] = Point2f{p1[2 * i], p1[2 * i + 1]};
+        b[(size_t)i] = Point2f{p2[2 * i], p2[2 * i + 1]};
+    }
+    const CameraIntrinsics c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    const std::vector<unsigned char> m = EssentialRansacMask(a, b, c, threshold, confidence, max_iters, seed);
+    for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
+    return (int)m.size();
 }
 
 }  // extern "C"

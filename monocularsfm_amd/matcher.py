@@ -62,10 +62,13 @@ class FeatureMatcher:
     """FeatureMatcher (FeatureMatching.h:18-57).  geometric_verification: "device" runs FeatureUtils::FilterMatches
     (F-matrix RANSAC, a "next" row of the scope table) on the GPU inside the matching call
     (msfm_match_pairs_verified, what the C++ CLI does by default); a callable is called as
-    f(kpts1, kpts2, matches) -> matches instead; None keeps the distance-filtered matches."""
+    f(kpts1, kpts2, matches) -> matches instead; None keeps the distance-filtered matches.  verification_model /
+    camera: the model of the "device" verification (0: fundamental matrix, the default; 1: essential matrix with
+    camera = fx, fy, cx, cy[, k1, k2, p1, p2] -- Context.set_verification_model)."""
 
     def __init__(self, database_path, max_num_matches=10240, max_distance=0.7, distance_ratio=0.8,
-                 cross_check=True, ctx=None, device=0, geometric_verification=None, verbose=True):
+                 cross_check=True, ctx=None, device=0, geometric_verification=None, verbose=True,
+                 verification_model=0, camera=None):
         self.database_path_ = database_path
         self.max_num_matches_ = max_num_matches  # stored, never read (as in the reference)
         self.max_distance_ = float(max_distance)
@@ -74,6 +77,8 @@ class FeatureMatcher:
         self.database_ = None
         self.ctx = ctx if ctx is not None else _lib.Context(device)
         self.geometric_verification = geometric_verification
+        if verification_model != 0 or camera is not None:
+            self.ctx.set_verification_model(verification_model, camera)
         self.verbose = verbose
         self._resident = set()
 
