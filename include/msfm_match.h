@@ -296,10 +296,17 @@ int msfm_upload_keypoints(msfm_ctx* ctx, int image_id, const float* kpts, int n,
  * host twin EssentialRansacMask (csrc/msfm_emat.h).  One camera for every image; per context; honoured by msfm_match_pairs_verified
  * and msfm_match_pairs_begin(.., geometric_verification = 1, ..).  MSFM_E_INVALID: unknown model, NULL camera for model 1,
  * fx / fy <= 0 or any parameter non-finite; MSFM_E_STATE while a streaming series is open.
- * msfm_get_verification_stats: hypotheses solved and rounds of kVeRound = 32 hypotheses run (the largest over the pairs) by the
- * last verified call / series under model 1 (0 under model 0). */
+ * MSFM_VERIFY_HOMOGRAPHY verifies planar scenes and rotation-only views, where F and E are degenerate (the reference runs
+ * cv::findHomography beside findFundamentalMat on its initial pairs, src/Reconstruction/Initializer.cpp:38-66): 4-point homography
+ * RANSAC on the keypoints' pixel coordinates (OpenCV's subset check, Hartley-normalised DLT), one-sided reprojection error
+ * |x2 - H x1|^2 <= threshold^2, the same adaptive stopping rule with sample size 4, no refit; < 4 matches or a consensus below 4
+ * keeps none.  Bit-identical to the host twin HomographyRansacMask (csrc/msfm_hmat.h).  It takes no camera: a non-NULL camera is
+ * MSFM_E_INVALID.
+ * msfm_get_verification_stats: hypotheses solved and rounds run (the largest over the pairs; kVeRound = 32 hypotheses per round
+ * under model 1, kVhRound = 64 under model 2) by the last verified call / series (0 under model 0). */
 #define MSFM_VERIFY_FUNDAMENTAL 0
 #define MSFM_VERIFY_ESSENTIAL 1
+#define MSFM_VERIFY_HOMOGRAPHY 2
 typedef struct msfm_camera {
     double fx, fy, cx, cy, k1, k2, p1, p2;
 } msfm_camera;

@@ -30,7 +30,7 @@ EXPORTS = [
     "msfm_train_vocabulary", "msfm_set_vocabulary", "msfm_image_words", "msfm_retrieve_pairs", "msfm_get_retrieval_profile",
     "msfm_set_verification_model", "msfm_get_verification_stats",
 ]
-VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL = 0, 1
+VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
 
 class MatchParams(C.Structure):
@@ -448,8 +448,10 @@ class Context:
 
     def set_verification_model(self, model, camera=None):
         """Model of the geometric verification of match_pairs_verified and the verified streaming form: VERIFY_FUNDAMENTAL (0,
-        the default: FeatureUtils::FilterMatches) or VERIFY_ESSENTIAL (1: 5-point essential-matrix RANSAC with `camera`, a dict
-        or sequence fx, fy, cx, cy[, k1, k2, p1, p2] -- missing distortion coefficients are 0)."""
+        the default: FeatureUtils::FilterMatches), VERIFY_ESSENTIAL (1: 5-point essential-matrix RANSAC with `camera`, a dict
+        or sequence fx, fy, cx, cy[, k1, k2, p1, p2] -- missing distortion coefficients are 0) or VERIFY_HOMOGRAPHY (2: 4-point
+        homography RANSAC on pixel coordinates, for planar scenes and rotation-only views; it takes no camera, and a given one is
+        passed on and refused with E_INVALID)."""
         cam = None
         if camera is not None:
             keys = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")
@@ -458,7 +460,7 @@ class Context:
         self._chk(self._L.msfm_set_verification_model(self._h, int(model), C.byref(cam) if cam is not None else None))
 
     def verification_stats(self):
-        """(hypotheses solved, rounds run) of the last verified call / series under VERIFY_ESSENTIAL."""
+        """(hypotheses solved, rounds run) of the last verified call / series under VERIFY_ESSENTIAL or VERIFY_HOMOGRAPHY."""
         solved, rounds = C.c_int64(), C.c_int()
         self._chk(self._L.msfm_get_verification_stats(self._h, C.byref(solved), C.byref(rounds)))
         return int(solved.value), int(rounds.value)

@@ -686,10 +686,10 @@ struct msfm_ctx {
     DevBuf ret_words, ret_cn;
     int ret_v = 0;
     msfm_retrieval_profile ret_prof = {};
-    // geometric verification model (msfm_set_verification_model): 0 fundamental matrix, 1 essential matrix with `camera`
+    // geometric verification model (msfm_set_verification_model): 0 fundamental matrix, 1 essential matrix with `camera`, 2 homography
     int verify_model = MSFM_VERIFY_FUNDAMENTAL;
     msfm_emat::Camera camera = {};
-    long long ve_solved = 0;          // of the last verified call / series: hypotheses solved, rounds run (model 1)
+    long long ve_solved = 0;          // of the last verified call / series: hypotheses solved, rounds run (models 1 and 2)
     int ve_rounds = 0;
 };
 

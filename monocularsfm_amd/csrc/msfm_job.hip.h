@@ -246,8 +246,8 @@ struct MatchJob {
         const int* d_counts = SC.d_counts.as<int>();
         const int2* d_st_qt = SC.d_st_qt.as<int2>();
         const float* d_st_d = SC.d_st_d.as<float>();
-        if (verify && ctx->verify_model == MSFM_VERIFY_ESSENTIAL) {
-            rc = issue_essential(b, begin, oe, ev_base);
+        if (verify && (ctx->verify_model == MSFM_VERIFY_ESSENTIAL || ctx->verify_model == MSFM_VERIFY_HOMOGRAPHY)) {
+            rc = ctx->verify_model == MSFM_VERIFY_ESSENTIAL ? issue_essential(b, begin, oe, ev_base) : issue_homography(b, begin, oe, ev_base);
             if (rc != MSFM_OK) return rc;
             d_counts = SC.d_counts2.as<int>();
             d_st_qt = SC.d_st2_qt.as<int2>();
@@ -362,7 +362,7 @@ struct MatchJob {
                 HIPCHK(ctx, hipGetLastError());
             }
             eprm.round = r;
-            hipLaunchKernelGGL(ve_decide_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts,
+            hipLaunchKernelGGL((ve_decide_kernel<5, kVeRound>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts,
                                (const int*)SC.d_vf_hyp.as<int>(), (int)P, eprm, state, list, SC.d_vf_best_it.as<int>(),
                                SC.d_vf_best_count.as<int>(), stats);
             HIPCHK(ctx, hipGetLastError());
@@ -370,6 +370,68 @@ struct MatchJob {
         hipLaunchKernelGGL(ve_mask_compact_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts,
                            (const int2*)SC.d_st_qt.as<int2>(), (const float*)SC.d_st_d.as<float>(), (const double*)x1, (const double*)y1,
                            (const double*)x2, (const double*)y2, (const int*)SC.d_vf_best_it.as<int>(), eprm, SC.d_st2_qt.as<int2>(),
+                           SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(v1, SC.stream));
+        return MSFM_OK;
+    }
+
+    // the homography verification (msfm_verify_h.hip.h), staged like issue_essential on the pixel coordinates of vf_points_kernel.
+    // The lists go to the second staging buffer.
+    int issue_homography(Batch& b, int begin, long long oe, size_t ev_base) {
+        const size_t P = b.pairs.size();
+        VerifyEParams hprm = {verify->threshold * verify->threshold, verify->confidence, verify->max_iters, 0, verify->seed};
+        std::vector<VerifyPair>& vpairs = b.verify_pairs;   // (lives as long as the sub-batch: the copy below may still be in flight)
+        vpairs.resize(P);
+        for (size_t p = 0; p < P; ++p)
+            vpairs[p] = VerifyPair{ctx->images[pairs[2 * (begin + (int)p)]].kxy, ctx->images[pairs[2 * (begin + (int)p) + 1]].kxy};
+        HIPCHK(ctx, SC.d_vf_pairs.ensure(P * sizeof(VerifyPair)));
+        HIPCHK(ctx, SC.d_vf_x1.ensure(oe * 4));
+        HIPCHK(ctx, SC.d_vf_y1.ensure(oe * 4));
+        HIPCHK(ctx, SC.d_vf_x2.ensure(oe * 4));
+        HIPCHK(ctx, SC.d_vf_y2.ensure(oe * 4));
+        HIPCHK(ctx, SC.d_vf_hyp.ensure(P * (size_t)hprm.max_iters * 4));
+        HIPCHK(ctx, SC.d_vf_best_it.ensure(P * 4));
+        HIPCHK(ctx, SC.d_vf_best_count.ensure(P * 4));
+        HIPCHK(ctx, SC.d_ve_state.ensure((3 * P + 2) * 4));   // state[P] | two pair lists [P] | their two counts
+        HIPCHK(ctx, SC.d_ve_stats.ensure(sizeof(VerifyEStats)));
+        HIPCHK(ctx, SC.d_st2_qt.ensure(oe * sizeof(int2)));
+        HIPCHK(ctx, SC.d_st2_d.ensure(oe * 4));
+        HIPCHK(ctx, SC.d_counts2.ensure(P * 4));
+        HIPCHK(ctx, hipMemcpyAsync(SC.d_vf_pairs.p, vpairs.data(), P * sizeof(VerifyPair), hipMemcpyHostToDevice, SC.stream));
+        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_state.p, 0, (3 * P + 2) * 4, SC.stream));
+        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_stats.p, 0, sizeof(VerifyEStats), SC.stream));
+        hipEvent_t v0 = get_event(ctx, ev_base + 6), v1 = get_event(ctx, ev_base + 7);
+        if (!v0 || !v1) return fail(ctx, MSFM_E_DEVICE, "hipEventCreate failed");
+        HIPCHK(ctx, hipEventRecord(v0, SC.stream));
+        const PairDesc* dp = SC.d_pairs.as<PairDesc>();
+        const int* d_counts = SC.d_counts.as<int>();
+        float *x1 = SC.d_vf_x1.as<float>(), *y1 = SC.d_vf_y1.as<float>(), *x2 = SC.d_vf_x2.as<float>(), *y2 = SC.d_vf_y2.as<float>();
+        hipLaunchKernelGGL(vf_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, SC.d_vf_pairs.as<VerifyPair>(), d_counts,
+                           (const int2*)SC.d_st_qt.as<int2>(), x1, y1, x2, y2);
+        HIPCHK(ctx, hipGetLastError());
+        VerifyEStats* stats = SC.d_ve_stats.as<VerifyEStats>();
+        int* state = SC.d_ve_state.as<int>();
+        int* list = state + P;
+        const int rounds = (hprm.max_iters + kVhRound - 1) / kVhRound;
+        const unsigned grid = (unsigned)std::min<size_t>(P, (size_t)kVhGroupsPerCU * (size_t)std::max(1, ctx->cu_count));
+        for (int r = -1; r < rounds; ++r) {
+            if (r >= 0) {
+                hprm.round = r;
+                hipLaunchKernelGGL(vh_round_kernel, dim3(grid), dim3(kVhRound), 0, SC.stream, dp, d_counts, (const float*)x1,
+                                   (const float*)y1, (const float*)x2, (const float*)y2, list, (int)P, SC.d_vf_hyp.as<int>(), hprm,
+                                   stats);
+                HIPCHK(ctx, hipGetLastError());
+            }
+            hprm.round = r;
+            hipLaunchKernelGGL((ve_decide_kernel<4, kVhRound>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts,
+                               (const int*)SC.d_vf_hyp.as<int>(), (int)P, hprm, state, list, SC.d_vf_best_it.as<int>(),
+                               SC.d_vf_best_count.as<int>(), stats);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(vh_mask_compact_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts,
+                           (const int2*)SC.d_st_qt.as<int2>(), (const float*)SC.d_st_d.as<float>(), (const float*)x1, (const float*)y1,
+                           (const float*)x2, (const float*)y2, (const int*)SC.d_vf_best_it.as<int>(), hprm, SC.d_st2_qt.as<int2>(),
                            SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(v1, SC.stream));
@@ -462,7 +524,7 @@ struct MatchJob {
             float vms = 0.f;
             HIPCHK(ctx, hipEventElapsedTime(&vms, ctx->ev_pool[w.ev_base + 6], ctx->ev_pool[w.ev_base + 7]));
             SC.prof.verify_ms += vms;
-            if (ctx->verify_model == MSFM_VERIFY_ESSENTIAL) {   // (the stream has been synchronised above)
+            if (ctx->verify_model == MSFM_VERIFY_ESSENTIAL || ctx->verify_model == MSFM_VERIFY_HOMOGRAPHY) {   // (the stream has been synchronised above)
                 VerifyEStats st = {};
                 HIPCHK(ctx, hipMemcpyAsync(&st, SC.d_ve_stats.p, sizeof(st), hipMemcpyDeviceToHost, SC.stream));
                 HIPCHK(ctx, hipStreamSynchronize(SC.stream));   // (on this set's stream: the other sets' sub-batches stay in flight)

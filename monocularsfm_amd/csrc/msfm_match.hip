@@ -13,6 +13,7 @@
 #include "msfm_prefilter.hip.h"
 #include "msfm_verify.hip.h"
 #include "msfm_verify_e.hip.h"
+#include "msfm_verify_h.hip.h"
 #include "msfm_retrieval.hip.h"
 
 #include <sys/mman.h>
@@ -408,6 +409,11 @@ int msfm_set_verification_model(msfm_ctx* ctx, int model, const msfm_camera* cam
     if (!ctx) return MSFM_E_INVALID;
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "a streaming series is open");
     if (model == MSFM_VERIFY_FUNDAMENTAL) {
+        ctx->verify_model = model;
+        return MSFM_OK;
+    }
+    if (model == MSFM_VERIFY_HOMOGRAPHY) {
+        if (camera) return fail(ctx, MSFM_E_INVALID, "the homography model takes no camera");
         ctx->verify_model = model;
         return MSFM_OK;
     }

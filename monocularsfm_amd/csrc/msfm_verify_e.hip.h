@@ -117,7 +117,8 @@ __global__ __launch_bounds__(kVeRound) void ve_round_kernel(const PairDesc* __re
 }
 
 // after round prm.round (-1: before round 0): the stopping rule over the counts so far, and the list of the next round.  One thread
-// per pair.
+// per pair.  kSample / kRound: 5 / kVeRound here, 4 / kVhRound for the homography (msfm_verify_h.hip.h).
+template <int kSample, int kRound>
 __global__ void ve_decide_kernel(const int* __restrict__ counts, const int* __restrict__ hyp_counts, int n_pairs, VerifyEParams prm,
                                  int* __restrict__ state, int* __restrict__ list, int* __restrict__ best_it, int* __restrict__ best_count,
                                  VerifyEStats* __restrict__ stats) {
@@ -125,18 +126,18 @@ __global__ void ve_decide_kernel(const int* __restrict__ counts, const int* __re
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_pairs || state[p] != 0) return;
     const int n = counts[p];
-    if (n < 5) {
+    if (n < kSample) {
         state[p] = 1;
         best_it[p] = -1;
         best_count[p] = 0;
         return;
     }
     if (prm.round >= 0) {
-        const int avail = min((prm.round + 1) * kVeRound, prm.max_iters);
+        const int avail = min((prm.round + 1) * kRound, prm.max_iters);
         const int* hc = hyp_counts + (long long)p * prm.max_iters;
         int bc = 0;
         bool decided = false;
-        const int bi = msfm_fmat::replay_adaptive<5>(n, prm.max_iters, prm.confidence, [&](int it) { return hc[it]; }, &bc, avail, &decided);
+        const int bi = msfm_fmat::replay_adaptive<kSample>(n, prm.max_iters, prm.confidence, [&](int it) { return hc[it]; }, &bc, avail, &decided);
         if (decided) {
             state[p] = 1;
             best_it[p] = bi;

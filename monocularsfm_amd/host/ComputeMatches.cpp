@@ -64,11 +64,13 @@ int main(int argc, char** argv) {
     }
 
     // SIFTmatch.verification_model : 0 (default: the reference's F-matrix check) | 1 (essential matrix with the camera of
-    // Reconstruction.Camera.*, the keys the reference's reconstruction reads from the same file; distortion defaults to 0)
+    // Reconstruction.Camera.*, the keys the reference's reconstruction reads from the same file; distortion defaults to 0) |
+    // 2 (homography, for planar scenes and rotation-only views; no camera)
     int verification_model = 0;
     fs.Get("SIFTmatch.verification_model", &verification_model);
-    if (!(verification_model == 0 || verification_model == 1)) {
-        std::cerr << "ComputeMatches: SIFTmatch.verification_model must be 0 (fundamental matrix) or 1 (essential matrix)" << std::endl;
+    if (!(verification_model == 0 || verification_model == 1 || verification_model == 2)) {
+        std::cerr << "ComputeMatches: SIFTmatch.verification_model must be 0 (fundamental matrix), 1 (essential matrix) or 2 (homography)"
+                  << std::endl;
         return EXIT_FAILURE;
     }
     CameraIntrinsics camera = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -123,6 +125,7 @@ int main(int argc, char** argv) {
     }
 
     if (verification_model == 1) matcher->SetEssentialVerification(camera);
+    if (verification_model == 2) matcher->SetHomographyVerification();
 
     Timer timer;
     timer.Start();

@@ -151,6 +151,7 @@ void FeatureMatcher::OpenDatabaseAndDevice() {
                 const msfm_camera cam = {camera_.fx, camera_.fy, camera_.cx, camera_.cy, camera_.k1, camera_.k2, camera_.p1, camera_.p2};
                 status[g] = msfm_set_verification_model(c, MSFM_VERIFY_ESSENTIAL, &cam);
             }
+            if (status[g] == MSFM_OK && homography_) status[g] = msfm_set_verification_model(c, MSFM_VERIFY_HOMOGRAPHY, nullptr);
             // An ordinal listed k times (the tests' way to run the fan-out on a one-GPU box): every context would size its scratch
             // for a quarter of the device's free memory on its own -- four of them on one MI355X ran out of memory at config-4 scale.
             // They share the default budget instead (MSFM_SCRATCH_MIB still overrides: it is read at msfm_create, this only applies without it).
@@ -472,6 +473,8 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                         kept.clear();   // (FilterMatches appends, and returns without touching the list for an empty input)
                         if (essential_)
                             FilterMatchesEssential(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, camera_, &kept);
+                        else if (homography_)
+                            FilterMatchesHomography(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept);
                         else
                             FilterMatches(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept);
                         list.swap(kept);

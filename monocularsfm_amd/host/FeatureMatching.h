@@ -45,6 +45,9 @@ public:
         essential_ = true;
         camera_ = camera;
     }
+    // SIFTmatch.verification_model : 2 -- the homography instead of F (planar scenes, rotation-only views), on every device
+    // context or in the host twin (FilterMatchesHomography).  Call before RunMatching.
+    void SetHomographyVerification() { homography_ = true; }
 
 protected:
     void OpenDatabaseAndDevice();
@@ -65,6 +68,7 @@ protected:
     bool verification_on_host_ = false;  // MSFM_GEOMETRIC_VERIFICATION=host
     bool essential_ = false;             // SetEssentialVerification
     CameraIntrinsics camera_ = {};
+    bool homography_ = false;            // SetHomographyVerification
     Database* database_ = nullptr;
     // One context per GPU: MSFM_DEVICE (default 0), MSFM_DEVICES="0,1,..." or "all".  The whole descriptor store is replicated on
     // each; the pairs of a run are dealt to the devices in small cost-balanced blocks, round-robin, so that every device's results

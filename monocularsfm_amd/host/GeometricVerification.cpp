@@ -6,6 +6,7 @@
 
 #include "../csrc/msfm_emat.h"
 #include "../csrc/msfm_fmat.h"
+#include "../csrc/msfm_hmat.h"
 
 namespace MonocularSfM {
 
@@ -130,6 +131,53 @@ std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1,
     return mask;
 }
 
+// A literal sequential loop: hypothesis it is sampled, checked, solved and scored when the loop reaches it (a rejected sample
+// counts 0).  The winner's inliers are the mask.
+std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                                double threshold, double confidence, int max_iters, unsigned long long seed) {
+    using namespace msfm_hmat;
+    const int n = (int)pts1.size();
+    if (n < 4) return {};
+    std::vector<float> x1((size_t)n), y1((size_t)n), x2((size_t)n), y2((size_t)n);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        x1[i] = pts1[i].x;
+        y1[i] = pts1[i].y;
+        x2[i] = pts2[i].x;
+        y2[i] = pts2[i].y;
+    }
+    const double thr2 = threshold * threshold;
+    auto count = [&](const double H[9]) {
+        int c = 0;
+        for (size_t i = 0; i < (size_t)n; ++i) c += reproj_error(H, x1[i], y1[i], x2[i], y2[i]) <= thr2 ? 1 : 0;
+        return c;
+    };
+    int best_count = 0, best_it = -1, iters = max_iters;
+    for (int it = 0; it < iters; ++it) {
+        double H[9];
+        const int c = hypothesis(x1.data(), y1.data(), x2.data(), y2.data(), n, seed, it, H) ? count(H) : 0;
+        if (c > best_count) {
+            best_count = c;
+            best_it = it;
+            const double w = (double)c / n;
+            const double w2 = w * w;
+            double q = 1.0 - w2 * w2;
+            if (q < 1e-300) q = 1e-300;
+            const double need = msfm_fmat::det_log(1.0 - confidence) / msfm_fmat::det_log(q);
+            if (need > 0.0 && need < (double)iters) {
+                int ni = (int)need;
+                if ((double)ni < need) ni += 1;
+                iters = ni > it + 1 ? ni : it + 1;
+            }
+        }
+    }
+    if (best_count < 4 || best_it < 0) return {};
+    double H[9];
+    hypothesis(x1.data(), y1.data(), x2.data(), y2.data(), n, seed, best_it, H);
+    std::vector<unsigned char> mask((size_t)n, 0);
+    for (size_t i = 0; i < (size_t)n; ++i) mask[i] = reproj_error(H, x1[i], y1[i], x2[i], y2[i]) <= thr2 ? 1 : 0;
+    return mask;
+}
+
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
                    const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches) {
     if (kpts1.empty() || matches.empty()) return;  // FeatureUtils.cpp:181-184
@@ -157,6 +205,21 @@ void FilterMatchesEssential(const std::vector<KeyPoint>& kpts1, const std::vecto
         b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
     }
     const std::vector<unsigned char> mask = EssentialRansacMask(a, b, camera, 3.0, 0.99);
+    for (size_t i = 0; i < mask.size(); ++i)
+        if (mask[i]) prune_matches->push_back(matches[i]);
+}
+
+void FilterMatchesHomography(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
+                             const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches) {
+    if (kpts1.empty() || matches.empty()) return;
+    std::vector<Point2f> a, b;
+    a.reserve(matches.size());
+    b.reserve(matches.size());
+    for (const DMatch& m : matches) {
+        a.push_back(Point2f{kpts1[(size_t)m.queryIdx].x, kpts1[(size_t)m.queryIdx].y});
+        b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
+    }
+    const std::vector<unsigned char> mask = HomographyRansacMask(a, b, 3.0, 0.99);
     for (size_t i = 0; i < mask.size(); ++i)
         if (mask[i]) prune_matches->push_back(matches[i]);
 }

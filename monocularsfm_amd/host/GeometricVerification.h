@@ -36,6 +36,14 @@ std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1,
                                                double confidence = 0.99, int max_iters = 1000,
                                                unsigned long long seed = 0x5eed5eedULL);
 
+// The planar / rotation-only alternative (msfm_hmat.h): RANSAC over 4-point homographies in pixel coordinates (OpenCV's
+// subset check, Hartley-normalised DLT), one-sided reprojection error <= threshold^2, the replayed adaptive stopping rule with
+// sample size 4, no refit.  < 4 points or a best consensus below 4 -> empty mask (the caller keeps nothing); otherwise a mask of
+// n entries.  Host twin of the staged device RANSAC (csrc/msfm_verify_h.hip.h): the same bits.
+std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                                double threshold = 3.0, double confidence = 0.99, int max_iters = 1000,
+                                                unsigned long long seed = 0x5eed5eedULL);
+
 // FeatureUtils::GetAlignedPointsFromMatches + FilterMatches
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
                    const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches);
@@ -44,5 +52,9 @@ void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoin
 void FilterMatchesEssential(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
                             const std::vector<DMatch>& matches, const CameraIntrinsics& camera,
                             std::vector<DMatch>* prune_matches);
+
+// The same hand-off with HomographyRansacMask (SIFTmatch.verification_model : 2) and the reference's constants
+void FilterMatchesHomography(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
+                             const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches);
 
 }  // namespace MonocularSfM

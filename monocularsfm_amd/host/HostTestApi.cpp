@@ -1,4 +1,4 @@
-// HostTestApi.cpp -- C-linkage shims over the host-only pieces (YAML reader, Database, F- and E-RANSAC)
+// HostTestApi.cpp -- C-linkage shims over the host-only pieces (YAML reader, Database, F-, E- and H-RANSAC)
 // so that the CPU test-suite can exercise them through ctypes without a GPU.
 #include <cstring>
 #include <string>
@@ -10,6 +10,7 @@
 #include "YamlConfig.h"
 #include "../csrc/msfm_emat.h"
 #include "../csrc/msfm_fmat.h"
+#include "../csrc/msfm_hmat.h"
 
 using namespace MonocularSfM;
 
@@ -340,6 +341,70 @@ int host_essential_ransac(const float* p1, const float* p2, int n, const double*
     }
     const CameraIntrinsics c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
     const std::vector<unsigned char> m = EssentialRansacMask(a, b, c, threshold, confidence, max_iters, seed);
+    for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
+    return (int)m.size();
+}
+
+// ---- the pieces of msfm_hmat.h (tests/test_hmat_reference.py compares them with tests/hmat_ref.py) -------------------------
+void host_hmat_sample4(unsigned long long seed, int it, int n, int* idx) { msfm_hmat::sample4(seed, it, n, idx); }
+
+// q1, q2: 4 x 2 pixel points; 1 when the sample passes the subset check
+int host_hmat_check_subset(const double* q1, const double* q2) {
+    double a[4], b[4], c[4], d[4];
+    for (int k = 0; k < 4; ++k) {
+        a[k] = q1[2 * k];
+        b[k] = q1[2 * k + 1];
+        c[k] = q2[2 * k];
+        d[k] = q2[2 * k + 1];
+    }
+    return msfm_hmat::check_subset(a, b, c, d) ? 1 : 0;
+}
+
+// q1, q2: 4 x 2 pixel points; H: room for 9.  Returns 1 when solved (no subset check here)
+int host_hmat_four_point(const double* q1, const double* q2, double* H) {
+    double a[4], b[4], c[4], d[4];
+    for (int k = 0; k < 4; ++k) {
+        a[k] = q1[2 * k];
+        b[k] = q1[2 * k + 1];
+        c[k] = q2[2 * k];
+        d[k] = q2[2 * k + 1];
+    }
+    return msfm_hmat::four_point(a, b, c, d, H) ? 1 : 0;
+}
+
+double host_hmat_error(const double* H, double x, double y, double u, double v) { return msfm_hmat::reproj_error(H, x, y, u, v); }
+
+// replay_adaptive<4> over counts [0, avail); *decided = 0 when it needed more
+int host_hmat_replay(const int* counts, int avail, int n, int max_iters, double confidence, int* best_count, int* decided) {
+    bool dec = true;
+    const int r = msfm_fmat::replay_adaptive<4>(n, max_iters, confidence, [&](int it) { return counts[it]; }, best_count, avail, &dec);
+    *decided = dec ? 1 : 0;
+    return r;
+}
+
+// count of every hypothesis it0 .. it0 + n_its - 1 (0 for a rejected sample) and whether its sample was solved; pixel coordinates
+void host_hmat_counts(const float* x1, const float* y1, const float* x2, const float* y2, int n, unsigned long long seed, int it0,
+                      int n_its, double thr2, int* out_counts, int* out_solved) {
+    for (int k = 0; k < n_its; ++k) {
+        double H[9];
+        const bool ok = msfm_hmat::hypothesis(x1, y1, x2, y2, n, seed, it0 + k, H);
+        int c = 0;
+        if (ok)
+            for (int i = 0; i < n; ++i) c += msfm_hmat::reproj_error(H, x1[i], y1[i], x2[i], y2[i]) <= thr2 ? 1 : 0;
+        out_counts[k] = c;
+        out_solved[k] = ok ? 1 : 0;
+    }
+}
+
+// HomographyRansacMask on pixel coordinates p1, p2 (n x 2); returns the mask length (0: nothing kept)
+int host_homography_ransac(const float* p1, const float* p2, int n, double threshold, double confidence, int max_iters,
+                           unsigned long long seed, unsigned char* mask) {
+    std::vector<Point2f> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[(size_t)i] = Point2f{p1[2 * i], p1[2 * i + 1]};
+        b[(size_t)i] = Point2f{p2[2 * i], p2[2 * i + 1]};
+    }
+    const std::vector<unsigned char> m = HomographyRansacMask(a, b, threshold, confidence, max_iters, seed);
     for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
     return (int)m.size();
 }

@@ -64,7 +64,7 @@ class FeatureMatcher:
     (msfm_match_pairs_verified, what the C++ CLI does by default); a callable is called as
     f(kpts1, kpts2, matches) -> matches instead; None keeps the distance-filtered matches.  verification_model /
     camera: the model of the "device" verification (0: fundamental matrix, the default; 1: essential matrix with
-    camera = fx, fy, cx, cy[, k1, k2, p1, p2] -- Context.set_verification_model)."""
+    camera = fx, fy, cx, cy[, k1, k2, p1, p2]; 2: homography, no camera -- Context.set_verification_model)."""
 
     def __init__(self, database_path, max_num_matches=10240, max_distance=0.7, distance_ratio=0.8,
                  cross_check=True, ctx=None, device=0, geometric_verification=None, verbose=True,

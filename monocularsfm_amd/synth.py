@@ -124,6 +124,69 @@ def scene_keypoints(point_ids, cams, n_points, seed=0, noise_px=0.7, base=None):
     return out
 
 
+def _rotation(rng, scale):
+    w = rng.normal(size=3) * scale
+    th = np.linalg.norm(w)
+    k = w / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+
+
+def _homography_view_pair(Ht, n_in, n_out, rng, seed, width, height, noise_px):
+    """n_in rows of image 1 (uniform in the frame) mapped by Ht into the frame of image 2, then n_out planted outliers at fresh
+    random places in both images; Gaussian pixel noise on the inliers."""
+    k1 = keypoints(n_in + n_out, seed=seed + 1000, width=width, height=height)
+    k2 = keypoints(n_in + n_out, seed=seed + 1001, width=width, height=height)
+    got = np.zeros((0, 4))
+    while len(got) < n_in:
+        p = np.c_[rng.uniform(0, width, 4 * n_in + 16), rng.uniform(0, height, 4 * n_in + 16), np.ones(4 * n_in + 16)]
+        q = p @ Ht.T
+        ok = q[:, 2] > 1e-9
+        q = q[ok, :2] / q[ok, 2:]
+        p = p[ok]
+        inside = (q[:, 0] >= 0) & (q[:, 0] < width) & (q[:, 1] >= 0) & (q[:, 1] < height)
+        got = np.r_[got, np.c_[p[inside, :2], q[inside]]]
+    got = got[:n_in]
+    k1[:n_in, 0] = (got[:, 0] + rng.normal(0, noise_px, n_in)).astype(F32)
+    k1[:n_in, 1] = (got[:, 1] + rng.normal(0, noise_px, n_in)).astype(F32)
+    k2[:n_in, 0] = (got[:, 2] + rng.normal(0, noise_px, n_in)).astype(F32)
+    k2[:n_in, 1] = (got[:, 3] + rng.normal(0, noise_px, n_in)).astype(F32)
+    inlier = np.r_[np.ones(n_in, bool), np.zeros(n_out, bool)]
+    return k1, k2, inlier, Ht / np.linalg.norm(Ht)
+
+
+def planar_view_pair(n_in, n_out, seed=0, width=3072, height=2304, focal=2500.0, noise_px=0.5):
+    """Two views of a plane (a tilted facade in front of cameras placed as synth.scene_cameras places them): row i of image 1
+    corresponds to row i of image 2.  -> (k1, k2: n x 4 float32 keypoint rows, inlier: the first n_in rows see the plane, the
+    n_out others are planted outliers at random places, H: the true homography, unit Frobenius norm, x2 ~ H x1)."""
+    rng = np.random.default_rng(seed)
+    cams = scene_cameras(2, seed=seed, width=width, height=height, focal=focal)
+    K = np.array([[focal, 0, width / 2.0], [0, focal, height / 2.0], [0, 0, 1.0]])
+    e1 = np.array([1.0, 0.0, 0.25])
+    e2 = np.array([0.0, 1.0, -0.15])
+    p0 = np.array([0.0, 0.0, rng.uniform(-0.3, 0.3)])
+    M = [K @ np.c_[R @ e1, R @ e2, R @ p0 + t] for R, t, _, _, _ in cams]   # plane coordinates (a, b, 1) -> pixels
+    return _homography_view_pair(M[1] @ np.linalg.inv(M[0]), n_in, n_out, rng, seed, width, height, noise_px)
+
+
+def rotation_view_pair(n_in, n_out, seed=0, width=3072, height=2304, focal=2500.0, noise_px=0.5, angle=0.2):
+    """Two views from one centre (a panorama / tripod sweep): the camera turns by about `angle` radians.  -> the tuple of
+    planar_view_pair; H = K R K^-1."""
+    rng = np.random.default_rng(seed)
+    K = np.array([[focal, 0, width / 2.0], [0, focal, height / 2.0], [0, 0, 1.0]])
+    R = _rotation(rng, angle / np.sqrt(3.0))
+    return _homography_view_pair(K @ R @ np.linalg.inv(K), n_in, n_out, rng, seed, width, height, noise_px)
+
+
+def general_view_pair(n_in, n_out, seed=0, width=3072, height=2304, focal=2500.0, noise_px=0.5):
+    """Two views of a 3-D scene (synth.scene_keypoints' box of points): the tuple of planar_view_pair, with H None -- no
+    homography explains all the inliers."""
+    cams = scene_cameras(2, seed=seed, width=width, height=height, focal=focal)
+    ids = np.r_[np.arange(n_in), np.full(n_out, -1)]
+    k1, k2 = scene_keypoints([ids, ids], cams, max(n_in, 1), seed=seed, noise_px=noise_px)
+    return k1, k2, ids >= 0, None
+
+
 def all_pairs(n_images):
     """BruteFeatureMatcher::RunMatching's enumeration (FeatureMatching.cpp:110-139): (i, j), j < i, i-major."""
     i, j = np.tril_indices(int(n_images), -1)      # row-major over the lower triangle = i-major, j ascending
@@ -180,6 +243,39 @@ def south_building_database(path, n_images=128, n_desc=5000, seed=1234):
         protos[i][rows] = n_proto + pick                 # landmarks are scene points too
     kps = scene_keypoints(protos, scene_cameras(n_images, seed=seed + 7), n_proto + 120, seed=seed + 9, base=kps)
     database.write_synthetic_database(path, descs, kps)
+    return descs, kps
+
+
+def south_building_planar(n_images=128, n_desc=5000, seed=1234, noise_px=0.5):
+    """south_building_database's descriptors (the same draws: the same pairs match the same rows) with keypoints of a planar
+    scene: every prototype and landmark is a point of one facade seen through synth.scene_cameras, so one homography per pair
+    explains its true matches.  Rows that observe nothing keep their random positions.  -> (descriptors, keypoints); nothing is
+    written."""
+    rng = np.random.default_rng(seed)
+    n_proto = 20000
+    counts = rng.integers(int(n_desc * 0.92), int(n_desc * 1.08) + 1, n_images)
+    descs, protos = rootsift_images(n_images, counts.tolist(), seed=seed, n_proto=n_proto, return_proto=True)
+    kps = [keypoints(len(d), seed=50 + i) for i, d in enumerate(descs)]
+    pool = descs[0][:120].copy()
+    for i in range(n_images):
+        k = min(80, len(descs[i]))
+        pick = rng.choice(120, k, replace=False)
+        rows = rng.choice(len(descs[i]), k, replace=False)
+        v = np.abs(pool[pick] * (1 + 0.03 * rng.standard_normal((k, 128)).astype(F32)))
+        descs[i][rows] = v / np.linalg.norm(v, axis=1, keepdims=True)
+        kps[i][rows, 2] = 100 + rng.uniform(0, 50, k).astype(F32)
+        protos[i][rows] = n_proto + pick
+    prng = np.random.default_rng(seed + 9)
+    a, b = prng.uniform(-1.6, 1.6, n_proto + 120), prng.uniform(-1.1, 1.1, n_proto + 120)
+    X = np.c_[a, b, 0.25 * a - 0.15 * b]
+    cams = scene_cameras(n_images, seed=seed + 7)
+    for i in range(n_images):
+        ids = np.asarray(protos[i])
+        sel = np.nonzero(ids >= 0)[0]
+        R, t, f, cx, cy = cams[i]
+        Xc = X[ids[sel]] @ R.T + t
+        kps[i][sel, 0] = (f * Xc[:, 0] / Xc[:, 2] + cx + prng.normal(0, noise_px, len(sel))).astype(F32)
+        kps[i][sel, 1] = (f * Xc[:, 1] / Xc[:, 2] + cy + prng.normal(0, noise_px, len(sel))).astype(F32)
     return descs, kps
 
 
