@@ -580,8 +580,9 @@ struct Scratch {
     // geometric verification
     DevBuf d_vf_pairs, d_vf_x1, d_vf_y1, d_vf_x2, d_vf_y2, d_vf_hyp, d_vf_best_it, d_vf_best_count, d_vf_flags,
         d_st2_qt, d_st2_d, d_counts2;
-    // calibrated verification (msfm_verify_e.hip.h): normalised coordinates of the staged matches (fp64), per-pair state, counters
-    DevBuf d_ve_x1, d_ve_y1, d_ve_x2, d_ve_y2, d_ve_state, d_ve_stats;
+    // calibrated verification (msfm_verify_e.hip.h): normalised coordinates of the staged matches (fp64); the staged models
+    // (msfm_verify_staged.hip.h): per-pair state and round lists, counters
+    DevBuf d_ve_x1, d_ve_y1, d_ve_x2, d_ve_y2, d_staged_state, d_staged_stats;
     msfm_profile prof = {};           // this sub-batch's share; joins the call's profile when the sub-batch is accepted
     hipEvent_t sweep1_done = nullptr; // recorded behind sweep 1: the other stream's next sweep 1 waits for it
     bool sweep1_recorded = false;
@@ -595,7 +596,7 @@ struct Scratch {
                           &d_vpairs, &d_vpf, &d_vitems, &d_lists, &d_colmask, &d_gtot, &d_grow0, &d_cnt, &d_mrow, &d_summary, &d_overflow,
                           &d_totals, &d_vf_pairs,
                           &d_vf_x1, &d_vf_y1, &d_vf_x2, &d_vf_y2, &d_vf_hyp, &d_vf_best_it, &d_vf_best_count, &d_vf_flags, &d_st2_qt,
-                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_ve_state, &d_ve_stats, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
+                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
         for (DevBuf* b : bufs) fn(*b, arg);
     }
     long long device_bytes() {
@@ -689,8 +690,8 @@ struct msfm_ctx {
     // geometric verification model (msfm_set_verification_model): 0 fundamental matrix, 1 essential matrix with `camera`, 2 homography
     int verify_model = MSFM_VERIFY_FUNDAMENTAL;
     msfm_emat::Camera camera = {};
-    long long ve_solved = 0;          // of the last verified call / series: hypotheses solved, rounds run (models 1 and 2)
-    int ve_rounds = 0;
+    long long staged_solved = 0;      // of the last verified call / series: hypotheses solved, rounds run (models 1 and 2)
+    int staged_rounds = 0;
 };
 
 #define SC (*ctx->cur)

@@ -53,8 +53,8 @@ struct MatchJob {
         if (vp) {
             verify_store = *vp;
             verify = &verify_store;
-            c->ve_solved = 0;
-            c->ve_rounds = 0;
+            c->staged_solved = 0;
+            c->staged_rounds = 0;
         }
         for (SubBatch& w : sb) w = SubBatch{};
         next_begin = 0;
@@ -246,54 +246,9 @@ struct MatchJob {
         const int* d_counts = SC.d_counts.as<int>();
         const int2* d_st_qt = SC.d_st_qt.as<int2>();
         const float* d_st_d = SC.d_st_d.as<float>();
-        if (verify && (ctx->verify_model == MSFM_VERIFY_ESSENTIAL || ctx->verify_model == MSFM_VERIFY_HOMOGRAPHY)) {
-            rc = ctx->verify_model == MSFM_VERIFY_ESSENTIAL ? issue_essential(b, begin, oe, ev_base) : issue_homography(b, begin, oe, ev_base);
+        if (verify) {
+            rc = issue_verify(b, begin, oe, ev_base);
             if (rc != MSFM_OK) return rc;
-            d_counts = SC.d_counts2.as<int>();
-            d_st_qt = SC.d_st2_qt.as<int2>();
-            d_st_d = SC.d_st2_d.as<float>();
-        } else if (verify) {
-            // FeatureUtils::FilterMatches on the staged lists: all hypotheses of all pairs at once
-            VerifyParams vprm = {verify->threshold * verify->threshold, verify->confidence, verify->max_iters, 0, verify->seed};
-            std::vector<VerifyPair>& vpairs = b.verify_pairs;   // (lives as long as the sub-batch: the copy below may still be in flight)
-            vpairs.resize(P);
-            for (size_t p = 0; p < P; ++p)
-                vpairs[p] = VerifyPair{ctx->images[pairs[2 * (begin + (int)p)]].kxy, ctx->images[pairs[2 * (begin + (int)p) + 1]].kxy};
-            HIPCHK(ctx, SC.d_vf_pairs.ensure(P * sizeof(VerifyPair)));
-            HIPCHK(ctx, SC.d_vf_x1.ensure(oe * 4));
-            HIPCHK(ctx, SC.d_vf_y1.ensure(oe * 4));
-            HIPCHK(ctx, SC.d_vf_x2.ensure(oe * 4));
-            HIPCHK(ctx, SC.d_vf_y2.ensure(oe * 4));
-            HIPCHK(ctx, SC.d_vf_flags.ensure(oe));
-            HIPCHK(ctx, SC.d_vf_hyp.ensure(P * (size_t)vprm.max_iters * 4));
-            HIPCHK(ctx, SC.d_vf_best_it.ensure(P * 4));
-            HIPCHK(ctx, SC.d_vf_best_count.ensure(P * 4));
-            HIPCHK(ctx, SC.d_st2_qt.ensure(oe * sizeof(int2)));
-            HIPCHK(ctx, SC.d_st2_d.ensure(oe * 4));
-            HIPCHK(ctx, SC.d_counts2.ensure(P * 4));
-            HIPCHK(ctx, hipMemcpyAsync(SC.d_vf_pairs.p, vpairs.data(), P * sizeof(VerifyPair), hipMemcpyHostToDevice, SC.stream));
-            hipEvent_t v0 = get_event(ctx, ev_base + 6), v1 = get_event(ctx, ev_base + 7);
-            if (!v0 || !v1) return fail(ctx, MSFM_E_DEVICE, "hipEventCreate failed");
-            HIPCHK(ctx, hipEventRecord(v0, SC.stream));
-            const PairDesc* dp = SC.d_pairs.as<PairDesc>();
-            float *x1 = SC.d_vf_x1.as<float>(), *y1 = SC.d_vf_y1.as<float>(), *x2 = SC.d_vf_x2.as<float>(), *y2 = SC.d_vf_y2.as<float>();
-            hipLaunchKernelGGL(vf_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, SC.d_vf_pairs.as<VerifyPair>(),
-                               d_counts, d_st_qt, x1, y1, x2, y2);
-            HIPCHK(ctx, hipGetLastError());
-            hipLaunchKernelGGL(vf_hypotheses_kernel, dim3((unsigned)((vprm.max_iters + 255) / 256), (unsigned)P), dim3(256), 0, SC.stream,
-                               dp, d_counts, (const float*)x1, (const float*)y1, (const float*)x2, (const float*)y2,
-                               SC.d_vf_hyp.as<int>(), vprm);
-            HIPCHK(ctx, hipGetLastError());
-            hipLaunchKernelGGL(vf_select_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts,
-                               (const int*)SC.d_vf_hyp.as<int>(), (int)P, vprm, SC.d_vf_best_it.as<int>(), SC.d_vf_best_count.as<int>());
-            HIPCHK(ctx, hipGetLastError());
-            hipLaunchKernelGGL(vf_mask_compact_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, d_counts, d_st_qt, d_st_d,
-                               (const float*)x1, (const float*)y1, (const float*)x2, (const float*)y2,
-                               (const int*)SC.d_vf_best_it.as<int>(), (const int*)SC.d_vf_best_count.as<int>(),
-                               SC.d_vf_flags.as<unsigned char>(), vprm, SC.d_st2_qt.as<int2>(), SC.d_st2_d.as<float>(),
-                               SC.d_counts2.as<int>());
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipEventRecord(v1, SC.stream));
             d_counts = SC.d_counts2.as<int>();
             d_st_qt = SC.d_st2_qt.as<int2>();
             d_st_d = SC.d_st2_d.as<float>();
@@ -313,128 +268,116 @@ struct MatchJob {
         return MSFM_OK;
     }
 
-    // the calibrated verification (msfm_verify_e.hip.h), staged: the rounds are launched back to back (no host wait); an undecided
-    // pair's round kernel returns at once when ve_decide_kernel has marked it.  The lists go to the second staging buffer.
-    int issue_essential(Batch& b, int begin, long long oe, size_t ev_base) {
+    // models 1 and 2 verify by the staged RANSAC (msfm_verify_staged.hip.h); model 0 scores every hypothesis at once
+    bool staged() const { return ctx->verify_model == MSFM_VERIFY_ESSENTIAL || ctx->verify_model == MSFM_VERIFY_HOMOGRAPHY; }
+
+    // the geometric verification of the staged lists (FeatureUtils::FilterMatches, or the model msfm_set_verification_model
+    // chose) between the events ev_base + 6 and + 7; the kept matches go to the second staging buffer
+    int issue_verify(Batch& b, int begin, long long oe, size_t ev_base) {
         const size_t P = b.pairs.size();
-        const double f = (ctx->camera.fx + ctx->camera.fy) * 0.5, tn = verify->threshold / f;
-        VerifyEParams eprm = {tn * tn, verify->confidence, verify->max_iters, 0, verify->seed};
+        const int model = ctx->verify_model;
         std::vector<VerifyPair>& vpairs = b.verify_pairs;   // (lives as long as the sub-batch: the copy below may still be in flight)
         vpairs.resize(P);
         for (size_t p = 0; p < P; ++p)
             vpairs[p] = VerifyPair{ctx->images[pairs[2 * (begin + (int)p)]].kxy, ctx->images[pairs[2 * (begin + (int)p) + 1]].kxy};
         HIPCHK(ctx, SC.d_vf_pairs.ensure(P * sizeof(VerifyPair)));
-        HIPCHK(ctx, SC.d_ve_x1.ensure(oe * 8));
-        HIPCHK(ctx, SC.d_ve_y1.ensure(oe * 8));
-        HIPCHK(ctx, SC.d_ve_x2.ensure(oe * 8));
-        HIPCHK(ctx, SC.d_ve_y2.ensure(oe * 8));
-        HIPCHK(ctx, SC.d_vf_hyp.ensure(P * (size_t)eprm.max_iters * 4));
+        const bool e = model == MSFM_VERIFY_ESSENTIAL;   // (normalised fp64 coordinates; F and H: fp32 pixels)
+        for (DevBuf* xy : {e ? &SC.d_ve_x1 : &SC.d_vf_x1, e ? &SC.d_ve_y1 : &SC.d_vf_y1, e ? &SC.d_ve_x2 : &SC.d_vf_x2, e ? &SC.d_ve_y2 : &SC.d_vf_y2})
+            HIPCHK(ctx, xy->ensure(oe * (e ? 8 : 4)));
+        if (!staged()) HIPCHK(ctx, SC.d_vf_flags.ensure(oe));
+        HIPCHK(ctx, SC.d_vf_hyp.ensure(P * (size_t)verify->max_iters * 4));
         HIPCHK(ctx, SC.d_vf_best_it.ensure(P * 4));
         HIPCHK(ctx, SC.d_vf_best_count.ensure(P * 4));
-        HIPCHK(ctx, SC.d_ve_state.ensure((3 * P + 2) * 4));   // state[P] | two pair lists [P] | their two counts
-        HIPCHK(ctx, SC.d_ve_stats.ensure(sizeof(VerifyEStats)));
+        if (staged()) {
+            HIPCHK(ctx, SC.d_staged_state.ensure((3 * P + 2) * 4));   // state[P] | two pair lists [P] | their two counts
+            HIPCHK(ctx, SC.d_staged_stats.ensure(sizeof(StagedStats)));
+        }
         HIPCHK(ctx, SC.d_st2_qt.ensure(oe * sizeof(int2)));
         HIPCHK(ctx, SC.d_st2_d.ensure(oe * 4));
         HIPCHK(ctx, SC.d_counts2.ensure(P * 4));
         HIPCHK(ctx, hipMemcpyAsync(SC.d_vf_pairs.p, vpairs.data(), P * sizeof(VerifyPair), hipMemcpyHostToDevice, SC.stream));
-        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_state.p, 0, (3 * P + 2) * 4, SC.stream));
-        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_stats.p, 0, sizeof(VerifyEStats), SC.stream));
+        if (staged()) {
+            HIPCHK(ctx, hipMemsetAsync(SC.d_staged_state.p, 0, (3 * P + 2) * 4, SC.stream));
+            HIPCHK(ctx, hipMemsetAsync(SC.d_staged_stats.p, 0, sizeof(StagedStats), SC.stream));
+        }
         hipEvent_t v0 = get_event(ctx, ev_base + 6), v1 = get_event(ctx, ev_base + 7);
         if (!v0 || !v1) return fail(ctx, MSFM_E_DEVICE, "hipEventCreate failed");
         HIPCHK(ctx, hipEventRecord(v0, SC.stream));
         const PairDesc* dp = SC.d_pairs.as<PairDesc>();
+        const VerifyPair* vp = SC.d_vf_pairs.as<VerifyPair>();
         const int* d_counts = SC.d_counts.as<int>();
-        double *x1 = SC.d_ve_x1.as<double>(), *y1 = SC.d_ve_y1.as<double>(), *x2 = SC.d_ve_x2.as<double>(), *y2 = SC.d_ve_y2.as<double>();
-        hipLaunchKernelGGL(ve_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, SC.d_vf_pairs.as<VerifyPair>(), d_counts,
-                           (const int2*)SC.d_st_qt.as<int2>(), ctx->camera, x1, y1, x2, y2);
-        HIPCHK(ctx, hipGetLastError());
-        VerifyEStats* stats = SC.d_ve_stats.as<VerifyEStats>();
-        int* state = SC.d_ve_state.as<int>();
-        int* list = state + P;
-        const int rounds = (eprm.max_iters + kVeRound - 1) / kVeRound;
-        const unsigned grid = (unsigned)std::min<size_t>(P, (size_t)kVeGroupsPerCU * (size_t)std::max(1, ctx->cu_count));
-        for (int r = -1; r < rounds; ++r) {
-            if (r >= 0) {
-                eprm.round = r;
-                hipLaunchKernelGGL(ve_round_kernel, dim3(grid), dim3(kVeRound), 0, SC.stream, dp, d_counts, (const double*)x1,
-                                   (const double*)y1, (const double*)x2, (const double*)y2, list, (int)P, SC.d_vf_hyp.as<int>(), eprm,
-                                   stats);
-                HIPCHK(ctx, hipGetLastError());
-            }
-            eprm.round = r;
-            hipLaunchKernelGGL((ve_decide_kernel<5, kVeRound>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts,
-                               (const int*)SC.d_vf_hyp.as<int>(), (int)P, eprm, state, list, SC.d_vf_best_it.as<int>(),
-                               SC.d_vf_best_count.as<int>(), stats);
+        const int2* d_st_qt = SC.d_st_qt.as<int2>();
+        const float* d_st_d = SC.d_st_d.as<float>();
+        int* hyp = SC.d_vf_hyp.as<int>();
+        const int* best_it = SC.d_vf_best_it.as<int>();
+        if (model == MSFM_VERIFY_FUNDAMENTAL) {   // all hypotheses of all pairs at once (msfm_verify.hip.h)
+            VerifyParams vprm = {verify->threshold * verify->threshold, verify->confidence, verify->max_iters, 0, verify->seed};
+            float *x1 = SC.d_vf_x1.as<float>(), *y1 = SC.d_vf_y1.as<float>(), *x2 = SC.d_vf_x2.as<float>(), *y2 = SC.d_vf_y2.as<float>();
+            hipLaunchKernelGGL(vf_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, vp, d_counts, d_st_qt, x1, y1, x2, y2);
             HIPCHK(ctx, hipGetLastError());
+            hipLaunchKernelGGL(vf_hypotheses_kernel, dim3((unsigned)((vprm.max_iters + 255) / 256), (unsigned)P), dim3(256), 0, SC.stream,
+                               dp, d_counts, (const float*)x1, (const float*)y1, (const float*)x2, (const float*)y2, hyp, vprm);
+            HIPCHK(ctx, hipGetLastError());
+            hipLaunchKernelGGL(vf_select_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts, (const int*)hyp, (int)P,
+                               vprm, SC.d_vf_best_it.as<int>(), SC.d_vf_best_count.as<int>());
+            HIPCHK(ctx, hipGetLastError());
+            hipLaunchKernelGGL(vf_mask_compact_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, d_counts, d_st_qt, d_st_d,
+                               (const float*)x1, (const float*)y1, (const float*)x2, (const float*)y2, best_it,
+                               (const int*)SC.d_vf_best_count.as<int>(), SC.d_vf_flags.as<unsigned char>(), vprm, SC.d_st2_qt.as<int2>(),
+                               SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
+        } else if (model == MSFM_VERIFY_ESSENTIAL) {   // on normalised coordinates (msfm_verify_e.hip.h)
+            const double f = (ctx->camera.fx + ctx->camera.fy) * 0.5, tn = verify->threshold / f;
+            StagedParams prm = {tn * tn, verify->confidence, verify->max_iters, 0, verify->seed};
+            double *x1 = SC.d_ve_x1.as<double>(), *y1 = SC.d_ve_y1.as<double>(), *x2 = SC.d_ve_x2.as<double>(), *y2 = SC.d_ve_y2.as<double>();
+            hipLaunchKernelGGL(ve_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, vp, d_counts, d_st_qt, ctx->camera, x1, y1, x2, y2);
+            HIPCHK(ctx, hipGetLastError());
+            int rc = issue_rounds<5, kVeRound>(P, kVeGroupsPerCU, prm, [&](unsigned grid, int* list, StagedStats* stats) {
+                hipLaunchKernelGGL(ve_round_kernel, dim3(grid), dim3(kVeRound), 0, SC.stream, dp, d_counts, (const double*)x1, (const double*)y1,
+                                   (const double*)x2, (const double*)y2, list, (int)P, hyp, prm, stats);
+            });
+            if (rc != MSFM_OK) return rc;
+            hipLaunchKernelGGL(ve_mask_compact_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts, d_st_qt, d_st_d, (const double*)x1,
+                               (const double*)y1, (const double*)x2, (const double*)y2, best_it, prm, SC.d_st2_qt.as<int2>(),
+                               SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
+        } else {   // the homography, on pixel coordinates (msfm_verify_h.hip.h)
+            StagedParams prm = {verify->threshold * verify->threshold, verify->confidence, verify->max_iters, 0, verify->seed};
+            float *x1 = SC.d_vf_x1.as<float>(), *y1 = SC.d_vf_y1.as<float>(), *x2 = SC.d_vf_x2.as<float>(), *y2 = SC.d_vf_y2.as<float>();
+            hipLaunchKernelGGL(vf_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, vp, d_counts, d_st_qt, x1, y1, x2, y2);
+            HIPCHK(ctx, hipGetLastError());
+            int rc = issue_rounds<4, kVhRound>(P, kVhGroupsPerCU, prm, [&](unsigned grid, int* list, StagedStats* stats) {
+                hipLaunchKernelGGL(vh_round_kernel, dim3(grid), dim3(kVhRound), 0, SC.stream, dp, d_counts, (const float*)x1, (const float*)y1,
+                                   (const float*)x2, (const float*)y2, list, (int)P, hyp, prm, stats);
+            });
+            if (rc != MSFM_OK) return rc;
+            hipLaunchKernelGGL(vh_mask_compact_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts, d_st_qt, d_st_d, (const float*)x1,
+                               (const float*)y1, (const float*)x2, (const float*)y2, best_it, prm, SC.d_st2_qt.as<int2>(),
+                               SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
         }
-        hipLaunchKernelGGL(ve_mask_compact_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts,
-                           (const int2*)SC.d_st_qt.as<int2>(), (const float*)SC.d_st_d.as<float>(), (const double*)x1, (const double*)y1,
-                           (const double*)x2, (const double*)y2, (const int*)SC.d_vf_best_it.as<int>(), eprm, SC.d_st2_qt.as<int2>(),
-                           SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(v1, SC.stream));
         return MSFM_OK;
     }
 
-    // the homography verification (msfm_verify_h.hip.h), staged like issue_essential on the pixel coordinates of vf_points_kernel.
-    // The lists go to the second staging buffer.
-    int issue_homography(Batch& b, int begin, long long oe, size_t ev_base) {
-        const size_t P = b.pairs.size();
-        VerifyEParams hprm = {verify->threshold * verify->threshold, verify->confidence, verify->max_iters, 0, verify->seed};
-        std::vector<VerifyPair>& vpairs = b.verify_pairs;   // (lives as long as the sub-batch: the copy below may still be in flight)
-        vpairs.resize(P);
-        for (size_t p = 0; p < P; ++p)
-            vpairs[p] = VerifyPair{ctx->images[pairs[2 * (begin + (int)p)]].kxy, ctx->images[pairs[2 * (begin + (int)p) + 1]].kxy};
-        HIPCHK(ctx, SC.d_vf_pairs.ensure(P * sizeof(VerifyPair)));
-        HIPCHK(ctx, SC.d_vf_x1.ensure(oe * 4));
-        HIPCHK(ctx, SC.d_vf_y1.ensure(oe * 4));
-        HIPCHK(ctx, SC.d_vf_x2.ensure(oe * 4));
-        HIPCHK(ctx, SC.d_vf_y2.ensure(oe * 4));
-        HIPCHK(ctx, SC.d_vf_hyp.ensure(P * (size_t)hprm.max_iters * 4));
-        HIPCHK(ctx, SC.d_vf_best_it.ensure(P * 4));
-        HIPCHK(ctx, SC.d_vf_best_count.ensure(P * 4));
-        HIPCHK(ctx, SC.d_ve_state.ensure((3 * P + 2) * 4));   // state[P] | two pair lists [P] | their two counts
-        HIPCHK(ctx, SC.d_ve_stats.ensure(sizeof(VerifyEStats)));
-        HIPCHK(ctx, SC.d_st2_qt.ensure(oe * sizeof(int2)));
-        HIPCHK(ctx, SC.d_st2_d.ensure(oe * 4));
-        HIPCHK(ctx, SC.d_counts2.ensure(P * 4));
-        HIPCHK(ctx, hipMemcpyAsync(SC.d_vf_pairs.p, vpairs.data(), P * sizeof(VerifyPair), hipMemcpyHostToDevice, SC.stream));
-        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_state.p, 0, (3 * P + 2) * 4, SC.stream));
-        HIPCHK(ctx, hipMemsetAsync(SC.d_ve_stats.p, 0, sizeof(VerifyEStats), SC.stream));
-        hipEvent_t v0 = get_event(ctx, ev_base + 6), v1 = get_event(ctx, ev_base + 7);
-        if (!v0 || !v1) return fail(ctx, MSFM_E_DEVICE, "hipEventCreate failed");
-        HIPCHK(ctx, hipEventRecord(v0, SC.stream));
-        const PairDesc* dp = SC.d_pairs.as<PairDesc>();
-        const int* d_counts = SC.d_counts.as<int>();
-        float *x1 = SC.d_vf_x1.as<float>(), *y1 = SC.d_vf_y1.as<float>(), *x2 = SC.d_vf_x2.as<float>(), *y2 = SC.d_vf_y2.as<float>();
-        hipLaunchKernelGGL(vf_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, SC.d_vf_pairs.as<VerifyPair>(), d_counts,
-                           (const int2*)SC.d_st_qt.as<int2>(), x1, y1, x2, y2);
-        HIPCHK(ctx, hipGetLastError());
-        VerifyEStats* stats = SC.d_ve_stats.as<VerifyEStats>();
-        int* state = SC.d_ve_state.as<int>();
+    // the staged loop (msfm_verify_staged.hip.h): decide at r = -1, then round r and decide r for each round.  launch_round(grid,
+    // list, stats) launches the model's round kernel for prm.round on a persistent grid of groups_per_cu workgroups per CU.
+    template <int kSample, int kRound, class LaunchRound>
+    int issue_rounds(size_t P, int groups_per_cu, StagedParams& prm, LaunchRound launch_round) {
+        StagedStats* stats = SC.d_staged_stats.as<StagedStats>();
+        int* state = SC.d_staged_state.as<int>();
         int* list = state + P;
-        const int rounds = (hprm.max_iters + kVhRound - 1) / kVhRound;
-        const unsigned grid = (unsigned)std::min<size_t>(P, (size_t)kVhGroupsPerCU * (size_t)std::max(1, ctx->cu_count));
+        const int rounds = (prm.max_iters + kRound - 1) / kRound;
+        const unsigned grid = (unsigned)std::min<size_t>(P, (size_t)groups_per_cu * (size_t)std::max(1, ctx->cu_count));
         for (int r = -1; r < rounds; ++r) {
+            prm.round = r;
             if (r >= 0) {
-                hprm.round = r;
-                hipLaunchKernelGGL(vh_round_kernel, dim3(grid), dim3(kVhRound), 0, SC.stream, dp, d_counts, (const float*)x1,
-                                   (const float*)y1, (const float*)x2, (const float*)y2, list, (int)P, SC.d_vf_hyp.as<int>(), hprm,
-                                   stats);
+                launch_round(grid, list, stats);
                 HIPCHK(ctx, hipGetLastError());
             }
-            hprm.round = r;
-            hipLaunchKernelGGL((ve_decide_kernel<4, kVhRound>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream, d_counts,
-                               (const int*)SC.d_vf_hyp.as<int>(), (int)P, hprm, state, list, SC.d_vf_best_it.as<int>(),
-                               SC.d_vf_best_count.as<int>(), stats);
+            hipLaunchKernelGGL((staged_decide_kernel<kSample, kRound>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, SC.stream,
+                               (const int*)SC.d_counts.as<int>(), (const int*)SC.d_vf_hyp.as<int>(), (int)P, prm, state, list,
+                               SC.d_vf_best_it.as<int>(), SC.d_vf_best_count.as<int>(), stats);
             HIPCHK(ctx, hipGetLastError());
         }
-        hipLaunchKernelGGL(vh_mask_compact_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts,
-                           (const int2*)SC.d_st_qt.as<int2>(), (const float*)SC.d_st_d.as<float>(), (const float*)x1, (const float*)y1,
-                           (const float*)x2, (const float*)y2, (const int*)SC.d_vf_best_it.as<int>(), hprm, SC.d_st2_qt.as<int2>(),
-                           SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(v1, SC.stream));
         return MSFM_OK;
     }
 
@@ -524,12 +467,12 @@ struct MatchJob {
             float vms = 0.f;
             HIPCHK(ctx, hipEventElapsedTime(&vms, ctx->ev_pool[w.ev_base + 6], ctx->ev_pool[w.ev_base + 7]));
             SC.prof.verify_ms += vms;
-            if (ctx->verify_model == MSFM_VERIFY_ESSENTIAL || ctx->verify_model == MSFM_VERIFY_HOMOGRAPHY) {   // (the stream has been synchronised above)
-                VerifyEStats st = {};
-                HIPCHK(ctx, hipMemcpyAsync(&st, SC.d_ve_stats.p, sizeof(st), hipMemcpyDeviceToHost, SC.stream));
+            if (staged()) {   // (the stream has been synchronised above)
+                StagedStats st = {};
+                HIPCHK(ctx, hipMemcpyAsync(&st, SC.d_staged_stats.p, sizeof(st), hipMemcpyDeviceToHost, SC.stream));
                 HIPCHK(ctx, hipStreamSynchronize(SC.stream));   // (on this set's stream: the other sets' sub-batches stay in flight)
-                ctx->ve_solved += (long long)st.solved;
-                ctx->ve_rounds = std::max(ctx->ve_rounds, st.rounds);
+                ctx->staged_solved += (long long)st.solved;
+                ctx->staged_rounds = std::max(ctx->staged_rounds, st.rounds);
             }
         }
         SC.prof.sub_batches += 1;

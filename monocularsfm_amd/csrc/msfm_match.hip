@@ -331,7 +331,9 @@ int drain_streams(msfm_ctx* ctx) {
 
 }  // namespace
 
+extern "C++" {   // (MatchJob has member templates)
 #include "msfm_job.hip.h"
+}
 
 namespace {
 // behind an exception caught at the C ABI (msfm_guard.h): the text for msfm_last_error, nothing left in flight, no series left open
@@ -433,8 +435,8 @@ int msfm_set_verification_model(msfm_ctx* ctx, int model, const msfm_camera* cam
 int msfm_get_verification_stats(const msfm_ctx* ctx, int64_t* hypotheses_solved, int* rounds) {
     MSFM_API_BEGIN(nullptr)
     if (!ctx) return MSFM_E_INVALID;
-    if (hypotheses_solved) *hypotheses_solved = ctx->ve_solved;
-    if (rounds) *rounds = ctx->ve_rounds;
+    if (hypotheses_solved) *hypotheses_solved = ctx->staged_solved;
+    if (rounds) *rounds = ctx->staged_rounds;
     return MSFM_OK;
     MSFM_API_END
 }

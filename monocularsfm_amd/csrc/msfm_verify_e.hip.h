@@ -3,17 +3,13 @@
 // msfm_verify.hip.h, between the match epilogue and the CSR gather.  The arithmetic is msfm_emat.h, shared with the host twin
 // (host/GeometricVerification.cpp, EssentialRansacMask): the same bits.
 //
-// STAGED: the host launches the rounds r = 0, 1, .. of kVeRound hypotheses each (MatchJob::issue, no host wait in between);
-//   ve_decide_kernel   one thread per pair replays the sequential stopping rule (replay_adaptive<5>) over the counts so far, marks
-//                      the pair decided when the loop ended before it needed a count not yet computed, and appends the undecided
-//                      pairs to the list of the next round (r = -1: every pair with >= 5 matches, no replay);
-//   ve_round_kernel    a workgroup per (listed pair, round) -- a grid of two workgroups per CU walks the list, so a round with
-//                      nothing left costs one short dispatch, not one workgroup per pair: one lane per hypothesis solves it with
-//                      its workspace in LDS, then the pair's matches are staged through LDS in chunks and each lane counts the
-//                      inliers of each of its solutions.
-// The replay never reads a count beyond its stopping point, so the result equals scoring all max_iters hypotheses; the last
-// round reaches max_iters, where every pair is decided.  ve_mask_compact_kernel then re-solves the winner, picks its best
-// solution (lowest index among equal counts), and compacts the pair's inliers in order.  No refit (findEssentialMat has none).
+// STAGED (msfm_verify_staged.hip.h), in rounds of kVeRound hypotheses with the sample size 5:
+//   ve_points_kernel         the normalised, undistorted coordinates of every staged match, once;
+//   ve_round_kernel          a workgroup per (listed pair, round) -- a grid of two workgroups per CU walks the list: one lane per
+//                            hypothesis solves it with its workspace in LDS, then the pair's matches are staged through LDS in
+//                            chunks and each lane counts the inliers of each of its solutions (its count: the largest);
+//   ve_mask_compact_kernel   re-solves the winner, picks its best solution (lowest index among equal counts), and compacts the
+//                            pair's inliers in order.  No refit (findEssentialMat has none).
 //
 // LDS, not registers: the solver's 10 x 20 elimination alone is 200 doubles per hypothesis.  ve_round_kernel keeps the
 // kWork = 296-double workspace of each of its lanes in LDS, lane-interleaved, beside a 4 KiB match chunk and the per-solution
@@ -23,27 +19,14 @@
 // still stops after one round (the stopping rule needs ~6 hypotheses at 90 % inliers); a low-inlier one runs max_iters / 32 rounds.
 #pragma once
 #include "msfm_emat.h"
-#include "msfm_kernels.hip.h"
+#include "msfm_verify.hip.h"
+#include "msfm_verify_staged.hip.h"
 
 namespace msfm {
 
 constexpr int kVeRound = 32;    // hypotheses per round = lanes of a ve_round_kernel workgroup
 constexpr int kVeGroupsPerCU = 2;   // ve_round_kernel workgroups resident per CU (LDS-bound)
 constexpr int kVeChunk = 128;   // matches staged in LDS at a time (4 double arrays = 4 KiB)
-
-struct VerifyEParams {
-    double thr2;                // (threshold / ((fx + fy) / 2))^2
-    double confidence;
-    int max_iters;
-    int round;
-    unsigned long long seed;
-};
-
-struct VerifyEStats {           // per scratch set, zeroed per sub-batch
-    unsigned long long solved;  // hypotheses solved
-    int rounds;                 // rounds any pair of the sub-batch ran
-    int pad;
-};
 
 // normalised, undistorted coordinates of every staged match, once
 __global__ void ve_points_kernel(const PairDesc* __restrict__ pairs, const VerifyPair* __restrict__ vp, const int* __restrict__ counts,
@@ -66,7 +49,7 @@ __global__ __launch_bounds__(kVeRound) void ve_round_kernel(const PairDesc* __re
                                                             const double* __restrict__ x1, const double* __restrict__ y1,
                                                             const double* __restrict__ x2, const double* __restrict__ y2,
                                                             int* __restrict__ list, int n_pairs, int* __restrict__ hyp_counts,
-                                                            VerifyEParams prm, VerifyEStats* __restrict__ stats) {
+                                                            StagedParams prm, StagedStats* __restrict__ stats) {
     MSFM_TAIL_PRIO();
     using namespace msfm_emat;
     __shared__ double ws[kWork * kVeRound];
@@ -116,46 +99,11 @@ __global__ __launch_bounds__(kVeRound) void ve_round_kernel(const PairDesc* __re
     if (solved) atomicAdd(&stats->solved, solved);
 }
 
-// after round prm.round (-1: before round 0): the stopping rule over the counts so far, and the list of the next round.  One thread
-// per pair.  kSample / kRound: 5 / kVeRound here, 4 / kVhRound for the homography (msfm_verify_h.hip.h).
-template <int kSample, int kRound>
-__global__ void ve_decide_kernel(const int* __restrict__ counts, const int* __restrict__ hyp_counts, int n_pairs, VerifyEParams prm,
-                                 int* __restrict__ state, int* __restrict__ list, int* __restrict__ best_it, int* __restrict__ best_count,
-                                 VerifyEStats* __restrict__ stats) {
-    MSFM_TAIL_PRIO();
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pairs || state[p] != 0) return;
-    const int n = counts[p];
-    if (n < kSample) {
-        state[p] = 1;
-        best_it[p] = -1;
-        best_count[p] = 0;
-        return;
-    }
-    if (prm.round >= 0) {
-        const int avail = min((prm.round + 1) * kRound, prm.max_iters);
-        const int* hc = hyp_counts + (long long)p * prm.max_iters;
-        int bc = 0;
-        bool decided = false;
-        const int bi = msfm_fmat::replay_adaptive<kSample>(n, prm.max_iters, prm.confidence, [&](int it) { return hc[it]; }, &bc, avail, &decided);
-        if (decided) {
-            state[p] = 1;
-            best_it[p] = bi;
-            best_count[p] = bc;
-            atomicMax(&stats->rounds, prm.round + 1);
-            return;
-        }
-    }
-    const int nxt = (prm.round + 1) & 1;
-    const int k = atomicAdd(&list[2 * n_pairs + nxt], 1);
-    list[nxt * n_pairs + k] = p;
-}
-
 // the winner's best solution, its mask, and the ordered compaction of the pair's staged matches.  One wave per pair.
 __global__ __launch_bounds__(64) void ve_mask_compact_kernel(
     const PairDesc* __restrict__ pairs, const int* __restrict__ counts, const int2* __restrict__ st_qt, const float* __restrict__ st_d,
     const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2, const double* __restrict__ y2,
-    const int* __restrict__ best_it, VerifyEParams prm, int2* __restrict__ out_qt, float* __restrict__ out_d, int* __restrict__ out_counts) {
+    const int* __restrict__ best_it, StagedParams prm, int2* __restrict__ out_qt, float* __restrict__ out_d, int* __restrict__ out_counts) {
     MSFM_TAIL_PRIO();
     using namespace msfm_emat;
     __shared__ double ws[kWork];
@@ -187,7 +135,6 @@ __global__ __launch_bounds__(64) void ve_mask_compact_kernel(
         }
         __syncthreads();
     }
-    // ordered compaction (the one of vf_mask_compact_kernel, for a single wave)
     double E[9];
     if (run)
 #pragma unroll
@@ -197,13 +144,7 @@ __global__ __launch_bounds__(64) void ve_mask_compact_kernel(
         const int i = i0 + tid;
         bool keep = false;
         if (run && i < n) keep = sampson(E, x1[base + i], y1[base + i], x2[base + i], y2[base + i]) <= prm.thr2;
-        const unsigned long long bal = __ballot(keep);
-        const int pos = pos0 + __popcll(bal & ((1ull << tid) - 1ull));
-        if (keep) {
-            out_qt[base + pos] = st_qt[base + i];
-            out_d[base + pos] = st_d[base + i];
-        }
-        pos0 += __popcll(bal);
+        pos0 = staged_compact_step(keep, i, pos0, base, tid, st_qt, st_d, out_qt, out_d);
     }
     if (tid == 0) out_counts[p] = pos0;
 }

@@ -3,18 +3,13 @@
 // planar scenes and rotation-only views, where an epipolar model is degenerate.  The arithmetic is msfm_hmat.h, shared with the
 // host twin (host/GeometricVerification.cpp, HomographyRansacMask): the same bits.
 //
-// STAGED like the essential matrix (msfm_verify_e.hip.h), in rounds r = 0, 1, .. of kVhRound hypotheses each, launched back to
-// back by MatchJob::issue_homography (no host wait in between):
+// STAGED (msfm_verify_staged.hip.h), in rounds of kVhRound hypotheses with the sample size 4:
 //   vf_points_kernel          (msfm_verify.hip.h) the pixel coordinates of every staged match, once;
-//   ve_decide_kernel<4, ..>   one thread per pair replays the sequential stopping rule (replay_adaptive<4>) over the counts so far,
-//                             marks the pair decided when the loop ended before it needed a count not yet computed, and lists the
-//                             undecided pairs for the next round (r = -1: every pair with >= 4 matches, no replay);
 //   vh_round_kernel           a wave per (listed pair, round) -- a persistent grid of kVhGroupsPerCU waves per CU walks the list:
 //                             one lane per hypothesis samples, checks and solves it in registers, then the pair's matches are staged
 //                             through LDS in chunks and each lane counts its inliers;
 //   vh_mask_compact_kernel    every lane of a wave re-solves the winner (the same bits in each) and the pair's inliers are
 //                             compacted in order into the second staging buffer.
-// The replay never reads a count beyond its stopping point, so the result equals scoring all max_iters hypotheses.
 //
 // Registers, not LDS: the 8 x 9 system is 72 doubles, and with every loop of msfm_hmat::four_point unrolled each index is a
 // compile-time constant, so the solve lives in VGPRs with no scratch (DESIGN.md 11 quotes tools/kernel_resources.py).  The round is
@@ -24,7 +19,7 @@
 #pragma once
 #include "msfm_hmat.h"
 #include "msfm_verify.hip.h"
-#include "msfm_verify_e.hip.h"
+#include "msfm_verify_staged.hip.h"
 
 namespace msfm {
 
@@ -38,7 +33,7 @@ __global__ __launch_bounds__(kVhRound) void vh_round_kernel(const PairDesc* __re
                                                             const float* __restrict__ x1, const float* __restrict__ y1,
                                                             const float* __restrict__ x2, const float* __restrict__ y2,
                                                             int* __restrict__ list, int n_pairs, int* __restrict__ hyp_counts,
-                                                            VerifyEParams prm, VerifyEStats* __restrict__ stats) {
+                                                            StagedParams prm, StagedStats* __restrict__ stats) {
     MSFM_TAIL_PRIO();
     __shared__ float sx1[kVhChunk], sy1[kVhChunk], sx2[kVhChunk], sy2[kVhChunk];
     const int t = threadIdx.x;
@@ -81,7 +76,7 @@ __global__ __launch_bounds__(kVhRound) void vh_round_kernel(const PairDesc* __re
 __global__ __launch_bounds__(64) void vh_mask_compact_kernel(
     const PairDesc* __restrict__ pairs, const int* __restrict__ counts, const int2* __restrict__ st_qt, const float* __restrict__ st_d,
     const float* __restrict__ x1, const float* __restrict__ y1, const float* __restrict__ x2, const float* __restrict__ y2,
-    const int* __restrict__ best_it, VerifyEParams prm, int2* __restrict__ out_qt, float* __restrict__ out_d, int* __restrict__ out_counts) {
+    const int* __restrict__ best_it, StagedParams prm, int2* __restrict__ out_qt, float* __restrict__ out_d, int* __restrict__ out_counts) {
     MSFM_TAIL_PRIO();
     const int p = blockIdx.x;
     const int n = counts[p];
@@ -90,19 +85,12 @@ __global__ __launch_bounds__(64) void vh_mask_compact_kernel(
     const int bi = best_it[p];
     double H[9];
     const bool run = n >= 4 && bi >= 0 && msfm_hmat::hypothesis(x1 + base, y1 + base, x2 + base, y2 + base, n, prm.seed, bi, H);
-    // ordered compaction (the one of vf_mask_compact_kernel, for a single wave)
     int pos0 = 0;
     for (int i0 = 0; i0 < n; i0 += 64) {
         const int i = i0 + tid;
         bool keep = false;
         if (run && i < n) keep = msfm_hmat::reproj_error(H, x1[base + i], y1[base + i], x2[base + i], y2[base + i]) <= prm.thr2;
-        const unsigned long long bal = __ballot(keep);
-        const int pos = pos0 + __popcll(bal & ((1ull << tid) - 1ull));
-        if (keep) {
-            out_qt[base + pos] = st_qt[base + i];
-            out_d[base + pos] = st_d[base + i];
-        }
-        pos0 += __popcll(bal);
+        pos0 = staged_compact_step(keep, i, pos0, base, tid, st_qt, st_d, out_qt, out_d);
     }
     if (tid == 0) out_counts[p] = pos0;
 }

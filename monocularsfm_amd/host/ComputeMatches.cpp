@@ -124,8 +124,7 @@ int main(int argc, char** argv) {
             matcher.reset(new BruteFeatureMatcher(database_path));
     }
 
-    if (verification_model == 1) matcher->SetEssentialVerification(camera);
-    if (verification_model == 2) matcher->SetHomographyVerification();
+    matcher->SetVerificationModel(verification_model, camera);
 
     Timer timer;
     timer.Start();

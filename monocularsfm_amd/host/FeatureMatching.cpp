@@ -147,11 +147,9 @@ void FeatureMatcher::OpenDatabaseAndDevice() {
             status[g] = msfm_create(devs[g], &c);
             if (status[g] == MSFM_OK)
                 if (const char* o = std::getenv("MSFM_ACCUM_ORDER")) status[g] = msfm_set_accum_order(c, std::atoi(o));
-            if (status[g] == MSFM_OK && essential_) {
-                const msfm_camera cam = {camera_.fx, camera_.fy, camera_.cx, camera_.cy, camera_.k1, camera_.k2, camera_.p1, camera_.p2};
-                status[g] = msfm_set_verification_model(c, MSFM_VERIFY_ESSENTIAL, &cam);
-            }
-            if (status[g] == MSFM_OK && homography_) status[g] = msfm_set_verification_model(c, MSFM_VERIFY_HOMOGRAPHY, nullptr);
+            const msfm_camera cam = {camera_.fx, camera_.fy, camera_.cx, camera_.cy, camera_.k1, camera_.k2, camera_.p1, camera_.p2};
+            if (status[g] == MSFM_OK)
+                status[g] = msfm_set_verification_model(c, verification_model_, verification_model_ == MSFM_VERIFY_ESSENTIAL ? &cam : nullptr);
             // An ordinal listed k times (the tests' way to run the fan-out on a one-GPU box): every context would size its scratch
             // for a quarter of the device's free memory on its own -- four of them on one MI355X ran out of memory at config-4 scale.
             // They share the default budget instead (MSFM_SCRATCH_MIB still overrides: it is read at msfm_create, this only applies without it).
@@ -471,12 +469,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                     }
                     if (host_verify) {
                         kept.clear();   // (FilterMatches appends, and returns without touching the list for an empty input)
-                        if (essential_)
-                            FilterMatchesEssential(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, camera_, &kept);
-                        else if (homography_)
-                            FilterMatchesHomography(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept);
-                        else
-                            FilterMatches(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept);
+                        FilterMatches(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept, verification_model_, camera_);
                         list.swap(kept);
                     }
                     ApplyEmissionOptions(emission, id1, id2, &list);

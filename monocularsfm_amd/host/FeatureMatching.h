@@ -39,15 +39,13 @@ public:
     // on the device by default (msfm_match_pairs_verified), by the host twin with MSFM_GEOMETRIC_VERIFICATION=host
     // (GeometricVerification.h; the two give identical lists).
     void SetGeometricVerification(bool on) { geometric_verification_ = on; }
-    // SIFTmatch.verification_model : 1 -- the essential matrix with the reference's camera instead of F, on every device
-    // context (msfm_set_verification_model) or in the host twin (FilterMatchesEssential).  Call before RunMatching.
-    void SetEssentialVerification(const CameraIntrinsics& camera) {
-        essential_ = true;
+    // SIFTmatch.verification_model: MSFM_VERIFY_FUNDAMENTAL (the default, F as above), MSFM_VERIFY_ESSENTIAL (the essential
+    // matrix with the reference's camera) or MSFM_VERIFY_HOMOGRAPHY (planar scenes, rotation-only views; the camera is not read),
+    // on every device context (msfm_set_verification_model) or in the host twin (FilterMatches).  Call before RunMatching.
+    void SetVerificationModel(int model, const CameraIntrinsics& camera) {
+        verification_model_ = model;
         camera_ = camera;
     }
-    // SIFTmatch.verification_model : 2 -- the homography instead of F (planar scenes, rotation-only views), on every device
-    // context or in the host twin (FilterMatchesHomography).  Call before RunMatching.
-    void SetHomographyVerification() { homography_ = true; }
 
 protected:
     void OpenDatabaseAndDevice();
@@ -66,9 +64,8 @@ protected:
     bool cross_check_;
     bool geometric_verification_ = true;
     bool verification_on_host_ = false;  // MSFM_GEOMETRIC_VERIFICATION=host
-    bool essential_ = false;             // SetEssentialVerification
-    CameraIntrinsics camera_ = {};
-    bool homography_ = false;            // SetHomographyVerification
+    int verification_model_ = MSFM_VERIFY_FUNDAMENTAL;   // SetVerificationModel
+    CameraIntrinsics camera_ = {};                       // (model 1 only)
     Database* database_ = nullptr;
     // One context per GPU: MSFM_DEVICE (default 0), MSFM_DEVICES="0,1,..." or "all".  The whole descriptor store is replicated on
     // each; the pairs of a run are dealt to the devices in small cost-balanced blocks, round-robin, so that every device's results

@@ -71,8 +71,9 @@ std::vector<unsigned char> FundamentalRansacMask(const std::vector<Point2f>& pts
     return best;
 }
 
-// A literal sequential loop: hypothesis it is solved and scored when the loop reaches it; its count is the largest over its
-// solutions.  The winning solution (the lowest index among equal counts) gives the mask.
+// The sequential loop of msfm_fmat::replay_adaptive<5> over lazily scored hypotheses: hypothesis it is solved and scored when the
+// loop reaches it; its count is the largest over its solutions.  The winning solution (the lowest index among equal counts) gives
+// the mask.
 std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
                                                const CameraIntrinsics& camera, double threshold, double confidence,
                                                int max_iters, unsigned long long seed) {
@@ -87,7 +88,7 @@ std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1,
     }
     const double f = (camera.fx + camera.fy) * 0.5, t = threshold / f, thr2 = t * t;
     std::vector<double> ws((size_t)kWork);
-    // best solution of hypothesis it: (count, solution index); the solutions stay in ws
+    // best solution of hypothesis it: its count, and (sol) its index; the solutions stay in ws
     auto score = [&](int it, int* sol) {
         const int ns = hypothesis<1>(x1.data(), y1.data(), x2.data(), y2.data(), n, seed, it, ws.data());
         int best = 0, bs = -1;
@@ -100,29 +101,12 @@ std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1,
                 bs = s;
             }
         }
-        *sol = bs;
+        if (sol) *sol = bs;
         return best;
     };
-    int best_count = 0, best_it = -1, iters = max_iters;
-    for (int it = 0; it < iters; ++it) {
-        int sol;
-        const int c = score(it, &sol);
-        if (c > best_count) {
-            best_count = c;
-            best_it = it;
-            const double w = (double)c / n;
-            const double w2 = w * w, w4 = w2 * w2;
-            double q = 1.0 - w4 * w;
-            if (q < 1e-300) q = 1e-300;
-            const double need = msfm_fmat::det_log(1.0 - confidence) / msfm_fmat::det_log(q);
-            if (need > 0.0 && need < (double)iters) {
-                int ni = (int)need;
-                if ((double)ni < need) ni += 1;
-                iters = ni > it + 1 ? ni : it + 1;
-            }
-        }
-    }
-    if (best_count < 5 || best_it < 0) return {};
+    int best_count = 0;
+    const int best_it = msfm_fmat::replay_adaptive<5>(n, max_iters, confidence, [&](int it) { return score(it, nullptr); }, &best_count);
+    if (best_it < 0) return {};
     int sol;
     score(best_it, &sol);
     std::vector<unsigned char> mask((size_t)n, 0);
@@ -131,8 +115,8 @@ std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1,
     return mask;
 }
 
-// A literal sequential loop: hypothesis it is sampled, checked, solved and scored when the loop reaches it (a rejected sample
-// counts 0).  The winner's inliers are the mask.
+// The sequential loop of msfm_fmat::replay_adaptive<4> over lazily scored hypotheses: hypothesis it is sampled, checked, solved
+// and scored when the loop reaches it (a rejected sample counts 0).  The winner's inliers are the mask.
 std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
                                                 double threshold, double confidence, int max_iters, unsigned long long seed) {
     using namespace msfm_hmat;
@@ -151,26 +135,13 @@ std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1
         for (size_t i = 0; i < (size_t)n; ++i) c += reproj_error(H, x1[i], y1[i], x2[i], y2[i]) <= thr2 ? 1 : 0;
         return c;
     };
-    int best_count = 0, best_it = -1, iters = max_iters;
-    for (int it = 0; it < iters; ++it) {
+    auto count_at = [&](int it) {
         double H[9];
-        const int c = hypothesis(x1.data(), y1.data(), x2.data(), y2.data(), n, seed, it, H) ? count(H) : 0;
-        if (c > best_count) {
-            best_count = c;
-            best_it = it;
-            const double w = (double)c / n;
-            const double w2 = w * w;
-            double q = 1.0 - w2 * w2;
-            if (q < 1e-300) q = 1e-300;
-            const double need = msfm_fmat::det_log(1.0 - confidence) / msfm_fmat::det_log(q);
-            if (need > 0.0 && need < (double)iters) {
-                int ni = (int)need;
-                if ((double)ni < need) ni += 1;
-                iters = ni > it + 1 ? ni : it + 1;
-            }
-        }
-    }
-    if (best_count < 4 || best_it < 0) return {};
+        return hypothesis(x1.data(), y1.data(), x2.data(), y2.data(), n, seed, it, H) ? count(H) : 0;
+    };
+    int best_count = 0;
+    const int best_it = msfm_fmat::replay_adaptive<4>(n, max_iters, confidence, count_at, &best_count);
+    if (best_it < 0) return {};
     double H[9];
     hypothesis(x1.data(), y1.data(), x2.data(), y2.data(), n, seed, best_it, H);
     std::vector<unsigned char> mask((size_t)n, 0);
@@ -179,7 +150,8 @@ std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1
 }
 
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
-                   const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches) {
+                   const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches, int model,
+                   const CameraIntrinsics& camera) {
     if (kpts1.empty() || matches.empty()) return;  // FeatureUtils.cpp:181-184
     std::vector<Point2f> a, b;
     a.reserve(matches.size());
@@ -188,38 +160,9 @@ void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoin
         a.push_back(Point2f{kpts1[(size_t)m.queryIdx].x, kpts1[(size_t)m.queryIdx].y});
         b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
     }
-    const std::vector<unsigned char> mask = FundamentalRansacMask(a, b, 3.0, 0.99);
-    for (size_t i = 0; i < mask.size(); ++i)
-        if (mask[i]) prune_matches->push_back(matches[i]);
-}
-
-void FilterMatchesEssential(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
-                            const std::vector<DMatch>& matches, const CameraIntrinsics& camera,
-                            std::vector<DMatch>* prune_matches) {
-    if (kpts1.empty() || matches.empty()) return;
-    std::vector<Point2f> a, b;
-    a.reserve(matches.size());
-    b.reserve(matches.size());
-    for (const DMatch& m : matches) {
-        a.push_back(Point2f{kpts1[(size_t)m.queryIdx].x, kpts1[(size_t)m.queryIdx].y});
-        b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
-    }
-    const std::vector<unsigned char> mask = EssentialRansacMask(a, b, camera, 3.0, 0.99);
-    for (size_t i = 0; i < mask.size(); ++i)
-        if (mask[i]) prune_matches->push_back(matches[i]);
-}
-
-void FilterMatchesHomography(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
-                             const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches) {
-    if (kpts1.empty() || matches.empty()) return;
-    std::vector<Point2f> a, b;
-    a.reserve(matches.size());
-    b.reserve(matches.size());
-    for (const DMatch& m : matches) {
-        a.push_back(Point2f{kpts1[(size_t)m.queryIdx].x, kpts1[(size_t)m.queryIdx].y});
-        b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
-    }
-    const std::vector<unsigned char> mask = HomographyRansacMask(a, b, 3.0, 0.99);
+    const std::vector<unsigned char> mask = model == MSFM_VERIFY_ESSENTIAL    ? EssentialRansacMask(a, b, camera, 3.0, 0.99)
+                                            : model == MSFM_VERIFY_HOMOGRAPHY ? HomographyRansacMask(a, b, 3.0, 0.99)
+                                                                              : FundamentalRansacMask(a, b, 3.0, 0.99);
     for (size_t i = 0; i < mask.size(); ++i)
         if (mask[i]) prune_matches->push_back(matches[i]);
 }

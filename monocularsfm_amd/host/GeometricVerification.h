@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "Types.h"
+#include "msfm_match.h"
 
 namespace MonocularSfM {
 
@@ -44,17 +45,11 @@ std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1
                                                 double threshold = 3.0, double confidence = 0.99, int max_iters = 1000,
                                                 unsigned long long seed = 0x5eed5eedULL);
 
-// FeatureUtils::GetAlignedPointsFromMatches + FilterMatches
+// FeatureUtils::GetAlignedPointsFromMatches + FilterMatches, with the model of SIFTmatch.verification_model
+// (msfm_match.h: MSFM_VERIFY_FUNDAMENTAL as the reference, MSFM_VERIFY_ESSENTIAL with `camera`, MSFM_VERIFY_HOMOGRAPHY) and the
+// reference's constants
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
-                   const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches);
-
-// The same hand-off with EssentialRansacMask (SIFTmatch.verification_model : 1) and the reference's constants
-void FilterMatchesEssential(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
-                            const std::vector<DMatch>& matches, const CameraIntrinsics& camera,
-                            std::vector<DMatch>* prune_matches);
-
-// The same hand-off with HomographyRansacMask (SIFTmatch.verification_model : 2) and the reference's constants
-void FilterMatchesHomography(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
-                             const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches);
+                   const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches,
+                   int model = MSFM_VERIFY_FUNDAMENTAL, const CameraIntrinsics& camera = {});
 
 }  // namespace MonocularSfM
