@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ComputeMatches hot path on MI355X: descriptor-pairs/s (and image-pairs/s).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   (N > 1: either under python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ..., or plain
    `python bench.py --gpus N`: without WORLD_SIZE in the environment the script launches that command itself, one rank per
    GPU, passes rank 0's JSON line through and returns the job's exit code)
@@ -13,15 +13,23 @@ kNN-2 in both directions + ratio + cross-check + distance cut, with the match li
 rank at the end (N > 1: per-pair counts all-reduced, the lists sent over RCCL from HBM to the writer).
 Descriptors are resident in HBM before the timed region.
 
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line (`roofline` comes from the timed steps' own profile).  `--full` adds everything else this script measures:
+the cold end-to-end runs of the ComputeMatches executable (`end_to_end`, before this process touches the GPU) and, after
+the timed steps, the sustained steps, the sweeps-alone pass (`roofline.solo`), the strong-scaling job (`strong_u8`) and the CPU baseline
+(`cpu_baseline`); `--no-e2e`, `--sustained-steps`, `--no-solo`, `--u8-steps`, `--no-cpu-baseline` and `--cpu-budget` shape
+that run and change nothing in a plain one.  --dump-outputs writes the same arrays in both runs: a plain run that dumps also
+runs the strong-scaling job (`--u8-images` of it) once, unmeasured, for its u8_* arrays.
+
 STRONG scaling: the SAME job at every N (the N = 1 line is the BENCH line); the pair list is cut into N contiguous
-cost-balanced ranges, the store is replicated.  `strong_u8` in the same JSON line is the strong-scaling measurement
+cost-balanced ranges, the store is replicated.  `strong_u8` in the same JSON line (--full) is the strong-scaling measurement
 north_star's >= 6x target is stated on: BASELINE configs[3] IN FULL (1329 images x 8192 u8 descriptors, 882 456 pairs,
 5.92e13 descriptor pairs; ~9 s per step on one GPU), one warm-up step + `--u8-steps` (default 1) timed steps at every N --
 strong_u8.value at N = 8 over the value at N = 1 IS that measurement.  `--u8-images M` (< 1329) runs a seeded M-image subset
 instead (tests), 0 skips the job.  `--workload synthetic-u8 --images 1329 --desc 8192` runs it as the main workload.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (sweep 1 of the MFMA prefilter), timed with
-HIP events on the library's own stream inside the timed region; `cpu_baseline` is the CPU oracle ("port": a
+HIP events on the library's own stream inside the timed region; `cpu_baseline` (--full) is the CPU oracle ("port": a
 restatement of the OpenCV BFMatcher path, not OpenCV itself) on a bounded sample of the same pairs, on this box's
 host cores, parallel over image pairs.
 """
@@ -338,7 +346,10 @@ def main():
     ap.add_argument("--desc", type=int, default=None)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--order", type=int, default=0, help="0: OpenCV SSE order (default), 1: AVX2+FMA order")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure as well: end_to_end, the sustained steps, roofline.solo, strong_u8 "
+                         "and cpu_baseline (a plain run skips them all; the options that shape them act under --full only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (cpu_baseline)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo (+ --share-gpu) runs the multi-rank flow on a box with fewer GPUs than ranks")
     ap.add_argument("--share-gpu", action="store_true", help="every rank uses GPU 0 (flow check only: the value is meaningless)")
@@ -347,30 +358,38 @@ def main():
     ap.add_argument("--no-prefilter", action="store_true",
                     help="brute-force exact-order kernel for every pair (same results, ~20x slower)")
     ap.add_argument("--f16-only", action="store_true", help="byte stores on the fp16 matrix cores too (default: integer matrix cores)")
-    ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds the CPU baseline may spend")
     ap.add_argument("--u8-images", type=int, default=1329,
-                    help="images of the strong-scaling job on the 1329 x 8192 u8 config (default: the config in full; fewer = "
+                    help="images of the strong-scaling job (strong_u8 under --full; a plain run only for --dump-outputs) on the 1329 x 8192 u8 config (default: the config in full; fewer = "
                          "a seeded subset); 0 = skip")
     ap.add_argument("--u8-steps", type=int, default=None, help="timed steps of that job (default 1 for the full config, else 2)")
     ap.add_argument("--sustained-steps", type=int, default=200,
-                    help="extra untimed-for-`value` run of this many steps after the K timed ones -> sustained_ms_per_step "
+                    help="--full: extra untimed-for-`value` run of this many steps after the K timed ones -> sustained_ms_per_step "
                          "(the part's clock is set by a power budget: a 1 s burst and a 10 s run differ); 0 = skip")
     ap.add_argument("--super-batch-pairs", type=int, default=0,
                     help="bounded memory: the step's lists are produced and consumed chunk by chunk -- N = 1: the streaming form of the C ABI "
                          "(msfm_match_pairs_begin / _next, one device sub-batch per chunk; the value only switches it on); N > 1: "
                          "ShardedMatcher.match_to_writer_batches with super-batches of this many pairs.  0 = one call, lists resident")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the cold end-to-end run of the ComputeMatches executable (end_to_end)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the cold end-to-end run of the ComputeMatches executable (end_to_end)")
     ap.add_argument("--no-solo", action="store_true",
-                    help="skip the 4 extra steps with the pipeline off that measure the sweeps alone (roofline.solo); for kernel traces")
+                    help="--full: skip the 4 extra steps with the pipeline off that measure the sweeps alone (roofline.solo); for kernel traces")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32 / float64, "
                          "%d MB at most; a seeded sample of the rows of a larger job): offsets, qt, dist of the main workload, "
-                         "u8_offsets, u8_qt, u8_dist of strong_u8" % (DUMP_BYTES >> 20))
+                         "u8_offsets, u8_qt, u8_dist of the strong-scaling job (a plain run runs that job once for them, unmeasured)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.u8_steps is None:
         args.u8_steps = 1 if args.u8_images >= 1329 else 2
+    if not args.full:
+        # a plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the dump, the line.  The
+        # strong-scaling job runs only for the u8_* arrays a dump has always held, and is not measured (no strong_u8)
+        args.no_e2e = args.no_solo = args.no_cpu_baseline = True
+        args.sustained_steps = 0
+        if not args.dump_outputs:
+            args.u8_images = 0
+    u8_wanted = args.u8_images > 1 and args.workload == "south-building" and not args.no_prefilter
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run, rank 0's JSON line
@@ -401,6 +420,22 @@ def main():
             e2e = end_to_end(None, None, n_images=args.images or 128)
         except Exception as e:  # noqa: BLE001  (a failure here must not take the headline line with it)
             e2e = {"error": "%s: %s" % (type(e).__name__, e)}
+
+    # A plain run that dumps needs the strong-scaling job's images for its u8_* arrays only: they are generated (13 s for the
+    # config in full, one host core) on a thread beside this process's set-up, and waited for before the first warm-up step
+    u8_prefetch = None
+    if not args.full and u8_wanted and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+        import threading
+        from monocularsfm_amd import synth
+        u8_prefetch = {}
+
+        def u8_generate():
+            try:
+                u8_prefetch["job"] = synth.job("synthetic-u8", min(args.u8_images, 1329), 8192, seed=1329)
+            except BaseException as e:  # noqa: BLE001  (raised again where the images are used)
+                u8_prefetch["error"] = e
+        u8_prefetch["thread"] = threading.Thread(target=u8_generate, daemon=True)
+        u8_prefetch["thread"].start()
 
     import torch
     import torch.distributed as dist
@@ -579,6 +614,8 @@ def main():
         last_prof.update(p)
 
     dump_bytes = DUMP_BYTES if args.dump_outputs else 0
+    if u8_prefetch is not None:   # (nothing runs beside the warm-up and the timed steps)
+        u8_prefetch["thread"].join()
     dt, result, upload_s, per_rank, n_rows = run_job(imgs, pairs, args.steps, args.warmup, collect, args.sustained_steps,
                                                      dump_bytes=dump_bytes * 3 // 4, **main_kw)
     outputs = dict(run_job.outputs or {})
@@ -715,7 +752,8 @@ def main():
             out["roofline"] = exact
 
     # ---- the strong-scaling job of north_star's >= 6x target: BASELINE configs[3] (1329 x 8192 u8), in full by default --------
-    def u8_job():
+    def u8_job(outputs_only=False):
+        """-> the strong_u8 block.  outputs_only: one untimed step for the u8_* arrays of --dump-outputs, nothing measured -> None."""
         full = args.u8_images >= 1329
         n_img = min(args.u8_images, 1329)
         t_gen = time.perf_counter()
@@ -734,9 +772,18 @@ def main():
             u_imgs = [stack[i] for i in range(n_img)]
             u_pairs = synth.all_pairs(n_img)
             u_name = "synthetic u8 descriptors: %d images x 8192 desc, brute-force all pairs" % n_img
+        elif u8_prefetch is not None:
+            if "error" in u8_prefetch:
+                raise u8_prefetch["error"]
+            u_imgs, u_pairs, u_name = u8_prefetch.pop("job")
         else:
             u_imgs, u_pairs, u_name = synth.job("synthetic-u8", n_img, 8192, seed=1329)
         gen_s = time.perf_counter() - t_gen
+        if outputs_only:
+            # the lists of a step do not depend on the steps before it: one step, no warm-up, the same arrays as a --full run's
+            run_job(u_imgs, u_pairs, 1, 0, None, solo_pass=False, dump_bytes=dump_bytes // 4, max_distance=1e9)
+            outputs.update(("u8_" + k, v) for k, v in (run_job.outputs or {}).items())
+            return None
         u_acc = {"approx_kernel_ms": 0.0, "prefilter_descriptor_pairs": 0, "sweep1_i8_launches": 0, "sub_batches": 0,
                  "approx_kernel_launches": 0, "order_sensitive_rows": 0, "candidates": 0}
 
@@ -778,7 +825,9 @@ def main():
             "full_config_seconds_at_this_rate": 882456 * 8192.0 * 8192.0 / u_val,
         }
 
-    if args.u8_images > 1 and args.workload == "south-building" and not args.no_prefilter:
+    if u8_wanted and not args.full:
+        u8_job(outputs_only=True)
+    elif u8_wanted:
         if world == 1:
             try:   # (a failure of the second job must not take the headline line with it)
                 out["strong_u8"] = u8_job()

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--images", "24", "--cpu-budget", "2", "--u8-images", "6"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--images", "24", "--cpu-budget", "2", "--u8-images", "6", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line on stdout"
@@ -64,13 +65,45 @@ def test_bench_line_contract():
     assert d["pcie_inclusive"]["upload_ms"] > 0
 
 
+def test_plain_bench_run_is_lean(tmp_path):
+    """Without --full the run is set-up, warm-up, the timed steps, the dump and the line: none of the extra measurements, the
+    headline keys as in a --full run, and the same dumped arrays, bit for bit, as a --full run writes (the strong-scaling job's
+    among them: a plain run that dumps runs that job once, unmeasured)."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--images", "24", "--u8-images", "6"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-e2e", "--no-cpu-baseline", "--sustained-steps", "3"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, (name, r.stderr[-2000:])
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, name
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[k] == full[k], k
+    assert abs(plain["value"] - plain["config"]["descriptor_pairs_per_step"] / (plain["ms_per_step"] * 1e-3)) < 1e-6 * plain["value"]
+    for k in ("strong_u8", "cpu_baseline", "gpu_over_cpu", "end_to_end"):
+        assert k not in plain, k
+    assert plain["sustained_ms_per_step"] is None and plain["sustained_steps"] == 0 and plain["roofline"]["solo"] is None
+    assert full["strong_u8"]["value"] > 0 and full["sustained_ms_per_step"] > 0 and full["roofline"]["solo"] is not None
+    assert plain["config"]["matches_per_step"] == full["config"]["matches_per_step"] > 0
+    assert plain["exchange_checksum"] == full["exchange_checksum"]
+    names = {"offsets", "qt", "dist", "u8_offsets", "u8_qt", "u8_dist"}
+    assert set(plain["dumped_outputs"]["arrays"]) == set(full["dumped_outputs"]["arrays"]) == names
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(os.listdir(tmp_path / "full")) == sorted(k + ".npy" for k in names)
+    for k in sorted(names):
+        a, b = np.load(tmp_path / "plain" / (k + ".npy")), np.load(tmp_path / "full" / (k + ".npy"))
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
+
+
 def test_bench_two_ranks_sharing_the_gpu():
     """The multi-rank flow of bench.py (partition, per-rank match, count all_reduce, send of the lists to the writer)
     with two ranks on this box's one GPU over gloo: RCCL itself needs a GPU per rank (driver's SCALE run)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--images", "20", "--u8-images", "5", "--backend", "gloo", "--share-gpu"],
+                        "--warmup", "1", "--images", "20", "--u8-images", "5", "--backend", "gloo", "--share-gpu", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -92,7 +125,7 @@ def test_bench_gpus_2_launches_itself():
     script becomes the launcher, rank 0's JSON line is the only line on stdout, the exit code is the job's."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--images", "20", "--u8-images", "5", "--backend", "gloo", "--share-gpu"],
+                        "--images", "20", "--u8-images", "5", "--backend", "gloo", "--share-gpu", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

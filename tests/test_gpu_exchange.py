@@ -88,7 +88,7 @@ def test_fetch_matches_device_without_results_is_a_state_error(built_lib):
 
 def _bench(*extra, env=None):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--images", "24", "--u8-images", "6", "--no-cpu-baseline", *extra],
+                        "--images", "24", "--u8-images", "6", "--no-cpu-baseline", "--full", *extra],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -3,7 +3,7 @@
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out; mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --u8-images 0"
+BENCH="python $ROOT/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --u8-images 0"
 cd /tmp; rm -rf $OUT/prof_stats
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_stats -- $BENCH > $OUT/prof_stats.log 2>&1; echo "stats rc=$?"
 cd $ROOT

@@ -12,14 +12,14 @@ rocm-smi --showpower --showclocks --showmaxpower > $OUT/smi_idle.txt 2>&1
 ./tools/power_sampler 45 20 > $OUT/power_f16.csv 2>$OUT/power_f16.err &
 SP=$!
 sleep 3
-timeout 300 python bench.py --steps 400 --warmup 3 --no-cpu-baseline --u8-images 0 --sustained-steps 0 > $OUT/bench_400.json 2> $OUT/bench_400.err; echo "bench400 rc=$?"
+timeout 300 python bench.py --full --steps 400 --warmup 3 --no-cpu-baseline --u8-images 0 --sustained-steps 0 > $OUT/bench_400.json 2> $OUT/bench_400.err; echo "bench400 rc=$?"
 sleep 3
 kill $SP 2>/dev/null; wait $SP 2>/dev/null
 # (b) byte job on the integer cores, sustained
 ./tools/power_sampler 40 20 > $OUT/power_i8.csv 2>$OUT/power_i8.err &
 SP=$!
 sleep 3
-timeout 300 python bench.py --workload synthetic-u8 --images 192 --desc 8192 --steps 100 --warmup 2 --no-cpu-baseline --sustained-steps 0 > $OUT/bench_i8_100.json 2> $OUT/bench_i8_100.err; echo "bench i8 rc=$?"
+timeout 300 python bench.py --full --workload synthetic-u8 --images 192 --desc 8192 --steps 100 --warmup 2 --no-cpu-baseline --sustained-steps 0 > $OUT/bench_i8_100.json 2> $OUT/bench_i8_100.err; echo "bench i8 rc=$?"
 sleep 2
 kill $SP 2>/dev/null; wait $SP 2>/dev/null
 # (c) MFMA-only / VALU-only loops
@@ -33,8 +33,8 @@ kill $SP 2>/dev/null; wait $SP 2>/dev/null
 export TMPDIR=/tmp
 cd /tmp
 rm -rf $OUT/pmc_grbm
-timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT --output-format csv -d $OUT/pmc_grbm -- python $ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --u8-images 0 --sustained-steps 0 > $OUT/pmc_grbm.log 2>&1; echo "grbm rc=$?"
-timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/pmc_grbm_trace -- python $ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --u8-images 0 --sustained-steps 0 > $OUT/pmc_grbm_trace.log 2>&1
+timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT --output-format csv -d $OUT/pmc_grbm -- python $ROOT/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --u8-images 0 --sustained-steps 0 > $OUT/pmc_grbm.log 2>&1; echo "grbm rc=$?"
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/pmc_grbm_trace -- python $ROOT/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --u8-images 0 --sustained-steps 0 > $OUT/pmc_grbm_trace.log 2>&1
 cd $ROOT
 python tools/pmc_summary.py $OUT/pmc_grbm.json "sweep_kernel<1>,sweep_kernel<3>" $OUT/pmc_grbm | tail -20
 python tools/power_summary.py $OUT > $OUT/power_trace.txt 2>&1; cat $OUT/power_trace.txt

@@ -28,7 +28,7 @@ store)   # the rebuilt store: whole GPU suite, fuzz, the bench line's upload fig
     run fuzz_routes python tools/fuzz_routes.py 821 400; tail -2 $OUT/fuzz_routes.txt
     MSFM_Q8=2 run fuzz_routes_q8 python tools/fuzz_routes.py 822 300; tail -2 $OUT/fuzz_routes_q8.txt
     run fuzz_jobs python tools/fuzz_jobs.py 823 150; tail -2 $OUT/fuzz_jobs.txt
-    run bench python bench.py --u8-images 0 --steps 10 --warmup 3 --sustained-steps 0; python - <<'PY'
+    run bench python bench.py --full --u8-images 0 --steps 10 --warmup 3 --sustained-steps 0; python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r5/store/bench.txt").read().strip().splitlines()[-1])
 print("ms_per_step", round(d["ms_per_step"],3), "upload_ms", round(d["pcie_inclusive"]["upload_ms"],2), "matches", d["config"]["matches_per_step"], "checksum", d["exchange_checksum"], "gpu/cpu", round(d.get("gpu_over_cpu",0)))
@@ -65,7 +65,7 @@ cli)   # where the CLI's wall clock goes
     ;;
 evidence)   # the round's evidence in one call on one box (copy what is judged into profiles/ as r05_*)
     TMO=1500 run pytest_gpu python -m pytest tests -m gpu -q; tail -2 $OUT/pytest_gpu.txt
-    TMO=900 run bench python bench.py; python - <<'PY'
+    TMO=900 run bench python bench.py --full; python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r5/evidence/bench.txt") if l.startswith("{")][-1]); r=d["roofline"]
 json.dump(d, open("gpurun_out/r5/evidence/bench.json","w"), indent=1)
@@ -115,7 +115,7 @@ fuzz)   # long seeded fuzz on the final build: routes, jobs (incl. the streaming
     ;;
 final)   # the final tree once more: the GPU suite, the default bench line, the kernel statistics of the timed region
     TMO=1500 run pytest_gpu python -m pytest tests -m gpu -q; tail -2 $OUT/pytest_gpu.txt
-    TMO=900 run bench python bench.py; python - <<'PY'
+    TMO=900 run bench python bench.py --full; python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r5/final/bench.txt") if l.startswith("{")][-1]); r=d["roofline"]
 json.dump(d, open("gpurun_out/r5/final/bench.json","w"), indent=1)

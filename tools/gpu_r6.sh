@@ -26,14 +26,14 @@ suite)   # the whole GPU suite
     ;;
 nccl1)   # the exchange path on ONE rank over RCCL, config 4 in full -- the library's copy into the torch-allocated
          # send tensor (the cross-runtime pointer) timed, and the streamed form with the exchange pipelined under the next super-batch
-    TMO=900 run bench_nccl1 python bench.py --backend nccl --force-collectives --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --sustained-steps 0 --no-solo
+    TMO=900 run bench_nccl1 python bench.py --full --backend nccl --force-collectives --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --sustained-steps 0 --no-solo
     python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r6/nccl1/bench_nccl1.txt") if l.startswith("{")][-1])
 print("config 2:", round(d["ms_per_step"],2), "ms/step", d["per_rank_ms"], d.get("exchange_detail_rank0"))
 u=d.get("strong_u8",{}); print("config 4:", u.get("seconds_per_step"), "s/step", u.get("per_rank_ms"), u.get("exchange_detail_rank0"))
 PY
-    TMO=900 run bench_nccl1_stream python bench.py --backend nccl --force-collectives --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --sustained-steps 0 --no-solo --super-batch-pairs 65536
+    TMO=900 run bench_nccl1_stream python bench.py --full --backend nccl --force-collectives --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --sustained-steps 0 --no-solo --super-batch-pairs 65536
     python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r6/nccl1/bench_nccl1_stream.txt") if l.startswith("{")][-1])
@@ -48,7 +48,7 @@ multi)   # the executable's device fan-out at config-4 scale with SEVERAL CONTEX
     ;;
 evidence)   # the round's evidence in one call on one box (copy what is judged into profiles/ as r06_*)
     TMO=1500 run pytest_gpu python -m pytest tests -m gpu -q; tail -2 $OUT/pytest_gpu.txt
-    TMO=900 run bench python bench.py; python - <<'PY'
+    TMO=900 run bench python bench.py --full; python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r6/evidence/bench.txt") if l.startswith("{")][-1]); r=d["roofline"]
 json.dump(d, open("gpurun_out/r6/evidence/bench.json","w"), indent=1)
