@@ -21,15 +21,21 @@ def quantize(x):
     raise ValueError("values neither integers in [0, 255] nor in [0, 1]")
 
 
-def assign(q, words):
-    """the nearest word of every row: argmin_w |c'_w|^2 - 2 q'.c'_w, the lower w on a tie"""
+def assign(q, words, block_bytes=256 << 20):
+    """the nearest word of every row: argmin_w |c'_w|^2 - 2 q'.c'_w, the lower w on a tie.  Rows go in chunks whose fp64 key block
+    stays within `block_bytes`; every row's key is the same whatever the chunk, so the result does not depend on it."""
     q = np.asarray(q, np.int64).reshape(-1, 128)
     if len(q) == 0:
         return np.zeros(0, np.int64)
     c = np.asarray(words, np.int64).reshape(-1, 128) - 128
-    qq = (q - 128).astype(np.float64)
-    key = (c * c).sum(1)[None, :].astype(np.float64) - 2.0 * (qq @ c.T.astype(np.float64))
-    return np.argmin(key, axis=1)
+    cn = (c * c).sum(1)[None, :].astype(np.float64)
+    ct = c.T.astype(np.float64)
+    step = max(1, int(block_bytes) // (8 * len(c)))
+    out = np.empty(len(q), np.int64)
+    for r0 in range(0, len(q), step):
+        qq = (q[r0:r0 + step] - 128).astype(np.float64)
+        out[r0:r0 + step] = np.argmin(cn - 2.0 * (qq @ ct), axis=1)
+    return out
 
 
 def sample_plan(rows, max_rows):
@@ -106,6 +112,77 @@ def scores(images, ids, words):
     s = a @ a.T
     np.fill_diagonal(s, 0.0)
     return order, s, (h > 0).sum(1)
+
+
+def tfidf(h):
+    """the fp64 unit tf-idf vectors of the histograms h (n x V, images in ascending id order); 0 for an image whose vector is 0"""
+    h = np.asarray(h)
+    n = len(h)
+    nw = (h > 0).sum(0)
+    idf = np.where(nw > 0, np.log(n / np.maximum(nw, 1)), 0.0)
+    v = h * idf[None, :]
+    nrm = np.sqrt((v * v).sum(1))
+    return np.where(nrm[:, None] > 0, v / np.where(nrm > 0, nrm, 1)[:, None], 0.0)
+
+
+def histograms_from_words(word_lists, v):
+    """c_iw from the nearest word of every row of every image (a list of int arrays, ascending id order)"""
+    h = np.zeros((len(word_lists), v), np.int64)
+    for k, w in enumerate(word_lists):
+        if len(w):
+            h[k] = np.bincount(np.asarray(w, np.int64), minlength=v)
+    return h
+
+
+def scores_from_words(word_lists, v, rows=None):
+    """fp64 S from given per-image words -> (S, nnz per image).  rows=None: the full n x n S (0 on the diagonal), as `scores`;
+    otherwise the rows `rows` of it only, a[rows] @ a.T (len(rows) x n, 0 at (r, rows[r]))."""
+    h = histograms_from_words(word_lists, v)
+    a = tfidf(h)
+    nnz = (h > 0).sum(1)
+    if rows is None:
+        s = a @ a.T
+        np.fill_diagonal(s, 0.0)
+        return s, nnz
+    rows = np.asarray(rows, np.int64)
+    s = a[rows] @ a.T
+    s[np.arange(len(rows)), rows] = 0.0
+    return s, nnz
+
+
+def select_rows(s, ids, k, rows=None):
+    """`topk` of every row of a score matrix, vectorised: a list of arrays of positions.  s is n x n (rows and columns in the order
+    of ids), or len(rows) x n for the rows `rows` of it."""
+    s = np.asarray(s)
+    n = len(ids)
+    rows = np.arange(n) if rows is None else np.asarray(rows, np.int64)
+    ids = np.asarray(ids, np.int64)
+    cand = s > 0
+    cand[np.arange(len(rows)), rows] = False
+    sf = s.astype(np.float64)
+    order = np.lexsort((np.broadcast_to(ids, s.shape), -np.where(cand, sf, -np.inf)), axis=1)
+    cnt = cand.sum(1)
+    return [order[r, :min(k, int(cnt[r]))] for r in range(len(rows))]
+
+
+def select_fast(s, ids, k):
+    """`select` through `select_rows`: the same pairs"""
+    out = set()
+    for i, top in enumerate(select_rows(s, ids, k)):
+        for j in top.tolist():
+            out.add((max(ids[i], ids[j]), min(ids[i], ids[j])))
+    return sorted(out)
+
+
+def group_ends(pairs, per_group):
+    """msfm_ret_group_ends: a group ends after every `per_group` pairs of a row and at the end of every row"""
+    ends, in_group = [], 0
+    for t in range(len(pairs)):
+        in_group += 1
+        if in_group == per_group or t + 1 == len(pairs) or pairs[t + 1][0] != pairs[t][0]:
+            ends.append(t + 1)
+            in_group = 0
+    return ends
 
 
 def score_bound(nnz_i, nnz_j):

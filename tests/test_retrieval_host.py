@@ -180,3 +180,78 @@ def test_reference_assign_ties_and_quantisation():
     assert qq[0, 0] == np.rint(np.float32(x[0, 0]) * np.float32(255))
     with pytest.raises(ValueError):
         ref.quantize(np.full((2, 128), 1.5, np.float32))
+
+
+def _small_scenes():
+    rng = np.random.default_rng(41)
+    images, _ = ref.covis_scene(24, window=8, stride=2, seed=3)
+    yield images, 64
+    fimages, _ = ref.covis_scene(12, window=6, stride=3, seed=4, as_float=True)
+    fimages[12] = np.zeros((0, 128), np.float32)                          # an empty image between non-empty ones
+    fimages[13] = rng.integers(0, 2, size=(30, 128)).astype(np.float32)   # 0.0 / 1.0 only: q = x
+    yield fimages, 40
+
+
+def test_reference_helpers_equal_scores_and_assign():
+    for images, v in _small_scenes():
+        ids = list(images)
+        words, _ = ref.train(images, ids, num_words=v, iters=4)
+        order, s, nnz = ref.scores(images, ids, words)
+        wl = []
+        for i in order:
+            q = ref.quantize(images[i])
+            w = ref.assign(q, words)
+            # any chunking gives the same words: one row, a few rows, everything at once
+            for block in (8 * len(words), 8 * len(words) * 7, 1 << 40):
+                assert np.array_equal(ref.assign(q, words, block_bytes=block), w)
+            wl.append(w)
+        s2, nnz2 = ref.scores_from_words(wl, len(words))
+        assert np.array_equal(nnz2, nnz)
+        assert np.array_equal(s2, s)
+        rows = [0, 5, len(order) - 1, 3]
+        s3, _ = ref.scores_from_words(wl, len(words), rows=rows)
+        assert np.allclose(s3, s[rows], rtol=0, atol=1e-15)
+        assert all(s3[r, p] == 0 for r, p in enumerate(rows))
+        for k in (1, 3, 6, len(order)):
+            assert ref.select_fast(s, order, k) == ref.select(s, order, k)
+            top = ref.select_rows(s3, order, k, rows=rows)
+            assert [t.tolist() for t in top] == [ref.topk(s3[r], order, p, k) for r, p in enumerate(rows)]
+
+
+def test_select_rows_equals_topk_under_heavy_ties():
+    rng = np.random.default_rng(42)
+    for n, k in [(50, 1), (50, 7), (120, 119), (200, 40)]:
+        s = rng.choice(np.array([-0.5, 0.0, 0.25, 0.5, 0.75], np.float32), size=(n, n))
+        s = np.triu(s, 1) + np.triu(s, 1).T
+        ids = rng.permutation(10 * n)[:n].tolist()
+        got = ref.select_rows(s, ids, k)
+        for i in range(n):
+            assert got[i].tolist() == ref.topk(s[i], ids, i, k)
+        assert ref.select_fast(s, ids, k) == ref.select(s, ids, k)
+
+
+def test_group_ends_twin(policy):
+    rng = np.random.default_rng(43)
+    pairs = sorted({(int(i), int(j)) for i, j in rng.integers(0, 300, size=(2000, 2)) if i > j})
+    for per in (1, 7, 100):
+        line = "groups %d %d %s" % (len(pairs), per, " ".join("%d %d" % p for p in pairs))
+        assert [int(x) for x in policy([line])[0].split()] == ref.group_ends(pairs, per)
+
+
+@pytest.mark.parametrize("n,k,seed", [(1329, 50, 0), (2000, 1024, 1), (10000, 1, 2), (10000, 1024, 3), (10000, 513, 4), (300, 1024, 5)])
+def test_topk_policy_at_scale(policy, n, k, seed):
+    # a handful of levels: hundreds of exact ties, zeros and negatives (never candidates), ids not in position order
+    rng = np.random.default_rng(50 + seed)
+    levels = np.array([-1.0, -2.0 ** -20, 0.0, 2.0 ** -24, 0.125, 0.5, 0.5000001, 0.9], np.float32)
+    ids = rng.permutation(10000)[:n].astype(np.int32)
+    lines, want = [], []
+    for self_pos in (0, n // 2, n - 1):
+        s = levels[rng.integers(0, len(levels), size=n)]
+        if seed == 5:
+            s[:] = np.float32(0.5)                     # every candidate tied, K >= N - 1
+        lines.append(_topk_line(s, ids.tolist(), self_pos, k))
+        want.append(ref.topk(s, ids.tolist(), self_pos, k))
+    got = policy(lines)
+    for g, w in zip(got, want):
+        assert [int(x) for x in g.split()] == w
+        assert len(w) == min(k, len(w)) and len(w) > 0
