@@ -312,6 +312,22 @@ typedef struct msfm_camera {
 } msfm_camera;
 int msfm_set_verification_model(msfm_ctx* ctx, int model, const msfm_camera* camera);
 int msfm_get_verification_stats(const msfm_ctx* ctx, int64_t* hypotheses_solved, int* rounds);
+
+/* ---- two-view model selection -----------------------------------------------------------------
+ * Off by default.  When on and the verification model is MSFM_VERIFY_FUNDAMENTAL or MSFM_VERIFY_ESSENTIAL, every verified pair runs
+ * two RANSACs on its matches: that epipolar model, exactly as above, and the homography, exactly as MSFM_VERIFY_HOMOGRAPHY.  With
+ * nE and nH the lengths of the two lists, the pair keeps the homography's list iff nE > 0 and (double)nH >= h_ratio * (double)nE
+ * (one rounded product), else the epipolar one: the choice of the reference's Initializer, F when nH / nF < 0.7
+ * (src/Reconstruction/Initializer.cpp:38-66).  So every pair's list is bit for bit the model 0 / 1 list or the model 2 list of the
+ * same call parameters.  Under MSFM_VERIFY_HOMOGRAPHY the selection has no effect.  msfm_get_verification_stats then sums the
+ * hypotheses of the staged models that ran (H, and E under model 1) and reports the larger rounds count.
+ * msfm_set_model_selection: enable 0 / 1, h_ratio finite and > 0 (the reference: 0.7), else MSFM_E_INVALID; MSFM_E_STATE while a
+ * streaming series is open.  Per context.
+ * msfm_fetch_model_selection: per pair of the last msfm_match_pairs_verified call, or of the chunk the last msfm_match_pairs_next
+ * returned (verified streaming form): the model whose list was kept (MSFM_VERIFY_FUNDAMENTAL / _ESSENTIAL / _HOMOGRAPHY), nE, nH.
+ * Any pointer may be NULL.  MSFM_E_STATE if that call / chunk ran without the selection. */
+int msfm_set_model_selection(msfm_ctx* ctx, int enable, double h_ratio);
+int msfm_fetch_model_selection(msfm_ctx* ctx, int32_t* out_model, int32_t* out_n_epipolar, int32_t* out_n_homography);
 int msfm_match_pairs_verified(msfm_ctx* ctx, const int32_t* pairs, int n_pairs,
                               const msfm_match_params* params, const msfm_verify_params* verify,
                               int64_t* out_offsets);

@@ -28,7 +28,7 @@ EXPORTS = [
     "msfm_fetch_order_certificate", "msfm_set_pipeline", "msfm_device_count", "msfm_finalize_store", "msfm_store_info",
     "msfm_match_pairs_begin", "msfm_match_pairs_next", "msfm_read_device", "msfm_memory_info", "msfm_match_pairs_end",
     "msfm_train_vocabulary", "msfm_set_vocabulary", "msfm_image_words", "msfm_retrieve_pairs", "msfm_get_retrieval_profile",
-    "msfm_set_verification_model", "msfm_get_verification_stats",
+    "msfm_set_verification_model", "msfm_get_verification_stats", "msfm_set_model_selection", "msfm_fetch_model_selection",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -156,6 +156,8 @@ def load():
         pass
     L.msfm_set_verification_model.argtypes = [vp, C.c_int, C.POINTER(Camera)]
     L.msfm_get_verification_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    L.msfm_set_model_selection.argtypes = [vp, C.c_int, C.c_double]
+    L.msfm_fetch_model_selection.argtypes = [vp, ip, ip, ip]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if the library lacks a declared symbol
     _lib = L
@@ -387,8 +389,11 @@ class Context:
                 sens = np.ctypeslib.as_array(ch.sensitive_rows, shape=(n,))
                 if copy:
                     offs, qt, d, sens = offs.copy(), qt.copy(), d.copy(), sens.copy()
-                yield {"first": ch.first_pair, "n_pairs": n, "offsets": offs, "qt": qt, "dist": d, "sensitive": sens,
-                       "d_qt": ch.d_qt, "d_dist": ch.d_dist}
+                item = {"first": ch.first_pair, "n_pairs": n, "offsets": offs, "qt": qt, "dist": d, "sensitive": sens,
+                        "d_qt": ch.d_qt, "d_dist": ch.d_dist}
+                if verified and self._selection_ran():
+                    item["model_selection"] = self.model_selection(n)
+                yield item
         finally:
             # a consumer that breaks out of the loop (GeneratorExit) or whose body raises must not leave the series open: the store
             # would stay locked for uploads until the next matching call
@@ -464,6 +469,23 @@ class Context:
         solved, rounds = C.c_int64(), C.c_int()
         self._chk(self._L.msfm_get_verification_stats(self._h, C.byref(solved), C.byref(rounds)))
         return int(solved.value), int(rounds.value)
+
+    def set_model_selection(self, enable=True, h_ratio=0.7):
+        """The two-view model selection of the verified calls (include/msfm_match.h): under VERIFY_FUNDAMENTAL or VERIFY_ESSENTIAL every
+        pair also runs the homography and keeps the homography's list iff nE > 0 and nH >= h_ratio * nE, else the epipolar one.
+        No effect under VERIFY_HOMOGRAPHY.  A bad h_ratio (not finite, <= 0) is E_INVALID; E_STATE while a series is open."""
+        self._chk(self._L.msfm_set_model_selection(self._h, int(bool(enable)), float(h_ratio)))
+
+    def model_selection(self, n_pairs):
+        """Per pair of the last match_pairs_verified call (or of the last verified stream chunk): (model kept, nE, nH), three int32
+        arrays.  E_STATE if that call ran without the selection."""
+        n = int(n_pairs)
+        out = [np.zeros(max(n, 1), np.int32) for _ in range(3)]
+        self._chk(self._L.msfm_fetch_model_selection(self._h, *[_ip(a) for a in out]))
+        return tuple(a[:n] for a in out)
+
+    def _selection_ran(self):
+        return self._L.msfm_fetch_model_selection(self._h, None, None, None) == OK
 
     def knn2_pair(self, id1, id2):
         n1, n2 = self.image_rows(id1), self.image_rows(id2)

@@ -1132,8 +1132,10 @@ __global__ void export_tail_kernel(ExportSegs segs) {
     __threadfence_system();
 }
 
-int queue_tail_copies(msfm_ctx* ctx, size_t P) {
-    HIPCHK(ctx, SC.h_tail.ensure(8 + (P + 1) * 8 + P * 4 + 64, 0));
+// records: the sub-batch's SelectRecords under the model selection (behind the certificate counts), else NULL
+int queue_tail_copies(msfm_ctx* ctx, size_t P, const DevBuf* records = nullptr) {
+    const size_t rec_bytes = records ? P * 12 : 0;
+    HIPCHK(ctx, SC.h_tail.ensure(8 + (P + 1) * 8 + P * 4 + rec_bytes + 64, 0));
     HIPCHK(ctx, SC.h_summary.ensure(kHsOverflow + P + 64, 0));
     char *h = nullptr, *hs = nullptr;
     HIPCHK(ctx, hipHostGetDevicePointer((void**)&h, SC.h_tail.p, 0));
@@ -1142,6 +1144,7 @@ int queue_tail_copies(msfm_ctx* ctx, size_t P) {
     segs.s[0] = ExportSeg{SC.d_fix_count.as<char>(), h, 4};
     if (SC.d_offsets.p) segs.s[1] = ExportSeg{SC.d_offsets.as<char>(), h + 8, (unsigned)((P + 1) * 8)};
     if (SC.d_sens.p) segs.s[2] = ExportSeg{SC.d_sens.as<char>(), h + 8 + (P + 1) * 8, (unsigned)(P * 4)};
+    if (records) segs.s[7] = ExportSeg{records->as<char>(), h + 8 + (P + 1) * 8 + P * 4, (unsigned)rec_bytes};
     if (SC.pf_pending.active) {
         if (SC.pf_pending.compact) segs.s[3] = ExportSeg{SC.d_summary.as<char>(), hs, (unsigned)sizeof(PlanSummary)};
         if (SC.pf_pending.refine) segs.s[6] = ExportSeg{SC.d_summary_a.as<char>(), hs + sizeof(PlanSummary), (unsigned)sizeof(PlanSummary)};

@@ -576,13 +576,14 @@ struct Scratch {
     DevBuf d_colmask, d_gtot, d_grow0, d_cnt, d_mrow, d_summary, d_overflow, d_totals;
     PfPending pf_pending;
     PinnedBuf h_summary;              // PlanSummary | totals[2] | overflow bytes
-    PinnedBuf h_tail;                 // tie-queue count | CSR offsets [P + 1] | certificate counts [P]: read at the end of the sub-batch
+    PinnedBuf h_tail;                 // tie-queue count | CSR offsets [P + 1] | certificate counts [P] | selection records [P] (model selection): read at the end of the sub-batch
     // geometric verification
     DevBuf d_vf_pairs, d_vf_x1, d_vf_y1, d_vf_x2, d_vf_y2, d_vf_hyp, d_vf_best_it, d_vf_best_count, d_vf_flags,
         d_st2_qt, d_st2_d, d_counts2;
     // calibrated verification (msfm_verify_e.hip.h): normalised coordinates of the staged matches (fp64); the staged models
     // (msfm_verify_staged.hip.h): per-pair state and round lists, counters
     DevBuf d_ve_x1, d_ve_y1, d_ve_x2, d_ve_y2, d_staged_state, d_staged_stats;
+    DevBuf d_vs_records;              // the two-view model selection (msfm_verify_select.hip.h): a SelectRecord per pair
     msfm_profile prof = {};           // this sub-batch's share; joins the call's profile when the sub-batch is accepted
     hipEvent_t sweep1_done = nullptr; // recorded behind sweep 1: the other stream's next sweep 1 waits for it
     bool sweep1_recorded = false;
@@ -596,7 +597,7 @@ struct Scratch {
                           &d_vpairs, &d_vpf, &d_vitems, &d_lists, &d_colmask, &d_gtot, &d_grow0, &d_cnt, &d_mrow, &d_summary, &d_overflow,
                           &d_totals, &d_vf_pairs,
                           &d_vf_x1, &d_vf_y1, &d_vf_x2, &d_vf_y2, &d_vf_hyp, &d_vf_best_it, &d_vf_best_count, &d_vf_flags, &d_st2_qt,
-                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
+                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
         for (DevBuf* b : bufs) fn(*b, arg);
     }
     long long device_bytes() {
@@ -690,8 +691,15 @@ struct msfm_ctx {
     // geometric verification model (msfm_set_verification_model): 0 fundamental matrix, 1 essential matrix with `camera`, 2 homography
     int verify_model = MSFM_VERIFY_FUNDAMENTAL;
     msfm_emat::Camera camera = {};
-    long long staged_solved = 0;      // of the last verified call / series: hypotheses solved, rounds run (models 1 and 2)
-    int staged_rounds = 0;
+    long long staged_solved = 0;      // of the last verified call / series: hypotheses solved, rounds run (models 1 and 2, and H under
+    int staged_rounds = 0;            //   the model selection)
+    // two-view model selection (msfm_set_model_selection): under model 0 or 1 every verified pair also runs the homography and keeps
+    // one of the two lists; sel_records: {model, nE, nH} per pair of the last verified call, or of the chunk the last
+    // msfm_match_pairs_next returned (sel_valid: that call / chunk ran with the selection)
+    bool model_select = false;
+    double h_ratio = 0.7;
+    std::vector<int32_t> sel_records;
+    bool sel_valid = false;
 };
 
 #define SC (*ctx->cur)

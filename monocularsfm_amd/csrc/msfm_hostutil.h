@@ -1,7 +1,7 @@
 // msfm_hostutil.h -- small pure functions shared by device and host code, compilable on their own (tests/test_hostutil.py builds a
 // g++ driver around them): the 4-byte packing of the integer sweeps' column partials, the cost marks of a call's sub-batches, the
 // scratch memory one image pair of a sub-batch needs, the matching route of a sub-batch, the fold of a candidate's key into a slot's
-// (best, second).
+// (best, second), the two-view model selection's rule.
 #pragma once
 #include <vector>
 
@@ -227,4 +227,13 @@ MSFM_HD void msfm_fold_key(unsigned long long* best, unsigned long long* second,
         if (loser == ~0ull) return;
     }
     if (loser < seen_second) (void)amin(second, loser);
+}
+
+// The two-view model selection (msfm_set_model_selection): a pair keeps the homography's list iff the epipolar model (F or E) keeps
+// something and nH >= h_ratio * nE -- the reference's Initializer takes F when num_inliers_H / num_inliers_F < 0.7
+// (src/Reconstruction/Initializer.cpp:38-66).  One rounded product and an exact compare; nE = 0 keeps the (empty) epipolar list, so
+// a pair of 4 .. 6 matches never keeps an unverified 4-point fit.  The device's two_view_select_kernel and the host twin
+// (host/GeometricVerification.cpp) both call this.
+MSFM_HD bool msfm_select_homography(int n_epipolar, int n_homography, double h_ratio) {
+    return n_epipolar > 0 && (double)n_homography >= h_ratio * (double)n_epipolar;
 }

@@ -28,6 +28,7 @@ struct MatchJob {
     msfm_verify_params verify_store = {};
     const msfm_verify_params* verify = nullptr;
     bool streaming = false;
+    bool select = false;   // the two-view model selection runs (msfm_verify_select.hip.h): verified, selection on, model 0 or 1
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     int kSets = kInFlight;
     long long kScratchBytes = 1;
@@ -50,6 +51,9 @@ struct MatchJob {
         n_pairs = n;
         streaming = stream_mode;
         verify = nullptr;
+        select = vp && c->model_select && c->verify_model != MSFM_VERIFY_HOMOGRAPHY;
+        c->sel_valid = false;
+        c->sel_records.assign(select && !stream_mode ? 3 * (size_t)n : 0, 0);
         if (vp) {
             verify_store = *vp;
             verify = &verify_store;
@@ -262,7 +266,7 @@ struct MatchJob {
                            d_counts, SC.d_offsets.as<long long>(), d_st_qt,
                            d_st_d, SC.d_sub_qt.as<int2>(), SC.d_sub_d.as<float>());
         HIPCHK(ctx, hipGetLastError());
-        rc = queue_tail_copies(ctx, P);
+        rc = queue_tail_copies(ctx, P, select ? &SC.d_vs_records : nullptr);
         if (rc != MSFM_OK) return rc;
         w.active = true;
         return MSFM_OK;
@@ -284,19 +288,22 @@ struct MatchJob {
         const bool e = model == MSFM_VERIFY_ESSENTIAL;   // (normalised fp64 coordinates; F and H: fp32 pixels)
         for (DevBuf* xy : {e ? &SC.d_ve_x1 : &SC.d_vf_x1, e ? &SC.d_ve_y1 : &SC.d_vf_y1, e ? &SC.d_ve_x2 : &SC.d_vf_x2, e ? &SC.d_ve_y2 : &SC.d_vf_y2})
             HIPCHK(ctx, xy->ensure(oe * (e ? 8 : 4)));
+        if (select && e)   // (the homography's fp32 pixel coordinates beside E's normalised ones)
+            for (DevBuf* xy : {&SC.d_vf_x1, &SC.d_vf_y1, &SC.d_vf_x2, &SC.d_vf_y2}) HIPCHK(ctx, xy->ensure(oe * 4));
         if (!staged()) HIPCHK(ctx, SC.d_vf_flags.ensure(oe));
         HIPCHK(ctx, SC.d_vf_hyp.ensure(P * (size_t)verify->max_iters * 4));
         HIPCHK(ctx, SC.d_vf_best_it.ensure(P * 4));
         HIPCHK(ctx, SC.d_vf_best_count.ensure(P * 4));
-        if (staged()) {
+        if (staged() || select) {
             HIPCHK(ctx, SC.d_staged_state.ensure((3 * P + 2) * 4));   // state[P] | two pair lists [P] | their two counts
             HIPCHK(ctx, SC.d_staged_stats.ensure(sizeof(StagedStats)));
         }
+        if (select) HIPCHK(ctx, SC.d_vs_records.ensure(P * sizeof(SelectRecord)));
         HIPCHK(ctx, SC.d_st2_qt.ensure(oe * sizeof(int2)));
         HIPCHK(ctx, SC.d_st2_d.ensure(oe * 4));
         HIPCHK(ctx, SC.d_counts2.ensure(P * 4));
         HIPCHK(ctx, hipMemcpyAsync(SC.d_vf_pairs.p, vpairs.data(), P * sizeof(VerifyPair), hipMemcpyHostToDevice, SC.stream));
-        if (staged()) {
+        if (staged() || select) {
             HIPCHK(ctx, hipMemsetAsync(SC.d_staged_state.p, 0, (3 * P + 2) * 4, SC.stream));
             HIPCHK(ctx, hipMemsetAsync(SC.d_staged_stats.p, 0, sizeof(StagedStats), SC.stream));
         }
@@ -354,7 +361,40 @@ struct MatchJob {
                                SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
         }
         HIPCHK(ctx, hipGetLastError());
+        if (select) {
+            const int rc = issue_select(P, dp, vp);
+            if (rc != MSFM_OK) return rc;
+        }
         HIPCHK(ctx, hipEventRecord(v1, SC.stream));
+        return MSFM_OK;
+    }
+
+    // the two-view model selection (msfm_verify_select.hip.h), behind the epipolar path: the homography's staged RANSAC on the same
+    // staged matches, then two_view_select_kernel keeps one list per pair in the second staging buffer.  The round buffers
+    // (d_vf_hyp, d_vf_best_*) are reused: the epipolar mask kernel has read them by then, in stream order.  The stats are not
+    // re-zeroed: under model 1 they sum E's and H's hypotheses and keep the larger rounds count.
+    int issue_select(size_t P, const PairDesc* dp, const VerifyPair* vp) {
+        StagedParams prm = {verify->threshold * verify->threshold, verify->confidence, verify->max_iters, 0, verify->seed};
+        const int* d_counts = SC.d_counts.as<int>();
+        const int2* d_st_qt = SC.d_st_qt.as<int2>();
+        const float* d_st_d = SC.d_st_d.as<float>();
+        int* hyp = SC.d_vf_hyp.as<int>();
+        float *x1 = SC.d_vf_x1.as<float>(), *y1 = SC.d_vf_y1.as<float>(), *x2 = SC.d_vf_x2.as<float>(), *y2 = SC.d_vf_y2.as<float>();
+        if (ctx->verify_model == MSFM_VERIFY_ESSENTIAL) {   // (model 0: the F path wrote the pixel coordinates)
+            hipLaunchKernelGGL(vf_points_kernel, dim3((unsigned)P), dim3(256), 0, SC.stream, dp, vp, d_counts, d_st_qt, x1, y1, x2, y2);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        HIPCHK(ctx, hipMemsetAsync(SC.d_staged_state.p, 0, (3 * P + 2) * 4, SC.stream));
+        int rc = issue_rounds<4, kVhRound>(P, kVhGroupsPerCU, prm, [&](unsigned grid, int* list, StagedStats* stats) {
+            hipLaunchKernelGGL(vh_round_kernel, dim3(grid), dim3(kVhRound), 0, SC.stream, dp, d_counts, (const float*)x1, (const float*)y1,
+                               (const float*)x2, (const float*)y2, list, (int)P, hyp, prm, stats);
+        });
+        if (rc != MSFM_OK) return rc;
+        hipLaunchKernelGGL(two_view_select_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, dp, d_counts, d_st_qt, d_st_d, (const float*)x1,
+                           (const float*)y1, (const float*)x2, (const float*)y2, (const int*)SC.d_vf_best_it.as<int>(), prm, ctx->verify_model,
+                           ctx->h_ratio, SC.d_st2_qt.as<int2>(), SC.d_st2_d.as<float>(), SC.d_counts2.as<int>(),
+                           SC.d_vs_records.as<SelectRecord>());
+        HIPCHK(ctx, hipGetLastError());
         return MSFM_OK;
     }
 
@@ -419,6 +459,8 @@ struct MatchJob {
             }
             w.offsets.assign(offs, offs + P + 1);
             w.sens.assign(sens, sens + P);
+            if (select) w.sel.assign(sens + P, sens + 4 * P);   // (the records follow the certificate counts: queue_tail_copies)
+            else w.sel.clear();
             for (size_t p = 0; p < P; ++p) SC.prof.order_sensitive_rows += sens[p];
             ctx->res_count += (size_t)total;   // (matches of the job so far)
         } else {
@@ -458,6 +500,7 @@ struct MatchJob {
                 ctx->res_sens[(size_t)w.begin + p] = sens[p];
                 SC.prof.order_sensitive_rows += sens[p];
             }
+            if (select) std::memcpy(ctx->sel_records.data() + 3 * (size_t)w.begin, sens + P, P * 12);
         }
         SC.prof.descriptor_pairs += b.desc_pairs;
         SC.prof.dist_algo_bytes += b.algo_bytes;
@@ -467,7 +510,7 @@ struct MatchJob {
             float vms = 0.f;
             HIPCHK(ctx, hipEventElapsedTime(&vms, ctx->ev_pool[w.ev_base + 6], ctx->ev_pool[w.ev_base + 7]));
             SC.prof.verify_ms += vms;
-            if (staged()) {   // (the stream has been synchronised above)
+            if (staged() || select) {   // (the stream has been synchronised above)
                 StagedStats st = {};
                 HIPCHK(ctx, hipMemcpyAsync(&st, SC.d_staged_stats.p, sizeof(st), hipMemcpyDeviceToHost, SC.stream));
                 HIPCHK(ctx, hipStreamSynchronize(SC.stream));   // (on this set's stream: the other sets' sub-batches stay in flight)

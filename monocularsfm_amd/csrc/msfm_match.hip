@@ -14,6 +14,7 @@
 #include "msfm_verify.hip.h"
 #include "msfm_verify_e.hip.h"
 #include "msfm_verify_h.hip.h"
+#include "msfm_verify_select.hip.h"
 #include "msfm_retrieval.hip.h"
 
 #include <sys/mman.h>
@@ -289,6 +290,7 @@ struct SubBatch {
     long long cost_begin = 0;
     std::vector<int64_t> offsets; // streaming form: the completed sub-batch's CSR offsets (relative to the sub-batch) and
     std::vector<int32_t> sens;    //   order-certificate counts, until the caller asks for the next chunk
+    std::vector<int32_t> sel;     //   and the model selection's records {model, nE, nH} per pair (msfm_fetch_model_selection)
 };
 
 void add_profile(msfm_profile& to, const msfm_profile& d) {
@@ -385,6 +387,7 @@ static int match_pairs_impl(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, co
     if (rc != MSFM_OK) return rc;
     std::memcpy(out_offsets, ctx->res_offsets.data(), ((size_t)n_pairs + 1) * sizeof(int64_t));
     ctx->have_results = true;
+    ctx->sel_valid = job.select;
     return MSFM_OK;
 }
 
@@ -432,6 +435,32 @@ int msfm_set_verification_model(msfm_ctx* ctx, int model, const msfm_camera* cam
     MSFM_API_END
 }
 
+int msfm_set_model_selection(msfm_ctx* ctx, int enable, double h_ratio) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "a streaming series is open");
+    if (enable != 0 && enable != 1) return fail(ctx, MSFM_E_INVALID, "enable must be 0 or 1");
+    if (!std::isfinite(h_ratio) || !(h_ratio > 0.0)) return fail(ctx, MSFM_E_INVALID, "h_ratio must be finite and > 0");
+    ctx->model_select = enable != 0;
+    ctx->h_ratio = h_ratio;
+    return MSFM_OK;
+    MSFM_API_END
+}
+
+int msfm_fetch_model_selection(msfm_ctx* ctx, int32_t* out_model, int32_t* out_n_epipolar, int32_t* out_n_homography) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (!ctx->sel_valid) return fail(ctx, MSFM_E_STATE, "the last verified call / chunk ran without the model selection");
+    const size_t n = ctx->sel_records.size() / 3;
+    for (size_t p = 0; p < n; ++p) {
+        if (out_model) out_model[p] = ctx->sel_records[3 * p];
+        if (out_n_epipolar) out_n_epipolar[p] = ctx->sel_records[3 * p + 1];
+        if (out_n_homography) out_n_homography[p] = ctx->sel_records[3 * p + 2];
+    }
+    return MSFM_OK;
+    MSFM_API_END
+}
+
 int msfm_get_verification_stats(const msfm_ctx* ctx, int64_t* hypotheses_solved, int* rounds) {
     MSFM_API_BEGIN(nullptr)
     if (!ctx) return MSFM_E_INVALID;
@@ -474,11 +503,18 @@ static int next_impl(msfm_ctx* ctx, msfm_chunk* out) {
     MatchJob& job = *ctx->job;
     if (!job.open || !job.streaming) return fail(ctx, MSFM_E_STATE, "msfm_match_pairs_next without msfm_match_pairs_begin");
     *out = msfm_chunk{};
-    if (!job.more()) return job.finish();   // n_pairs == 0: the series is complete
+    ctx->sel_valid = false;
+    ctx->sel_records.clear();
+    if (!job.more()) {   // n_pairs == 0: the series is complete
+        ctx->sel_valid = job.select;
+        return job.finish();
+    }
     int slot = 0;
     const int rc = job.step(&slot);
     if (rc != MSFM_OK) return rc;
     const SubBatch& w = job.sb[slot];
+    ctx->sel_records = w.sel;
+    ctx->sel_valid = job.select;
     const Scratch& sc = ctx->sc[slot];
     out->first_pair = w.begin;
     out->n_pairs = w.end - w.begin;

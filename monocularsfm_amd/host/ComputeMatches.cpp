@@ -97,6 +97,27 @@ int main(int argc, char** argv) {
         }
     }
 
+    // SIFTmatch.model_selection : 0 (default) | 1 (under models 0 and 1 every pair also runs the homography and keeps the H list iff
+    // nE > 0 and nH >= model_selection_h_ratio * nE -- the reference's Initializer rule, 0.7 by default; include/msfm_match.h)
+    int model_selection = 0;
+    double h_ratio = 0.7;
+    fs.Get("SIFTmatch.model_selection", &model_selection);
+    fs.Get("SIFTmatch.model_selection_h_ratio", &h_ratio);
+    if (!(model_selection == 0 || model_selection == 1)) {
+        std::cerr << "ComputeMatches: SIFTmatch.model_selection must be 0 or 1" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (model_selection == 1 && verification_model == 2) {
+        std::cerr << "ComputeMatches: SIFTmatch.model_selection : 1 chooses between the epipolar model and the homography; it needs "
+                     "SIFTmatch.verification_model 0 or 1, not 2"
+                  << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (!(std::isfinite(h_ratio) && h_ratio > 0)) {
+        std::cerr << "ComputeMatches: SIFTmatch.model_selection_h_ratio must be finite and > 0" << std::endl;
+        return EXIT_FAILURE;
+    }
+
     const char* honour = std::getenv("MSFM_HONOUR_YAML_MATCH_PARAMS");
     const bool use_yaml = honour && honour[0] == '1';
 
@@ -125,6 +146,7 @@ int main(int argc, char** argv) {
     }
 
     matcher->SetVerificationModel(verification_model, camera);
+    matcher->SetModelSelection(model_selection == 1, h_ratio);
 
     Timer timer;
     timer.Start();

@@ -40,6 +40,8 @@ namespace {
 struct PhaseClock {
     double exist = 0, read_desc = 0, device = 0, layout = 0, read_kp = 0, emit = 0, wait = 0, preemptive = 0, open_dev = 0, close_dev = 0, run = 0;
     long long pairs = 0, matches = 0;
+    long long two_view_pairs = 0, two_view_h = 0;   // the model selection: pairs verified, pairs that kept the homography's list
+    bool two_view = false;
     int devices = 1;
     bool on = std::getenv("MSFM_CLI_TIMING") != nullptr;
     void Report() const {
@@ -53,6 +55,7 @@ struct PhaseClock {
                              "msfm_match_pairs_next %.3f s + row layout %.3f s (mean per device) | calling thread: waiting for results %.3f s, "
                              "stdout + WriteMatches %.3f s -> bound by %s\n",
                      devices, pairs, matches, run, device / devices, layout / devices, wait, emit, wait > emit ? "the devices" : "emission");
+        if (two_view) std::fprintf(stderr, "[msfm two-view] pairs verified %lld | kept the homography's list %lld\n", two_view_pairs, two_view_h);
     }
 } g_clock;
 struct Lap {
@@ -92,6 +95,7 @@ struct DeviceRun {
     int status = MSFM_OK;
     std::string error;
     double in_next = 0, in_layout = 0;   // seconds inside msfm_match_pairs_next / laying the rows out
+    long long two_view_pairs = 0, two_view_h = 0;   // the model selection's pairs verified / that kept H
     // emitter side
     std::unique_ptr<ResultChunk> cur;
     size_t consumed = 0;
@@ -150,6 +154,7 @@ void FeatureMatcher::OpenDatabaseAndDevice() {
             const msfm_camera cam = {camera_.fx, camera_.fy, camera_.cx, camera_.cy, camera_.k1, camera_.k2, camera_.p1, camera_.p2};
             if (status[g] == MSFM_OK)
                 status[g] = msfm_set_verification_model(c, verification_model_, verification_model_ == MSFM_VERIFY_ESSENTIAL ? &cam : nullptr);
+            if (status[g] == MSFM_OK && model_selection_) status[g] = msfm_set_model_selection(c, 1, h_ratio_);
             // An ordinal listed k times (the tests' way to run the fan-out on a one-GPU box): every context would size its scratch
             // for a quarter of the device's free memory on its own -- four of them on one MI355X ran out of memory at config-4 scale.
             // They share the default budget instead (MSFM_SCRATCH_MIB still overrides: it is read at msfm_create, this only applies without it).
@@ -339,6 +344,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
     const size_t G = devices_.size();
     const bool verify_on_device = geometric_verification_ && !verification_on_host_;
     const bool host_verify = geometric_verification_ && verification_on_host_;
+    const bool two_view = geometric_verification_ && model_selection_ && verification_model_ != MSFM_VERIFY_HOMOGRAPHY;
     static const EmissionOptions emission = EmissionOptions::FromEnvironment();
 
     // ---- everything the device threads will touch is made resident / read now, on this thread (SQLite)
@@ -424,6 +430,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
         }
         Timer chunk_timer;
         chunk_timer.Start();
+        std::vector<int32_t> sel_model;
         while (!give_up.load(std::memory_order_relaxed)) {
             msfm_chunk ch;
             Timer t;
@@ -435,6 +442,16 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                 break;
             }
             if (ch.n_pairs == 0) break;
+            if (two_view && verify_on_device) {   // (the records of this chunk: valid until the next msfm_match_pairs_next)
+                sel_model.resize((size_t)ch.n_pairs);
+                rc = msfm_fetch_model_selection(r.ctx, sel_model.data(), nullptr, nullptr);
+                if (rc != MSFM_OK) {
+                    fail("msfm_fetch_model_selection", rc);
+                    break;
+                }
+                r.two_view_pairs += ch.n_pairs;
+                for (int32_t m : sel_model) r.two_view_h += m == MSFM_VERIFY_HOMOGRAPHY ? 1 : 0;
+            }
             t.Restart();
             std::unique_ptr<ResultChunk> out(new ResultChunk());
             out->first = (size_t)ch.first_pair;
@@ -469,8 +486,14 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                     }
                     if (host_verify) {
                         kept.clear();   // (FilterMatches appends, and returns without touching the list for an empty input)
-                        FilterMatches(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept, verification_model_, camera_);
+                        int chosen = verification_model_;
+                        FilterMatches(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept, verification_model_, camera_,
+                                      model_selection_, h_ratio_, &chosen);
                         list.swap(kept);
+                        if (two_view) {
+                            r.two_view_pairs += 1;
+                            r.two_view_h += chosen == MSFM_VERIFY_HOMOGRAPHY ? 1 : 0;
+                        }
                     }
                     ApplyEmissionOptions(emission, id1, id2, &list);
                     m = list.size();
@@ -625,7 +648,10 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
         }
         g_clock.device += r.in_next;
         g_clock.layout += r.in_layout;
+        g_clock.two_view_pairs += r.two_view_pairs;
+        g_clock.two_view_h += r.two_view_h;
     }
+    g_clock.two_view = g_clock.two_view || two_view;
     g_clock.devices = (int)G;
     g_clock.wait += waited;
     g_clock.emit += emit_timer.ElapsedSeconds() - waited;

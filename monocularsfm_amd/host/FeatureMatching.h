@@ -46,6 +46,13 @@ public:
         verification_model_ = model;
         camera_ = camera;
     }
+    // SIFTmatch.model_selection / model_selection_h_ratio: under models 0 and 1, every pair also runs the homography and keeps the
+    // list msfm_select_homography picks (msfm_set_model_selection on every device context, or TwoViewSelectMask in the host twin).
+    // Call before RunMatching.
+    void SetModelSelection(bool on, double h_ratio) {
+        model_selection_ = on;
+        h_ratio_ = h_ratio;
+    }
 
 protected:
     void OpenDatabaseAndDevice();
@@ -66,6 +73,8 @@ protected:
     bool verification_on_host_ = false;  // MSFM_GEOMETRIC_VERIFICATION=host
     int verification_model_ = MSFM_VERIFY_FUNDAMENTAL;   // SetVerificationModel
     CameraIntrinsics camera_ = {};                       // (model 1 only)
+    bool model_selection_ = false;                       // SetModelSelection
+    double h_ratio_ = 0.7;
     Database* database_ = nullptr;
     // One context per GPU: MSFM_DEVICE (default 0), MSFM_DEVICES="0,1,..." or "all".  The whole descriptor store is replicated on
     // each; the pairs of a run are dealt to the devices in small cost-balanced blocks, round-robin, so that every device's results

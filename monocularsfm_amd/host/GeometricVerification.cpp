@@ -7,6 +7,7 @@
 #include "../csrc/msfm_emat.h"
 #include "../csrc/msfm_fmat.h"
 #include "../csrc/msfm_hmat.h"
+#include "../csrc/msfm_hostutil.h"
 
 namespace MonocularSfM {
 
@@ -149,9 +150,26 @@ std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1
     return mask;
 }
 
+std::vector<unsigned char> TwoViewSelectMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2, int model,
+                                             const CameraIntrinsics& camera, double h_ratio, double threshold, double confidence,
+                                             int max_iters, unsigned long long seed, int* chosen, int* n_epipolar, int* n_homography) {
+    std::vector<unsigned char> me = model == MSFM_VERIFY_ESSENTIAL
+                                        ? EssentialRansacMask(pts1, pts2, camera, threshold, confidence, max_iters, seed)
+                                        : FundamentalRansacMask(pts1, pts2, threshold, confidence, max_iters, seed);
+    std::vector<unsigned char> mh = HomographyRansacMask(pts1, pts2, threshold, confidence, max_iters, seed);
+    const int ne = (int)std::count(me.begin(), me.end(), (unsigned char)1);
+    const int nh = (int)std::count(mh.begin(), mh.end(), (unsigned char)1);
+    const bool take_h = msfm_select_homography(ne, nh, h_ratio);
+    if (chosen) *chosen = take_h ? MSFM_VERIFY_HOMOGRAPHY : model;
+    if (n_epipolar) *n_epipolar = ne;
+    if (n_homography) *n_homography = nh;
+    return take_h ? mh : me;
+}
+
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
                    const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches, int model,
-                   const CameraIntrinsics& camera) {
+                   const CameraIntrinsics& camera, bool model_selection, double h_ratio, int* chosen_model) {
+    if (chosen_model) *chosen_model = model;
     if (kpts1.empty() || matches.empty()) return;  // FeatureUtils.cpp:181-184
     std::vector<Point2f> a, b;
     a.reserve(matches.size());
@@ -159,6 +177,12 @@ void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoin
     for (const DMatch& m : matches) {
         a.push_back(Point2f{kpts1[(size_t)m.queryIdx].x, kpts1[(size_t)m.queryIdx].y});
         b.push_back(Point2f{kpts2[(size_t)m.trainIdx].x, kpts2[(size_t)m.trainIdx].y});
+    }
+    if (model_selection && model != MSFM_VERIFY_HOMOGRAPHY) {
+        const std::vector<unsigned char> mask = TwoViewSelectMask(a, b, model, camera, h_ratio, 3.0, 0.99, 1000, 0x5eed5eedULL, chosen_model);
+        for (size_t i = 0; i < mask.size(); ++i)
+            if (mask[i]) prune_matches->push_back(matches[i]);
+        return;
     }
     const std::vector<unsigned char> mask = model == MSFM_VERIFY_ESSENTIAL    ? EssentialRansacMask(a, b, camera, 3.0, 0.99)
                                             : model == MSFM_VERIFY_HOMOGRAPHY ? HomographyRansacMask(a, b, 3.0, 0.99)

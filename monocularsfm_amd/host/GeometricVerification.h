@@ -45,11 +45,23 @@ std::vector<unsigned char> HomographyRansacMask(const std::vector<Point2f>& pts1
                                                 double threshold = 3.0, double confidence = 0.99, int max_iters = 1000,
                                                 unsigned long long seed = 0x5eed5eedULL);
 
+// The two-view model selection (msfm_set_model_selection): the epipolar mask of `model` (FundamentalRansacMask, or
+// EssentialRansacMask with `camera`) and HomographyRansacMask on the same points; the homography's mask is returned iff
+// msfm_select_homography(nE, nH, h_ratio) (csrc/msfm_hostutil.h), else the epipolar one.  *chosen = the model whose mask was returned,
+// *n_epipolar / *n_homography = the two masks' counts (any may be NULL).  Host twin of two_view_select_kernel
+// (csrc/msfm_verify_select.hip.h): the same bits.
+std::vector<unsigned char> TwoViewSelectMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2, int model,
+                                             const CameraIntrinsics& camera, double h_ratio, double threshold = 3.0,
+                                             double confidence = 0.99, int max_iters = 1000, unsigned long long seed = 0x5eed5eedULL,
+                                             int* chosen = nullptr, int* n_epipolar = nullptr, int* n_homography = nullptr);
+
 // FeatureUtils::GetAlignedPointsFromMatches + FilterMatches, with the model of SIFTmatch.verification_model
 // (msfm_match.h: MSFM_VERIFY_FUNDAMENTAL as the reference, MSFM_VERIFY_ESSENTIAL with `camera`, MSFM_VERIFY_HOMOGRAPHY) and the
-// reference's constants
+// reference's constants.  model_selection (SIFTmatch.model_selection, models 0 and 1 only): TwoViewSelectMask with h_ratio;
+// *chosen_model (may be NULL) = the model whose list was kept.
 void FilterMatches(const std::vector<KeyPoint>& kpts1, const std::vector<KeyPoint>& kpts2,
                    const std::vector<DMatch>& matches, std::vector<DMatch>* prune_matches,
-                   int model = MSFM_VERIFY_FUNDAMENTAL, const CameraIntrinsics& camera = {});
+                   int model = MSFM_VERIFY_FUNDAMENTAL, const CameraIntrinsics& camera = {}, bool model_selection = false,
+                   double h_ratio = 0.7, int* chosen_model = nullptr);
 
 }  // namespace MonocularSfM

@@ -11,6 +11,7 @@
 #include "../csrc/msfm_emat.h"
 #include "../csrc/msfm_fmat.h"
 #include "../csrc/msfm_hmat.h"
+#include "../csrc/msfm_hostutil.h"
 
 using namespace MonocularSfM;
 
@@ -408,5 +409,25 @@ int host_homography_ransac(const float* p1, const float* p2, int n, double thres
     for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
     return (int)m.size();
 }
+
+// TwoViewSelectMask on pixel coordinates p1, p2 (n x 2): model 0 (F) or 1 (E with the camera fx, fy, cx, cy, k1, k2, p1, p2 of `cam`;
+// NULL under model 0) against the homography.  out3 = {chosen model, nE, nH}; returns the mask length (0: nothing kept)
+int host_two_view_select(const float* p1, const float* p2, int n, int model, const double* cam, double h_ratio, double threshold,
+                         double confidence, int max_iters, unsigned long long seed, unsigned char* mask, int* out3) {
+    std::vector<Point2f> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[(size_t)i] = Point2f{p1[2 * i], p1[2 * i + 1]};
+        b[(size_t)i] = Point2f{p2[2 * i], p2[2 * i + 1]};
+    }
+    CameraIntrinsics c = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (cam) c = CameraIntrinsics{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    const std::vector<unsigned char> m =
+        TwoViewSelectMask(a, b, model, c, h_ratio, threshold, confidence, max_iters, seed, &out3[0], &out3[1], &out3[2]);
+    for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
+    return (int)m.size();
+}
+
+// msfm_select_homography (csrc/msfm_hostutil.h), the rule itself
+int host_select_homography(int n_epipolar, int n_homography, double h_ratio) { return msfm_select_homography(n_epipolar, n_homography, h_ratio) ? 1 : 0; }
 
 }  // extern "C"

@@ -64,11 +64,13 @@ class FeatureMatcher:
     (msfm_match_pairs_verified, what the C++ CLI does by default); a callable is called as
     f(kpts1, kpts2, matches) -> matches instead; None keeps the distance-filtered matches.  verification_model /
     camera: the model of the "device" verification (0: fundamental matrix, the default; 1: essential matrix with
-    camera = fx, fy, cx, cy[, k1, k2, p1, p2]; 2: homography, no camera -- Context.set_verification_model)."""
+    camera = fx, fy, cx, cy[, k1, k2, p1, p2]; 2: homography, no camera -- Context.set_verification_model).  model_selection /
+    h_ratio: under models 0 and 1, every pair also runs the homography and keeps its list iff nE > 0 and nH >= h_ratio * nE
+    (Context.set_model_selection; the CLI's SIFTmatch.model_selection / model_selection_h_ratio)."""
 
     def __init__(self, database_path, max_num_matches=10240, max_distance=0.7, distance_ratio=0.8,
                  cross_check=True, ctx=None, device=0, geometric_verification=None, verbose=True,
-                 verification_model=0, camera=None):
+                 verification_model=0, camera=None, model_selection=False, h_ratio=0.7):
         self.database_path_ = database_path
         self.max_num_matches_ = max_num_matches  # stored, never read (as in the reference)
         self.max_distance_ = float(max_distance)
@@ -79,6 +81,8 @@ class FeatureMatcher:
         self.geometric_verification = geometric_verification
         if verification_model != 0 or camera is not None:
             self.ctx.set_verification_model(verification_model, camera)
+        if model_selection:
+            self.ctx.set_model_selection(True, h_ratio)
         self.verbose = verbose
         self._resident = set()
 

@@ -279,6 +279,54 @@ def south_building_planar(n_images=128, n_desc=5000, seed=1234, noise_px=0.5):
     return descs, kps
 
 
+def mixed_capture(n_facade=64, n_scene=64, n_desc=5000, seed=1234, noise_px=0.5, n_proto=20000, path=None):
+    """A capture that mixes the two kinds of view pairs (a walk around a building: some images see mostly one facade, the others
+    depth): images 0 .. n_facade - 1 see points of one plane (south_building_planar's facade), images n_facade .. see a 3-D box of
+    points (scene_keypoints'); each group draws its descriptors from a prototype pool and a landmark pool of its own, so a cross
+    pair shares no scene point (its matches are chance ones).  Within a group, the descriptors, landmarks and cameras are drawn as
+    south_building_database draws them.  path: also written as a database (database.write_synthetic_database).
+    -> (descriptors, keypoints, facade: bool per image)"""
+    descs, kps = [], []
+    for g, n in enumerate((n_facade, n_scene)):
+        if n == 0:
+            continue
+        gseed = seed + 7919 * g
+        rng = np.random.default_rng(gseed)
+        counts = rng.integers(int(n_desc * 0.92), int(n_desc * 1.08) + 1, n)
+        d, protos = rootsift_images(n, counts.tolist(), seed=gseed, n_proto=n_proto, return_proto=True)
+        k = [keypoints(len(x), seed=gseed + 50 + i) for i, x in enumerate(d)]
+        pool = d[0][:120].copy()
+        for i in range(n):
+            m = min(80, len(d[i]))
+            pick = rng.choice(120, m, replace=False)
+            rows = rng.choice(len(d[i]), m, replace=False)
+            v = np.abs(pool[pick] * (1 + 0.03 * rng.standard_normal((m, 128)).astype(F32)))
+            d[i][rows] = v / np.linalg.norm(v, axis=1, keepdims=True)
+            k[i][rows, 2] = 100 + rng.uniform(0, 50, m).astype(F32)
+            protos[i][rows] = n_proto + pick
+        cams = scene_cameras(n, seed=gseed + 7)
+        if g == 1:
+            k = scene_keypoints(protos, cams, n_proto + 120, seed=gseed + 9, noise_px=noise_px, base=k)
+        else:
+            prng = np.random.default_rng(gseed + 9)
+            a, b = prng.uniform(-1.6, 1.6, n_proto + 120), prng.uniform(-1.1, 1.1, n_proto + 120)
+            X = np.c_[a, b, 0.25 * a - 0.15 * b]
+            for i in range(n):
+                ids = np.asarray(protos[i])
+                sel = np.nonzero(ids >= 0)[0]
+                R, t, f, cx, cy = cams[i]
+                Xc = X[ids[sel]] @ R.T + t
+                k[i][sel, 0] = (f * Xc[:, 0] / Xc[:, 2] + cx + prng.normal(0, noise_px, len(sel))).astype(F32)
+                k[i][sel, 1] = (f * Xc[:, 1] / Xc[:, 2] + cy + prng.normal(0, noise_px, len(sel))).astype(F32)
+        descs += d
+        kps += k
+    facade = np.r_[np.ones(n_facade, bool), np.zeros(n_scene, bool)]
+    if path is not None:
+        from . import database
+        database.write_synthetic_database(path, descs, kps)
+    return descs, kps, facade
+
+
 def u8_database(path, n_images=1329, n_desc=8192, seed=1329, f32_table=True, u8_table=True, progress=None):
     """A BASELINE-configs[3]-shaped database (1329 x 8192 raw byte SIFT-like descriptors) for the ComputeMatches EXECUTABLE at the
     scale the strong-scaling target is stated on: the images of ``job("synthetic-u8", ...)`` (same seed -> same descriptors), written as
