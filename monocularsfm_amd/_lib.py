@@ -366,13 +366,19 @@ class Context:
         self._chk(self._L.msfm_fetch_matches(self._h, _ip(qt), _fp(d)))
         return offs, qt[:M], d[:M]
 
-    def match_pairs_stream(self, pairs, ratio=0.8, cross_check=True, max_distance=0.7, verified=False, copy=True):
+    def match_pairs_stream(self, pairs, ratio=0.8, cross_check=True, max_distance=0.7, verified=False, copy=True, verify=None):
         """Generator over the device sub-batches of the job, in pair order (msfm_match_pairs_begin / _next): nothing accumulates in the
         library.  Yields dicts {first, n_pairs, offsets[n+1] (relative to the chunk), qt[m, 2], dist[m], sensitive[n], d_qt, d_dist
-        (device pointers)}; with copy=False qt / dist / offsets are views, valid until the next item is requested."""
+        (device pointers)}; with copy=False qt / dist / offsets are views, valid until the next item is requested.  verify: None (the
+        reference's constants) or a dict of match_pairs_verified's threshold, confidence, max_iters, seed."""
         pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
         prm = MatchParams(ratio, int(bool(cross_check)), max_distance)
-        self._chk(self._L.msfm_match_pairs_begin(self._h, _ip(pairs), pairs.shape[0], C.byref(prm), int(bool(verified)), None))
+        vprm = None
+        if verify is not None:
+            v = dict(dict(threshold=3.0, confidence=0.99, max_iters=1000, seed=0x5eed5eed), **verify)
+            vprm = VerifyParams(v["threshold"], v["confidence"], int(v["max_iters"]), int(v["seed"]))
+        self._chk(self._L.msfm_match_pairs_begin(self._h, _ip(pairs), pairs.shape[0], C.byref(prm), int(bool(verified)),
+                                                 C.byref(vprm) if vprm is not None else None))
         ch = Chunk()
         done = False
         try:

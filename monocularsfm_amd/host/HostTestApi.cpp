@@ -1,5 +1,6 @@
 // HostTestApi.cpp -- C-linkage shims over the host-only pieces (YAML reader, Database, F-, E- and H-RANSAC)
 // so that the CPU test-suite can exercise them through ctypes without a GPU.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -425,6 +426,78 @@ int host_two_view_select(const float* p1, const float* p2, int n, int model, con
         TwoViewSelectMask(a, b, model, c, h_ratio, threshold, confidence, max_iters, seed, &out3[0], &out3[1], &out3[2]);
     for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
     return (int)m.size();
+}
+
+// The staging schedule of the device's staged RANSAC (csrc/msfm_verify_staged.hip.h) for one pair of model 1 (E, `cam` as in
+// host_essential_ransac) or 2 (H) on pixel coordinates p1, p2 (n x 2): the counts of the twin, computed lazily, replayed with
+// avail = min((r + 1) * kRound, max_iters) for r = 0, 1, .. until the replay is decided.  *rounds = r + 1 (the rounds the pair
+// runs) and *solved = min(*rounds * kRound, max_iters) (the live lanes of those rounds); 0 and 0 when n < kSample.  Returns 0, or
+// -1 for another model.
+int host_staged_schedule(int model, const float* p1, const float* p2, int n, const double* cam, double threshold, double confidence,
+                         int max_iters, unsigned long long seed, int* rounds, long long* solved) {
+    constexpr int kEmatRound = 32;   // kVeRound (csrc/msfm_verify_e.hip.h)
+    constexpr int kHmatRound = 64;   // kVhRound (csrc/msfm_verify_h.hip.h)
+    *rounds = 0;
+    *solved = 0;
+    if (model != MSFM_VERIFY_ESSENTIAL && model != MSFM_VERIFY_HOMOGRAPHY) return -1;
+    const bool e = model == MSFM_VERIFY_ESSENTIAL;
+    const int k_sample = e ? 5 : 4, k_round = e ? kEmatRound : kHmatRound;
+    if (n < k_sample) return 0;
+    std::vector<double> dx1((size_t)n), dy1((size_t)n), dx2((size_t)n), dy2((size_t)n);
+    std::vector<float> fx1((size_t)n), fy1((size_t)n), fx2((size_t)n), fy2((size_t)n);
+    double thr2;
+    if (e) {
+        const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+        for (int i = 0; i < n; ++i) {
+            msfm_emat::undistort(c, (double)p1[2 * i], (double)p1[2 * i + 1], &dx1[(size_t)i], &dy1[(size_t)i]);
+            msfm_emat::undistort(c, (double)p2[2 * i], (double)p2[2 * i + 1], &dx2[(size_t)i], &dy2[(size_t)i]);
+        }
+        const double t = threshold / ((cam[0] + cam[1]) * 0.5);
+        thr2 = t * t;
+    } else {
+        for (int i = 0; i < n; ++i) {
+            fx1[(size_t)i] = p1[2 * i];
+            fy1[(size_t)i] = p1[2 * i + 1];
+            fx2[(size_t)i] = p2[2 * i];
+            fy2[(size_t)i] = p2[2 * i + 1];
+        }
+        thr2 = threshold * threshold;
+    }
+    std::vector<double> ws((size_t)msfm_emat::kWork);
+    std::vector<int> counts;   // hypotheses 0 .. counts.size() - 1, computed so far
+    auto count_at = [&](int it) {
+        while ((int)counts.size() <= it) {
+            const int h = (int)counts.size();
+            int c = 0;
+            if (e) {   // the largest count over the hypothesis' solutions (EssentialRansacMask)
+                const int ns = msfm_emat::hypothesis<1>(dx1.data(), dy1.data(), dx2.data(), dy2.data(), n, seed, h, ws.data());
+                for (int s = 0; s < ns; ++s) {
+                    const double* E = ws.data() + msfm_emat::kWsSol + 9 * s;
+                    int cs = 0;
+                    for (int i = 0; i < n; ++i) cs += msfm_emat::sampson(E, dx1[(size_t)i], dy1[(size_t)i], dx2[(size_t)i], dy2[(size_t)i]) <= thr2 ? 1 : 0;
+                    c = std::max(c, cs);
+                }
+            } else {   // 0 for a rejected sample (HomographyRansacMask)
+                double H[9];
+                if (msfm_hmat::hypothesis(fx1.data(), fy1.data(), fx2.data(), fy2.data(), n, seed, h, H))
+                    for (int i = 0; i < n; ++i) c += msfm_hmat::reproj_error(H, fx1[(size_t)i], fy1[(size_t)i], fx2[(size_t)i], fy2[(size_t)i]) <= thr2 ? 1 : 0;
+            }
+            counts.push_back(c);
+        }
+        return counts[(size_t)it];
+    };
+    for (int r = 0;; ++r) {
+        const int avail = std::min((r + 1) * k_round, max_iters);
+        int best_count = 0;
+        bool decided = false;
+        if (e) msfm_fmat::replay_adaptive<5>(n, max_iters, confidence, count_at, &best_count, avail, &decided);
+        else msfm_fmat::replay_adaptive<4>(n, max_iters, confidence, count_at, &best_count, avail, &decided);
+        if (decided) {
+            *rounds = r + 1;
+            *solved = std::min((long long)(r + 1) * k_round, (long long)max_iters);
+            return 0;
+        }
+    }
 }
 
 // msfm_select_homography (csrc/msfm_hostutil.h), the rule itself

@@ -156,11 +156,10 @@ def replay(counts, n, max_iters, confidence, sample=5):
     return (best_it if best >= sample else -1), best, iters
 
 
-def ransac(cam, p1, p2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0x5EED5EED):
-    """The whole calibrated RANSAC as a literal loop over this module's pieces: the mask (None: nothing kept)."""
+def scorer(cam, p1, p2, threshold=3.0, seed=0x5EED5EED):
+    """Hypothesis it of the calibrated RANSAC on pixel points p1, p2: score(it) -> (count, mask) of its best solution (the first
+    among equal counts; 0 and None when the sample has no solution)."""
     n = len(p1)
-    if n < 5:
-        return None
     q1 = np.array([undistort(cam, float(u), float(v)) for u, v in p1])
     q2 = np.array([undistort(cam, float(u), float(v)) for u, v in p2])
     thr2 = (threshold / ((cam[0] + cam[1]) / 2)) ** 2
@@ -174,6 +173,15 @@ def ransac(cam, p1, p2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0x5
             if bm is None or m.sum() > best:
                 best, bm = int(m.sum()), m
         return best, bm
+    return score
+
+
+def ransac(cam, p1, p2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0x5EED5EED):
+    """The whole calibrated RANSAC as a literal loop over this module's pieces: the mask (None: nothing kept)."""
+    n = len(p1)
+    if n < 5:
+        return None
+    score = scorer(cam, p1, p2, threshold, seed)
 
     best, best_it, best_mask, iters, it = 0, -1, None, max_iters, 0
     while it < iters:

@@ -99,13 +99,11 @@ def sequential_replay(counts, n, max_iters, confidence, sample=4):
     return (best_it if best >= sample else -1), best
 
 
-def ransac_mask(p1, p2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0x5EED5EED):
-    """The whole RANSAC in numpy (no subset shortcut): a mask of n entries, or None when nothing is kept."""
+def counter(p1, p2, threshold=3.0, seed=0x5EED5EED):
+    """Hypothesis it of the RANSAC on pixel points p1, p2: count(it) -> (inliers, H), (0, None) for a rejected sample."""
     p1 = np.asarray(p1, np.float64)
     p2 = np.asarray(p2, np.float64)
     n = len(p1)
-    if n < 4:
-        return None
     thr2 = threshold * threshold
 
     def count(it):
@@ -114,6 +112,18 @@ def ransac_mask(p1, p2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0x5
             return 0, None
         H = dlt(p1[idx], p2[idx])
         return sum(reproj_error(H, *p1[i], *p2[i]) <= thr2 for i in range(n)), H
+    return count
+
+
+def ransac_mask(p1, p2, threshold=3.0, confidence=0.99, max_iters=1000, seed=0x5EED5EED):
+    """The whole RANSAC in numpy (no subset shortcut): a mask of n entries, or None when nothing is kept."""
+    p1 = np.asarray(p1, np.float64)
+    p2 = np.asarray(p2, np.float64)
+    n = len(p1)
+    if n < 4:
+        return None
+    thr2 = threshold * threshold
+    count = counter(p1, p2, threshold, seed)
 
     counts = {}
 
