@@ -328,6 +328,52 @@ int msfm_get_verification_stats(const msfm_ctx* ctx, int64_t* hypotheses_solved,
  * Any pointer may be NULL.  MSFM_E_STATE if that call / chunk ran without the selection. */
 int msfm_set_model_selection(msfm_ctx* ctx, int enable, double h_ratio);
 int msfm_fetch_model_selection(msfm_ctx* ctx, int32_t* out_model, int32_t* out_n_epipolar, int32_t* out_n_homography);
+
+/* ---- two-view geometry --------------------------------------------------------------------------
+ * Off by default; MSFM_VERIFY_ESSENTIAL only.  When on, every verified pair also gets a record of what the reference's
+ * Initializer::RecoverPoseFromFundanmental computes after its model choice (src/Reconstruction/Initializer.cpp:300-420): the
+ * winning E of the pair's RANSAC is decomposed, the four-fold ambiguity resolved by cheirality over the pair's kept matches
+ * (the nE E-inliers, in list order), each kept match triangulated by the reference's DLT under the winner, and the reference's
+ * statistics and its test for an initial pair reduced from them.  The arithmetic is csrc/msfm_pose.h, bit-identical to the host
+ * twin TwoViewGeometry.  The match lists, the statistics and the selection records do not change.
+ *   R, t              x2 ~ R x1 + t in normalised camera coordinates, R row-major and proper, |t| = 1
+ *   n_kept            nE
+ *   n_positive_depth  kept matches in front of both cameras under (R, t)
+ *   n_triangulated    of those, the ones with a reprojection error < tri_max_error: the mean of the two views' Euclidean errors
+ *                     against the undistorted observations, in pixels through (fx + fy) / 2
+ *   median_tri_angle  over all nE kept matches (the mean of the two middle ones for an even nE), degrees
+ *   mean_tri_angle, mean_residual   over the n_triangulated matches (0 when there are none)
+ *   is_initial_candidate   n_triangulated >= min_num_inliers && median_tri_angle >= tri_min_angle && mean_tri_angle >= tri_min_angle
+ *                          && mean_residual <= tri_max_error
+ * valid = 0 and everything else 0: the pair has fewer than 5 staged matches or its RANSAC has no winner (a consensus below 5), no candidate puts a match in front of both cameras, E has
+ * fewer than two non-zero singular values, or the model selection kept the homography's list for the pair (the pose of a
+ * homography is not computed).
+ * msfm_set_two_view_geometry: enable 0 / 1; params NULL = the reference's defaults {100, 2.0 px, 4.0 degrees}.  MSFM_E_INVALID for a
+ * negative or non-finite parameter and when enabled under another model than MSFM_VERIFY_ESSENTIAL; MSFM_E_STATE while a streaming
+ * series is open.  msfm_set_verification_model away from MSFM_VERIFY_ESSENTIAL while this is on is MSFM_E_INVALID: switch it off first.
+ * msfm_fetch_two_view_geometry: one record per pair of the last msfm_match_pairs_verified call, or of the chunk the last
+ * msfm_match_pairs_next returned (verified streaming form); out may be NULL.  MSFM_E_STATE if that call / chunk ran without it. */
+typedef struct msfm_two_view_params {
+    int32_t min_num_inliers;     /* Initializer::Parameters::rel_pose_min_num_inlier: 100 */
+    int32_t reserved;
+    double tri_max_error;        /* init_tri_max_error: 2.0 pixels */
+    double tri_min_angle;        /* init_tri_min_angle: 4.0 degrees */
+} msfm_two_view_params;
+typedef struct msfm_two_view_record {   /* 144 bytes, no implicit padding */
+    int32_t valid;
+    int32_t reserved;
+    double R[9];
+    double t[3];
+    int32_t n_kept;
+    int32_t n_positive_depth;
+    int32_t n_triangulated;
+    int32_t is_initial_candidate;
+    double median_tri_angle;
+    double mean_tri_angle;
+    double mean_residual;
+} msfm_two_view_record;
+int msfm_set_two_view_geometry(msfm_ctx* ctx, int enable, const msfm_two_view_params* params);
+int msfm_fetch_two_view_geometry(msfm_ctx* ctx, msfm_two_view_record* out);
 int msfm_match_pairs_verified(msfm_ctx* ctx, const int32_t* pairs, int n_pairs,
                               const msfm_match_params* params, const msfm_verify_params* verify,
                               int64_t* out_offsets);

@@ -29,8 +29,19 @@ EXPORTS = [
     "msfm_match_pairs_begin", "msfm_match_pairs_next", "msfm_read_device", "msfm_memory_info", "msfm_match_pairs_end",
     "msfm_train_vocabulary", "msfm_set_vocabulary", "msfm_image_words", "msfm_retrieve_pairs", "msfm_get_retrieval_profile",
     "msfm_set_verification_model", "msfm_get_verification_stats", "msfm_set_model_selection", "msfm_fetch_model_selection",
+    "msfm_set_two_view_geometry", "msfm_fetch_two_view_geometry",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
+
+
+class TwoViewParams(C.Structure):
+    _fields_ = [("min_num_inliers", C.c_int32), ("reserved", C.c_int32), ("tri_max_error", C.c_double), ("tri_min_angle", C.c_double)]
+
+
+# msfm_two_view_record (include/msfm_match.h): 144 bytes, no implicit padding
+TWO_VIEW_RECORD = np.dtype([("valid", "<i4"), ("reserved", "<i4"), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_kept", "<i4"),
+                            ("n_positive_depth", "<i4"), ("n_triangulated", "<i4"), ("is_initial_candidate", "<i4"),
+                            ("median_tri_angle", "<f8"), ("mean_tri_angle", "<f8"), ("mean_residual", "<f8")])
 
 
 class MatchParams(C.Structure):
@@ -158,6 +169,8 @@ def load():
     L.msfm_get_verification_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.msfm_set_model_selection.argtypes = [vp, C.c_int, C.c_double]
     L.msfm_fetch_model_selection.argtypes = [vp, ip, ip, ip]
+    L.msfm_set_two_view_geometry.argtypes = [vp, C.c_int, C.POINTER(TwoViewParams)]
+    L.msfm_fetch_two_view_geometry.argtypes = [vp, C.c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if the library lacks a declared symbol
     _lib = L
@@ -399,6 +412,8 @@ class Context:
                         "d_qt": ch.d_qt, "d_dist": ch.d_dist}
                 if verified and self._selection_ran():
                     item["model_selection"] = self.model_selection(n)
+                if verified and self._two_view_ran():
+                    item["two_view_geometry"] = self.two_view_geometry(n)
                 yield item
         finally:
             # a consumer that breaks out of the loop (GeneratorExit) or whose body raises must not leave the series open: the store
@@ -492,6 +507,25 @@ class Context:
 
     def _selection_ran(self):
         return self._L.msfm_fetch_model_selection(self._h, None, None, None) == OK
+
+    def set_two_view_geometry(self, enable=True, min_num_inliers=100, tri_max_error=2.0, tri_min_angle=4.0):
+        """The two-view geometry of the verified calls under VERIFY_ESSENTIAL (include/msfm_match.h): every pair also gets a record
+        with the relative pose of its winning E, the triangulation statistics of its kept matches and the reference's test for an
+        initial pair (defaults: the reference's).  The lists do not change.  E_INVALID for a negative / non-finite parameter or under
+        another model; E_STATE while a series is open."""
+        prm = TwoViewParams(int(min_num_inliers), 0, float(tri_max_error), float(tri_min_angle))
+        self._chk(self._L.msfm_set_two_view_geometry(self._h, int(bool(enable)), C.byref(prm)))
+
+    def two_view_geometry(self, n_pairs):
+        """Per pair of the last match_pairs_verified call (or of the last verified stream chunk): a structured array of dtype
+        TWO_VIEW_RECORD.  E_STATE if that call ran without the two-view geometry."""
+        n = int(n_pairs)
+        out = np.zeros(max(n, 1), TWO_VIEW_RECORD)
+        self._chk(self._L.msfm_fetch_two_view_geometry(self._h, out.ctypes.data))
+        return out[:n]
+
+    def _two_view_ran(self):
+        return self._L.msfm_fetch_two_view_geometry(self._h, None) == OK
 
     def knn2_pair(self, id1, id2):
         n1, n2 = self.image_rows(id1), self.image_rows(id2)

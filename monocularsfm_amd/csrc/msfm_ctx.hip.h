@@ -584,6 +584,10 @@ struct Scratch {
     // (msfm_verify_staged.hip.h): per-pair state and round lists, counters
     DevBuf d_ve_x1, d_ve_y1, d_ve_x2, d_ve_y2, d_staged_state, d_staged_stats;
     DevBuf d_vs_records;              // the two-view model selection (msfm_verify_select.hip.h): a SelectRecord per pair
+    // the two-view geometry (msfm_verify_pose.hip.h): a record per pair, the kept-index and angle slots of the staged lists' size, the E
+    // winners saved from the homography's rounds under the selection; h_tv: the records on the host, read at the end of the sub-batch
+    DevBuf d_tv_records, d_tv_idx, d_tv_angles, d_tv_best_it;
+    PinnedBuf h_tv;
     msfm_profile prof = {};           // this sub-batch's share; joins the call's profile when the sub-batch is accepted
     hipEvent_t sweep1_done = nullptr; // recorded behind sweep 1: the other stream's next sweep 1 waits for it
     bool sweep1_recorded = false;
@@ -597,7 +601,7 @@ struct Scratch {
                           &d_vpairs, &d_vpf, &d_vitems, &d_lists, &d_colmask, &d_gtot, &d_grow0, &d_cnt, &d_mrow, &d_summary, &d_overflow,
                           &d_totals, &d_vf_pairs,
                           &d_vf_x1, &d_vf_y1, &d_vf_x2, &d_vf_y2, &d_vf_hyp, &d_vf_best_it, &d_vf_best_count, &d_vf_flags, &d_st2_qt,
-                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
+                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_tv_records, &d_tv_idx, &d_tv_angles, &d_tv_best_it, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
         for (DevBuf* b : bufs) fn(*b, arg);
     }
     long long device_bytes() {
@@ -613,6 +617,7 @@ struct Scratch {
         h_sub_d.release();
         h_summary.release();
         h_tail.release();
+        h_tv.release();
     }
 };
 
@@ -700,6 +705,12 @@ struct msfm_ctx {
     double h_ratio = 0.7;
     std::vector<int32_t> sel_records;
     bool sel_valid = false;
+    // two-view geometry (msfm_set_two_view_geometry): under model 1 every verified pair also gets a msfm_two_view_record; tv_records /
+    // tv_valid: as sel_records / sel_valid
+    bool two_view = false;
+    msfm_two_view_params tv_params = {100, 0, 2.0, 4.0};
+    std::vector<msfm_two_view_record> tv_records;
+    bool tv_valid = false;
 };
 
 #define SC (*ctx->cur)

@@ -53,6 +53,13 @@ inline std::vector<long long> msfm_pipeline_marks(long long total, long long n_s
     return marks;
 }
 
+// What the two-view geometry (msfm_set_two_view_geometry) adds to msfm_pair_scratch_bytes for one pair: per staged match (at most
+// n1) the kept-index slot (4 B) and the angle slot (8 B) of tv_pose_kernel, per pair its record (144 B) and the saved winner (4 B).
+inline long long msfm_pair_two_view_bytes(int n1, int n2) {
+    if (n1 <= 0 || n2 <= 0) return 0;
+    return 12LL * n1 + 148;
+}
+
 // Device scratch ONE image pair adds to a sub-batch, in bytes -- what MatchJob::build (msfm_job.hip.h) cuts a call by, and
 // what the buffers of a scratch set really hold (round 3 charged 2 x a_blocks128 x n2pad 4-byte units per pair whatever the
 // route: 2.6 - 3.4 x what the matrix-core route allocates, so a "48 GiB" budget produced 200 sub-batches of config 4 on a
@@ -70,10 +77,12 @@ inline std::vector<long long> msfm_pipeline_marks(long long total, long long n_s
 //   route 2, matrix cores, dense sweep 2 (kNN-level API, ratio > 0.95): candidate lists of 16 entries per row and column instead;
 //   route 0, brute force: three 4-byte row partials per padded row, three per 128-row block and column.
 // (A mixed sub-batch -- byte pairs next to float pairs -- allocates by route 1's sizes for all of them: this is the cut, not a cap.)
-inline long long msfm_pair_scratch_bytes(int n1, int n2, int n1pad, int n2pad, int blocks128, int blocks512, int route) {
+// two_view: the call computes two-view geometry records (msfm_pair_two_view_bytes on top, whatever the route).
+inline long long msfm_pair_scratch_bytes(int n1, int n2, int n1pad, int n2pad, int blocks128, int blocks512, int route,
+                                         bool two_view = false) {
     if (n1 <= 0 || n2 <= 0) return 0;
     const long long slots = (long long)n1pad + n2pad;
-    const long long common = (route == 3 ? 24LL : 36LL) * slots + 24LL * n1 + 1024;
+    const long long common = (route == 3 ? 24LL : 36LL) * slots + 24LL * n1 + 1024 + (two_view ? msfm_pair_two_view_bytes(n1, n2) : 0);
     if (route == 0) return common + 12LL * n1pad + 12LL * (long long)blocks128 * n2pad;
     const long long partials = 8LL * n1pad + (route == 3 ? 4LL : 8LL) * (long long)blocks512 * n2pad;
     if (route == 2) return common + partials + 128LL * ((long long)n1 + n2) + 16384;
@@ -236,4 +245,14 @@ MSFM_HD void msfm_fold_key(unsigned long long* best, unsigned long long* second,
 // (host/GeometricVerification.cpp) both call this.
 MSFM_HD bool msfm_select_homography(int n_epipolar, int n_homography, double h_ratio) {
     return n_epipolar > 0 && (double)n_homography >= h_ratio * (double)n_epipolar;
+}
+
+// The two-view geometry's test for an initial pair (msfm_set_two_view_geometry): the reference's, in the positive
+// (Initializer::RecoverPoseFromFundanmental fails a pair when num_inliers < rel_pose_min_num_inlier || median_tri_angle <
+// init_tri_min_angle || ave_tri_angle < init_tri_min_angle || ave_residual > init_tri_max_error,
+// src/Reconstruction/Initializer.cpp:400-405).  Exact compares only.  tv_pose_kernel and the host twin (TwoViewGeometry) both call this.
+MSFM_HD bool msfm_initial_candidate(int n_triangulated, double median_tri_angle, double mean_tri_angle, double mean_residual,
+                                    int min_num_inliers, double tri_max_error, double tri_min_angle) {
+    return n_triangulated >= min_num_inliers && median_tri_angle >= tri_min_angle && mean_tri_angle >= tri_min_angle &&
+           mean_residual <= tri_max_error;
 }

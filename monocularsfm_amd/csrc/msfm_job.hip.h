@@ -29,6 +29,7 @@ struct MatchJob {
     const msfm_verify_params* verify = nullptr;
     bool streaming = false;
     bool select = false;   // the two-view model selection runs (msfm_verify_select.hip.h): verified, selection on, model 0 or 1
+    bool pose = false;     // the two-view geometry runs (msfm_verify_pose.hip.h): verified, switched on (model 1, by msfm_set_two_view_geometry)
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     int kSets = kInFlight;
     long long kScratchBytes = 1;
@@ -54,6 +55,9 @@ struct MatchJob {
         select = vp && c->model_select && c->verify_model != MSFM_VERIFY_HOMOGRAPHY;
         c->sel_valid = false;
         c->sel_records.assign(select && !stream_mode ? 3 * (size_t)n : 0, 0);
+        pose = vp && c->two_view && c->verify_model == MSFM_VERIFY_ESSENTIAL;
+        c->tv_valid = false;
+        c->tv_records.assign(pose && !stream_mode ? (size_t)n : 0, msfm_two_view_record{});
         if (vp) {
             verify_store = *vp;
             verify = &verify_store;
@@ -194,7 +198,7 @@ struct MatchJob {
                 return fail(ctx, MSFM_E_STATE, "geometric verification needs msfm_upload_keypoints for image " +
                                                    std::to_string(ia.nk < ia.n ? pairs[2 * end] : pairs[2 * end + 1]));
             const int route = msfm_scratch_route(knobs, prune.prune, prune.ratio, pp.use != 0, ia.is_u8, ib.is_u8);
-            const long long need = pd.valid ? msfm_pair_scratch_bytes(pd.n1, pd.n2, pd.n1pad, pd.n2pad, pd.a_blocks, pd.a_blocks256, route) : 0;
+            const long long need = pd.valid ? msfm_pair_scratch_bytes(pd.n1, pd.n2, pd.n1pad, pd.n2pad, pd.a_blocks, pd.a_blocks256, route, pose) : 0;
             const long long c = pd.valid ? (long long)pd.n1 * pd.n2 : 0;
             if (end > begin && est + need > kScratchBytes) break;
             if (end > begin && !marks.empty() && cost_begin + cost + c / 2 > mark) break;
@@ -268,6 +272,15 @@ struct MatchJob {
         HIPCHK(ctx, hipGetLastError());
         rc = queue_tail_copies(ctx, P, select ? &SC.d_vs_records : nullptr);
         if (rc != MSFM_OK) return rc;
+        if (pose) {   // the records leave by a copy of their own (export_tail_kernel once more): the tail above stays what it is
+            HIPCHK(ctx, SC.h_tv.ensure(P * sizeof(msfm_two_view_record) + 64, 0));
+            char* h = nullptr;
+            HIPCHK(ctx, hipHostGetDevicePointer((void**)&h, SC.h_tv.p, 0));
+            ExportSegs segs = {};
+            segs.s[0] = ExportSeg{SC.d_tv_records.as<char>(), h, (unsigned)(P * sizeof(msfm_two_view_record))};
+            hipLaunchKernelGGL(export_tail_kernel, dim3(32), dim3(256), 0, SC.stream, segs);
+            HIPCHK(ctx, hipGetLastError());
+        }
         w.active = true;
         return MSFM_OK;
     }
@@ -361,9 +374,32 @@ struct MatchJob {
                                SC.d_st2_d.as<float>(), SC.d_counts2.as<int>());
         }
         HIPCHK(ctx, hipGetLastError());
+        if (pose) {
+            HIPCHK(ctx, SC.d_tv_records.ensure(P * sizeof(msfm_two_view_record)));
+            HIPCHK(ctx, SC.d_tv_idx.ensure(oe * 4));
+            HIPCHK(ctx, SC.d_tv_angles.ensure(oe * 8));
+            if (select) {   // the homography's rounds reuse d_vf_best_it: the E winners are saved first (a copy by export_tail_kernel)
+                HIPCHK(ctx, SC.d_tv_best_it.ensure(P * 4));
+                ExportSegs segs = {};
+                segs.s[0] = ExportSeg{SC.d_vf_best_it.as<char>(), SC.d_tv_best_it.as<char>(), (unsigned)(P * 4)};
+                hipLaunchKernelGGL(export_tail_kernel, dim3(32), dim3(256), 0, SC.stream, segs);
+                HIPCHK(ctx, hipGetLastError());
+            }
+        }
         if (select) {
             const int rc = issue_select(P, dp, vp);
             if (rc != MSFM_OK) return rc;
+        }
+        if (pose) {   // (model 1: the normalised coordinates and E's parameters)
+            const double f = (ctx->camera.fx + ctx->camera.fy) * 0.5, tn = verify->threshold / f;
+            const StagedParams prm = {tn * tn, verify->confidence, verify->max_iters, 0, verify->seed};
+            const unsigned grid = (unsigned)std::min<size_t>(P, (size_t)kTvGroupsPerCU * (size_t)std::max(1, ctx->cu_count));
+            hipLaunchKernelGGL(tv_pose_kernel, dim3(grid), dim3(kTvThreads), 0, SC.stream, dp, d_counts, (const double*)SC.d_ve_x1.as<double>(),
+                               (const double*)SC.d_ve_y1.as<double>(), (const double*)SC.d_ve_x2.as<double>(),
+                               (const double*)SC.d_ve_y2.as<double>(), (const int*)(select ? SC.d_tv_best_it.as<int>() : SC.d_vf_best_it.as<int>()),
+                               (const SelectRecord*)(select ? SC.d_vs_records.as<SelectRecord>() : nullptr), prm, f, ctx->tv_params, (int)P,
+                               SC.d_tv_idx.as<int>(), SC.d_tv_angles.as<double>(), SC.d_tv_records.as<msfm_two_view_record>());
+            HIPCHK(ctx, hipGetLastError());
         }
         HIPCHK(ctx, hipEventRecord(v1, SC.stream));
         return MSFM_OK;
@@ -461,6 +497,8 @@ struct MatchJob {
             w.sens.assign(sens, sens + P);
             if (select) w.sel.assign(sens + P, sens + 4 * P);   // (the records follow the certificate counts: queue_tail_copies)
             else w.sel.clear();
+            if (pose) w.tv.assign(SC.h_tv.as<msfm_two_view_record>(), SC.h_tv.as<msfm_two_view_record>() + P);
+            else w.tv.clear();
             for (size_t p = 0; p < P; ++p) SC.prof.order_sensitive_rows += sens[p];
             ctx->res_count += (size_t)total;   // (matches of the job so far)
         } else {
@@ -501,6 +539,7 @@ struct MatchJob {
                 SC.prof.order_sensitive_rows += sens[p];
             }
             if (select) std::memcpy(ctx->sel_records.data() + 3 * (size_t)w.begin, sens + P, P * 12);
+            if (pose) std::memcpy(ctx->tv_records.data() + (size_t)w.begin, SC.h_tv.p, P * sizeof(msfm_two_view_record));
         }
         SC.prof.descriptor_pairs += b.desc_pairs;
         SC.prof.dist_algo_bytes += b.algo_bytes;

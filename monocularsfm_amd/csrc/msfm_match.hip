@@ -15,6 +15,7 @@
 #include "msfm_verify_e.hip.h"
 #include "msfm_verify_h.hip.h"
 #include "msfm_verify_select.hip.h"
+#include "msfm_verify_pose.hip.h"
 #include "msfm_retrieval.hip.h"
 
 #include <sys/mman.h>
@@ -291,6 +292,7 @@ struct SubBatch {
     std::vector<int64_t> offsets; // streaming form: the completed sub-batch's CSR offsets (relative to the sub-batch) and
     std::vector<int32_t> sens;    //   order-certificate counts, until the caller asks for the next chunk
     std::vector<int32_t> sel;     //   and the model selection's records {model, nE, nH} per pair (msfm_fetch_model_selection)
+    std::vector<msfm_two_view_record> tv;   //   and the two-view geometry's (msfm_fetch_two_view_geometry)
 };
 
 void add_profile(msfm_profile& to, const msfm_profile& d) {
@@ -388,6 +390,7 @@ static int match_pairs_impl(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, co
     std::memcpy(out_offsets, ctx->res_offsets.data(), ((size_t)n_pairs + 1) * sizeof(int64_t));
     ctx->have_results = true;
     ctx->sel_valid = job.select;
+    ctx->tv_valid = job.pose;
     return MSFM_OK;
 }
 
@@ -413,6 +416,8 @@ int msfm_set_verification_model(msfm_ctx* ctx, int model, const msfm_camera* cam
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "a streaming series is open");
+    if (ctx->two_view && model != MSFM_VERIFY_ESSENTIAL)
+        return fail(ctx, MSFM_E_INVALID, "the two-view geometry is on and needs the essential-matrix model: switch it off first");
     if (model == MSFM_VERIFY_FUNDAMENTAL) {
         ctx->verify_model = model;
         return MSFM_OK;
@@ -461,6 +466,34 @@ int msfm_fetch_model_selection(msfm_ctx* ctx, int32_t* out_model, int32_t* out_n
     MSFM_API_END
 }
 
+int msfm_set_two_view_geometry(msfm_ctx* ctx, int enable, const msfm_two_view_params* params) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "a streaming series is open");
+    if (enable != 0 && enable != 1) return fail(ctx, MSFM_E_INVALID, "enable must be 0 or 1");
+    msfm_two_view_params p = {100, 0, 2.0, 4.0};   // Initializer::Parameters (include/Reconstruction/Initializer.h:19-30)
+    if (params) p = *params;
+    if (p.min_num_inliers < 0 || !std::isfinite(p.tri_max_error) || p.tri_max_error < 0.0 || !std::isfinite(p.tri_min_angle) ||
+        p.tri_min_angle < 0.0)
+        return fail(ctx, MSFM_E_INVALID, "two-view parameters must be finite and not negative");
+    if (enable && ctx->verify_model != MSFM_VERIFY_ESSENTIAL)
+        return fail(ctx, MSFM_E_INVALID, "the two-view geometry needs the essential-matrix model (msfm_set_verification_model)");
+    p.reserved = 0;
+    ctx->two_view = enable != 0;
+    ctx->tv_params = p;
+    return MSFM_OK;
+    MSFM_API_END
+}
+
+int msfm_fetch_two_view_geometry(msfm_ctx* ctx, msfm_two_view_record* out) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (!ctx->tv_valid) return fail(ctx, MSFM_E_STATE, "the last verified call / chunk ran without the two-view geometry");
+    if (out && !ctx->tv_records.empty()) std::memcpy(out, ctx->tv_records.data(), ctx->tv_records.size() * sizeof(msfm_two_view_record));
+    return MSFM_OK;
+    MSFM_API_END
+}
+
 int msfm_get_verification_stats(const msfm_ctx* ctx, int64_t* hypotheses_solved, int* rounds) {
     MSFM_API_BEGIN(nullptr)
     if (!ctx) return MSFM_E_INVALID;
@@ -505,8 +538,11 @@ static int next_impl(msfm_ctx* ctx, msfm_chunk* out) {
     *out = msfm_chunk{};
     ctx->sel_valid = false;
     ctx->sel_records.clear();
+    ctx->tv_valid = false;
+    ctx->tv_records.clear();
     if (!job.more()) {   // n_pairs == 0: the series is complete
         ctx->sel_valid = job.select;
+        ctx->tv_valid = job.pose;
         return job.finish();
     }
     int slot = 0;
@@ -515,6 +551,8 @@ static int next_impl(msfm_ctx* ctx, msfm_chunk* out) {
     const SubBatch& w = job.sb[slot];
     ctx->sel_records = w.sel;
     ctx->sel_valid = job.select;
+    ctx->tv_records = w.tv;
+    ctx->tv_valid = job.pose;
     const Scratch& sc = ctx->sc[slot];
     out->first_pair = w.begin;
     out->n_pairs = w.end - w.begin;
@@ -589,7 +627,7 @@ int msfm_memory_info(msfm_ctx* ctx, msfm_memory* out) {
     for (Scratch& sc : ctx->sc) {
         scratch += sc.device_bytes();
         for (const PinnedBuf& h : sc.h_up) pinned += own(h);
-        pinned += own(sc.h_summary) + own(sc.h_tail) + sc.h_sub_qt.cap + sc.h_sub_d.cap;
+        pinned += own(sc.h_summary) + own(sc.h_tail) + sc.h_sub_qt.cap + sc.h_sub_d.cap + sc.h_tv.cap;
     }
     out->scratch = scratch;
     for (const OutSeg& s : ctx->out_segs) out->results_device += (int64_t)(s.qt.cap + s.d.cap);

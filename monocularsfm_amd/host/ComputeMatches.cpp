@@ -118,6 +118,34 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
     }
 
+    // SIFTmatch.two_view_geometry : 0 (default) | 1 (under verification_model 1 every verified pair also gets a row of the
+    // two_view_geometries table: relative pose, triangulation statistics, the reference's test for an initial pair; include/msfm_match.h)
+    int two_view_geometry = 0;
+    msfm_two_view_params two_view_params = {100, 0, 2.0, 4.0};
+    int two_view_min_num_inliers = two_view_params.min_num_inliers;
+    fs.Get("SIFTmatch.two_view_geometry", &two_view_geometry);
+    fs.Get("SIFTmatch.two_view_min_num_inliers", &two_view_min_num_inliers);
+    fs.Get("SIFTmatch.two_view_tri_max_error", &two_view_params.tri_max_error);
+    fs.Get("SIFTmatch.two_view_tri_min_angle", &two_view_params.tri_min_angle);
+    two_view_params.min_num_inliers = two_view_min_num_inliers;
+    if (!(two_view_geometry == 0 || two_view_geometry == 1)) {
+        std::cerr << "ComputeMatches: SIFTmatch.two_view_geometry must be 0 or 1" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (two_view_geometry == 1 && verification_model != 1) {
+        std::cerr << "ComputeMatches: SIFTmatch.two_view_geometry : 1 decomposes the essential matrix; it needs "
+                     "SIFTmatch.verification_model : 1"
+                  << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (two_view_min_num_inliers < 0 || !(std::isfinite(two_view_params.tri_max_error) && two_view_params.tri_max_error >= 0) ||
+        !(std::isfinite(two_view_params.tri_min_angle) && two_view_params.tri_min_angle >= 0)) {
+        std::cerr << "ComputeMatches: SIFTmatch.two_view_min_num_inliers, two_view_tri_max_error and two_view_tri_min_angle must be "
+                     "finite and not negative"
+                  << std::endl;
+        return EXIT_FAILURE;
+    }
+
     const char* honour = std::getenv("MSFM_HONOUR_YAML_MATCH_PARAMS");
     const bool use_yaml = honour && honour[0] == '1';
 
@@ -147,6 +175,7 @@ int main(int argc, char** argv) {
 
     matcher->SetVerificationModel(verification_model, camera);
     matcher->SetModelSelection(model_selection == 1, h_ratio);
+    matcher->SetTwoViewGeometry(two_view_geometry == 1, two_view_params);
 
     Timer timer;
     timer.Start();

@@ -2,6 +2,7 @@
 // src/Database/Database.cpp (tables :710-764, pragmas :299-302, statements :779-892, blob codec
 // :230-278, pair ids :656-694); errors print and exit like the reference's SQLITE3_CALL (:8-22).
 #include "Database.h"
+#include "msfm_match.h"
 
 #include <cassert>
 #include <cstdio>
@@ -203,6 +204,44 @@ bool Database::HasDescriptorsU8() const {
     return has;
 }
 
+void Database::CreateTwoViewGeometriesTable() const {
+    Exec(database_,
+         "CREATE TABLE IF NOT EXISTS two_view_geometries"
+         "   (pair_id               INTEGER    PRIMARY KEY    NOT NULL,"
+         "    valid                 INTEGER                   NOT NULL,"
+         "    n_kept                INTEGER                   NOT NULL,"
+         "    n_positive_depth      INTEGER                   NOT NULL,"
+         "    n_triangulated        INTEGER                   NOT NULL,"
+         "    is_initial_candidate  INTEGER                   NOT NULL,"
+         "    median_tri_angle      REAL                      NOT NULL,"
+         "    mean_tri_angle        REAL                      NOT NULL,"
+         "    mean_residual         REAL                      NOT NULL,"
+         "    pose                  BLOB);");
+    if (!sql_stmt_add_two_view_)
+        SQL_CALL(Sqlite().prepare_v2(database_,
+                                     "INSERT OR REPLACE INTO two_view_geometries(pair_id, valid, n_kept, n_positive_depth, n_triangulated, "
+                                     "is_initial_candidate, median_tri_angle, mean_tri_angle, mean_residual, pose) VALUES(?, ?, ?, ?, ?, ?, ?, ?, ?, ?);",
+                                     -1, &sql_stmt_add_two_view_, nullptr));
+}
+
+void Database::WriteTwoViewGeometry(const image_t image_id1, const image_t image_id2, const void* record) const {
+    const msfm_two_view_record& r = *static_cast<const msfm_two_view_record*>(record);
+    sqlite3_stmt* s = sql_stmt_add_two_view_;
+    SQL_CALL(Sqlite().bind_int64(s, 1, ImagePairToPairId(image_id1, image_id2)));
+    SQL_CALL(Sqlite().bind_int64(s, 2, r.valid));
+    SQL_CALL(Sqlite().bind_int64(s, 3, r.n_kept));
+    SQL_CALL(Sqlite().bind_int64(s, 4, r.n_positive_depth));
+    SQL_CALL(Sqlite().bind_int64(s, 5, r.n_triangulated));
+    SQL_CALL(Sqlite().bind_int64(s, 6, r.is_initial_candidate));
+    SQL_CALL(Sqlite().bind_double(s, 7, r.median_tri_angle));
+    SQL_CALL(Sqlite().bind_double(s, 8, r.mean_tri_angle));
+    SQL_CALL(Sqlite().bind_double(s, 9, r.mean_residual));
+    static_assert(sizeof(r.R) + sizeof(r.t) == 96, "the pose blob is R[9] | t[3]");
+    SQL_CALL(Sqlite().bind_blob(s, 10, r.R, 96, nullptr));   // (R and t are adjacent; static: the record outlives the step below)
+    SQL_CALL(Sqlite().step(s));
+    SQL_CALL(Sqlite().reset(s));
+}
+
 void Database::CreateDescriptorsU8Table() const {
     Exec(database_,
          "CREATE TABLE IF NOT EXISTS descriptors_u8"
@@ -383,6 +422,7 @@ void Database::PrepareSQLStatements() {
 
 void Database::FinalizeSQLStatements() {
     for (sqlite3_stmt* s : sql_stmts_) SQL_CALL(Sqlite().finalize(s));
+    if (sql_stmt_add_two_view_) SQL_CALL(Sqlite().finalize(sql_stmt_add_two_view_));
     sql_stmts_.clear();
 }
 

@@ -56,6 +56,13 @@ public:
     // on the matrix cores).  Not part of the reference's schema: only read when present, only written on request.
     bool HasDescriptorsU8() const;
     void CreateDescriptorsU8Table() const;
+    // The two-view geometry's side table (SIFTmatch.two_view_geometry : 1), created on demand -- the reference opens its tables by name
+    // and never sees it: two_view_geometries(pair_id INTEGER PRIMARY KEY, valid, n_kept, n_positive_depth, n_triangulated,
+    // is_initial_candidate INTEGER, median_tri_angle, mean_tri_angle, mean_residual REAL, pose BLOB: R[9] | t[3] as 12 little-endian
+    // doubles, x2 ~ R x1 + t from the image the pair was matched FROM (the larger id in brute mode) to the other one).
+    // `record`: a msfm_two_view_record (include/msfm_match.h).  Written in the transaction of the pair's matches row.
+    void CreateTwoViewGeometriesTable() const;
+    void WriteTwoViewGeometry(const image_t image_id1, const image_t image_id2, const void* record) const;
     void WriteDescriptorsU8(const image_t image_id, const unsigned char* data, size_t rows, size_t cols) const;
     size_t VisitAllDescriptorsU8(BlobVisitor visit, void* user) const;
 
@@ -90,6 +97,7 @@ private:
     sqlite3_stmt *sql_stmt_read_images_, *sql_stmt_read_keypoints_, *sql_stmt_read_descriptors_,
         *sql_stmt_read_matches_, *sql_stmt_read_matches_num_, *sql_stmt_read_matches_all_;
     sqlite3_stmt *sql_stmt_add_image_, *sql_stmt_add_keypoints_, *sql_stmt_add_descriptors_, *sql_stmt_add_matches_;
+    mutable sqlite3_stmt* sql_stmt_add_two_view_ = nullptr;
 };
 
 }  // namespace MonocularSfM

@@ -155,6 +155,8 @@ void FeatureMatcher::OpenDatabaseAndDevice() {
             if (status[g] == MSFM_OK)
                 status[g] = msfm_set_verification_model(c, verification_model_, verification_model_ == MSFM_VERIFY_ESSENTIAL ? &cam : nullptr);
             if (status[g] == MSFM_OK && model_selection_) status[g] = msfm_set_model_selection(c, 1, h_ratio_);
+            if (status[g] == MSFM_OK && two_view_geometry_ && geometric_verification_ && !verification_on_host_)
+                status[g] = msfm_set_two_view_geometry(c, 1, &two_view_params_);
             // An ordinal listed k times (the tests' way to run the fan-out on a one-GPU box): every context would size its scratch
             // for a quarter of the device's free memory on its own -- four of them on one MI355X ran out of memory at config-4 scale.
             // They share the default budget instead (MSFM_SCRATCH_MIB still overrides: it is read at msfm_create, this only applies without it).
@@ -345,6 +347,9 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
     const bool verify_on_device = geometric_verification_ && !verification_on_host_;
     const bool host_verify = geometric_verification_ && verification_on_host_;
     const bool two_view = geometric_verification_ && model_selection_ && verification_model_ != MSFM_VERIFY_HOMOGRAPHY;
+    const bool geometry = geometric_verification_ && two_view_geometry_ && verification_model_ == MSFM_VERIFY_ESSENTIAL;
+    constexpr size_t kRec = sizeof(msfm_two_view_record);
+    if (geometry) database_->CreateTwoViewGeometriesTable();
     static const EmissionOptions emission = EmissionOptions::FromEnvironment();
 
     // ---- everything the device threads will touch is made resident / read now, on this thread (SQLite)
@@ -456,6 +461,16 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
             std::unique_ptr<ResultChunk> out(new ResultChunk());
             out->first = (size_t)ch.first_pair;
             out->n = (size_t)ch.n_pairs;
+            if (geometry) {
+                out->geometry.assign((size_t)ch.n_pairs * kRec, 0);
+                if (verify_on_device) {   // (the records of this chunk: valid until the next msfm_match_pairs_next)
+                    rc = msfm_fetch_two_view_geometry(r.ctx, reinterpret_cast<msfm_two_view_record*>(out->geometry.data()));
+                    if (rc != MSFM_OK) {
+                        fail("msfm_fetch_two_view_geometry", rc);
+                        break;
+                    }
+                }
+            }
             out->offsets.resize(out->n + 1);
             out->rows.resize((size_t)ch.count * 2);
             int64_t at = 0;
@@ -490,6 +505,17 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                         FilterMatches(keypoints_cache_.at(id1), keypoints_cache_.at(id2), list, &kept, verification_model_, camera_,
                                       model_selection_, h_ratio_, &chosen);
                         list.swap(kept);
+                        if (geometry && chosen == MSFM_VERIFY_ESSENTIAL) {   // (a pair that kept the homography's list: the zero record)
+                            const std::vector<KeyPoint>&ka = keypoints_cache_.at(id1), &kb = keypoints_cache_.at(id2);
+                            std::vector<Point2f> a(m), b(m);
+                            for (size_t i = 0; i < m; ++i) {
+                                a[i] = Point2f{ka[(size_t)qt[2 * i]].x, ka[(size_t)qt[2 * i]].y};
+                                b[i] = Point2f{kb[(size_t)qt[2 * i + 1]].x, kb[(size_t)qt[2 * i + 1]].y};
+                            }
+                            msfm_two_view_record rec;
+                            TwoViewGeometry(a, b, camera_, two_view_params_, &rec);
+                            std::memcpy(out->geometry.data() + p * kRec, &rec, kRec);
+                        }
                         if (two_view) {
                             r.two_view_pairs += 1;
                             r.two_view_h += chosen == MSFM_VERIFY_HOMOGRAPHY ? 1 : 0;
@@ -541,6 +567,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
         const point2D_t* rows;
         size_t m;
         double seconds;
+        const unsigned char* geometry;   // the pair's msfm_two_view_record, or NULL
     };
     auto fetch = [&](size_t w) -> Fetched {
         DeviceRun& r = runs[dev_of[w]];
@@ -561,7 +588,8 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
         }
         const size_t li = r.consumed - r.cur->first;
         ++r.consumed;
-        return Fetched{r.cur->rows.data() + 2 * r.cur->offsets[li], (size_t)(r.cur->offsets[li + 1] - r.cur->offsets[li]), r.cur->seconds_per_pair};
+        return Fetched{r.cur->rows.data() + 2 * r.cur->offsets[li], (size_t)(r.cur->offsets[li + 1] - r.cur->offsets[li]), r.cur->seconds_per_pair,
+                       r.cur->geometry.empty() ? nullptr : r.cur->geometry.data() + li * sizeof(msfm_two_view_record)};
     };
     // one group's stdout lines (and, in the reference's order, its rows): "Existing, Continue!" or the pair's three lines
     std::vector<uint32_t> count_of;    // key order: what the stdout lines need, by todo index
@@ -581,6 +609,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
             if (write_rows) {
                 const Fetched f = fetch((size_t)p);
                 database_->WriteMatchesStored(image_id1, image_id2, f.rows, f.m);
+                if (f.geometry) database_->WriteTwoViewGeometry(image_id1, image_id2, f.geometry);
                 m = f.m;
                 seconds = f.seconds;
                 matches_written += (long long)m;
@@ -621,6 +650,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                 const size_t p = (size_t)work_order[w];
                 const Fetched f = fetch(w);
                 database_->WriteMatchesStored(todo[2 * p], todo[2 * p + 1], f.rows, f.m);
+                if (f.geometry) database_->WriteTwoViewGeometry(todo[2 * p], todo[2 * p + 1], f.geometry);
                 count_of[p] = (uint32_t)f.m;
                 seconds_of[p] = (float)f.seconds;
                 matches_written += (long long)f.m;

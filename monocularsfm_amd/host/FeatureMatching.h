@@ -49,6 +49,13 @@ public:
     // SIFTmatch.model_selection / model_selection_h_ratio: under models 0 and 1, every pair also runs the homography and keeps the
     // list msfm_select_homography picks (msfm_set_model_selection on every device context, or TwoViewSelectMask in the host twin).
     // Call before RunMatching.
+    // SIFTmatch.two_view_geometry (+ two_view_min_num_inliers / _tri_max_error / _tri_min_angle), model 1 only: every verified pair's
+    // msfm_two_view_record (msfm_set_two_view_geometry on every device context, or TwoViewGeometry in the host twin) goes into the
+    // two_view_geometries table, in the transaction of the pair's matches row.  Call before RunMatching.
+    void SetTwoViewGeometry(bool on, const msfm_two_view_params& params) {
+        two_view_geometry_ = on;
+        two_view_params_ = params;
+    }
     void SetModelSelection(bool on, double h_ratio) {
         model_selection_ = on;
         h_ratio_ = h_ratio;
@@ -71,6 +78,8 @@ protected:
     bool cross_check_;
     bool geometric_verification_ = true;
     bool verification_on_host_ = false;  // MSFM_GEOMETRIC_VERIFICATION=host
+    bool two_view_geometry_ = false;                     // SetTwoViewGeometry
+    msfm_two_view_params two_view_params_ = {100, 0, 2.0, 4.0};
     int verification_model_ = MSFM_VERIFY_FUNDAMENTAL;   // SetVerificationModel
     CameraIntrinsics camera_ = {};                       // (model 1 only)
     bool model_selection_ = false;                       // SetModelSelection

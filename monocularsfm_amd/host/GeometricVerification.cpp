@@ -8,6 +8,7 @@
 #include "../csrc/msfm_fmat.h"
 #include "../csrc/msfm_hmat.h"
 #include "../csrc/msfm_hostutil.h"
+#include "../csrc/msfm_pose.h"
 
 namespace MonocularSfM {
 
@@ -75,9 +76,10 @@ std::vector<unsigned char> FundamentalRansacMask(const std::vector<Point2f>& pts
 // The sequential loop of msfm_fmat::replay_adaptive<5> over lazily scored hypotheses: hypothesis it is solved and scored when the
 // loop reaches it; its count is the largest over its solutions.  The winning solution (the lowest index among equal counts) gives
 // the mask.
-std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
-                                               const CameraIntrinsics& camera, double threshold, double confidence,
-                                               int max_iters, unsigned long long seed) {
+// (E_out, xy_out: the winner and the normalised coordinates x1 | y1 | x2 | y2 of every match, for TwoViewGeometry; may be NULL)
+static std::vector<unsigned char> essential_ransac(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                                   const CameraIntrinsics& camera, double threshold, double confidence, int max_iters,
+                                                   unsigned long long seed, double* E_out, std::vector<double>* xy_out) {
     using namespace msfm_emat;
     const int n = (int)pts1.size();
     if (n < 5) return {};
@@ -113,6 +115,36 @@ std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1,
     std::vector<unsigned char> mask((size_t)n, 0);
     const double* E = ws.data() + kWsSol + 9 * sol;
     for (int i = 0; i < n; ++i) mask[(size_t)i] = sampson(E, x1[(size_t)i], y1[(size_t)i], x2[(size_t)i], y2[(size_t)i]) <= thr2 ? 1 : 0;
+    if (E_out) std::copy(E, E + 9, E_out);
+    if (xy_out) {
+        xy_out->clear();
+        for (const std::vector<double>* a : {&x1, &y1, &x2, &y2}) xy_out->insert(xy_out->end(), a->begin(), a->end());
+    }
+    return mask;
+}
+
+std::vector<unsigned char> EssentialRansacMask(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                               const CameraIntrinsics& camera, double threshold, double confidence,
+                                               int max_iters, unsigned long long seed) {
+    return essential_ransac(pts1, pts2, camera, threshold, confidence, max_iters, seed, nullptr, nullptr);
+}
+
+std::vector<unsigned char> TwoViewGeometry(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                           const CameraIntrinsics& camera, const msfm_two_view_params& params,
+                                           msfm_two_view_record* record, double threshold, double confidence, int max_iters,
+                                           unsigned long long seed) {
+    double E[9];
+    std::vector<double> xy;
+    msfm_pose::clear_record(record);
+    const std::vector<unsigned char> mask = essential_ransac(pts1, pts2, camera, threshold, confidence, max_iters, seed, E, &xy);
+    if (mask.empty()) return mask;
+    const size_t n = mask.size();
+    std::vector<double> k[4];
+    for (size_t i = 0; i < n; ++i)
+        if (mask[i])
+            for (int c = 0; c < 4; ++c) k[c].push_back(xy[(size_t)c * n + i]);
+    msfm_pose::two_view_record(E, k[0].data(), k[1].data(), k[2].data(), k[3].data(), (int)k[0].size(),
+                               (camera.fx + camera.fy) * 0.5, params, record);
     return mask;
 }
 

@@ -55,6 +55,15 @@ std::vector<unsigned char> TwoViewSelectMask(const std::vector<Point2f>& pts1, c
                                              double confidence = 0.99, int max_iters = 1000, unsigned long long seed = 0x5eed5eedULL,
                                              int* chosen = nullptr, int* n_epipolar = nullptr, int* n_homography = nullptr);
 
+// The two-view geometry (msfm_set_two_view_geometry, csrc/msfm_pose.h) on top of EssentialRansacMask: the same mask, and in *record
+// the relative pose, the triangulation statistics and the reference's test for an initial pair, from the RANSAC's winning E and the
+// kept matches in list order (valid = 0 when the mask is empty or no candidate pose puts a match in front of both cameras).  Host
+// twin of tv_pose_kernel (csrc/msfm_verify_pose.hip.h): the same bits.
+std::vector<unsigned char> TwoViewGeometry(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2,
+                                           const CameraIntrinsics& camera, const msfm_two_view_params& params,
+                                           msfm_two_view_record* record, double threshold = 3.0, double confidence = 0.99,
+                                           int max_iters = 1000, unsigned long long seed = 0x5eed5eedULL);
+
 // FeatureUtils::GetAlignedPointsFromMatches + FilterMatches, with the model of SIFTmatch.verification_model
 // (msfm_match.h: MSFM_VERIFY_FUNDAMENTAL as the reference, MSFM_VERIFY_ESSENTIAL with `camera`, MSFM_VERIFY_HOMOGRAPHY) and the
 // reference's constants.  model_selection (SIFTmatch.model_selection, models 0 and 1 only): TwoViewSelectMask with h_ratio;

@@ -13,6 +13,7 @@
 #include "../csrc/msfm_fmat.h"
 #include "../csrc/msfm_hmat.h"
 #include "../csrc/msfm_hostutil.h"
+#include "../csrc/msfm_pose.h"
 
 using namespace MonocularSfM;
 
@@ -502,5 +503,57 @@ int host_staged_schedule(int model, const float* p1, const float* p2, int n, con
 
 // msfm_select_homography (csrc/msfm_hostutil.h), the rule itself
 int host_select_homography(int n_epipolar, int n_homography, double h_ratio) { return msfm_select_homography(n_epipolar, n_homography, h_ratio) ? 1 : 0; }
+
+// ---- the pieces of msfm_pose.h (tests/test_pose_reference.py compares them with tests/pose_ref.py) --------------------------
+// the four candidates of E, each R[9] | t[3]; returns 1, or 0 when E has no decomposition
+int host_pose_decompose(const double* E, double* cand48) { return msfm_pose::decompose<1>(E, cand48) ? 1 : 0; }
+
+// the DLT point of one match under P = R[9] | t[3]; returns 1 when triangulated
+int host_pose_triangulate(const double* P, double x1, double y1, double x2, double y2, double* X) {
+    return msfm_pose::triangulate(P, x1, y1, x2, y2, X) ? 1 : 0;
+}
+
+// one kept match under P: out3 = {positive depth (0 / 1), error in pixels, angle in degrees}
+void host_pose_evaluate(const double* P, double f, double x1, double y1, double x2, double y2, double* out3) {
+    bool depth;
+    msfm_pose::evaluate(P, f, x1, y1, x2, y2, &depth, &out3[1], &out3[2]);
+    out3[0] = depth ? 1.0 : 0.0;
+}
+
+void host_pose_acos(const double* x, int n, double* out) {
+    for (int i = 0; i < n; ++i) out[i] = msfm_pose::acos(x[i]);
+}
+
+int host_initial_candidate(int n_triangulated, double median_tri_angle, double mean_tri_angle, double mean_residual, int min_num_inliers,
+                           double tri_max_error, double tri_min_angle) {
+    return msfm_initial_candidate(n_triangulated, median_tri_angle, mean_tri_angle, mean_residual, min_num_inliers, tri_max_error,
+                                  tri_min_angle) ? 1 : 0;
+}
+
+// msfm_pose::two_view_record on a given E and kept matches in normalised coordinates (n each); returns the winning candidate or -1
+int host_pose_record(const double* E, const double* x1, const double* y1, const double* x2, const double* y2, int n, double f,
+                     int min_num_inliers, double tri_max_error, double tri_min_angle, msfm_two_view_record* record) {
+    const msfm_two_view_params prm = {min_num_inliers, 0, tri_max_error, tri_min_angle};
+    int winner = -1;
+    msfm_pose::two_view_record(E, x1, y1, x2, y2, n, f, prm, record, &winner);
+    return winner;
+}
+
+// TwoViewGeometry on pixel coordinates p1, p2 (n x 2) with the camera fx, fy, cx, cy, k1, k2, p1, p2 of `cam`; returns the mask
+// length (0: nothing kept)
+int host_two_view_geometry(const float* p1, const float* p2, int n, const double* cam, int min_num_inliers, double tri_max_error,
+                           double tri_min_angle, double threshold, double confidence, int max_iters, unsigned long long seed,
+                           unsigned char* mask, msfm_two_view_record* record) {
+    std::vector<Point2f> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[(size_t)i] = Point2f{p1[2 * i], p1[2 * i + 1]};
+        b[(size_t)i] = Point2f{p2[2 * i], p2[2 * i + 1]};
+    }
+    const CameraIntrinsics c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    const msfm_two_view_params prm = {min_num_inliers, 0, tri_max_error, tri_min_angle};
+    const std::vector<unsigned char> m = TwoViewGeometry(a, b, c, prm, record, threshold, confidence, max_iters, seed);
+    for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
+    return (int)m.size();
+}
 
 }  // extern "C"

@@ -25,8 +25,9 @@ struct ResultChunk {
     size_t first = 0, n = 0;             // local pair indices [first, first + n)
     std::vector<int64_t> offsets;        // n + 1
     std::vector<point2D_t> rows;         // 2 * offsets[n]
+    std::vector<unsigned char> geometry; // empty, or n two-view geometry records (msfm_two_view_record, 144 bytes each)
     double seconds_per_pair = 0;         // wall clock of the chunk on the device thread / n (the "Elapsed time" line of a pair)
-    size_t Bytes() const { return rows.size() * sizeof(point2D_t) + offsets.size() * 8 + sizeof(*this); }
+    size_t Bytes() const { return rows.size() * sizeof(point2D_t) + offsets.size() * 8 + geometry.size() + sizeof(*this); }
 };
 
 // Bounded single-producer / single-consumer queue: the producer blocks while more than `cap` bytes wait (emission is the slower side

@@ -35,6 +35,7 @@ const SqliteApi& Sqlite() {
     BIND(free, "sqlite3_free");
     BIND(prepare_v2, "sqlite3_prepare_v2");
     BIND(bind_int64, "sqlite3_bind_int64");
+    BIND(bind_double, "sqlite3_bind_double");
     BIND(bind_blob, "sqlite3_bind_blob");
     BIND(bind_text, "sqlite3_bind_text");
     BIND(bind_null, "sqlite3_bind_null");

@@ -19,6 +19,7 @@ struct SqliteApi {
     void (*free)(void*);
     int (*prepare_v2)(sqlite3*, const char*, int, sqlite3_stmt**, const char**);
     int (*bind_int64)(sqlite3_stmt*, int, int64_t);
+    int (*bind_double)(sqlite3_stmt*, int, double);
     int (*bind_blob)(sqlite3_stmt*, int, const void*, int, void (*)(void*));
     int (*bind_text)(sqlite3_stmt*, int, const char*, int, void (*)(void*));
     int (*bind_null)(sqlite3_stmt*, int);
