@@ -441,6 +441,90 @@ int msfm_retrieve_pairs(msfm_ctx* ctx, const int32_t* ids, int n, int num_neares
                         int* out_n_pairs, float* out_score_matrix);
 int msfm_get_retrieval_profile(const msfm_ctx* ctx, msfm_retrieval_profile* out);
 
+/* ---- feature tracks: the kept matches of a run, joined across pairs --------------------------------
+ * Off by default.  What every consumer of a `matches` table does first is join the pairwise matches into multi-view correspondences:
+ * the reference in SceneGraph::Load -> AddCorrespondences (src/Reconstruction/SceneGraph.cpp:11-85, 170-251: per-keypoint lists over the
+ * pairs with at least min_num_matches = 10 matches, include/Reconstruction/MapBuilder.h:48), walked transitively while MapBuilder grows
+ * its Tracks (src/Reconstruction/MapBuilder.cpp:333-340, 469-488).  A TRACK SESSION does it on the device while the lists are still in
+ * HBM: one resident union-find forest, 4 bytes per keypoint, into which every sub-batch's final lists are folded as the sub-batch
+ * completes -- in the streaming form too, so a job whose lists never fit memory still gets its tracks.  Exact integer work: the result
+ * equals the host twin (csrc/msfm_tracks.h) and the numpy reference (tests/tracks_ref.py) element for element.
+ *   nodes       msfm_tracks_begin declares the images (any order, distinct, resident).  Ranked by ascending id, the image of rank p has
+ *               rows_p keypoints (its descriptor rows, msfm_image_rows) and base_p = rows_0 + .. + rows_(p-1); keypoint k of it is NODE
+ *               base_p + k.
+ *   edges       a match (q, t) of the pair (id1, id2) joins node (id1, q) and node (id2, t).  Per pair, in this order: an image outside
+ *               the declared set (the pre-emptive filter's subsets live at MSFM_MAX_IMAGES + id) -> the pair is SKIPPED; id1 == id2 ->
+ *               all its matches are IGNORED; a list shorter than min_pair_matches -> the pair contributes nothing (SceneGraph::Load's
+ *               rule, SceneGraph.cpp:35, 68; 0 = every pair); else the pair is folded in, a match with an index outside [0, rows) of
+ *               its image IGNORED as AddCorrespondences ignores it (SceneGraph.cpp:172-176, 198-248), every other one an edge (counted
+ *               with its multiplicity: folding a list twice changes `edges`, not the tracks).
+ *   while open  EVERY batch matching call on the context folds the lists it hands out: msfm_match_pairs, msfm_match_pairs_verified
+ *               (the lists after verification / model selection), every chunk of msfm_match_pairs_begin / _next.  msfm_match_pair and
+ *               msfm_knn2_pair do not take part.  msfm_tracks_add folds HOST lists in (CSR as msfm_match_pairs returns them): rows
+ *               already in the database on a resumed run, lists verified on the host, lists of another process.
+ *   forests     msfm_tracks_export_forest: one int32 per node, a node of the same component (no particular one);
+ *               msfm_tracks_import_forest: every node v is joined with parent[v].  Contexts that declared the same images join their
+ *               sessions this way (one context per GPU: the others' forests imported into the first).
+ *   result      msfm_tracks_finish closes the accumulation (matching calls no longer fold, msfm_tracks_add / _import_forest return
+ *               MSFM_E_STATE) and builds the result; it may be called again with another filter.  COMPONENT: a connected component of
+ *               the node graph.  TRACK: a component of at least 2 nodes.  A track is CONSISTENT iff no two of its nodes belong to one
+ *               image.  Kept: max(2, min_length) <= length, length <= max_length (0 = no bound), and consistent unless
+ *               keep_inconsistent.  Kept tracks are numbered 0 .. T-1 by ascending smallest node, the elements of a track listed by
+ *               ascending node, i.e. by (image id, keypoint index): a function of the SET of edges alone -- not of pair order,
+ *               sub-batch cuts, streams, the number of contexts or the scheduling of atomics.
+ *   stats       tracks_total / _inconsistent / _over_max_length count all tracks (before the filter); longest_track is the longest
+ *               KEPT one; device_bytes what the session holds when msfm_tracks_finish returns (forest + result); fold_ms the summed HIP-event
+ *               time of the fold kernels so far, finish_ms that of the last msfm_tracks_finish.
+ * Errors: msfm_tracks_begin -- an id outside [0, MSFM_MAX_IMAGES), twice in the list, n < 0, 2^31 nodes or more: MSFM_E_INVALID; an id
+ * not resident: MSFM_E_NOIMAGE; a session or a streaming series open: MSFM_E_STATE (a pending store build is done first).  Without a
+ * session every other entry point here returns MSFM_E_STATE; so do the fetches before msfm_tracks_finish, msfm_tracks_finish while a
+ * streaming series is open, and -- while a session is open -- msfm_clear_images and msfm_upload_image / msfm_subset_image INTO a
+ * declared image.  msfm_tracks_import_forest: an entry outside [0, nodes) is MSFM_E_INVALID (nothing is joined then).
+ * A matching call that FAILS (any status but MSFM_OK, in any of its sub-batches) may already have folded the sub-batches it completed
+ * before the failure -- lists the caller never received; a repeat of the call leaves the tracks right (unions are idempotent) but
+ * counts those edges and pairs twice.  After a failed matching call the session's content is therefore unspecified: msfm_tracks_end
+ * it and begin again.  A msfm_tracks_finish that fails leaves the accumulation closed and no result (the fetches return MSFM_E_STATE
+ * until a finish succeeds).
+ * msfm_fetch_tracks: offsets T + 1 entries, image_ids / point_idx `observations_kept` entries, consistent T entries; any pointer may
+ * be NULL.  msfm_fetch_track_ids: per keypoint of a declared image its kept track's number or -1.  msfm_tracks_end frees the session
+ * (no session: MSFM_OK); msfm_destroy does too. */
+typedef struct msfm_track_params {
+    int32_t min_pair_matches;    /* 0 = every pair (the reference's MapBuilder::Parameters::min_num_matches: 10) */
+    int32_t add_only;            /* != 0: the matching calls on the context do NOT fold; only msfm_tracks_add / _import_forest do (a caller
+                                    whose stored lists are not the device's: host-side verification, rows filtered before they are written) */
+} msfm_track_params;
+typedef struct msfm_track_filter {
+    int32_t min_length;          /* values below 2 mean 2 */
+    int32_t max_length;          /* 0 = no bound */
+    int32_t keep_inconsistent;
+    int32_t reserved;
+} msfm_track_filter;
+typedef struct msfm_track_stats {   /* 120 bytes, no implicit padding */
+    int64_t nodes;
+    int64_t edges;                   /* matches folded in */
+    int64_t pairs;                   /* pairs folded in */
+    int64_t pairs_skipped;           /* an image outside the declared set */
+    int64_t pairs_below_min;         /* shorter than min_pair_matches */
+    int64_t matches_ignored;         /* index out of range, or a pair with id1 == id2 */
+    int64_t tracks_total;
+    int64_t tracks_inconsistent;
+    int64_t tracks_over_max_length;
+    int64_t tracks_kept;             /* T */
+    int64_t observations_kept;
+    int64_t longest_track;
+    int64_t device_bytes;
+    double fold_ms;
+    double finish_ms;
+} msfm_track_stats;
+int msfm_tracks_begin(msfm_ctx* ctx, const int32_t* ids, int n, const msfm_track_params* params);
+int msfm_tracks_add(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, const int64_t* offsets, const int32_t* qt);
+int msfm_tracks_export_forest(msfm_ctx* ctx, int32_t* parent);
+int msfm_tracks_import_forest(msfm_ctx* ctx, const int32_t* parent);
+int msfm_tracks_finish(msfm_ctx* ctx, const msfm_track_filter* filter, msfm_track_stats* stats);
+int msfm_fetch_tracks(msfm_ctx* ctx, int64_t* offsets, int32_t* image_ids, int32_t* point_idx, uint8_t* consistent);
+int msfm_fetch_track_ids(msfm_ctx* ctx, int image_id, int32_t* out);
+int msfm_tracks_end(msfm_ctx* ctx);
+
 /* ---- host-side helpers (no device work) ------------------------------------------------- */
 /* FeatureUtils::ExtractTopScaleDescriptors' row selection (FeatureUtils.cpp:68-96):
  * kpts = n x 4 float (x, y, size, angle); writes min(k, n) indices, k > n => identity.

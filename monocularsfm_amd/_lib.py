@@ -30,6 +30,8 @@ EXPORTS = [
     "msfm_train_vocabulary", "msfm_set_vocabulary", "msfm_image_words", "msfm_retrieve_pairs", "msfm_get_retrieval_profile",
     "msfm_set_verification_model", "msfm_get_verification_stats", "msfm_set_model_selection", "msfm_fetch_model_selection",
     "msfm_set_two_view_geometry", "msfm_fetch_two_view_geometry",
+    "msfm_tracks_begin", "msfm_tracks_add", "msfm_tracks_export_forest", "msfm_tracks_import_forest", "msfm_tracks_finish",
+    "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -42,6 +44,21 @@ class TwoViewParams(C.Structure):
 TWO_VIEW_RECORD = np.dtype([("valid", "<i4"), ("reserved", "<i4"), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_kept", "<i4"),
                             ("n_positive_depth", "<i4"), ("n_triangulated", "<i4"), ("is_initial_candidate", "<i4"),
                             ("median_tri_angle", "<f8"), ("mean_tri_angle", "<f8"), ("mean_residual", "<f8")])
+
+
+class TrackParams(C.Structure):
+    _fields_ = [("min_pair_matches", C.c_int32), ("add_only", C.c_int32)]
+
+
+class TrackFilter(C.Structure):
+    _fields_ = [("min_length", C.c_int32), ("max_length", C.c_int32), ("keep_inconsistent", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TrackStats(C.Structure):
+    """msfm_track_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("nodes", "edges", "pairs", "pairs_skipped", "pairs_below_min", "matches_ignored", "tracks_total",
+                                         "tracks_inconsistent", "tracks_over_max_length", "tracks_kept", "observations_kept",
+                                         "longest_track", "device_bytes")] + [("fold_ms", C.c_double), ("finish_ms", C.c_double)]
 
 
 class MatchParams(C.Structure):
@@ -171,6 +188,15 @@ def load():
     L.msfm_fetch_model_selection.argtypes = [vp, ip, ip, ip]
     L.msfm_set_two_view_geometry.argtypes = [vp, C.c_int, C.POINTER(TwoViewParams)]
     L.msfm_fetch_two_view_geometry.argtypes = [vp, C.c_void_p]
+    i64p = C.POINTER(C.c_int64)
+    L.msfm_tracks_begin.argtypes = [vp, ip, C.c_int, C.POINTER(TrackParams)]
+    L.msfm_tracks_add.argtypes = [vp, ip, C.c_int, i64p, ip]
+    L.msfm_tracks_export_forest.argtypes = [vp, ip]
+    L.msfm_tracks_import_forest.argtypes = [vp, ip]
+    L.msfm_tracks_finish.argtypes = [vp, C.POINTER(TrackFilter), C.POINTER(TrackStats)]
+    L.msfm_fetch_tracks.argtypes = [vp, i64p, ip, ip, C.POINTER(C.c_uint8)]
+    L.msfm_fetch_track_ids.argtypes = [vp, C.c_int, ip]
+    L.msfm_tracks_end.argtypes = [vp]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if the library lacks a declared symbol
     _lib = L
@@ -526,6 +552,75 @@ class Context:
 
     def _two_view_ran(self):
         return self._L.msfm_fetch_two_view_geometry(self._h, None) == OK
+
+    # ---- feature tracks (include/msfm_match.h) ----
+    def tracks_begin(self, ids, min_pair_matches=0, add_only=False):
+        """Open a track session over the resident images `ids`: from now on every match_pairs / match_pairs_verified call and every
+        chunk of match_pairs_stream folds the lists it hands out into one union-find forest on the device.  A pair with fewer than
+        min_pair_matches matches contributes nothing (0: every pair; the reference's SceneGraph::Load uses 10).  add_only: the matching
+        calls do not fold, only tracks_add / tracks_import_forest do."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        prm = TrackParams(int(min_pair_matches), int(bool(add_only)))
+        self._chk(self._L.msfm_tracks_begin(self._h, _ip(ids), len(ids), C.byref(prm)))
+        self._track_nodes = int(sum(self.image_rows(int(i)) for i in ids))
+
+    def tracks_add(self, pairs, offsets, qt):
+        """Fold host lists in (CSR as match_pairs returns them: pairs P x 2, offsets P + 1, qt M x 2).  An index outside its image's
+        rows and a pair with id1 == id2 are ignored and counted, a pair with an undeclared image is skipped and counted."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        qt = np.ascontiguousarray(np.asarray(qt, dtype=np.int32).reshape(-1, 2))
+        if len(offsets) != len(pairs) + 1 or (len(pairs) and int(offsets[-1]) > len(qt)):
+            raise ValueError("offsets must have P + 1 entries within qt")
+        self._chk(self._L.msfm_tracks_add(self._h, _ip(pairs), len(pairs), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ip(qt)))
+
+    def tracks_finish(self, min_length=2, max_length=0, keep_inconsistent=False):
+        """Close the accumulation and build the tracks under the filter (may be called again with another filter) -> stats dict."""
+        f = TrackFilter(int(min_length), int(max_length), int(bool(keep_inconsistent)), 0)
+        st = TrackStats()
+        self._chk(self._L.msfm_tracks_finish(self._h, C.byref(f), C.byref(st)))
+        self._track_stats = {k: getattr(st, k) for k, _ in TrackStats._fields_}
+        return dict(self._track_stats)
+
+    def tracks(self):
+        """-> (offsets[T + 1] int64, image_ids[O] int32, point_idx[O] int32, consistent[T] uint8) of the last tracks_finish: kept tracks
+        by ascending smallest (image id, keypoint index), the elements of each in that order."""
+        st = getattr(self, "_track_stats", None) or {"tracks_kept": 0, "observations_kept": 0}
+        T, O = int(st["tracks_kept"]), int(st["observations_kept"])
+        offs = np.zeros(T + 1, np.int64)
+        img, idx = np.zeros(max(O, 1), np.int32), np.zeros(max(O, 1), np.int32)
+        cons = np.zeros(max(T, 1), np.uint8)
+        self._chk(self._L.msfm_fetch_tracks(self._h, offs.ctypes.data_as(C.POINTER(C.c_int64)), _ip(img), _ip(idx),
+                                            cons.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return offs, img[:O], idx[:O], cons[:T]
+
+    def track_ids(self, image_id):
+        """Per keypoint of a declared image: the number of its kept track or -1."""
+        n = self.image_rows(image_id)
+        out = np.full(max(n, 1), -1, np.int32)
+        self._chk(self._L.msfm_fetch_track_ids(self._h, int(image_id), _ip(out)))
+        return out[:n]
+
+    def tracks_export_forest(self):
+        """The session's forest: one int32 per node (the declared images' rows, images by ascending id), each a node of the same
+        component."""
+        nodes = int(getattr(self, "_track_nodes", 0) or 0)
+        out = np.zeros(max(nodes, 1), np.int32)
+        self._chk(self._L.msfm_tracks_export_forest(self._h, _ip(out)))
+        return out[:nodes]
+
+    def tracks_import_forest(self, parent):
+        """Join every node v with parent[v] (a forest exported by a session over the same images, e.g. on another GPU)."""
+        parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        nodes = getattr(self, "_track_nodes", None)   # (None: no session was opened through this object -- the library says so)
+        if nodes is not None and len(parent) != nodes:
+            raise ValueError("the forest must have one entry per node of the session (%d), got %d" % (nodes, len(parent)))
+        self._chk(self._L.msfm_tracks_import_forest(self._h, _ip(parent)))
+
+    def tracks_end(self):
+        self._track_stats = None
+        self._track_nodes = None
+        self._chk(self._L.msfm_tracks_end(self._h))
 
     def knn2_pair(self, id1, id2):
         n1, n2 = self.image_rows(id1), self.image_rows(id2)

@@ -588,6 +588,8 @@ struct Scratch {
     // winners saved from the homography's rounds under the selection; h_tv: the records on the host, read at the end of the sub-batch
     DevBuf d_tv_records, d_tv_idx, d_tv_angles, d_tv_best_it;
     PinnedBuf h_tv;
+    DevBuf d_tk_pairs;                // feature tracks (msfm_tracks.hip.h): the sub-batch's (id1, id2) per pair, for the fold
+    PinnedBuf h_tk_pairs;             //   and its page-locked staging, rewritten only after the set's stream has been waited for
     msfm_profile prof = {};           // this sub-batch's share; joins the call's profile when the sub-batch is accepted
     hipEvent_t sweep1_done = nullptr; // recorded behind sweep 1: the other stream's next sweep 1 waits for it
     bool sweep1_recorded = false;
@@ -601,7 +603,7 @@ struct Scratch {
                           &d_vpairs, &d_vpf, &d_vitems, &d_lists, &d_colmask, &d_gtot, &d_grow0, &d_cnt, &d_mrow, &d_summary, &d_overflow,
                           &d_totals, &d_vf_pairs,
                           &d_vf_x1, &d_vf_y1, &d_vf_x2, &d_vf_y2, &d_vf_hyp, &d_vf_best_it, &d_vf_best_count, &d_vf_flags, &d_st2_qt,
-                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_tv_records, &d_tv_idx, &d_tv_angles, &d_tv_best_it, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
+                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_tv_records, &d_tv_idx, &d_tv_angles, &d_tv_best_it, &d_tk_pairs, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
         for (DevBuf* b : bufs) fn(*b, arg);
     }
     long long device_bytes() {
@@ -618,10 +620,52 @@ struct Scratch {
         h_summary.release();
         h_tail.release();
         h_tv.release();
+        h_tk_pairs.release();
     }
 };
 
 struct MatchJob;   // msfm_job.hip.h
+
+// A track session (include/msfm_match.h "feature tracks", kernels and host side in msfm_tracks.hip.h): the declared images and their
+// node numbering, the resident forest, the result of the last msfm_tracks_finish.  Not part of the sub-batch scratch budget.
+struct TrackSession {
+    bool open = false;
+    bool closed = false;               // msfm_tracks_finish has closed the accumulation: nothing folds any more
+    bool finished = false;             // the result of the last msfm_tracks_finish is valid (a finish that failed leaves none)
+    bool suppress = false;             // msfm_match_pair is running: its one-pair call does not take part
+    MsfmTrackNodes nd;                 // msfm_tracks.h
+    std::vector<int> rank_of;          // per image id < MSFM_MAX_IMAGES: rank or -1 (empty without a session)
+    int min_pair_matches = 0;
+    bool add_only = false;             // msfm_track_params::add_only: matching calls do not fold
+    DevBuf d_parent;                   // the forest: one int32 per node
+    DevBuf d_table;                    // TkImage per id < MSFM_MAX_IMAGES (base, rows; base -1: not declared)
+    DevBuf d_base, d_ids;              // per rank: base (n + 1 entries), image id
+    DevBuf r_offsets, r_img, r_idx, r_cons, r_tid;   // the result: CSR offsets (T + 1 int64), image id / keypoint index per kept
+                                                     // observation, consistent flag per track, kept track number per node
+    msfm_track_stats stats = {};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;   // around fold launches whose time has not been read yet
+    std::vector<hipEvent_t> ev_free;
+    bool declares(int id) const { return open && id >= 0 && id < (int)rank_of.size() && rank_of[(size_t)id] >= 0; }
+    long long device_bytes() const {
+        long long s = 0;
+        for (const DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid}) s += (long long)b->cap;
+        return s;
+    }
+    void release() {   // (the caller has drained the streams)
+        for (DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid}) b->release();
+        for (auto& e : ev_pending) {
+            (void)hipEventDestroy(e.first);
+            (void)hipEventDestroy(e.second);
+        }
+        for (hipEvent_t e : ev_free) (void)hipEventDestroy(e);
+        ev_pending.clear();
+        ev_free.clear();
+        rank_of.clear();
+        nd = MsfmTrackNodes{};
+        stats = msfm_track_stats{};
+        open = closed = finished = suppress = add_only = false;
+    }
+};
 
 struct msfm_ctx {
     int device = 0;
@@ -711,6 +755,7 @@ struct msfm_ctx {
     msfm_two_view_params tv_params = {100, 0, 2.0, 4.0};
     std::vector<msfm_two_view_record> tv_records;
     bool tv_valid = false;
+    TrackSession tracks;              // feature tracks (msfm_tracks_begin .. msfm_tracks_end)
 };
 
 #define SC (*ctx->cur)

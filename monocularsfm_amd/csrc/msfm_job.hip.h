@@ -483,6 +483,11 @@ struct MatchJob {
         const int32_t* sens = reinterpret_cast<const int32_t*>(h + 8 + (P + 1) * 8);
         const long long total = offs[P];
         const size_t base = streaming ? 0 : ctx->res_count;
+        if (ctx->tracks.open && !ctx->tracks.closed && !ctx->tracks.suppress && !ctx->tracks.add_only) {
+            // a track session is open: the accepted sub-batch's final lists join its forest (msfm_tracks.hip.h), on this set's stream
+            rc = tk_fold_sub_batch(ctx, SC, b.id1.data(), b.id2.data(), P, offs);
+            if (rc != MSFM_OK) return rc;
+        }
         if (streaming) {
             // the streaming form (msfm_match_pairs_begin / _next): the sub-batch's lists go to page-locked buffers of ITS scratch set
             // and stay, with the device copy in d_sub_qt / d_sub_d, until the caller asks for the next chunk -- nothing accumulates

@@ -9,6 +9,7 @@
 #include "msfm_match.h"
 #include "msfm_hostutil.h"
 #include "msfm_guard.h"
+#include "msfm_tracks.h"
 #include "msfm_kernels.hip.h"
 #include "msfm_prefilter.hip.h"
 #include "msfm_verify.hip.h"
@@ -40,6 +41,7 @@ using namespace msfm;
 #include "msfm_ctx.hip.h"
 #include "msfm_store_host.hip.h"
 #include "msfm_batch.hip.h"
+#include "msfm_tracks.hip.h"
 
 // =========================================================================================
 // C ABI
@@ -131,7 +133,7 @@ int msfm_create(int device_ordinal, msfm_ctx** out_ctx) {
     ctx->job = new_match_job();
     for (Scratch& sc : ctx->sc) {
         for (PinnedBuf& h : sc.h_up) h.pool = &ctx->pinned_pool;
-        sc.h_summary.pool = sc.h_tail.pool = &ctx->pinned_pool;
+        sc.h_summary.pool = sc.h_tail.pool = sc.h_tk_pairs.pool = &ctx->pinned_pool;
     }
     ctx->h_jobs.pool = ctx->h_store_maxima.pool = &ctx->pinned_pool;
     ctx->cu_count = prop.multiProcessorCount;
@@ -190,6 +192,7 @@ void msfm_destroy(msfm_ctx* ctx) {
     for (Scratch& sc : ctx->sc)
         if (sc.stream) (void)hipStreamSynchronize(sc.stream);
     ctx->deferred.flush();
+    ctx->tracks.release();
     ctx->store.release_all();
     ctx->inbox.release_all();
     hc.lap("destroy: store");
@@ -627,7 +630,7 @@ int msfm_memory_info(msfm_ctx* ctx, msfm_memory* out) {
     for (Scratch& sc : ctx->sc) {
         scratch += sc.device_bytes();
         for (const PinnedBuf& h : sc.h_up) pinned += own(h);
-        pinned += own(sc.h_summary) + own(sc.h_tail) + sc.h_sub_qt.cap + sc.h_sub_d.cap + sc.h_tv.cap;
+        pinned += own(sc.h_summary) + own(sc.h_tail) + own(sc.h_tk_pairs) + sc.h_sub_qt.cap + sc.h_sub_d.cap + sc.h_tv.cap;
     }
     out->scratch = scratch;
     for (const OutSeg& s : ctx->out_segs) out->results_device += (int64_t)(s.qt.cap + s.d.cap);
@@ -673,7 +676,9 @@ int msfm_match_pair(msfm_ctx* ctx, int id1, int id2, float ratio, int cross_chec
     const int32_t pr[2] = {id1, id2};
     msfm_match_params prm = {ratio, cross_check, max_distance};
     int64_t offs[2] = {0, 0};
+    ctx->tracks.suppress = true;   // (the operator-level call takes no part in a track session)
     int rc = msfm_match_pairs(ctx, pr, 1, &prm, offs);
+    ctx->tracks.suppress = false;
     if (rc != MSFM_OK) return rc;
     *out_count = (int)offs[1];
     return msfm_fetch_matches(ctx, out_qt, out_dist);
@@ -780,6 +785,64 @@ static int knn2_pair_impl(msfm_ctx* ctx, int id1, int id2, int32_t* fwd_idx0, fl
             HIPCHK(ctx, hipMemcpyAsync(c.dst, c.src->as<char>() + c.off * 4, (size_t)c.n * 4, hipMemcpyDeviceToHost, SC.stream));
     HIPCHK(ctx, hipStreamSynchronize(SC.stream));
     return MSFM_OK;
+}
+
+// ---- feature tracks (msfm_tracks.hip.h) ---------------------------------------------------------------------------------------------
+
+int msfm_tracks_begin(msfm_ctx* ctx, const int32_t* ids, int n, const msfm_track_params* params) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_begin_impl(ctx, ids, n, params);
+    MSFM_API_END
+}
+
+int msfm_tracks_add(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, const int64_t* offsets, const int32_t* qt) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_add_impl(ctx, pairs, n_pairs, offsets, qt);
+    MSFM_API_END
+}
+
+int msfm_tracks_export_forest(msfm_ctx* ctx, int32_t* parent) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_export_impl(ctx, parent);
+    MSFM_API_END
+}
+
+int msfm_tracks_import_forest(msfm_ctx* ctx, const int32_t* parent) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_import_impl(ctx, parent);
+    MSFM_API_END
+}
+
+int msfm_tracks_finish(msfm_ctx* ctx, const msfm_track_filter* filter, msfm_track_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_finish_impl(ctx, filter, stats);
+    MSFM_API_END
+}
+
+int msfm_fetch_tracks(msfm_ctx* ctx, int64_t* offsets, int32_t* image_ids, int32_t* point_idx, uint8_t* consistent) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_fetch_impl(ctx, offsets, image_ids, point_idx, consistent);
+    MSFM_API_END
+}
+
+int msfm_fetch_track_ids(msfm_ctx* ctx, int image_id, int32_t* out) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_fetch_ids_impl(ctx, image_id, out);
+    MSFM_API_END
+}
+
+int msfm_tracks_end(msfm_ctx* ctx) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return tracks_end_impl(ctx);
+    MSFM_API_END
 }
 
 // ---- host-only helpers --------------------------------------------------------------------

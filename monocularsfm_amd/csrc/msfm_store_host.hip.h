@@ -493,6 +493,7 @@ int msfm_upload_image(msfm_ctx* ctx, int image_id, const void* desc, int n, int 
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "the store cannot change while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (ctx->tracks.declares(image_id)) return fail(ctx, MSFM_E_STATE, "the images of an open track session cannot change (msfm_tracks_end)");
     if (image_id < 0 || image_id >= kSlots) return fail(ctx, MSFM_E_INVALID, "image id out of range");
     if (n < 0 || dim != MSFM_DIM) return fail(ctx, MSFM_E_INVALID, "descriptors must be n x 128");
     if (n >= (1 << 18)) return fail(ctx, MSFM_E_INVALID, "more than 2^18 - 1 rows (BFMatcher packs the train index in 18 bits)");
@@ -537,6 +538,7 @@ int msfm_subset_image(msfm_ctx* ctx, int src_image_id, int dst_image_id, const i
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "the store cannot change while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (ctx->tracks.declares(dst_image_id)) return fail(ctx, MSFM_E_STATE, "the images of an open track session cannot change (msfm_tracks_end)");
     if (src_image_id < 0 || src_image_id >= kSlots || dst_image_id < 0 || dst_image_id >= kSlots || src_image_id == dst_image_id)
         return fail(ctx, MSFM_E_INVALID, "bad image ids for msfm_subset_image");
     if (count < 0 || (count > 0 && !rows)) return fail(ctx, MSFM_E_INVALID, "bad row list");
@@ -582,6 +584,7 @@ int msfm_clear_images(msfm_ctx* ctx) {
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "the store cannot change while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (ctx->tracks.open) return fail(ctx, MSFM_E_STATE, "the images of an open track session cannot change (msfm_tracks_end)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (Scratch& sc : ctx->sc)
         if (sc.stream) HIPCHK(ctx, hipStreamSynchronize(sc.stream));

@@ -120,6 +120,21 @@ int main(int argc, char** argv) {
 
     // SIFTmatch.two_view_geometry : 0 (default) | 1 (under verification_model 1 every verified pair also gets a row of the
     // two_view_geometries table: relative pose, triangulation statistics, the reference's test for an initial pair; include/msfm_match.h)
+    // SIFTmatch.tracks : 0 (default) | 1 (the run's kept matches joined into multi-view tracks, written into the `tracks` table;
+    // tracks_min_num_matches: pairs with fewer matches contribute nothing, default 10 = MapBuilder::Parameters::min_num_matches;
+    // tracks_min_length / tracks_max_length (0 = no bound) / tracks_keep_inconsistent: the filter; include/msfm_match.h)
+    int tracks = 0, tracks_min_num_matches = 10, tracks_min_length = 2, tracks_max_length = 0, tracks_keep_inconsistent = 0;
+    fs.Get("SIFTmatch.tracks", &tracks);
+    fs.Get("SIFTmatch.tracks_min_num_matches", &tracks_min_num_matches);
+    fs.Get("SIFTmatch.tracks_min_length", &tracks_min_length);
+    fs.Get("SIFTmatch.tracks_max_length", &tracks_max_length);
+    fs.Get("SIFTmatch.tracks_keep_inconsistent", &tracks_keep_inconsistent);
+    if (!(tracks == 0 || tracks == 1) || !(tracks_keep_inconsistent == 0 || tracks_keep_inconsistent == 1) || tracks_min_num_matches < 0 ||
+        tracks_max_length < 0) {
+        std::cerr << "ComputeMatches: SIFTmatch.tracks and tracks_keep_inconsistent must be 0 or 1, tracks_min_num_matches and "
+                     "tracks_max_length must not be negative" << std::endl;
+        return EXIT_FAILURE;
+    }
     int two_view_geometry = 0;
     msfm_two_view_params two_view_params = {100, 0, 2.0, 4.0};
     int two_view_min_num_inliers = two_view_params.min_num_inliers;
@@ -176,6 +191,7 @@ int main(int argc, char** argv) {
     matcher->SetVerificationModel(verification_model, camera);
     matcher->SetModelSelection(model_selection == 1, h_ratio);
     matcher->SetTwoViewGeometry(two_view_geometry == 1, two_view_params);
+    matcher->SetTracks(tracks == 1, tracks_min_num_matches, tracks_min_length, tracks_max_length, tracks_keep_inconsistent == 1);
 
     Timer timer;
     timer.Start();

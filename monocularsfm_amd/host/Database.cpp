@@ -242,6 +242,40 @@ void Database::WriteTwoViewGeometry(const image_t image_id1, const image_t image
     SQL_CALL(Sqlite().reset(s));
 }
 
+void Database::WriteTracks(size_t n_tracks, const int64_t* offsets, const int32_t* image_ids, const int32_t* point_idx,
+                           const unsigned char* consistent) const {
+    Exec(database_, "DROP TABLE IF EXISTS tracks;");
+    Exec(database_,
+         "CREATE TABLE tracks"
+         "   (track_id      INTEGER    PRIMARY KEY    NOT NULL,"
+         "    length        INTEGER                   NOT NULL,"
+         "    consistent    INTEGER                   NOT NULL,"
+         "    elements      BLOB);");
+    sqlite3_stmt* s = nullptr;
+    SQL_CALL(Sqlite().prepare_v2(database_, "INSERT INTO tracks(track_id, length, consistent, elements) VALUES(?, ?, ?, ?);", -1, &s, nullptr));
+    std::vector<int32_t> blob;
+    constexpr size_t kPerTransaction = 4096;
+    for (size_t t0 = 0; t0 < n_tracks; t0 += kPerTransaction) {
+        BeginTransaction();
+        for (size_t t = t0; t < std::min(n_tracks, t0 + kPerTransaction); ++t) {
+            const size_t len = (size_t)(offsets[t + 1] - offsets[t]);
+            blob.resize(2 * len);
+            for (size_t k = 0; k < len; ++k) {
+                blob[2 * k] = image_ids[(size_t)offsets[t] + k];
+                blob[2 * k + 1] = point_idx[(size_t)offsets[t] + k];
+            }
+            SQL_CALL(Sqlite().bind_int64(s, 1, (long long)t));
+            SQL_CALL(Sqlite().bind_int64(s, 2, (long long)len));
+            SQL_CALL(Sqlite().bind_int64(s, 3, consistent[t] ? 1 : 0));
+            SQL_CALL(Sqlite().bind_blob(s, 4, blob.data(), (int)(len * 8), nullptr));   // (static: the blob outlives the step below)
+            SQL_CALL(Sqlite().step(s));
+            SQL_CALL(Sqlite().reset(s));
+        }
+        EndTransaction();
+    }
+    SQL_CALL(Sqlite().finalize(s));
+}
+
 void Database::CreateDescriptorsU8Table() const {
     Exec(database_,
          "CREATE TABLE IF NOT EXISTS descriptors_u8"

@@ -62,6 +62,11 @@ public:
     // doubles, x2 ~ R x1 + t from the image the pair was matched FROM (the larger id in brute mode) to the other one).
     // `record`: a msfm_two_view_record (include/msfm_match.h).  Written in the transaction of the pair's matches row.
     void CreateTwoViewGeometriesTable() const;
+    // The feature tracks' table (SIFTmatch.tracks : 1), rebuilt WHOLE on every run -- tracks are a property of the whole matches table,
+    // not of a pair: tracks(track_id INTEGER PRIMARY KEY, length, consistent, elements BLOB = length x (image_id int32, point2D_idx
+    // int32), little endian, by ascending (image_id, point2D_idx)).  offsets: n_tracks + 1 entries.  Transactions of its own.
+    void WriteTracks(size_t n_tracks, const int64_t* offsets, const int32_t* image_ids, const int32_t* point_idx,
+                     const unsigned char* consistent) const;
     void WriteTwoViewGeometry(const image_t image_id1, const image_t image_id2, const void* record) const;
     void WriteDescriptorsU8(const image_t image_id, const unsigned char* data, size_t rows, size_t cols) const;
     size_t VisitAllDescriptorsU8(BlobVisitor visit, void* user) const;

@@ -178,7 +178,75 @@ void FeatureMatcher::OpenDatabaseAndDevice() {
     }
 }
 
+// Every device context opens a session over ALL images of the database (the numbering is the images' rows: they all have to be
+// resident).  add_only: the stored lists are not the device's, they will come through msfm_tracks_add.
+void FeatureMatcher::OpenTrackSessions(bool add_only) {
+    if (tracks_open_) return;
+    const std::vector<Database::Image> images = database_->ReadAllImages();
+    tracks_ids_.clear();
+    for (size_t i = 0; i < images.size(); ++i) {   // image ids as the matchers form them: 0 .. N-1
+        EnsureResident((image_t)i);
+        tracks_ids_.push_back((int32_t)i);
+    }
+    msfm_track_params prm = tracks_params_;
+    prm.add_only = add_only ? 1 : 0;
+    for (Device& d : devices_) MSFM_CALL(d.ctx, msfm_tracks_begin(d.ctx, tracks_ids_.data(), (int)tracks_ids_.size(), &prm));
+    tracks_open_ = true;
+}
+
+void FeatureMatcher::FinishTracks() {
+    if (!tracks_open_) return;
+    Timer timer;
+    timer.Start();
+    long long nodes = 0;
+    for (int32_t id : tracks_ids_) {
+        int n = 0;
+        MSFM_CALL(ctx_, msfm_image_rows(ctx_, id, &n));
+        nodes += n;
+    }
+    // one context per GPU: the others' forests are imported into the first
+    std::vector<int32_t> forest((size_t)std::max<long long>(1, nodes));
+    for (size_t g = 1; g < devices_.size(); ++g) {
+        MSFM_CALL(devices_[g].ctx, msfm_tracks_export_forest(devices_[g].ctx, forest.data()));
+        MSFM_CALL(ctx_, msfm_tracks_import_forest(ctx_, forest.data()));
+    }
+    forest = std::vector<int32_t>();
+    msfm_track_stats st;
+    MSFM_CALL(ctx_, msfm_tracks_finish(ctx_, &tracks_filter_, &st));
+    for (size_t g = 1; g < devices_.size(); ++g) {   // (the counters of the other sessions: their pairs were folded there)
+        msfm_track_stats o;
+        msfm_track_filter none = {2, 0, 1, 0};
+        MSFM_CALL(devices_[g].ctx, msfm_tracks_finish(devices_[g].ctx, &none, &o));
+        st.edges += o.edges;
+        st.pairs += o.pairs;
+        st.pairs_skipped += o.pairs_skipped;
+        st.pairs_below_min += o.pairs_below_min;
+        st.matches_ignored += o.matches_ignored;
+        st.fold_ms += o.fold_ms;
+    }
+    std::vector<int64_t> offsets((size_t)st.tracks_kept + 1, 0);
+    std::vector<int32_t> image_ids((size_t)std::max<int64_t>(1, st.observations_kept)), point_idx(image_ids.size());
+    std::vector<unsigned char> consistent((size_t)std::max<int64_t>(1, st.tracks_kept));
+    MSFM_CALL(ctx_, msfm_fetch_tracks(ctx_, offsets.data(), image_ids.data(), point_idx.data(), consistent.data()));
+    const double device_s = timer.ElapsedSeconds();
+    database_->WriteTracks((size_t)st.tracks_kept, offsets.data(), image_ids.data(), point_idx.data(), consistent.data());
+    for (Device& d : devices_) MSFM_CALL(d.ctx, msfm_tracks_end(d.ctx));
+    tracks_open_ = false;
+    if (std::getenv("MSFM_CLI_TIMING"))
+        std::fprintf(stderr, "[msfm tracks] nodes %lld | edges %lld | pairs %lld (below min %lld, skipped %lld) | matches ignored %lld | tracks %lld "
+                             "(inconsistent %lld, over max length %lld) | kept %lld with %lld observations, longest %lld | fold kernels %.3f ms | "
+                             "finish %.3f ms | join + finish + fetch %.3f s | table %.3f s\n",
+                     (long long)st.nodes, (long long)st.edges, (long long)st.pairs, (long long)st.pairs_below_min, (long long)st.pairs_skipped,
+                     (long long)st.matches_ignored, (long long)st.tracks_total, (long long)st.tracks_inconsistent,
+                     (long long)st.tracks_over_max_length, (long long)st.tracks_kept, (long long)st.observations_kept, (long long)st.longest_track,
+                     st.fold_ms, st.finish_ms, device_s, timer.ElapsedSeconds() - device_s);
+}
+
 void FeatureMatcher::CloseDatabaseAndDevice() {
+    if (tracks_ && database_ && !devices_.empty()) {   // (a run without a pair still rebuilds the table: empty)
+        OpenTrackSessions(false);
+        FinishTracks();
+    }
     {
     Lap lap_close(&g_clock.close_dev);
     if (database_) {
@@ -311,6 +379,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
     // ---- which pairs have a row already (the reference asks per pair, FeatureMatching.cpp:21-25)
     std::vector<std::vector<int>> slot(groups.size());   // index into `todo`, or -1: a row exists (or an earlier pair of this call writes it)
     std::vector<int32_t> todo;
+    std::vector<std::pair<image_t, image_t>> resumed;   // feature tracks: pairs whose row was in the table already
     {
         Lap lap(&g_clock.exist);
         size_t total = 0;
@@ -333,6 +402,7 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                 const bool exists = sweep ? std::binary_search(have.begin(), have.end(), Database::ImagePairToPairId(image_id1, image_id2))
                                           : database_->ExistMatches(image_id1, image_id2);
                 if (exists || !scheduled.insert(key).second) {
+                    if (exists && tracks_) resumed.emplace_back(image_id1, image_id2);
                     slot[g][k] = -1;
                     continue;
                 }
@@ -351,6 +421,9 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
     constexpr size_t kRec = sizeof(msfm_two_view_record);
     if (geometry) database_->CreateTwoViewGeometriesTable();
     static const EmissionOptions emission = EmissionOptions::FromEnvironment();
+    // feature tracks: the device folds the lists it hands out itself unless the rows that are stored are not those lists
+    const bool tracks_by_add = tracks_ && (host_verify || emission.scene_graph_order || emission.min_num_matches > 0);
+    if (tracks_) OpenTrackSessions(tracks_by_add);
 
     // ---- everything the device threads will touch is made resident / read now, on this thread (SQLite)
     if (P > 0) {
@@ -532,6 +605,22 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
             }
             out->offsets[out->n] = at;
             out->rows.resize((size_t)at * 2);
+            if (tracks_by_add) {
+                // the STORED rows (column 0 = the smaller image id's index: the pair in that orientation undoes the swap); a row stored
+                // with rows = 0 contributes nothing, so that the table and the tracks agree
+                std::vector<int32_t> stored_pairs(2 * out->n);
+                for (size_t p = 0; p < out->n; ++p) {
+                    const image_t id1 = r.pairs[2 * (out->first + p)], id2 = r.pairs[2 * (out->first + p) + 1];
+                    stored_pairs[2 * p] = std::min(id1, id2);
+                    stored_pairs[2 * p + 1] = std::max(id1, id2);
+                }
+                static_assert(sizeof(point2D_t) == sizeof(int32_t), "stored rows are int32 pairs");
+                rc = msfm_tracks_add(r.ctx, stored_pairs.data(), (int)out->n, out->offsets.data(), reinterpret_cast<const int32_t*>(out->rows.data()));
+                if (rc != MSFM_OK) {
+                    fail("msfm_tracks_add", rc);
+                    break;
+                }
+            }
             out->seconds_per_pair = chunk_timer.ElapsedSeconds() / (double)out->n;
             chunk_timer.Restart();
             r.in_layout += t.ElapsedSeconds();
@@ -680,6 +769,23 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
         g_clock.layout += r.in_layout;
         g_clock.two_view_pairs += r.two_view_pairs;
         g_clock.two_view_h += r.two_view_h;
+    }
+    // feature tracks: the rows of the pairs the exist-check skipped (a resumed run), read back and folded in on the first context --
+    // the device threads have ended.  ReadMatches undoes the column swap: (queryIdx, trainIdx) belong to (image_id1, image_id2).
+    for (size_t b = 0; b < resumed.size(); b += 1024) {
+        const size_t e = std::min(resumed.size(), b + 1024);
+        std::vector<int32_t> rp, rq;
+        std::vector<int64_t> ro(1, 0);
+        for (size_t k = b; k < e; ++k) {
+            rp.push_back(resumed[k].first);
+            rp.push_back(resumed[k].second);
+            for (const DMatch& m : database_->ReadMatches(resumed[k].first, resumed[k].second)) {
+                rq.push_back(m.queryIdx);
+                rq.push_back(m.trainIdx);
+            }
+            ro.push_back((int64_t)(rq.size() / 2));
+        }
+        MSFM_CALL(ctx_, msfm_tracks_add(ctx_, rp.data(), (int)(e - b), ro.data(), rq.data()));
     }
     g_clock.two_view = g_clock.two_view || two_view;
     g_clock.devices = (int)G;

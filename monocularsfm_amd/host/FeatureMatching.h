@@ -56,6 +56,16 @@ public:
         two_view_geometry_ = on;
         two_view_params_ = params;
     }
+    // SIFTmatch.tracks (+ tracks_min_num_matches / _min_length / _max_length / _keep_inconsistent): the run's kept matches joined
+    // into multi-view tracks (include/msfm_match.h "feature tracks") and written into the `tracks` table, rebuilt whole at the end of
+    // the run.  Every device context opens a session over all images in front of the run's matching; rows the run computes are
+    // folded on the device as their chunks complete, unless the stored lists are not the device's (host verification, the emission
+    // options), in which case the stored rows go through msfm_tracks_add, as do the rows of pairs the exist-check skipped.
+    void SetTracks(bool on, int min_num_matches, int min_length, int max_length, bool keep_inconsistent) {
+        tracks_ = on;
+        tracks_params_ = msfm_track_params{min_num_matches, 0};
+        tracks_filter_ = msfm_track_filter{min_length, max_length, keep_inconsistent ? 1 : 0, 0};
+    }
     void SetModelSelection(bool on, double h_ratio) {
         model_selection_ = on;
         h_ratio_ = h_ratio;
@@ -83,6 +93,13 @@ protected:
     int verification_model_ = MSFM_VERIFY_FUNDAMENTAL;   // SetVerificationModel
     CameraIntrinsics camera_ = {};                       // (model 1 only)
     bool model_selection_ = false;                       // SetModelSelection
+    bool tracks_ = false;                                // SetTracks
+    msfm_track_params tracks_params_ = {10, 0};
+    msfm_track_filter tracks_filter_ = {2, 0, 0, 0};
+    bool tracks_open_ = false;                           // the sessions are open on every device context
+    std::vector<int32_t> tracks_ids_;
+    void OpenTrackSessions(bool add_only);
+    void FinishTracks();                                 // join the devices' forests, finish, write the table, end the sessions
     double h_ratio_ = 0.7;
     Database* database_ = nullptr;
     // One context per GPU: MSFM_DEVICE (default 0), MSFM_DEVICES="0,1,..." or "all".  The whole descriptor store is replicated on

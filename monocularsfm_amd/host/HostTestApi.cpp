@@ -14,6 +14,7 @@
 #include "../csrc/msfm_hmat.h"
 #include "../csrc/msfm_hostutil.h"
 #include "../csrc/msfm_pose.h"
+#include "../csrc/msfm_tracks.h"
 
 using namespace MonocularSfM;
 
@@ -555,5 +556,43 @@ int host_two_view_geometry(const float* p1, const float* p2, int n, const double
     for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
     return (int)m.size();
 }
+
+// ---- feature tracks: the host twin of the device session (csrc/msfm_tracks.h) ------------------------------------------------------
+// One session in one call: begin over (ids, rows), the CSR lists, optional forests to import (n_forests x nodes), finish under the
+// filter.  counts: the 12 integer fields of msfm_track_stats in order.  Returns 0, 1 + the numbering error, 10 for a forest entry out of
+// range, 11 when the result does not fit the caller's capacities (counts are valid then).
+int host_tracks_build(const int* ids, const int* rows, int n, int min_pair_matches, const int* pairs, int n_pairs, const long long* offsets,
+                      const int* qt, const int* forests, int n_forests, int min_length, int max_length, int keep_inconsistent,
+                      long long* counts, long long* out_offsets, int* out_image_ids, int* out_point_idx, unsigned char* out_consistent,
+                      int* out_track_of, int* out_forest, long long cap_tracks, long long cap_observations) {
+    MsfmTrackNodes nd;
+    const int e = msfm_track_number_nodes(ids, rows, n, MSFM_MAX_IMAGES, &nd);
+    if (e != MSFM_TRACK_NODES_OK) return 1 + e;
+    MsfmTrackTwin tw;
+    tw.begin(nd, min_pair_matches);
+    std::vector<int64_t> offs((size_t)n_pairs + 1, 0);
+    for (int p = 0; p <= n_pairs && offsets; ++p) offs[(size_t)p] = offsets[p];
+    tw.add(pairs, n_pairs, offs.data(), qt);
+    for (int k = 0; k < n_forests; ++k)
+        if (!tw.import_forest(forests + (size_t)k * (size_t)nd.nodes())) return 10;
+    MsfmTrackFilter f;
+    f.min_length = min_length;
+    f.max_length = max_length;
+    f.keep_inconsistent = keep_inconsistent;
+    const MsfmTrackResult r = tw.finish(f);
+    const long long c[12] = {r.counts.nodes, r.counts.edges, r.counts.pairs, r.counts.pairs_skipped, r.counts.pairs_below_min,
+                             r.counts.matches_ignored, r.counts.tracks_total, r.counts.tracks_inconsistent,
+                             r.counts.tracks_over_max_length, r.counts.tracks_kept, r.counts.observations_kept, r.counts.longest_track};
+    for (int k = 0; k < 12; ++k) counts[k] = c[k];
+    if (out_forest) tw.export_forest(out_forest);
+    if (r.counts.tracks_kept > cap_tracks || r.counts.observations_kept > cap_observations) return 11;
+    std::copy(r.offsets.begin(), r.offsets.end(), out_offsets);
+    std::copy(r.image_ids.begin(), r.image_ids.end(), out_image_ids);
+    std::copy(r.point_idx.begin(), r.point_idx.end(), out_point_idx);
+    std::copy(r.consistent.begin(), r.consistent.end(), out_consistent);
+    std::copy(r.track_of.begin(), r.track_of.end(), out_track_of);
+    return 0;
+}
+
 
 }  // extern "C"
