@@ -525,6 +525,76 @@ int msfm_fetch_tracks(msfm_ctx* ctx, int64_t* offsets, int32_t* image_ids, int32
 int msfm_fetch_track_ids(msfm_ctx* ctx, int image_id, int32_t* out);
 int msfm_tracks_end(msfm_ctx* ctx);
 
+/* ---- track triangulation: 3-D points from the kept tracks and known poses --------------------------
+ * Off by default; needs a track session with a successful msfm_tracks_finish.  What the reference's MapBuilder::Triangulate ->
+ * Triangulator::Triangulate does with a multi-view correspondence (src/Reconstruction/Triangulator.cpp:15-117, MapBuilder.cpp:516-560):
+ * the multi-view DLT point, the reprojection test in every view, the parallax test -- for every kept track at once, on the device,
+ * from the track result, the uploaded keypoints and a pose table given with the call (poses of a rig, an INS, an earlier
+ * reconstruction, the two-view record of an initial pair).  The arithmetic is csrc/msfm_triangulate.h, bit-identical to the host twin
+ * TriangulateTracks.  Nothing else changes: not the tracks, not the match lists.
+ *   poses       n_poses entries, image_ids[k] (declared in the session, each at most once) with poses[k]: x_cam = R X + t, R row-major.
+ *               R is taken as given: it is NOT re-orthogonalised.  valid == 0: the image counts as unposed (as every declared image
+ *               that is not listed).
+ *   attempted   a track is attempted iff it is consistent and at least max(2, min_views) of its elements lie in posed images; those
+ *               are its USED OBSERVATIONS, in element order; the others are skipped.  Else status = 0 and every field 0.
+ *   observation pixel (fp32 -> fp64) -> normalised undistorted (u, v) with `camera`; errors are measured against it and scaled by
+ *               f = (fx + fy) / 2 (the two-view records' convention; the reference folds K into P and uses the distorted pixels).
+ *   point       A = sum over the used observations of r1^T r1 + r2^T r2, r1 = u P.row(2) - P.row(0), r2 = v P.row(2) - P.row(1),
+ *               P = [R | t]; the right singular vector of the smallest singular value, X = h[0..2] / h[3]; h[3] == 0 or a non-finite
+ *               X: no point.
+ *   errors      per used observation err = |proj(R X + t) - (u, v)| f; ERROR_OK iff every err <= max_error (NaN fails);
+ *               mean_residual = their sum in observation order / n_views.  Every error is reported: out_residuals is aligned with
+ *               the tracks' observations (observations_kept doubles), -1.0 where none was computed (unposed elements, tracks not
+ *               attempted or without a point).
+ *   parallax    pairs of used observations in the order for i: for j < i; the first pair whose angle at X between the two camera
+ *               centres (-R^T t) is >= min_angle ends the scan: tri_angle is its angle and ANGLE_OK is set; if none reaches it,
+ *               tri_angle is the largest angle seen.  Degrees, min(a, pi - a).
+ *   status      MSFM_TRI_ATTEMPTED | _POINT | _ERROR_OK | _ANGLE_OK | _DEPTH_OK.  The reference's is_succeed is POINT & ERROR_OK &
+ *               ANGLE_OK.  DEPTH_OK (every used view has the point in front of it, depth > DBL_EPSILON) is extra information: the
+ *               reference has no depth test, and it is not part of the verdict.
+ * params NULL = the reference's Triangulator::Parameters {2.0 px, 1.5 degrees} and min_views 2.
+ * Errors: MSFM_E_STATE -- no track session, before a successful msfm_tracks_finish, or while a streaming series is open.
+ * MSFM_E_INVALID -- NULL camera; fx / fy <= 0; a non-finite camera or triangulation parameter; a non-finite R or t of a valid pose; an
+ * image id that is not declared in the session, or given twice; a negative max_error or min_angle; n_poses < 0.  MSFM_E_NOIMAGE -- a
+ * posed image without uploaded keypoints (fewer keypoints than rows).  After an error the previous points (if any) are gone.
+ * A later msfm_tracks_finish invalidates the points: msfm_fetch_points3d returns MSFM_E_STATE until msfm_triangulate_tracks has run
+ * again.  msfm_tracks_end frees them.  msfm_fetch_points3d: T = tracks_kept records, observations_kept doubles; either may be NULL. */
+enum { MSFM_TRI_ATTEMPTED = 1, MSFM_TRI_POINT = 2, MSFM_TRI_ERROR_OK = 4, MSFM_TRI_ANGLE_OK = 8, MSFM_TRI_DEPTH_OK = 16 };
+typedef struct msfm_pose_rt {   /* 104 bytes, no implicit padding */
+    int32_t valid;
+    int32_t reserved;
+    double R[9];
+    double t[3];
+} msfm_pose_rt;
+typedef struct msfm_triangulation_params {
+    double max_error;            /* Triangulator::Parameters::regis_tri_max_error: 2.0 pixels */
+    double min_angle;            /* regis_tri_min_angle: 1.5 degrees */
+    int32_t min_views;           /* values below 2 mean 2 */
+    int32_t reserved;
+} msfm_triangulation_params;
+typedef struct msfm_point3d {   /* 48 bytes, no implicit padding */
+    int32_t status;
+    int32_t n_views;             /* used observations */
+    double X[3];
+    double mean_residual;
+    double tri_angle;
+} msfm_point3d;
+typedef struct msfm_triangulation_stats {   /* 80 bytes, no implicit padding */
+    int64_t tracks;              /* T: records written */
+    int64_t attempted;           /* counts per status bit ... */
+    int64_t with_point;
+    int64_t error_ok;
+    int64_t angle_ok;
+    int64_t depth_ok;
+    int64_t succeeded;           /* ... and of POINT & ERROR_OK & ANGLE_OK */
+    int64_t observations_used;   /* summed n_views */
+    int64_t device_bytes;        /* records + residuals held by the session */
+    double triangulate_ms;       /* HIP events around the two kernels */
+} msfm_triangulation_stats;
+int msfm_triangulate_tracks(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
+                            const msfm_triangulation_params* params, msfm_triangulation_stats* stats);
+int msfm_fetch_points3d(msfm_ctx* ctx, msfm_point3d* out_points, double* out_residuals);
+
 /* ---- host-side helpers (no device work) ------------------------------------------------- */
 /* FeatureUtils::ExtractTopScaleDescriptors' row selection (FeatureUtils.cpp:68-96):
  * kpts = n x 4 float (x, y, size, angle); writes min(k, n) indices, k > n => identity.

@@ -32,6 +32,7 @@ EXPORTS = [
     "msfm_set_two_view_geometry", "msfm_fetch_two_view_geometry",
     "msfm_tracks_begin", "msfm_tracks_add", "msfm_tracks_export_forest", "msfm_tracks_import_forest", "msfm_tracks_finish",
     "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
+    "msfm_triangulate_tracks", "msfm_fetch_points3d",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -59,6 +60,49 @@ class TrackStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("nodes", "edges", "pairs", "pairs_skipped", "pairs_below_min", "matches_ignored", "tracks_total",
                                          "tracks_inconsistent", "tracks_over_max_length", "tracks_kept", "observations_kept",
                                          "longest_track", "device_bytes")] + [("fold_ms", C.c_double), ("finish_ms", C.c_double)]
+
+
+# track triangulation (include/msfm_match.h): status bits, the 104-byte pose, the 48-byte record
+TRI_ATTEMPTED, TRI_POINT, TRI_ERROR_OK, TRI_ANGLE_OK, TRI_DEPTH_OK = 1, 2, 4, 8, 16
+POSE_RT = np.dtype([("valid", "<i4"), ("reserved", "<i4"), ("R", "<f8", (9,)), ("t", "<f8", (3,))])
+POINT3D = np.dtype([("status", "<i4"), ("n_views", "<i4"), ("X", "<f8", (3,)), ("mean_residual", "<f8"), ("tri_angle", "<f8")])
+
+
+class TriangulationParams(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("min_angle", C.c_double), ("min_views", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TriangulationStats(C.Structure):
+    """msfm_triangulation_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("tracks", "attempted", "with_point", "error_ok", "angle_ok", "depth_ok", "succeeded",
+                                         "observations_used", "device_bytes")] + [("triangulate_ms", C.c_double)]
+
+
+def succeeded(points):
+    """The reference's is_succeed per record of a POINT3D array: POINT & ERROR_OK & ANGLE_OK."""
+    want = TRI_POINT | TRI_ERROR_OK | TRI_ANGLE_OK
+    return (np.asarray(points)["status"] & want) == want
+
+
+def camera_struct(camera):
+    """A dict or sequence fx, fy, cx, cy[, k1, k2, p1, p2] (missing distortion coefficients are 0) -> Camera."""
+    keys = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")
+    vals = [camera.get(k, 0.0) for k in keys] if isinstance(camera, dict) else list(camera) + [0.0] * (8 - len(camera))
+    return Camera(*[float(v) for v in vals[:8]])
+
+
+def pose_table(poses):
+    """dict image id -> (R 3 x 3, t 3) [or None: listed but not valid] -> (ids int32, POSE_RT array), by ascending id."""
+    ids = np.asarray(sorted(int(i) for i in poses), np.int32)
+    tab = np.zeros(max(len(ids), 1), POSE_RT)
+    for k, i in enumerate(ids):
+        if poses[int(i)] is None:
+            continue
+        R, t = poses[int(i)]
+        tab[k]["valid"] = 1
+        tab[k]["R"] = np.asarray(R, np.float64).reshape(9)
+        tab[k]["t"] = np.asarray(t, np.float64).reshape(3)
+    return ids, tab[:len(ids)]
 
 
 class MatchParams(C.Structure):
@@ -197,6 +241,9 @@ def load():
     L.msfm_fetch_tracks.argtypes = [vp, i64p, ip, ip, C.POINTER(C.c_uint8)]
     L.msfm_fetch_track_ids.argtypes = [vp, C.c_int, ip]
     L.msfm_tracks_end.argtypes = [vp]
+    L.msfm_triangulate_tracks.argtypes = [vp, C.POINTER(Camera), ip, C.c_void_p, C.c_int, C.POINTER(TriangulationParams),
+                                          C.POINTER(TriangulationStats)]
+    L.msfm_fetch_points3d.argtypes = [vp, C.c_void_p, C.POINTER(C.c_double)]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if the library lacks a declared symbol
     _lib = L
@@ -621,6 +668,29 @@ class Context:
         self._track_stats = None
         self._track_nodes = None
         self._chk(self._L.msfm_tracks_end(self._h))
+
+    # ---- track triangulation (include/msfm_match.h) ----
+    def triangulate_tracks(self, camera, poses, max_error=2.0, min_angle=1.5, min_views=2):
+        """3-D points of the kept tracks of the last tracks_finish under known poses: camera as set_verification_model takes it, poses a
+        dict image id -> (R, t) with x_cam = R X + t (None: listed but unposed; declared images that are not listed are unposed too).
+        Defaults: the reference's Triangulator::Parameters.  -> stats dict.  The points are fetched with points3d()."""
+        cam = camera_struct(camera) if camera is not None else None
+        ids, tab = pose_table(poses)
+        prm = TriangulationParams(float(max_error), float(min_angle), int(min_views), 0)
+        st = TriangulationStats()
+        self._chk(self._L.msfm_triangulate_tracks(self._h, C.byref(cam) if cam is not None else None, _ip(ids), tab.ctypes.data, len(ids),
+                                                  C.byref(prm), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in TriangulationStats._fields_}
+
+    def points3d(self):
+        """-> (points: POINT3D array, one per kept track; residuals: float64, one per kept observation in the tracks' order, -1.0 where
+        no error was computed) of the last triangulate_tracks.  succeeded(points) is the reference's verdict."""
+        st = getattr(self, "_track_stats", None) or {"tracks_kept": 0, "observations_kept": 0}
+        T, O = int(st["tracks_kept"]), int(st["observations_kept"])
+        pts = np.zeros(max(T, 1), POINT3D)
+        res = np.zeros(max(O, 1), np.float64)
+        self._chk(self._L.msfm_fetch_points3d(self._h, pts.ctypes.data, res.ctypes.data_as(C.POINTER(C.c_double))))
+        return pts[:T], res[:O]
 
     def knn2_pair(self, id1, id2):
         n1, n2 = self.image_rows(id1), self.image_rows(id2)

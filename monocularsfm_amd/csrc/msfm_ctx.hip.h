@@ -643,6 +643,10 @@ struct TrackSession {
     DevBuf r_offsets, r_img, r_idx, r_cons, r_tid;   // the result: CSR offsets (T + 1 int64), image id / keypoint index per kept
                                                      // observation, consistent flag per track, kept track number per node
     msfm_track_stats stats = {};
+    // track triangulation (msfm_triangulate.hip.h): a record per kept track, a residual per kept observation; tri_valid: they belong to
+    // the current result (msfm_tracks_finish clears it)
+    DevBuf t_points, t_resid;
+    bool tri_valid = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;   // around fold launches whose time has not been read yet
     std::vector<hipEvent_t> ev_free;
     bool declares(int id) const { return open && id >= 0 && id < (int)rank_of.size() && rank_of[(size_t)id] >= 0; }
@@ -652,7 +656,7 @@ struct TrackSession {
         return s;
     }
     void release() {   // (the caller has drained the streams)
-        for (DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid}) b->release();
+        for (DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid, &t_points, &t_resid}) b->release();
         for (auto& e : ev_pending) {
             (void)hipEventDestroy(e.first);
             (void)hipEventDestroy(e.second);
@@ -663,7 +667,7 @@ struct TrackSession {
         rank_of.clear();
         nd = MsfmTrackNodes{};
         stats = msfm_track_stats{};
-        open = closed = finished = suppress = add_only = false;
+        open = closed = finished = suppress = add_only = tri_valid = false;
     }
 };
 

@@ -42,6 +42,7 @@ using namespace msfm;
 #include "msfm_store_host.hip.h"
 #include "msfm_batch.hip.h"
 #include "msfm_tracks.hip.h"
+#include "msfm_triangulate.hip.h"
 
 // =========================================================================================
 // C ABI
@@ -842,6 +843,23 @@ int msfm_tracks_end(msfm_ctx* ctx) {
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return tracks_end_impl(ctx);
+    MSFM_API_END
+}
+
+// ---- track triangulation (msfm_triangulate.hip.h) -----------------------------------------------------------------------------------
+
+int msfm_triangulate_tracks(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
+                            const msfm_triangulation_params* params, msfm_triangulation_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return triangulate_impl(ctx, camera, image_ids, poses, n_poses, params, stats);
+    MSFM_API_END
+}
+
+int msfm_fetch_points3d(msfm_ctx* ctx, msfm_point3d* out_points, double* out_residuals) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return fetch_points3d_impl(ctx, out_points, out_residuals);
     MSFM_API_END
 }
 

@@ -1,0 +1,246 @@
+// msfm_triangulate.h -- track triangulation arithmetic shared by the device kernels (msfm_triangulate.hip.h, hipcc) and the host twin
+// (host/HostTestApi.cpp, TriangulateTracks, g++): what the reference's MapBuilder::Triangulate -> Triangulator::Triangulate computes
+// for one multi-view correspondence under known poses (src/Reconstruction/Triangulator.cpp:15-117, MapBuilder.cpp:516-560): the
+// multi-view DLT point, the reprojection test in every view, the parallax test.
+//
+// The contract of msfm_pose.h holds: fp64 with +, -, *, /, sqrt only, static loop structure, -ffp-contract=off on both sides -> the host
+// twin and the device produce the SAME bits.  onesided_jacobi<4, 4>, acos and kDepthEps are msfm_pose.h's, undistort is msfm_emat.h's.
+//
+//   preconditions   a track is ATTEMPTED iff it is consistent (the track session's flag) and at least max(2, min_views) of its
+//                   elements belong to an image with a valid pose.  Those elements are the USED OBSERVATIONS, in the track's element
+//                   order (ascending (image id, keypoint index)); elements of unposed images are skipped.  Otherwise status = 0 and
+//                   every other field 0.
+//   observation     the pixel (x, y) of the uploaded keypoints, fp32 -> fp64, to normalised undistorted (u, v) by msfm_emat::undistort
+//                   with the call's camera: the convention of the two-view records -- the error is measured
+//                   against the undistorted observation and scaled by f = (fx + fy) / 2.  THE REFERENCE folds K into P = K [R | t] and
+//                   compares with the distorted pixel; for a camera without distortion and fx = fy the two agree up to rounding.
+//   DLT             P = [R | t] (x_cam = R X + t; R is taken as given, NOT re-orthogonalised).  A (4 x 4) starts at 0; per used
+//                   observation, in order:  A += r1^T r1;  A += r2^T r2  with r1 = u P.row(2) - P.row(0), r2 = v P.row(2) - P.row(1)
+//                   (two separate additions per entry).  onesided_jacobi<4, 4> on the columns of A; h = the column of V whose rotated
+//                   column of A has the smallest norm, the lowest index among equal norms; X = h[0..2] / h[3].  h[3] == 0 or a
+//                   non-finite X: no point (status = ATTEMPTED alone, every residual slot -1).
+//   per observation Y = R X + t;  depth_ok: Y.z > kDepthEps;  err = sqrt((Y.x / Y.z - u)^2 + (Y.y / Y.z - v)^2) * f.  EVERY error is
+//                   computed and reported (the reference stops at the first failure: the same verdict).  ERROR_OK iff err <= max_error
+//                   holds for every used observation (a NaN fails).  mean_residual = (the errors summed in observation order from 0.0)
+//                   / count, reported whenever a point exists.
+//   parallax        camera centres O = -R^T t, once per pose, by centre() below (Projection.cpp:149-194).  Pairs in the reference's loop
+//                   order, for i: for j < i over the used observations; the scan stops at the first pair with angle >= min_angle and
+//                   tri_angle is that pair's angle (ANGLE_OK set); if none reaches it tri_angle is the largest angle seen (ANGLE_OK
+//                   clear).  Angle as msfm_pose::evaluate: law of cosines, |acos|, NaN -> 0, min(a, pi - a), degrees.
+//   status bits     MSFM_TRI_ATTEMPTED 1, _POINT 2, _ERROR_OK 4, _ANGLE_OK 8, _DEPTH_OK 16 (every used view in front).  The
+//                   reference's is_succeed is POINT & ERROR_OK & ANGLE_OK.  THE REFERENCE HAS NO DEPTH TEST: DEPTH_OK is extra
+//                   information and not part of the verdict.
+#pragma once
+
+#include "msfm_pose.h"
+
+namespace msfm_tri {
+
+// a pose as the kernels and the twin read it: the caller's [R | t] plus the centre (128 bytes)
+struct Pose {
+    double R[9], t[3], O[3];
+    int32_t valid, reserved;
+};
+
+struct Params {
+    double max_error, min_angle;
+    int32_t min_views, reserved;
+};
+
+// O = -R^T t
+MSFM_FHD void centre(const double R[9], const double t[3], double O[3]) {
+MSFM_UNROLL
+    for (int k = 0; k < 3; ++k) O[k] = -(R[k] * t[0] + R[3 + k] * t[1] + R[6 + k] * t[2]);
+}
+
+// the caller's pose -> the table entry: valid iff flagged valid and every number finite
+MSFM_FHD void prepare_pose(const msfm_pose_rt& in, Pose* out) {
+    bool ok = in.valid != 0;
+MSFM_UNROLL
+    for (int k = 0; k < 9; ++k) {
+        out->R[k] = in.R[k];
+        ok = ok && msfm_pose::finite(in.R[k]);
+    }
+MSFM_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        out->t[k] = in.t[k];
+        ok = ok && msfm_pose::finite(in.t[k]);
+    }
+    centre(in.R, in.t, out->O);
+    out->valid = ok ? 1 : 0;
+    out->reserved = 0;
+}
+
+// the parallax angle at X between the centres Oi and Oj, degrees (Projection::CalculateParallaxAngle; msfm_pose::evaluate's form)
+MSFM_FHD double parallax(const double X[3], const double Oi[3], const double Oj[3]) {
+    const double b0 = Oi[0] - Oj[0], b1 = Oi[1] - Oj[1], b2 = Oi[2] - Oj[2];
+    const double baseline = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+    const double d0 = X[0] - Oi[0], d1 = X[1] - Oi[1], d2 = X[2] - Oi[2];
+    const double ray1 = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+    const double e0 = X[0] - Oj[0], e1 = X[1] - Oj[1], e2 = X[2] - Oj[2];
+    const double ray2 = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+    double ang = msfm_pose::acos((ray1 * ray1 + ray2 * ray2 - baseline * baseline) / (2.0 * ray1 * ray2));
+    if (ang < 0.0) ang = -ang;
+    if (!(ang == ang)) return 0.0;   // NaN -> 0
+    const double other = msfm_pose::kPi - ang;
+    return (ang < other ? ang : other) * 180.0 / msfm_pose::kPi;
+}
+
+MSFM_FHD void clear_point(msfm_point3d* r) {
+    r->status = 0;
+    r->n_views = 0;
+    r->X[0] = r->X[1] = r->X[2] = 0.0;
+    r->mean_residual = 0.0;
+    r->tri_angle = 0.0;
+}
+
+// One track.  `a` gives the track's elements k = 0 .. n - 1:  a.pose(k) -> const Pose* (nullptr: the element's image has no valid
+// pose),  a.pixel(k, &x, &y) -> the keypoint's pixel as fp64 (asked for posed elements only).  residuals: n slots, element-aligned;
+// -1.0 where no error was computed.  The arithmetic does not depend on where `a` reads from.
+template <class A>
+MSFM_FHD void triangulate_track(const A& a, int n, bool consistent, const msfm_emat::Camera& cam, const Params& prm, msfm_point3d* rec,
+                                double* residuals) {
+    clear_point(rec);
+    const int need = prm.min_views > 2 ? prm.min_views : 2;
+    int used = 0;
+    if (consistent)
+        for (int k = 0; k < n; ++k) used += a.pose(k) ? 1 : 0;
+    if (!consistent || used < need) {
+        for (int k = 0; k < n; ++k) residuals[k] = -1.0;
+        return;
+    }
+    rec->status = MSFM_TRI_ATTEMPTED;
+    rec->n_views = used;
+    double m[4][4], v[4][4];   // m[j][i]: column j, row i of A
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j)
+MSFM_UNROLL
+        for (int i = 0; i < 4; ++i) m[j][i] = 0.0;
+    for (int k = 0; k < n; ++k) {
+        const Pose* p = a.pose(k);
+        if (!p) continue;
+        double x, y, u, w;
+        a.pixel(k, &x, &y);
+        msfm_emat::undistort(cam, x, y, &u, &w);
+        double r1[4], r2[4];
+MSFM_UNROLL
+        for (int j = 0; j < 4; ++j) {
+            const double p0 = j < 3 ? p->R[j] : p->t[0], p1 = j < 3 ? p->R[3 + j] : p->t[1], p2 = j < 3 ? p->R[6 + j] : p->t[2];
+            r1[j] = u * p2 - p0;
+            r2[j] = w * p2 - p1;
+        }
+MSFM_UNROLL
+        for (int j = 0; j < 4; ++j)
+MSFM_UNROLL
+            for (int i = 0; i < 4; ++i) {
+                m[j][i] = m[j][i] + r1[i] * r1[j];
+                m[j][i] = m[j][i] + r2[i] * r2[j];
+            }
+    }
+    msfm_pose::onesided_jacobi<4, 4>(m, v);
+    double best = 0.0, h[4] = {0.0, 0.0, 0.0, 0.0};
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        const double nn = m[j][0] * m[j][0] + m[j][1] * m[j][1] + m[j][2] * m[j][2] + m[j][3] * m[j][3];
+        if (j == 0 || nn < best) {
+            best = nn;
+MSFM_UNROLL
+            for (int k = 0; k < 4; ++k) h[k] = v[j][k];
+        }
+    }
+    double X[3] = {0.0, 0.0, 0.0};
+    bool point = h[3] > 0.0 || h[3] < 0.0;
+    if (point) {
+        X[0] = h[0] / h[3];
+        X[1] = h[1] / h[3];
+        X[2] = h[2] / h[3];
+        point = msfm_pose::finite(X[0]) && msfm_pose::finite(X[1]) && msfm_pose::finite(X[2]);
+    }
+    if (!point) {
+        for (int k = 0; k < n; ++k) residuals[k] = -1.0;
+        return;
+    }
+    const double f = (cam.fx + cam.fy) / 2.0;
+    bool error_ok = true, depth_ok = true;
+    double sum = 0.0;
+    for (int k = 0; k < n; ++k) {
+        const Pose* p = a.pose(k);
+        if (!p) {
+            residuals[k] = -1.0;
+            continue;
+        }
+        double x, y, u, w;
+        a.pixel(k, &x, &y);
+        msfm_emat::undistort(cam, x, y, &u, &w);
+        const double Y0 = p->R[0] * X[0] + p->R[1] * X[1] + p->R[2] * X[2] + p->t[0];
+        const double Y1 = p->R[3] * X[0] + p->R[4] * X[1] + p->R[5] * X[2] + p->t[1];
+        const double Y2 = p->R[6] * X[0] + p->R[7] * X[1] + p->R[8] * X[2] + p->t[2];
+        depth_ok = depth_ok && Y2 > msfm_pose::kDepthEps;
+        const double dx = Y0 / Y2 - u, dy = Y1 / Y2 - w;
+        const double err = sqrt(dx * dx + dy * dy) * f;
+        error_ok = error_ok && err <= prm.max_error;   // (false for a NaN)
+        sum = sum + err;
+        residuals[k] = err;
+    }
+    // the parallax scan: for i: for j < i over the used observations, to the first pair that reaches min_angle
+    bool angle_ok = false;
+    double angle = 0.0;
+    for (int i = 1; i < n && !angle_ok; ++i) {
+        const Pose* pi = a.pose(i);
+        if (!pi) continue;
+        const double Oi[3] = {pi->O[0], pi->O[1], pi->O[2]};
+        for (int j = 0; j < i; ++j) {
+            const Pose* pj = a.pose(j);
+            if (!pj) continue;
+            const double Oj[3] = {pj->O[0], pj->O[1], pj->O[2]};
+            const double g = parallax(X, Oi, Oj);
+            if (g >= prm.min_angle) {
+                angle = g;
+                angle_ok = true;
+                break;
+            }
+            if (g > angle) angle = g;
+        }
+    }
+    rec->status = MSFM_TRI_ATTEMPTED | MSFM_TRI_POINT | (error_ok ? MSFM_TRI_ERROR_OK : 0) | (angle_ok ? MSFM_TRI_ANGLE_OK : 0) |
+                  (depth_ok ? MSFM_TRI_DEPTH_OK : 0);
+    rec->X[0] = X[0];
+    rec->X[1] = X[1];
+    rec->X[2] = X[2];
+    rec->mean_residual = sum / (double)used;
+    rec->tri_angle = angle;
+}
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host twin: TriangulateTracks over a finished track result ---------------------------------------------------------------
+// tracks as msfm_fetch_tracks returns them; kxy[rank]: the (x, y) fp32 pairs of the image of that rank (may be null for an image
+// without a valid pose); poses[rank]: prepared by prepare_pose; rank_of_id: per image id the rank or -1.
+struct HostTrack {
+    const int32_t* img;
+    const int32_t* idx;
+    const int* rank_of_id;
+    const float* const* kxy;
+    const Pose* poses;
+    const Pose* pose(int k) const {
+        const int r = rank_of_id[img[k]];
+        return (r >= 0 && poses[r].valid) ? poses + r : nullptr;
+    }
+    void pixel(int k, double* x, double* y) const {
+        const float* q = kxy[rank_of_id[img[k]]] + 2 * (size_t)idx[k];
+        *x = (double)q[0];
+        *y = (double)q[1];
+    }
+};
+
+inline void TriangulateTracks(const int64_t* offsets, const int32_t* image_ids, const int32_t* point_idx, const uint8_t* consistent,
+                              int64_t first_track, int64_t n_tracks, const int* rank_of_id, const float* const* kxy, const Pose* poses,
+                              const msfm_emat::Camera& cam, const Params& prm, msfm_point3d* out_points, double* out_residuals) {
+    for (int64_t t = first_track; t < first_track + n_tracks; ++t) {
+        const int64_t b = offsets[t], e = offsets[t + 1];
+        const HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
+        triangulate_track(a, (int)(e - b), consistent[t] != 0, cam, prm, out_points + t, out_residuals + b);
+    }
+}
+#endif
+
+}  // namespace msfm_tri

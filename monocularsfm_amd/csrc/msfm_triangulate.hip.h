@@ -1,0 +1,202 @@
+// msfm_triangulate.hip.h -- track triangulation on the device (include/msfm_match.h "track triangulation"): the
+// two kernels and the host side of msfm_triangulate_tracks / msfm_fetch_points3d (defined in msfm_match.hip).  The arithmetic is
+// msfm_triangulate.h, shared with the host twin TriangulateTracks: the same bits.  Included by msfm_match.hip behind msfm_tracks.hip.h.
+//
+//   tri_pose_kernel   one lane per declared image: the caller's pose -> msfm_tri::Pose (valid iff flagged valid and finite; the centre).
+//   tri_track_kernel  one lane per kept track, grid-stride, 256 threads, no LDS, on the library's stream.  Per used observation a
+//                     dependent gather: the element's (image id, keypoint index) from the track CSR, the image's table entry, the 8-byte
+//                     keypoint, the 128-byte pose.  The 4 x 4 normal matrix and the Jacobi state stay in registers (every index is a
+//                     compile-time constant); the track's elements are re-read in the error pass and the parallax scan instead of
+//                     being kept, so the register need does not depend on the track's length.  Plain vector loads and stores; the
+//                     counters of the stats are reduced per wave by shuffles and added with one atomic per wave and counter (they
+//                     only COUNT: no order reaches the output).
+#pragma once
+#include "msfm_triangulate.h"
+
+namespace msfm {
+
+struct TriImage {
+    const float2* kxy;   // the image's keypoints (not read unless the image is posed)
+    int rank;            // declared-image rank = index into the pose table; -1: not declared
+    int pad;
+};
+
+struct TriCounters {
+    unsigned long long attempted, with_point, error_ok, angle_ok, depth_ok, succeeded, observations_used;
+};
+constexpr int kTriCounters = 7;
+
+__global__ __launch_bounds__(256) void tri_pose_kernel(const msfm_pose_rt* __restrict__ in, int n, msfm_tri::Pose* __restrict__ out) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) msfm_tri::prepare_pose(in[p], out + p);
+}
+
+// the elements of one track as msfm_tri::triangulate_track reads them
+struct TriDevTrack {
+    const int* __restrict__ img;
+    const int* __restrict__ idx;
+    const TriImage* __restrict__ table;
+    const msfm_tri::Pose* __restrict__ poses;
+    __device__ __forceinline__ const msfm_tri::Pose* pose(int k) const {
+        const msfm_tri::Pose* p = poses + table[img[k]].rank;   // (a track's images are declared: rank >= 0)
+        return p->valid ? p : nullptr;
+    }
+    __device__ __forceinline__ void pixel(int k, double* x, double* y) const {
+        const float2 q = table[img[k]].kxy[idx[k]];
+        *x = (double)q.x;
+        *y = (double)q.y;
+    }
+};
+
+__global__ __launch_bounds__(256) void tri_track_kernel(const long long* __restrict__ offsets, const int* __restrict__ img,
+                                                        const int* __restrict__ idx, const unsigned char* __restrict__ cons, int T,
+                                                        const TriImage* __restrict__ table, const msfm_tri::Pose* __restrict__ poses,
+                                                        msfm_emat::Camera cam, msfm_tri::Params prm, msfm_point3d* __restrict__ points,
+                                                        double* __restrict__ residuals, TriCounters* __restrict__ counters) {
+    unsigned long long c[kTriCounters] = {0, 0, 0, 0, 0, 0, 0};
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += stride) {
+        const long long b = offsets[t], e = offsets[t + 1];
+        const TriDevTrack a{img + b, idx + b, table, poses};
+        msfm_point3d r;
+        msfm_tri::triangulate_track(a, (int)(e - b), cons[t] != 0, cam, prm, &r, residuals + b);
+        points[t] = r;
+        const int s = r.status;
+        c[0] += (s & MSFM_TRI_ATTEMPTED) ? 1 : 0;
+        c[1] += (s & MSFM_TRI_POINT) ? 1 : 0;
+        c[2] += (s & MSFM_TRI_ERROR_OK) ? 1 : 0;
+        c[3] += (s & MSFM_TRI_ANGLE_OK) ? 1 : 0;
+        c[4] += (s & MSFM_TRI_DEPTH_OK) ? 1 : 0;
+        c[5] += ((s & (MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK)) == (MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK)) ? 1 : 0;
+        c[6] += (unsigned long long)r.n_views;
+    }
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(counters);
+#pragma unroll
+    for (int k = 0; k < kTriCounters; ++k) {
+        unsigned long long v = c[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(out + k, v);
+    }
+}
+
+}  // namespace msfm
+
+namespace {
+
+int triangulate_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
+                     const msfm_triangulation_params* params, msfm_triangulation_stats* stats) {
+    TrackSession& ts = ctx->tracks;
+    ts.tri_valid = false;   // whatever happens below, the previous points are gone
+    if (!ts.open) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks without a track session (msfm_tracks_begin)");
+    if (!ts.finished) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks before a successful msfm_tracks_finish");
+    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (!camera) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: NULL camera");
+    const msfm_camera c = *camera;
+    for (double v : {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2})
+        if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: camera parameters must be finite");
+    if (!(c.fx > 0.0) || !(c.fy > 0.0)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: fx and fy must be positive");
+    msfm_tri::Params prm = {2.0, 1.5, 2, 0};   // Triangulator::Parameters
+    if (params) prm = msfm_tri::Params{params->max_error, params->min_angle, params->min_views, 0};
+    if (!std::isfinite(prm.max_error) || !std::isfinite(prm.min_angle)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: parameters must be finite");
+    if (prm.max_error < 0.0 || prm.min_angle < 0.0) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: max_error and min_angle must not be negative");
+    if (n_poses < 0 || (n_poses > 0 && (!image_ids || !poses))) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: bad pose list");
+    const int n_img = (int)ts.nd.ids.size();
+    std::vector<msfm_pose_rt> by_rank((size_t)std::max(n_img, 1), msfm_pose_rt{});
+    std::vector<char> given((size_t)std::max(n_img, 1), 0);
+    for (int k = 0; k < n_poses; ++k) {
+        const int id = image_ids[k];
+        if (!ts.declares(id)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: image not declared in the session: " + std::to_string(id));
+        const int r = ts.rank_of[(size_t)id];
+        if (given[(size_t)r]) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: an image is given twice: " + std::to_string(id));
+        given[(size_t)r] = 1;
+        if (poses[k].valid) {
+            for (double v : poses[k].R)
+                if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: non-finite R of image " + std::to_string(id));
+            for (double v : poses[k].t)
+                if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: non-finite t of image " + std::to_string(id));
+        }
+        by_rank[(size_t)r] = poses[k];
+        by_rank[(size_t)r].valid = poses[k].valid ? 1 : 0;
+        by_rank[(size_t)r].reserved = 0;
+    }
+    std::vector<TriImage> table((size_t)MSFM_MAX_IMAGES, TriImage{nullptr, -1, 0});
+    for (int r = 0; r < n_img; ++r) {
+        const int id = ts.nd.ids[(size_t)r];
+        const Image& im = ctx->images[(size_t)id];
+        if (by_rank[(size_t)r].valid && im.nk < ts.nd.rows[(size_t)r])
+            return fail(ctx, MSFM_E_NOIMAGE, "msfm_triangulate_tracks: posed image without keypoints (msfm_upload_keypoints): " + std::to_string(id));
+        table[(size_t)id] = TriImage{im.kxy, r, 0};
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
+    struct Tmp {   // freed when the call returns, whatever it returns
+        DevBuf in, poses, table, counters;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        ~Tmp() {
+            for (DevBuf* b : {&in, &poses, &table, &counters}) b->release();
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } t;
+    hipStream_t st = store_stream(ctx);
+    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
+    HIPCHK(ctx, t.in.ensure(by_rank.size() * sizeof(msfm_pose_rt)));
+    HIPCHK(ctx, t.poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose)));
+    HIPCHK(ctx, t.table.ensure(table.size() * sizeof(TriImage)));
+    HIPCHK(ctx, t.counters.ensure(sizeof(TriCounters)));
+    HIPCHK(ctx, ts.t_points.ensure((size_t)std::max<long long>(1, T) * sizeof(msfm_point3d)));
+    HIPCHK(ctx, ts.t_resid.ensure((size_t)std::max<long long>(1, O) * sizeof(double)));
+    // (synchronous copies of the two small tables: nothing queued reads host memory that an early return below would free)
+    HIPCHK(ctx, hipMemcpy(t.in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(t.table.p, table.data(), table.size() * sizeof(TriImage), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(TriCounters), st));
+    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
+    if (n_img > 0) {
+        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)t.in.as<msfm_pose_rt>(), n_img,
+                           t.poses.as<msfm_tri::Pose>());
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (T > 0) {
+        hipLaunchKernelGGL(tri_track_kernel, dim3(tk_grid(ctx, T)), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
+                           (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)T,
+                           (const TriImage*)t.table.as<TriImage>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(),
+                           msfm_emat::Camera{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2}, prm, ts.t_points.as<msfm_point3d>(),
+                           ts.t_resid.as<double>(), t.counters.as<TriCounters>());
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipEventRecord(t.ev[1], st));
+    const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
+    HIPCHK(ctx, done);
+    TriCounters hc = {};
+    HIPCHK(ctx, hipMemcpy(&hc, t.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+    msfm_triangulation_stats s = {};
+    s.tracks = T;
+    s.attempted = (int64_t)hc.attempted;
+    s.with_point = (int64_t)hc.with_point;
+    s.error_ok = (int64_t)hc.error_ok;
+    s.angle_ok = (int64_t)hc.angle_ok;
+    s.depth_ok = (int64_t)hc.depth_ok;
+    s.succeeded = (int64_t)hc.succeeded;
+    s.observations_used = (int64_t)hc.observations_used;
+    s.device_bytes = (int64_t)(ts.t_points.cap + ts.t_resid.cap);
+    s.triangulate_ms = ms;
+    ts.tri_valid = true;
+    if (stats) *stats = s;
+    return MSFM_OK;
+}
+
+int fetch_points3d_impl(msfm_ctx* ctx, msfm_point3d* out_points, double* out_residuals) {
+    TrackSession& ts = ctx->tracks;
+    if (!ts.open) return fail(ctx, MSFM_E_STATE, "msfm_fetch_points3d without a track session (msfm_tracks_begin)");
+    if (!ts.finished || !ts.tri_valid) return fail(ctx, MSFM_E_STATE, "msfm_fetch_points3d without points: msfm_triangulate_tracks has not run since the last msfm_tracks_finish");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t T = (size_t)ts.stats.tracks_kept, O = (size_t)ts.stats.observations_kept;
+    if (out_points && T) HIPCHK(ctx, hipMemcpy(out_points, ts.t_points.p, T * sizeof(msfm_point3d), hipMemcpyDeviceToHost));
+    if (out_residuals && O) HIPCHK(ctx, hipMemcpy(out_residuals, ts.t_resid.p, O * sizeof(double), hipMemcpyDeviceToHost));
+    return MSFM_OK;
+}
+
+}  // namespace

@@ -11,9 +11,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 #include <memory>
+#include <set>
+#include <sstream>
 #include <string>
+#include <vector>
 
 #include "FeatureMatching.h"
 #include "GeometricVerification.h"
@@ -29,6 +33,56 @@ void StampWallClock(const char* what) {
     if (!std::getenv("MSFM_CLI_TIMING")) return;
     const double now = std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count();
     std::fprintf(stderr, "[msfm timing] %s at %.6f\n", what, now);
+}
+
+// SIFTmatch.triangulation_poses: a text file, '#' starts a comment, every other non-empty line holds 13 numbers:
+// image_id r00 r01 r02 r10 r11 r12 r20 r21 r22 tx ty tz  (x_cam = R X + t, R row-major).  False with *error set: unreadable, a line with
+// another count of numbers or one that is not a number, a non-finite number, an id that is not an integer in [0, MSFM_MAX_IMAGES) or
+// that comes twice.
+bool ReadPosesFile(const std::string& path, std::vector<int32_t>* ids, std::vector<msfm_pose_rt>* poses, std::string* error) {
+    std::ifstream in(path);
+    if (!in) {
+        *error = "cannot open " + path;
+        return false;
+    }
+    std::set<int32_t> seen;
+    std::string line;
+    for (int number = 1; std::getline(in, line); ++number) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.erase(hash);
+        std::istringstream fields(line);
+        std::vector<double> v;
+        std::string word;
+        bool bad = false;
+        while (fields >> word) {
+            char* end = nullptr;
+            const double x = std::strtod(word.c_str(), &end);
+            if (end == word.c_str() || *end != 0 || !std::isfinite(x)) bad = true;
+            v.push_back(x);
+        }
+        if (v.empty() && !bad) continue;
+        const std::string where = path + ":" + std::to_string(number) + ": ";
+        if (bad || v.size() != 13) {
+            *error = where + "expected 13 finite numbers (image_id r00 .. r22 tx ty tz)";
+            return false;
+        }
+        if (v[0] != std::floor(v[0]) || v[0] < 0 || v[0] >= MSFM_MAX_IMAGES) {
+            *error = where + "the image id must be an integer in [0, " + std::to_string(MSFM_MAX_IMAGES) + ")";
+            return false;
+        }
+        const int32_t id = (int32_t)v[0];
+        if (!seen.insert(id).second) {
+            *error = where + "image " + std::to_string(id) + " is given twice";
+            return false;
+        }
+        msfm_pose_rt pose = {};
+        pose.valid = 1;
+        for (int k = 0; k < 9; ++k) pose.R[k] = v[(size_t)(1 + k)];
+        for (int k = 0; k < 3; ++k) pose.t[k] = v[(size_t)(10 + k)];
+        ids->push_back(id);
+        poses->push_back(pose);
+    }
+    return true;
 }
 }  // namespace
 
@@ -73,11 +127,21 @@ int main(int argc, char** argv) {
                   << std::endl;
         return EXIT_FAILURE;
     }
+    // SIFTmatch.triangulation : 0 (default) | 1 (the tracks' 3-D points under the poses of SIFTmatch.triangulation_poses and the camera
+    // of Reconstruction.Camera.*, written into the `points3D` table behind the tracks table; needs SIFTmatch.tracks : 1; optional
+    // triangulation_max_error 2.0 px, triangulation_min_angle 1.5 degrees, triangulation_min_views 2; include/msfm_match.h)
+    int triangulation = 0;
+    fs.Get("SIFTmatch.triangulation", &triangulation);
+    if (!(triangulation == 0 || triangulation == 1)) {
+        std::cerr << "ComputeMatches: SIFTmatch.triangulation must be 0 or 1" << std::endl;
+        return EXIT_FAILURE;
+    }
     CameraIntrinsics camera = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (verification_model == 1) {
+    if (verification_model == 1 || triangulation == 1) {
         for (const char* k : {"fx", "fy", "cx", "cy"})
             if (!fs.Has(std::string("Reconstruction.Camera.") + k)) {
-                std::cerr << "ComputeMatches: SIFTmatch.verification_model : 1 needs Reconstruction.Camera." << k << std::endl;
+                std::cerr << "ComputeMatches: SIFTmatch." << (verification_model == 1 ? "verification_model" : "triangulation")
+                          << " : 1 needs Reconstruction.Camera." << k << std::endl;
                 return EXIT_FAILURE;
             }
         fs.Get("Reconstruction.Camera.fx", &camera.fx);
@@ -134,6 +198,36 @@ int main(int argc, char** argv) {
         std::cerr << "ComputeMatches: SIFTmatch.tracks and tracks_keep_inconsistent must be 0 or 1, tracks_min_num_matches and "
                      "tracks_max_length must not be negative" << std::endl;
         return EXIT_FAILURE;
+    }
+    msfm_triangulation_params triangulation_params = {2.0, 1.5, 2, 0};   // Triangulator::Parameters
+    std::vector<int32_t> triangulation_ids;
+    std::vector<msfm_pose_rt> triangulation_poses;
+    if (triangulation == 1) {
+        if (tracks != 1) {
+            std::cerr << "ComputeMatches: SIFTmatch.triangulation : 1 triangulates the tracks; it needs SIFTmatch.tracks : 1" << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::string poses_path;
+        fs.Get("SIFTmatch.triangulation_poses", &poses_path);
+        if (!fs.Has("SIFTmatch.triangulation_poses") || poses_path.empty()) {
+            std::cerr << "ComputeMatches: SIFTmatch.triangulation : 1 needs SIFTmatch.triangulation_poses : <path>" << std::endl;
+            return EXIT_FAILURE;
+        }
+        fs.Get("SIFTmatch.triangulation_max_error", &triangulation_params.max_error);
+        fs.Get("SIFTmatch.triangulation_min_angle", &triangulation_params.min_angle);
+        int min_views = triangulation_params.min_views;
+        fs.Get("SIFTmatch.triangulation_min_views", &min_views);
+        triangulation_params.min_views = min_views;
+        if (!(std::isfinite(triangulation_params.max_error) && triangulation_params.max_error >= 0) ||
+            !(std::isfinite(triangulation_params.min_angle) && triangulation_params.min_angle >= 0)) {
+            std::cerr << "ComputeMatches: SIFTmatch.triangulation_max_error and triangulation_min_angle must be finite and not negative" << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::string error;
+        if (!ReadPosesFile(poses_path, &triangulation_ids, &triangulation_poses, &error)) {
+            std::cerr << "ComputeMatches: SIFTmatch.triangulation_poses: " << error << std::endl;
+            return EXIT_FAILURE;
+        }
     }
     int two_view_geometry = 0;
     msfm_two_view_params two_view_params = {100, 0, 2.0, 4.0};
@@ -192,6 +286,7 @@ int main(int argc, char** argv) {
     matcher->SetModelSelection(model_selection == 1, h_ratio);
     matcher->SetTwoViewGeometry(two_view_geometry == 1, two_view_params);
     matcher->SetTracks(tracks == 1, tracks_min_num_matches, tracks_min_length, tracks_max_length, tracks_keep_inconsistent == 1);
+    matcher->SetTriangulation(triangulation == 1, camera, triangulation_ids, triangulation_poses, triangulation_params);
 
     Timer timer;
     timer.Start();

@@ -276,6 +276,45 @@ void Database::WriteTracks(size_t n_tracks, const int64_t* offsets, const int32_
     SQL_CALL(Sqlite().finalize(s));
 }
 
+void Database::WritePoints3D(size_t n_tracks, const int64_t* offsets, const void* points, const double* residuals) const {
+    const msfm_point3d* pts = static_cast<const msfm_point3d*>(points);
+    Exec(database_, "DROP TABLE IF EXISTS points3D;");
+    Exec(database_,
+         "CREATE TABLE points3D"
+         "   (track_id         INTEGER    PRIMARY KEY    NOT NULL,"
+         "    status           INTEGER                   NOT NULL,"
+         "    n_views          INTEGER                   NOT NULL,"
+         "    x                REAL                      NOT NULL,"
+         "    y                REAL                      NOT NULL,"
+         "    z                REAL                      NOT NULL,"
+         "    mean_residual    REAL,"
+         "    tri_angle        REAL                      NOT NULL,"
+         "    residuals        BLOB);");
+    sqlite3_stmt* s = nullptr;
+    SQL_CALL(Sqlite().prepare_v2(database_, "INSERT INTO points3D(track_id, status, n_views, x, y, z, mean_residual, tri_angle, residuals) "
+                                            "VALUES(?, ?, ?, ?, ?, ?, ?, ?, ?);", -1, &s, nullptr));
+    constexpr size_t kPerTransaction = 4096;
+    for (size_t t0 = 0; t0 < n_tracks; t0 += kPerTransaction) {
+        BeginTransaction();
+        for (size_t t = t0; t < std::min(n_tracks, t0 + kPerTransaction); ++t) {
+            const size_t len = (size_t)(offsets[t + 1] - offsets[t]);
+            SQL_CALL(Sqlite().bind_int64(s, 1, (long long)t));
+            SQL_CALL(Sqlite().bind_int64(s, 2, (long long)pts[t].status));
+            SQL_CALL(Sqlite().bind_int64(s, 3, (long long)pts[t].n_views));
+            SQL_CALL(Sqlite().bind_double(s, 4, pts[t].X[0]));
+            SQL_CALL(Sqlite().bind_double(s, 5, pts[t].X[1]));
+            SQL_CALL(Sqlite().bind_double(s, 6, pts[t].X[2]));
+            SQL_CALL(Sqlite().bind_double(s, 7, pts[t].mean_residual));
+            SQL_CALL(Sqlite().bind_double(s, 8, pts[t].tri_angle));
+            SQL_CALL(Sqlite().bind_blob(s, 9, residuals + offsets[t], (int)(len * 8), nullptr));   // (static: the caller's array outlives the step)
+            SQL_CALL(Sqlite().step(s));
+            SQL_CALL(Sqlite().reset(s));
+        }
+        EndTransaction();
+    }
+    SQL_CALL(Sqlite().finalize(s));
+}
+
 void Database::CreateDescriptorsU8Table() const {
     Exec(database_,
          "CREATE TABLE IF NOT EXISTS descriptors_u8"

@@ -67,6 +67,10 @@ public:
     // int32), little endian, by ascending (image_id, point2D_idx)).  offsets: n_tracks + 1 entries.  Transactions of its own.
     void WriteTracks(size_t n_tracks, const int64_t* offsets, const int32_t* image_ids, const int32_t* point_idx,
                      const unsigned char* consistent) const;
+    // The triangulated tracks' table (SIFTmatch.triangulation : 1), rebuilt WHOLE behind the tracks table, one row per track of it:
+    // points3D(track_id INTEGER PRIMARY KEY, status, n_views, x, y, z, mean_residual, tri_angle, residuals BLOB = one little-endian
+    // double per element of the track, -1.0 where no error was computed; mean_residual is NULL when it is not a number).  points: n_tracks msfm_point3d.  Transactions of its own.
+    void WritePoints3D(size_t n_tracks, const int64_t* offsets, const void* points, const double* residuals) const;
     void WriteTwoViewGeometry(const image_t image_id1, const image_t image_id2, const void* record) const;
     void WriteDescriptorsU8(const image_t image_id, const unsigned char* data, size_t rows, size_t cols) const;
     size_t VisitAllDescriptorsU8(BlobVisitor visit, void* user) const;

@@ -183,6 +183,13 @@ void FeatureMatcher::OpenDatabaseAndDevice() {
 void FeatureMatcher::OpenTrackSessions(bool add_only) {
     if (tracks_open_) return;
     const std::vector<Database::Image> images = database_->ReadAllImages();
+    if (triangulation_)
+        for (int32_t id : triangulation_ids_)
+            if (id < 0 || (size_t)id >= images.size()) {   // (in front of the run's matching: nothing has been computed yet)
+                std::cerr << "ERROR: SIFTmatch.triangulation_poses names image " << id << ", the database holds images 0 .. "
+                          << (long long)images.size() - 1 << std::endl;
+                std::exit(EXIT_FAILURE);
+            }
     tracks_ids_.clear();
     for (size_t i = 0; i < images.size(); ++i) {   // image ids as the matchers form them: 0 .. N-1
         EnsureResident((image_t)i);
@@ -230,6 +237,27 @@ void FeatureMatcher::FinishTracks() {
     MSFM_CALL(ctx_, msfm_fetch_tracks(ctx_, offsets.data(), image_ids.data(), point_idx.data(), consistent.data()));
     const double device_s = timer.ElapsedSeconds();
     database_->WriteTracks((size_t)st.tracks_kept, offsets.data(), image_ids.data(), point_idx.data(), consistent.data());
+    if (triangulation_) {
+        // the posed images' keypoints are on the device already when it verified; else they go there now
+        if (!(geometric_verification_ && !verification_on_host_))
+            for (size_t k = 0; k < triangulation_ids_.size(); ++k) {
+                if (!triangulation_poses_[k].valid) continue;
+                const std::vector<KeyPoint>& kpts = KeyPointsOf((image_t)triangulation_ids_[k]);
+                MSFM_CALL(ctx_, msfm_upload_keypoints(ctx_, triangulation_ids_[k], reinterpret_cast<const float*>(kpts.data()), (int)kpts.size(), 4));
+            }
+        msfm_triangulation_stats ts;
+        MSFM_CALL(ctx_, msfm_triangulate_tracks(ctx_, &triangulation_camera_, triangulation_ids_.data(), triangulation_poses_.data(),
+                                                (int)triangulation_ids_.size(), &triangulation_params_, &ts));
+        std::vector<msfm_point3d> points((size_t)std::max<int64_t>(1, st.tracks_kept));
+        std::vector<double> residuals((size_t)std::max<int64_t>(1, st.observations_kept));
+        MSFM_CALL(ctx_, msfm_fetch_points3d(ctx_, points.data(), residuals.data()));
+        database_->WritePoints3D((size_t)st.tracks_kept, offsets.data(), points.data(), residuals.data());
+        if (std::getenv("MSFM_CLI_TIMING"))
+            std::fprintf(stderr, "[msfm triangulation] tracks %lld | attempted %lld | with a point %lld | error ok %lld | angle ok %lld | depth ok %lld | "
+                                 "succeeded %lld | observations used %lld | kernels %.3f ms\n",
+                         (long long)ts.tracks, (long long)ts.attempted, (long long)ts.with_point, (long long)ts.error_ok, (long long)ts.angle_ok,
+                         (long long)ts.depth_ok, (long long)ts.succeeded, (long long)ts.observations_used, ts.triangulate_ms);
+    }
     for (Device& d : devices_) MSFM_CALL(d.ctx, msfm_tracks_end(d.ctx));
     tracks_open_ = false;
     if (std::getenv("MSFM_CLI_TIMING"))

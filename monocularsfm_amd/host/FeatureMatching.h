@@ -66,6 +66,17 @@ public:
         tracks_params_ = msfm_track_params{min_num_matches, 0};
         tracks_filter_ = msfm_track_filter{min_length, max_length, keep_inconsistent ? 1 : 0, 0};
     }
+    // SIFTmatch.triangulation (+ triangulation_poses / _max_error / _min_angle / _min_views), needs SetTracks: behind the tracks table
+    // the kept tracks are triangulated on the first device context under the given poses (msfm_triangulate_tracks) and written into the
+    // `points3D` table, rebuilt whole.  A pose of an image the database does not hold ends the run before any matching.
+    void SetTriangulation(bool on, const CameraIntrinsics& camera, const std::vector<int32_t>& ids, const std::vector<msfm_pose_rt>& poses,
+                          const msfm_triangulation_params& params) {
+        triangulation_ = on;
+        triangulation_camera_ = msfm_camera{camera.fx, camera.fy, camera.cx, camera.cy, camera.k1, camera.k2, camera.p1, camera.p2};
+        triangulation_ids_ = ids;
+        triangulation_poses_ = poses;
+        triangulation_params_ = params;
+    }
     void SetModelSelection(bool on, double h_ratio) {
         model_selection_ = on;
         h_ratio_ = h_ratio;
@@ -98,6 +109,11 @@ protected:
     msfm_track_filter tracks_filter_ = {2, 0, 0, 0};
     bool tracks_open_ = false;                           // the sessions are open on every device context
     std::vector<int32_t> tracks_ids_;
+    bool triangulation_ = false;                         // SetTriangulation
+    msfm_camera triangulation_camera_ = {};
+    std::vector<int32_t> triangulation_ids_;
+    std::vector<msfm_pose_rt> triangulation_poses_;
+    msfm_triangulation_params triangulation_params_ = {2.0, 1.5, 2, 0};
     void OpenTrackSessions(bool add_only);
     void FinishTracks();                                 // join the devices' forests, finish, write the table, end the sessions
     double h_ratio_ = 0.7;

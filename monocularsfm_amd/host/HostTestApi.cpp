@@ -15,6 +15,7 @@
 #include "../csrc/msfm_hostutil.h"
 #include "../csrc/msfm_pose.h"
 #include "../csrc/msfm_tracks.h"
+#include "../csrc/msfm_triangulate.h"
 
 using namespace MonocularSfM;
 
@@ -594,5 +595,41 @@ int host_tracks_build(const int* ids, const int* rows, int n, int min_pair_match
     return 0;
 }
 
+// ---- track triangulation: the host twin of the device kernels (csrc/msfm_triangulate.h, TriangulateTracks) ---------------------------
+// A finished track result (offsets / image_ids / point_idx / consistent as msfm_fetch_tracks returns them), the declared images `ids`
+// (any order) with kxy[k] = the (x, y) fp32 pairs of ids[k] (may be NULL for an image without a valid pose), the pose list as
+// msfm_triangulate_tracks takes it, cam = fx, fy, cx, cy, k1, k2, p1, p2.  Tracks [first, first + count) are computed and written at
+// their own positions of out_points / out_residuals (so that several threads can share one result).  Returns 0; 1: a pose's image is
+// not declared or given twice; 2: an image id outside [0, MSFM_MAX_IMAGES).
+int host_triangulate_tracks(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                            const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
+                            int n_poses, const double* cam, double max_error, double min_angle, int min_views, long long first,
+                            long long count, msfm_point3d* out_points, double* out_residuals) {
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        rank_of[(size_t)ids[k]] = k;   // (any one-to-one numbering serves the twin: the device's ranks never reach the output)
+    }
+    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
+    }
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    const msfm_tri::Params prm = {max_error, min_angle, min_views, 0};
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are int64");
+    msfm_tri::TriangulateTracks(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(),
+                                kxy, table.data(), c, prm, out_points, out_residuals);
+    return 0;
+}
+
+// pieces, for tests/test_triangulation_reference.py
+void host_tri_centre(const double* R, const double* t, double* O) { msfm_tri::centre(R, t, O); }
+double host_tri_parallax(const double* X, const double* Oi, const double* Oj) { return msfm_tri::parallax(X, Oi, Oj); }
 
 }  // extern "C"

@@ -124,6 +124,48 @@ def scene_keypoints(point_ids, cams, n_points, seed=0, noise_px=0.7, base=None):
     return out
 
 
+def triangulation_job(n_images=1329, n_kp=8192, cam=(2500.0, 2500.0, 1536.0, 1152.0), seed=11, window=8000, step=1333, n_long=8, long_len=300):
+    """A capture for the track triangulation at a production shape, with known poses and no descriptors: image i's rows k < window
+    observe the scene points i * step + k (with the defaults a point is seen by six or seven consecutive images, cameras 0.81 degrees
+    apart on three turns of a circle around the scene: the parallax scan walks a few pairs, some tracks never reach 1.5 degrees); rows
+    window .. window + n_long - 1 of every third image observe n_long points through long_len images each (long tracks).  0.5 px of
+    noise (0.2 px on the long tracks); every 50th image stays unposed.
+    -> (ids, keypoints per image [n_kp x 4 float32], poses {id: (R, t)}, lists for Context.tracks_add [(pairs, offsets, qt)])."""
+    rng = np.random.default_rng(seed)
+    ids = np.arange(n_images, dtype=np.int32) * 7 + 2
+    n_pts = (n_images - 1) * step + window
+    X = np.stack([rng.uniform(-1.6, 1.6, n_pts), rng.uniform(-1.1, 1.1, n_pts), rng.uniform(-1.0, 1.0, n_pts)], 1)
+    XL = np.stack([rng.uniform(-1.0, 1.0, n_long), rng.uniform(-1.0, 1.0, n_long), rng.uniform(-1.0, 1.0, n_long)], 1)
+    noise = np.r_[np.full(window, 0.5), np.full(n_long, 0.2)]   # (0.2 px on the long tracks: none of their views may fail 2 px)
+    kps, poses = [], {}
+    for i in range(n_images):
+        th = 2 * np.pi * 3 * i / n_images
+        z = np.asarray([-np.sin(th), 0.0, np.cos(th)])           # the viewing direction: from the centre -6.5 z towards the origin
+        x = np.cross([0.0, 1.0, 0.0], z)
+        R = np.stack([x, np.cross(z, x), z])
+        t = np.asarray([0.0, 0.02 * np.sin(5 * th), 6.5])
+        k = keypoints(n_kp, seed=seed + i)
+        P = np.r_[X[i * step:i * step + window], XL]
+        Y = P @ R.T + t
+        n = len(P)
+        k[:n, 0] = (cam[0] * Y[:, 0] / Y[:, 2] + cam[2] + rng.normal(0, 1.0, n) * noise).astype(F32)
+        k[:n, 1] = (cam[1] * Y[:, 1] / Y[:, 2] + cam[3] + rng.normal(0, 1.0, n) * noise).astype(F32)
+        kps.append(k)
+        if i % 50 != 17:
+            poses[int(ids[i])] = (R, t)
+    kk = np.arange(step, window, dtype=np.int32)
+    one = np.stack([kk, kk - step], 1)
+    pairs = np.stack([ids[:-1], ids[1:]], 1).astype(np.int32)
+    lists = [(pairs, np.arange(n_images, dtype=np.int64) * len(one), np.tile(one, (n_images - 1, 1)))]
+    lp, lq = [], []
+    for j in range(n_long):
+        chain = ids[(j % 3) + 3 * np.arange(long_len)]
+        lp.append(np.stack([chain[:-1], chain[1:]], 1))
+        lq.append(np.full((long_len - 1, 2), window + j, np.int32))
+    lists.append((np.concatenate(lp).astype(np.int32), np.arange(n_long * (long_len - 1) + 1, dtype=np.int64), np.concatenate(lq)))
+    return ids, kps, poses, lists
+
+
 def _rotation(rng, scale):
     w = rng.normal(size=3) * scale
     th = np.linalg.norm(w)
