@@ -595,6 +595,68 @@ int msfm_triangulate_tracks(msfm_ctx* ctx, const msfm_camera* camera, const int3
                             const msfm_triangulation_params* params, msfm_triangulation_stats* stats);
 int msfm_fetch_points3d(msfm_ctx* ctx, msfm_point3d* out_points, double* out_residuals);
 
+/* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
+ * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
+ * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a
+ * Gauss-Newton refinement of the winner.  The arithmetic is csrc/msfm_register.h, shared with the host twin:
+ *   correspondences of image I   every kept track whose record has POINT & ERROR_OK & ANGLE_OK and which has an element (I, k), by
+ *               ascending track number; 2D: the keypoint pixel through the camera to normalised undistorted (u, v); 3D: the record's
+ *               X.  n of them.  ATTEMPTED iff n >= 3 and n >= min_inliers.
+ *   hypothesis  it = 0 .. : three distinct correspondences from the counter stream keyed by (image id, it), Grunert's P3P (up to 4
+ *               poses), scored by  Y = R X + t,  inlier iff Y.z > eps and |(Y.x / Y.z, Y.y / Y.z) - (u, v)|^2 f^2 <= max_error^2,
+ *               f = (fx + fy) / 2; the hypothesis counts the best of its poses.
+ *   stopping    the sequential adaptive rule (w^3, confidence) over at most max_iters hypotheses, run in rounds of 64; the winner is
+ *               the lowest iteration among the largest count; POSE iff it has >= 3 inliers.
+ *   refinement  refine_iters Gauss-Newton steps on the winner's inliers (0: none); the refined pose stands (REFINED) iff it has at
+ *               least the winner's number of inliers.  SUCCEEDED iff n_inliers >= min_inliers (the reference's is_succeed).
+ *   record      hypotheses: the hypotheses scored for the image (whole rounds, at most max_iters); R, t: x_cam = R X + t (0 without
+ *               POSE); mean_residual: mean pixel error of the inliers.  Per correspondence: the track number, the inlier flag and the
+ *               pixel error under the final pose (all correspondences; 0 / -1.0 without POSE).
+ * Images that already have a pose may be listed: they are localised again, from the points alone.  The tracks, the points and every
+ * match list are untouched.  params NULL = {4.0 px, 0.9999, 1024, 15, 10} (Registrant.h:22-26; max_iters is this library's).
+ * Errors: MSFM_E_STATE -- no track session, no points (msfm_triangulate_tracks has not run since the last msfm_tracks_finish), a
+ * streaming series open; msfm_fetch_registrations without a successful msfm_register_images since then.  MSFM_E_NOIMAGE -- a listed
+ * image that is not declared in the session or has no keypoints (msfm_upload_keypoints).  MSFM_E_INVALID -- NULL or bad camera, an id
+ * given twice, n_images < 0, non-finite or negative max_error, confidence outside (0, 1), max_iters outside 1 .. 65536, min_inliers
+ * < 0, refine_iters outside 0 .. 100.  The results live in the session (counted in msfm_register_stats::device_bytes); a later
+ * msfm_tracks_finish or msfm_triangulate_tracks invalidates them, msfm_tracks_end frees them.
+ * msfm_fetch_registrations: n_images records in the order of the list, n_images + 1 offsets, then offsets[n_images] track numbers,
+ * flags and errors; any pointer may be NULL. */
+enum { MSFM_REG_ATTEMPTED = 1, MSFM_REG_POSE = 2, MSFM_REG_SUCCEEDED = 4, MSFM_REG_REFINED = 8 };
+typedef struct msfm_register_params {   /* 32 bytes, no implicit padding */
+    double max_error;
+    double confidence;
+    int32_t max_iters;
+    int32_t min_inliers;
+    int32_t refine_iters;
+    int32_t reserved;
+} msfm_register_params;
+typedef struct msfm_registration {   /* 128 bytes, no implicit padding */
+    int32_t image_id;
+    int32_t status;
+    int32_t n_correspondences;
+    int32_t n_inliers;
+    int32_t hypotheses;
+    int32_t reserved;
+    double R[9];
+    double t[3];
+    double mean_residual;
+} msfm_registration;
+typedef struct msfm_register_stats {   /* 48 bytes, no implicit padding */
+    int32_t images;
+    int32_t attempted;
+    int32_t succeeded;
+    int32_t rounds;              /* rounds any image ran */
+    int64_t correspondences;
+    int64_t hypotheses;          /* hypotheses solved */
+    int64_t device_bytes;        /* the results held by the session */
+    double register_ms;          /* HIP events around the launches */
+} msfm_register_stats;
+int msfm_register_images(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, int n_images,
+                         const msfm_register_params* params, msfm_register_stats* stats);
+int msfm_fetch_registrations(msfm_ctx* ctx, msfm_registration* out, int64_t* out_offsets, int32_t* out_track_ids, uint8_t* out_inlier,
+                             double* out_residuals);
+
 /* ---- host-side helpers (no device work) ------------------------------------------------- */
 /* FeatureUtils::ExtractTopScaleDescriptors' row selection (FeatureUtils.cpp:68-96):
  * kpts = n x 4 float (x, y, size, angle); writes min(k, n) indices, k > n => identity.

@@ -32,7 +32,7 @@ EXPORTS = [
     "msfm_set_two_view_geometry", "msfm_fetch_two_view_geometry",
     "msfm_tracks_begin", "msfm_tracks_add", "msfm_tracks_export_forest", "msfm_tracks_import_forest", "msfm_tracks_finish",
     "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
-    "msfm_triangulate_tracks", "msfm_fetch_points3d",
+    "msfm_triangulate_tracks", "msfm_fetch_points3d", "msfm_register_images", "msfm_fetch_registrations",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -82,6 +82,36 @@ def succeeded(points):
     """The reference's is_succeed per record of a POINT3D array: POINT & ERROR_OK & ANGLE_OK."""
     want = TRI_POINT | TRI_ERROR_OK | TRI_ANGLE_OK
     return (np.asarray(points)["status"] & want) == want
+
+
+# image registration (include/msfm_match.h): status bits, the 128-byte record
+REG_ATTEMPTED, REG_POSE, REG_SUCCEEDED, REG_REFINED = 1, 2, 4, 8
+REGISTRATION = np.dtype([("image_id", "<i4"), ("status", "<i4"), ("n_correspondences", "<i4"), ("n_inliers", "<i4"), ("hypotheses", "<i4"),
+                         ("reserved", "<i4"), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("mean_residual", "<f8")])
+
+
+class RegisterParams(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("confidence", C.c_double), ("max_iters", C.c_int32), ("min_inliers", C.c_int32),
+                ("refine_iters", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RegisterStats(C.Structure):
+    """msfm_register_stats (include/msfm_match.h)."""
+    _fields_ = [("images", C.c_int32), ("attempted", C.c_int32), ("succeeded", C.c_int32), ("rounds", C.c_int32),
+                ("correspondences", C.c_int64), ("hypotheses", C.c_int64), ("device_bytes", C.c_int64), ("register_ms", C.c_double)]
+
+
+def registered(records):
+    """The reference's is_succeed per record of a REGISTRATION array: the SUCCEEDED bit."""
+    return (np.asarray(records)["status"] & REG_SUCCEEDED) != 0
+
+
+def registered_poses(records, poses=None):
+    """The succeeded records as the dict image id -> (R, t) that triangulate_tracks takes, merged over `poses` (which is not changed)."""
+    out = dict(poses) if poses else {}
+    for r in np.asarray(records)[registered(records)]:
+        out[int(r["image_id"])] = (r["R"].reshape(3, 3).copy(), r["t"].copy())
+    return out
 
 
 def camera_struct(camera):
@@ -244,6 +274,8 @@ def load():
     L.msfm_triangulate_tracks.argtypes = [vp, C.POINTER(Camera), ip, C.c_void_p, C.c_int, C.POINTER(TriangulationParams),
                                           C.POINTER(TriangulationStats)]
     L.msfm_fetch_points3d.argtypes = [vp, C.c_void_p, C.POINTER(C.c_double)]
+    L.msfm_register_images.argtypes = [vp, C.POINTER(Camera), ip, C.c_int, C.POINTER(RegisterParams), C.POINTER(RegisterStats)]
+    L.msfm_fetch_registrations.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if the library lacks a declared symbol
     _lib = L
@@ -691,6 +723,33 @@ class Context:
         res = np.zeros(max(O, 1), np.float64)
         self._chk(self._L.msfm_fetch_points3d(self._h, pts.ctypes.data, res.ctypes.data_as(C.POINTER(C.c_double))))
         return pts[:T], res[:O]
+
+    # ---- image registration (include/msfm_match.h) ----
+    def register_images(self, camera, image_ids, max_error=4.0, confidence=0.9999, max_iters=1024, min_inliers=15, refine_iters=10):
+        """Absolute poses of the listed images from their correspondences with the points of the last triangulate_tracks: P3P RANSAC
+        and a Gauss-Newton refinement per image, all images in one call.  Defaults: the reference's Registrant parameters.  -> stats
+        dict.  The records are fetched with registrations()."""
+        cam = camera_struct(camera) if camera is not None else None
+        ids = np.ascontiguousarray(image_ids, dtype=np.int32).reshape(-1)
+        prm = RegisterParams(float(max_error), float(confidence), int(max_iters), int(min_inliers), int(refine_iters), 0)
+        st = RegisterStats()
+        self._reg_shape = None
+        self._chk(self._L.msfm_register_images(self._h, C.byref(cam) if cam is not None else None, _ip(ids), len(ids), C.byref(prm),
+                                               C.byref(st)))
+        self._reg_shape = (len(ids), int(st.correspondences))
+        return {k: getattr(st, k) for k, _ in RegisterStats._fields_}
+
+    def registrations(self):
+        """-> (records: REGISTRATION array in the order of the list, offsets[n + 1] int64, track_ids int32, inlier uint8, residuals
+        float64 per correspondence) of the last register_images.  registered(records) is the reference's verdict;
+        registered_poses(records, poses) the pose dict for the next triangulate_tracks."""
+        n, m = getattr(self, "_reg_shape", None) or (0, 0)
+        rec = np.zeros(max(n, 1), REGISTRATION)
+        offs = np.zeros(n + 1, np.int64)
+        tid, inl, res = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.float64)
+        self._chk(self._L.msfm_fetch_registrations(self._h, rec.ctypes.data, offs.ctypes.data, tid.ctypes.data, inl.ctypes.data,
+                                                   res.ctypes.data))
+        return rec[:n], offs, tid[:m], inl[:m], res[:m]
 
     def knn2_pair(self, id1, id2):
         n1, n2 = self.image_rows(id1), self.image_rows(id2)

@@ -647,6 +647,12 @@ struct TrackSession {
     // the current result (msfm_tracks_finish clears it)
     DevBuf t_points, t_resid;
     bool tri_valid = false;
+    // image registration (msfm_register.hip.h): a record per listed image, the CSR of (track number, inlier flag, residual) per
+    // correspondence; reg_valid: they belong to the current points (msfm_tracks_finish and msfm_triangulate_tracks clear it)
+    DevBuf g_records, g_offsets, g_tid, g_inl, g_res;
+    bool reg_valid = false;
+    int reg_images = 0;
+    long long reg_corr = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;   // around fold launches whose time has not been read yet
     std::vector<hipEvent_t> ev_free;
     bool declares(int id) const { return open && id >= 0 && id < (int)rank_of.size() && rank_of[(size_t)id] >= 0; }
@@ -656,7 +662,7 @@ struct TrackSession {
         return s;
     }
     void release() {   // (the caller has drained the streams)
-        for (DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid, &t_points, &t_resid}) b->release();
+        for (DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid, &t_points, &t_resid, &g_records, &g_offsets, &g_tid, &g_inl, &g_res}) b->release();
         for (auto& e : ev_pending) {
             (void)hipEventDestroy(e.first);
             (void)hipEventDestroy(e.second);
@@ -667,7 +673,7 @@ struct TrackSession {
         rank_of.clear();
         nd = MsfmTrackNodes{};
         stats = msfm_track_stats{};
-        open = closed = finished = suppress = add_only = tri_valid = false;
+        open = closed = finished = suppress = add_only = tri_valid = reg_valid = false;
     }
 };
 

@@ -327,13 +327,13 @@ MSFM_FHD double det_log(double x) {
     return 2.0 * sum + (double)e * 0.6931471805599453;
 }
 
-// kSample is the minimal sample size (8 here, 5 for the essential matrix, msfm_emat.h, 4 for the homography, msfm_hmat.h): need = log(1 - conf) / log(1 - w^kSample),
+// kSample is the minimal sample size (8 here, 5 for the essential matrix, msfm_emat.h, 4 for the homography, msfm_hmat.h, 3 for the registration, msfm_register.h): need = log(1 - conf) / log(1 - w^kSample),
 // and a winner needs >= kSample inliers.  avail: the loop may only read counts [0, avail) -- the staged device form scores
 // hypotheses round by round; *decided (if given) is false when the loop needed a count beyond avail (the result is then not final).
 template <int kSample = 8, typename CountFn>
 MSFM_FHD int replay_adaptive(int n, int max_iters, double confidence, CountFn count_at, int* best_count_out,
                              int avail = 0x7fffffff, bool* decided = nullptr) {
-    static_assert(kSample == 8 || kSample == 5 || kSample == 4, "sample sizes of the F, E and H solvers");
+    static_assert(kSample == 8 || kSample == 5 || kSample == 4 || kSample == 3, "sample sizes of the F, E, H and P3P solvers");
     int best = 0, best_it = -1, iters = max_iters;
     if (decided) *decided = true;
     for (int it = 0; it < iters; ++it) {
@@ -350,6 +350,7 @@ MSFM_FHD int replay_adaptive(int n, int max_iters, double confidence, CountFn co
             double wk;
             if constexpr (kSample == 8) wk = w4 * w4;
             else if constexpr (kSample == 5) wk = w4 * w;
+            else if constexpr (kSample == 3) wk = w2 * w;
             else wk = w4;
             double q = 1.0 - wk;
             if (q < 1e-300) q = 1e-300;

@@ -43,6 +43,7 @@ using namespace msfm;
 #include "msfm_batch.hip.h"
 #include "msfm_tracks.hip.h"
 #include "msfm_triangulate.hip.h"
+#include "msfm_register.hip.h"
 
 // =========================================================================================
 // C ABI
@@ -860,6 +861,24 @@ int msfm_fetch_points3d(msfm_ctx* ctx, msfm_point3d* out_points, double* out_res
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return fetch_points3d_impl(ctx, out_points, out_residuals);
+    MSFM_API_END
+}
+
+// ---- image registration (msfm_register.hip.h) ---------------------------------------------------------------------------------------
+
+int msfm_register_images(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, int n_images,
+                         const msfm_register_params* params, msfm_register_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return register_impl(ctx, camera, image_ids, n_images, params, stats);
+    MSFM_API_END
+}
+
+int msfm_fetch_registrations(msfm_ctx* ctx, msfm_registration* out, int64_t* out_offsets, int32_t* out_track_ids, uint8_t* out_inlier,
+                             double* out_residuals) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return fetch_registrations_impl(ctx, out, out_offsets, out_track_ids, out_inlier, out_residuals);
     MSFM_API_END
 }
 

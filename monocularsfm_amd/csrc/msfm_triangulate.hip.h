@@ -88,6 +88,7 @@ int triangulate_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* im
                      const msfm_triangulation_params* params, msfm_triangulation_stats* stats) {
     TrackSession& ts = ctx->tracks;
     ts.tri_valid = false;   // whatever happens below, the previous points are gone
+    ts.reg_valid = false;   // ... and the registrations made from them (msfm_register.hip.h)
     if (!ts.open) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks without a track session (msfm_tracks_begin)");
     if (!ts.finished) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks before a successful msfm_tracks_finish");
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks while a streaming series (msfm_match_pairs_begin .. _next) is open");

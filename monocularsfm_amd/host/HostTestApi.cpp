@@ -16,6 +16,7 @@
 #include "../csrc/msfm_pose.h"
 #include "../csrc/msfm_tracks.h"
 #include "../csrc/msfm_triangulate.h"
+#include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
 
@@ -631,5 +632,61 @@ int host_triangulate_tracks(const long long* offsets, const int* image_ids, cons
 // pieces, for tests/test_triangulation_reference.py
 void host_tri_centre(const double* R, const double* t, double* O) { msfm_tri::centre(R, t, O); }
 double host_tri_parallax(const double* X, const double* Oi, const double* Oj) { return msfm_tri::parallax(X, Oi, Oj); }
+
+// ---- image registration: the host twin of the device kernels (csrc/msfm_register.h, RegisterImages) ---------------------------------
+// A finished track result and its points (msfm_fetch_tracks / msfm_fetch_points3d), the list of images to register with kxy[k] = the
+// (x, y) fp32 pairs of list_ids[k], cam = fx, fy, cx, cy, k1, k2, p1, p2.  host_register_counts: the correspondences per listed image.
+// host_register_images: the images [first, first + count) of the list, written at their own positions (out_offsets: n_list + 1, the
+// running sum of the counts), so that several threads can share one result.  Return 0; 1: an id twice in the list; 2: an id outside
+// [0, MSFM_MAX_IMAGES).
+static int reg_positions(const int* list_ids, int n_list, std::vector<int>* pos) {
+    pos->assign((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_list; ++k) {
+        if (list_ids[k] < 0 || list_ids[k] >= MSFM_MAX_IMAGES) return 2;
+        if ((*pos)[(size_t)list_ids[k]] >= 0) return 1;
+        (*pos)[(size_t)list_ids[k]] = k;
+    }
+    return 0;
+}
+
+int host_register_counts(const long long* offsets, const int* image_ids, long long n_tracks, const msfm_point3d* points,
+                         const int* list_ids, int n_list, long long* counts) {
+    std::vector<int> pos;
+    if (const int rc = reg_positions(list_ids, n_list, &pos)) return rc;
+    msfm_reg::CountCorrespondences(reinterpret_cast<const int64_t*>(offsets), image_ids, n_tracks, points, pos.data(), n_list,
+                                   reinterpret_cast<int64_t*>(counts));
+    return 0;
+}
+
+int host_register_images(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks,
+                         const msfm_point3d* points, const int* list_ids, int n_list, const float* const* kxy, const double* cam,
+                         double max_error, double confidence, int max_iters, int min_inliers, int refine_iters,
+                         const long long* out_offsets, int first, int count, msfm_registration* records, int* out_tid,
+                         unsigned char* out_flags, double* out_residuals) {
+    std::vector<int> pos;
+    if (const int rc = reg_positions(list_ids, n_list, &pos)) return rc;
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    const msfm_reg::Params prm = {max_error, confidence, max_iters, min_inliers, refine_iters, 0};
+    msfm_reg::RegisterImages(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, points, list_ids, pos.data(), kxy,
+                             c, prm, reinterpret_cast<const int64_t*>(out_offsets), first, count, records, out_tid, out_flags,
+                             out_residuals);
+    return 0;
+}
+
+// pieces, for tests/test_registration_reference.py
+void host_register_sample3(int image_id, int it, int n, int* idx3) { msfm_reg::sample3(msfm_reg::reg_seed(image_id), it, n, idx3); }
+// u[3], v[3]: normalised observations; X[9]: the three points; poses48: up to 4 x (R[9] | t[3]); returns the number of poses
+int host_p3p(const double* u, const double* v, const double* X, double* poses48) { return msfm_reg::p3p<1>(u, v, X, poses48); }
+// `steps` refinement steps of (R, t) on n correspondences (all of them inliers); returns the steps taken
+int host_register_refine(const double* cu, const double* cv, const double* cX, const double* cY, const double* cZ, int n, int steps,
+                         double* R, double* t) {
+    int done = 0;
+    for (; done < steps; ++done) {
+        double part[msfm_reg::kRegRound][msfm_reg::kRegSums];
+        msfm_reg::partial_sums(R, t, cu, cv, cX, cY, cZ, nullptr, n, part);
+        if (!msfm_reg::gn_step(part[0], R, t)) break;
+    }
+    return done;
+}
 
 }  // extern "C"
