@@ -19,6 +19,9 @@
 //                   into intervals where g' is monotone, the roots of g' found there split it into intervals where g is monotone;
 //                   a root is taken where the sign changes across an interval, by kRegBisect bisection steps and kRegNewton Newton
 //                   steps that are kept while they stay inside the bracket.  (A double root has no sign change: not a solution.)
+//                   Where the quadratics COINCIDE at qs = -l0 / l1 (d(qs) and k(qs) within kRegCoincide of their terms' sizes: a
+//                   triangle seen along its axis of symmetry) the linear equation is 0 p = 0 and qs is a double root: the roots of g
+//                   within kRegCoincideRadius of qs are not used, and both roots p of the second quadratic at qs give poses, last.
 //                   Per root, ascending: p from the linear equation, s1 = sqrt(b2 / D(q)); p, q, s1 must be finite and > 0 (a point
 //                   behind the camera: no pose).  The pose from the orthonormal frames of the triangles (X1, X2, X3) and
 //                   (s1 j1, s2 j2, s3 j3): e1 = d12 / |.|, e3 = d12 x d13 / |.|, e2 = e3 x e1; R = sum_k c_k w_k^T, t = Y1 - R X1.
@@ -49,6 +52,8 @@ namespace msfm_reg {
 constexpr int kRegRound = 64;            // hypotheses per round = lanes of a reg_round_kernel workgroup = partial sums
 constexpr int kRegBisect = 60;           // bisection steps per root
 constexpr int kRegNewton = 3;            // Newton steps inside the final bracket
+constexpr double kRegCoincide = 1e-12;        // |d(qs)|, |k(qs)| <= this x their terms' sizes: the two quadratics coincide at qs
+constexpr double kRegCoincideRadius = 1e-5;  // roots of g within this (relative) of such a qs are the split double root
 constexpr double kRegCollinear = 1e-10;  // |d12 x d13|^2 <= this x |d12|^2 |d13|^2 (an angle below 1e-5 rad): no triangle
 constexpr unsigned long long kRegSeed = 0x5265676973746572ULL;
 
@@ -108,6 +113,8 @@ MSFM_UNROLL
     return true;
 }
 
+MSFM_FHD double absd(double x) { return x < 0.0 ? -x : x; }
+
 MSFM_FHD double clamp(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 MSFM_FHD void cross3(const double a[3], const double b[3], double c[3]) {
@@ -131,6 +138,39 @@ MSFM_UNROLL
         e[6 + k] = w[k] * i3;
     }
     cross3(e + 6, e, e + 3);
+    return true;
+}
+
+// the pose of the depth ratios p = s2 / s1, q = s3 / s1 written at out[(12 ns + .) * S]; false: no pose (a depth that is not finite
+// and > 0, no triangle, a non-finite pose)
+template <int S>
+MSFM_FHD bool p3p_pose(double p, double q, double b2, double cos_b, const double j[9], const double X[9], const double ew[9], double* out, int ns) {
+    const double Dq = (q - 2.0 * cos_b) * q + 1.0;
+    const double s1 = sqrt(b2 / Dq);
+    const double s2 = p * s1, s3 = q * s1;
+    if (!(q > 0.0 && p > 0.0 && s1 > 0.0 && msfm_pose::finite(s1) && msfm_pose::finite(s2) && msfm_pose::finite(s3))) return false;
+    const double Y1[3] = {s1 * j[0], s1 * j[1], s1 * j[2]}, Y2[3] = {s2 * j[3], s2 * j[4], s2 * j[5]}, Y3[3] = {s3 * j[6], s3 * j[7], s3 * j[8]};
+    double ec[9];
+    if (!frame(Y1, Y2, Y3, ec)) return false;
+    double R[9], t[3];
+    bool ok = true;
+MSFM_UNROLL
+    for (int r = 0; r < 3; ++r)
+MSFM_UNROLL
+        for (int c = 0; c < 3; ++c) {
+            R[3 * r + c] = ec[r] * ew[c] + ec[3 + r] * ew[3 + c] + ec[6 + r] * ew[6 + c];
+            ok = ok && msfm_pose::finite(R[3 * r + c]);
+        }
+MSFM_UNROLL
+    for (int r = 0; r < 3; ++r) {
+        t[r] = Y1[r] - (R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2]);
+        ok = ok && msfm_pose::finite(t[r]);
+    }
+    if (!ok) return false;
+MSFM_UNROLL
+    for (int e = 0; e < 9; ++e) out[(12 * ns + e) * S] = R[e];
+MSFM_UNROLL
+    for (int e = 0; e < 3; ++e) out[(12 * ns + 9 + e) * S] = t[e];
     return true;
 }
 
@@ -200,39 +240,36 @@ MSFM_UNROLL
     if (bracket_root<3>(g1, r1, r2, &root)) c1 = root;
     if (bracket_root<3>(g1, r2, B, &root)) c2b = root;
     const double bp[5] = {0.0, c0, c1, c2b, B};
+    // Coincident quadratics: at qs = -l0 / l1 the linear equation is 0 p = d(qs); where d(qs) and k(qs) vanish too (to kRegCoincide of
+    // their terms' size) the two quadratics are THE SAME there, qs is a double root of g -- no sign change, or a pair of roots split
+    // by rounding whose p is 0 / 0 -- and both roots p of the second quadratic are solutions (a triangle seen along its axis of
+    // symmetry).  Then the roots of g within kRegCoincideRadius of qs are not used and those two poses come last.
+    bool coincide = false;
+    double qs = 0.0;
+    if (l[1] != 0.0) {
+        qs = -l[0] / l[1];
+        const double ds = (d[2] * qs + d[1]) * qs + d[0], ks = ((kk[3] * qs + kk[2]) * qs + kk[1]) * qs + kk[0];
+        const double sd = (absd(d[2]) * qs + absd(d[1])) * qs + absd(d[0]);
+        const double sk = ((absd(kk[3]) * qs + absd(kk[2])) * qs + absd(kk[1])) * qs + absd(kk[0]);
+        coincide = qs > 0.0 && msfm_pose::finite(qs) && sd > 0.0 && absd(ds) <= kRegCoincide * sd && absd(ks) <= kRegCoincide * sk;
+    }
     int ns = 0;
 MSFM_UNROLL
     for (int k = 0; k < 4; ++k) {
         double q = 0.0;
         if (!bracket_root<4>(g, bp[k], bp[k + 1], &q)) continue;
+        if (coincide && absd(q - qs) <= kRegCoincideRadius * qs) continue;
         const double p = -((d[2] * q + d[1]) * q + d[0]) / (l[1] * q + l[0]);
-        const double Dq = (q - 2.0 * cos_b) * q + 1.0;
-        const double s1 = sqrt(b2 / Dq);
-        const double s2 = p * s1, s3 = q * s1;
-        if (!(q > 0.0 && p > 0.0 && s1 > 0.0 && msfm_pose::finite(s1) && msfm_pose::finite(s2) && msfm_pose::finite(s3))) continue;
-        const double Y1[3] = {s1 * j[0], s1 * j[1], s1 * j[2]}, Y2[3] = {s2 * j[3], s2 * j[4], s2 * j[5]}, Y3[3] = {s3 * j[6], s3 * j[7], s3 * j[8]};
-        double ec[9];
-        if (!frame(Y1, Y2, Y3, ec)) continue;
-        double R[9], t[3];
-        bool ok = true;
-MSFM_UNROLL
-        for (int r = 0; r < 3; ++r)
-MSFM_UNROLL
-            for (int c = 0; c < 3; ++c) {
-                R[3 * r + c] = ec[r] * ew[c] + ec[3 + r] * ew[3 + c] + ec[6 + r] * ew[6 + c];
-                ok = ok && msfm_pose::finite(R[3 * r + c]);
-            }
-MSFM_UNROLL
-        for (int r = 0; r < 3; ++r) {
-            t[r] = Y1[r] - (R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2]);
-            ok = ok && msfm_pose::finite(t[r]);
+        if (p3p_pose<S>(p, q, b2, cos_b, j, X, ew, out, ns)) ns += 1;
+    }
+    if (coincide) {
+        const double q0s = (q0[2] * qs + q0[1]) * qs + q0[0];
+        const double dp = q1 * q1 - 4.0 * q0s;
+        if (dp >= 0.0) {
+            const double sq = sqrt(dp);
+            if (ns < 4 && p3p_pose<S>((-q1 - sq) / 2.0, qs, b2, cos_b, j, X, ew, out, ns)) ns += 1;
+            if (sq > 0.0 && ns < 4 && p3p_pose<S>((-q1 + sq) / 2.0, qs, b2, cos_b, j, X, ew, out, ns)) ns += 1;
         }
-        if (!ok) continue;
-MSFM_UNROLL
-        for (int e = 0; e < 9; ++e) out[(12 * ns + e) * S] = R[e];
-MSFM_UNROLL
-        for (int e = 0; e < 3; ++e) out[(12 * ns + 9 + e) * S] = t[e];
-        ns += 1;
     }
     return ns;
 }

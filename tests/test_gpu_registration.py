@@ -1,7 +1,10 @@
 """Image registration on the device (msfm_register_images / msfm_fetch_registrations, csrc/msfm_register.hip.h) against the host twin
 (csrc/msfm_register.h through tests/registration_twin.py): records, offsets, track ids, flags and residuals BYTE FOR BYTE -- on the
 tracks of real verified calls, on small hand-made sessions (0, 2, 3, a few and exactly min_inliers correspondences, collinear points,
-more images than the round kernel's grid has workgroups), with outliers, without refinement, and through every error.  The twin itself
+more images than the round kernel's grid has workgroups), with outliers, without refinement, and through every error; and at the kernels' edges: a distorted and an
+anisotropic camera, 63 .. 513 correspondences (ballot words and LDS tiles full, one short, one over) with flags that differ across the
+seams, max_iters 1 .. 129 and 4097 .. 65536 (reg_finish_kernel's replay beyond its first chunk of 64 rounds, never decided and decided
+in round 74), image ids 0 and 9999.  The twin itself
 is checked against the independent numpy reference in tests/test_registration_reference.py."""
 import numpy as np
 import pytest
@@ -155,15 +158,18 @@ def test_refined_pose_that_loses_inliers_is_dropped(tctx, host):
     assert np.all(rec["n_inliers"][kept] >= rec0["n_inliers"][kept]) and (rec["n_inliers"][kept] > rec0["n_inliers"][kept]).any()
 
 
-def small_session(ctx, counts, n_points=40, seed=9, line=()):
+def small_session(ctx, counts, n_points=40, seed=9, line=(), ids=None):
     """Three posed images that see all n_points scene points and one target image per entry of `counts` that sees that many of them
-    (targets listed in `line` see points on one straight line).  Exact projections, tracks by tracks_add.  -> (ids, kp, poses, targets)"""
+    (targets listed in `line` see points on one straight line).  Exact projections, tracks by tracks_add.  ids: the declared image
+    ids (the first three are the posed images, the first one must be the smallest: then track t is point t); default 1, 3, 5, ..
+    -> (ids, kp, poses, targets, truth)"""
     rng = np.random.default_rng(seed)
     n = 3 + len(counts)
     cams = synth.scene_cameras(n, seed=seed)
     X = np.stack([rng.uniform(-1.6, 1.6, n_points), rng.uniform(-1.1, 1.1, n_points), rng.uniform(-1.0, 1.0, n_points)], 1)
     X[:8] = X[0] + np.outer(np.arange(8), [0.11, 0.07, -0.05])           # the first eight points lie on a line
-    ids = np.arange(n, dtype=np.int32) * 2 + 1
+    ids = np.arange(n, dtype=np.int32) * 2 + 1 if ids is None else np.asarray(ids, np.int32)
+    assert len(ids) == n and ids[0] == ids.min()
     seen = [np.arange(n_points)] * 3
     for j, m in enumerate(counts):
         seen.append(np.arange(m) if j in line else 8 + rng.permutation(n_points - 8)[:m])
@@ -251,3 +257,174 @@ def test_more_images_than_the_round_kernel_has_workgroups(tctx, host):
     tctx.triangulate_tracks(CAM, poses)
     st, (rec, *_rest) = same(tctx, host, targets, kp)
     assert st["succeeded"] == n and st["images"] == n > 4 * 256
+
+
+# ---- the kernels' edges ---------------------------------------------------------------------------------------------------------------
+def capture_session(ctx, cam):
+    """tests/test_registration_reference.py's capture (ground-truth tracks, 0.3 px of noise) under `cam`, folded through tracks_add"""
+    import test_triangulation_reference as tri
+    c = tri.capture(77, noise_px=0.3, cam=cam)
+    rng = np.random.default_rng(2)
+    for i in c["ids"]:
+        ctx.upload_image(int(i), rng.integers(0, 256, (len(c["kps"][int(i)]), 128), dtype=np.uint8))
+        ctx.upload_keypoints(int(i), c["kps"][int(i)])
+    offs, img, idx = c["tracks"][0], c["tracks"][1], c["tracks"][2]
+    edges = {}
+    for t in range(len(offs) - 1):                      # a chain through every track's elements
+        for e in range(offs[t], offs[t + 1] - 1):
+            edges.setdefault((int(img[e]), int(img[e + 1])), []).append((int(idx[e]), int(idx[e + 1])))
+    ctx.tracks_begin(c["ids"], min_pair_matches=1)
+    ctx.tracks_add(*fx.csr(sorted(edges.items())))
+    ctx.tracks_finish()
+    assert all(a.tobytes() == np.asarray(b).astype(a.dtype).tobytes() for a, b in zip(ctx.tracks()[:3], c["tracks"][:3]))
+    return c
+
+
+def test_distorted_and_anisotropic_cameras(tctx, host):
+    """reg_fill_kernel's undistort with k1, k2, p1, p2 != 0 and register_impl's f = (fx + fy) / 2 with fx != fy: the distorted capture
+    registered under its own camera (the twin's bytes, and the true poses within the CPU reference test's bounds), then the same
+    points under fx = 2400, fy = 2600 (the twin's bytes; that geometry is not consistent any more, but the camera must show)."""
+    import test_registration_reference as rr
+    import test_triangulation_reference as tri
+    c = capture_session(tctx, tri.CAM_D)
+    s3 = tctx.triangulate_tracks(tri.CAM_D, c["poses"])
+    assert s3["succeeded"] > 1000
+    st, (rec, roffs, *_rest) = same(tctx, host, c["ids"], c["kps"], cam=tri.CAM_D)
+    assert st["succeeded"] == len(c["ids"]) and np.diff(roffs).min() > 200
+    for r in rec:
+        R, t = c["poses"][int(r["image_id"])]
+        assert np.abs(r["R"].reshape(3, 3) - R).max() <= rr.TRUTH_R and np.abs(r["t"] - t).max() <= rr.TRUTH_T
+    # the same keypoints read as undistorted pixels are another problem: the distortion is not ignored
+    _, (rec_p, *_rest) = same(tctx, host, c["ids"], c["kps"], cam=tri.CAM_D[:4])
+    assert any(a.tobytes() != b.tobytes() for a, b in zip(rec, rec_p))
+    cam_a = (2400.0, 2600.0, 1536.0, 1152.0) + tri.CAM_D[4:]
+    _, (rec_a, *_rest) = same(tctx, host, c["ids"], c["kps"], cam=cam_a)
+    assert any(a.tobytes() != b.tobytes() for a, b in zip(rec, rec_a))
+    same(tctx, host, c["ids"], c["kps"], cam=cam_a, max_error=40.0, min_inliers=3)    # (enough tolerance for poses to be found)
+
+
+EDGE_COUNTS = [63, 64, 65, 0, 127, 128, 129, 255, 256, 0, 257, 511, 512, 513, 100, 300]
+EDGE_HEAVY = (14, 15)        # the targets of 100 and 300 correspondences: 70 % moved, so that the rule needs more than one round
+EDGE_SEAMS = (0, 63, 64, 255, 256)
+
+
+def edge_session(ctx):
+    """One target per count at which a ballot word or an LDS tile fills up (63 .. 513, two empty ones between them) and two more
+    (EDGE_HEAVY).  -> (targets, exact keypoints, moved keypoints, moved keypoints of the other side, masks of the moved positions)
+    moved: about 30 % of every target's correspondences displaced by 20 to 60 px, ALWAYS those at positions 0, 63, 64, 255, 256 and the
+    last one (70 % in the EDGE_HEAVY targets).  other: the same, but those positions are NEVER moved and their neighbours 1, 62, 65,
+    254, 257 and the last but one always are.  Positions are positions in the image's correspondence list (ascending track number)."""
+    ids, kp, poses, targets, truth = small_session(ctx, EDGE_COUNTS, n_points=640, seed=12)
+    assert ctx.triangulate_tracks(CAM, poses)["succeeded"] == 640
+    rng = np.random.default_rng(21)
+    moved, other, masks = {i: k.copy() for i, k in kp.items()}, {i: k.copy() for i, k in kp.items()}, {}
+    for j, (i, m) in enumerate(zip(targets, EDGE_COUNTS)):
+        if m == 0:
+            continue
+        row_of = np.argsort(ctx.track_ids(i)[:m], kind="stable")       # position in the list -> keypoint row
+        for dst, always, never in ((moved, EDGE_SEAMS + (m - 1,), ()), (other, (1, 62, 65, 254, 257, m - 2), EDGE_SEAMS + (m - 1,))):
+            sel = rng.random(m) < (0.7 if j in EDGE_HEAVY else 0.3)
+            sel[[p for p in always if 0 <= p < m]] = True
+            sel[[p for p in never if 0 <= p < m]] = False
+            d = rng.uniform(20, 60, (int(sel.sum()), 2)) * rng.choice([-1, 1], (int(sel.sum()), 2))
+            dst[i][row_of[sel], :2] += d.astype(np.float32)
+            if dst is moved:
+                masks[i] = sel
+    return targets, truth, kp, moved, other, masks
+
+
+def upload(ctx, targets, kp):
+    for i in targets:
+        ctx.upload_keypoints(i, kp[i])
+
+
+def test_correspondence_counts_on_every_boundary(tctx, host):
+    """63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513 correspondences: the last ballot word of reg_finish_kernel is full, one
+    short and one over, reg_round_kernel's last LDS tile likewise (m = min(kRegTile, n - c0)), the second and the third tile begin.
+    Exact data first (every target finds the true pose), then with outliers whose flags differ across the ballot words' and the tiles'
+    seams -- the inlier list's prefix mask (1 << lane) - 1 carries mixed flags at lanes 0 and 63 -- with and without refinement."""
+    targets, truth, kp, moved, other, masks = edge_session(tctx)
+    live = [k for k, m in enumerate(EDGE_COUNTS) if m]
+    st, (rec, roffs, tid, flags, res) = same(tctx, host, targets, kp)
+    assert np.diff(roffs).tolist() == EDGE_COUNTS
+    assert st["succeeded"] == len(live) and np.all(rec["status"][live] == 15) and np.all(rec["n_inliers"] == EDGE_COUNTS) and flags.all()
+    for k in live:
+        R, t = truth[targets[k]]
+        assert np.abs(rec[k]["R"].reshape(3, 3) - R).max() < 1e-5 and np.abs(rec[k]["t"] - t).max() < 1e-4
+    same(tctx, host, targets, kp, refine_iters=0)
+    for kps, boundary_moved in ((moved, True), (other, False)):
+        upload(tctx, targets, kps)
+        for refine_iters in (10, 0):
+            st, (rec, roffs, tid, flags, res) = same(tctx, host, targets, kps, refine_iters=refine_iters)
+            assert np.diff(roffs).tolist() == EDGE_COUNTS and st["succeeded"] == len(live)
+            for k in live:
+                m, f = EDGE_COUNTS[k], flags[roffs[k]:roffs[k + 1]]
+                for p in EDGE_SEAMS + (m - 1,):
+                    assert p >= m or f[p] == (0 if boundary_moved else 1), (m, p)
+                for seam in (64, 256):            # both values on each side of the seam (a side of one position has that one's)
+                    for side in (f[:seam], f[seam:]):
+                        assert m <= seam or len(side) < 2 or (side.min() == 0 and side.max() == 1), (m, seam)
+                if boundary_moved:                # exactly the moved ones are outliers
+                    assert np.array_equal(f == 0, masks[targets[k]]), m
+
+
+@pytest.mark.parametrize("max_iters", [1, 3, 63, 64, 65, 127, 129])
+def test_max_iters_edges(tctx, host, max_iters):
+    """max_iters below, at and just over one and two rounds of 64: reg_round_kernel's live lanes, avail = min(r * 64, max_iters) and
+    the record's hypotheses = min(rounds * 64, max_iters).  The EDGE_HEAVY targets (70 % outliers: the rule asks for ~340 hypotheses)
+    run to max_iters."""
+    targets, truth, kp, moved, other, masks = edge_session(tctx)
+    upload(tctx, targets, moved)
+    st, (rec, *_rest) = same(tctx, host, targets, moved, max_iters=max_iters, min_inliers=3)
+    live = [k for k, m in enumerate(EDGE_COUNTS) if m]
+    assert st["attempted"] == len(live) and np.all(rec["hypotheses"] <= max_iters) and np.all(rec["hypotheses"][live] >= min(max_iters, 64))
+    assert np.all(rec["hypotheses"][list(EDGE_HEAVY)] == max_iters)
+    assert st["rounds"] == -(-int(rec["hypotheses"].max()) // 64) == tw.schedule(rec, max_iters)[0] == -(-max_iters // 64)
+
+
+@pytest.mark.parametrize("max_iters", [4097, 4160, 4161, 65536])
+def test_more_than_64_rounds_never_decided(tctx, host, max_iters):
+    """Correspondences on one line: no hypothesis has a pose, the rule is never decided, and reg_finish_kernel's replay walks through
+    every chunk of 64 candidate rounds (65, 65, 66 and 1024 rounds) to the end."""
+    ids, kp, poses, targets, truth = small_session(tctx, [8, 5, 7], line=(0, 1, 2))
+    tctx.triangulate_tracks(CAM, poses)
+    st, (rec, *_rest) = same(tctx, host, targets, kp, max_iters=max_iters, min_inliers=3)
+    assert rec["status"].tolist() == [_lib.REG_ATTEMPTED] * 3 and rec["hypotheses"].tolist() == [max_iters] * 3
+    assert st["rounds"] == -(-max_iters // 64) and st["hypotheses"] == 3 * max_iters
+
+
+LATE_SEED, LATE_EXACT, LATE_COUNT = 0, 16, 128
+
+
+def test_more_than_64_rounds_decided_in_between(tctx, host):
+    """One target of 128 correspondences of which 16 are exact and 112 are moved by 50 to 120 px, max_iters = 8192, min_inliers = 12:
+    at confidence 0.9999 the rule needs ln(1e-4) / ln(1 - (16 / 128)^3) = 4712 hypotheses, so it is decided in round 74 -- in
+    reg_finish_kernel's SECOND chunk of candidate rounds, with undecided and unrun rounds on both sides."""
+    ids, kp, poses, targets, truth = small_session(tctx, [LATE_COUNT], n_points=160, seed=LATE_SEED)
+    assert tctx.triangulate_tracks(CAM, poses)["succeeded"] == 160
+    rng = np.random.default_rng(LATE_SEED + 100)
+    sel = np.ones(LATE_COUNT, bool)
+    sel[rng.permutation(LATE_COUNT)[:LATE_EXACT]] = False
+    d = rng.uniform(50, 120, (int(sel.sum()), 2)) * rng.choice([-1, 1], (int(sel.sum()), 2))
+    kp[targets[0]][sel, :2] += d.astype(np.float32)
+    tctx.upload_keypoints(targets[0], kp[targets[0]])
+    params = dict(max_iters=8192, min_inliers=12)
+    want = tw.run(host, tctx.tracks(), tctx.points3d()[0], targets, kp, CAM, **params)[0]
+    assert 4096 < int(want[0]["hypotheses"]) < 8192 and int(want[0]["status"]) & _lib.REG_SUCCEEDED, want[0]
+    st, (rec, roffs, tid, flags, res) = same(tctx, host, targets, kp, **params)
+    assert st["rounds"] == int(rec[0]["hypotheses"]) // 64 > 64 and int(rec[0]["n_inliers"]) == LATE_EXACT
+    R, t = truth[targets[0]]
+    assert np.abs(rec[0]["R"].reshape(3, 3) - R).max() < 1e-5 and np.abs(rec[0]["t"] - t).max() < 1e-4
+
+
+def test_image_ids_at_the_ends(tctx, host):
+    """Ids 0 and MSFM_MAX_IMAGES - 1 = 9999 declared and listed, the list in descending order: the sampler's seed is keyed by the image
+    id, the sort key by the position in the list."""
+    ids, kp, poses, targets, truth = small_session(tctx, [20, 33, 0, 70, 15], n_points=80, ids=[0, 5, 8, 9999, 4000, 17, 9998, 3])
+    tctx.triangulate_tracks(CAM, poses)
+    order = sorted((int(i) for i in ids), reverse=True)
+    assert order[0] == 9999 and order[-1] == 0
+    st, (rec, roffs, *_rest) = same(tctx, host, order, kp)
+    assert rec["image_id"].tolist() == order and np.diff(roffs).tolist() == [20, 70, 33, 0, 80, 80, 15, 80]
+    assert rec["status"].tolist() == [15, 15, 15, 0, 15, 15, 15, 15]
+    same(tctx, host, [0, 9999], kp, min_inliers=3, max_iters=65)

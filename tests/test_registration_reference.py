@@ -16,7 +16,21 @@ entry) and 6.8e-4 (t) of the true cameras; the twin's must lie within 16 x that 
 is the sharper statement.
 At max_error = 0.3 px (the noise level; test_refined_pose_that_loses_inliers_is_dropped, seed 77) one image keeps its unrefined P3P pose,
 whose conditioning shows: R 5.42e-14, t 1.75e-13, residuals 7.99e-11 px  ->  TOL_LOW_R = 8.7e-13,  TOL_LOW_T = 2.8e-12,
-TOL_LOW_RES = 1.3e-9 px."""
+TOL_LOW_RES = 1.3e-9 px.
+
+host_p3p off the easy cases: the same generator UNFILTERED down to a reference gap of 1e-3 (3000 triples kept, 12 draws = 0.4 % below
+1e-3 skipped; 143 / 488 / 2369 triples per decade).  Worst twin - reference and worst backward error (an observation against the
+projection of its point under a pose the twin returned, normalised units) per decade of gap, and the bounds, 16 x:
+    gap [1e-3, 1e-2)   R 5.66e-5,  t 6.67e-5,  backward 1.07e-6    ->  9.1e-4,  1.1e-3,  1.7e-5
+    gap [1e-2, 5e-2)   R 4.30e-7,  t 2.07e-7,  backward 1.15e-8    ->  6.9e-6,  3.3e-6,  1.8e-7
+    gap >= 5e-2        R 9.12e-9,  t 9.20e-9,  backward 1.55e-10   ->  1.5e-7,  1.5e-7,  2.5e-9
+(the differences grow with 1 / gap as the roots' sensitivity does; the pose counts and orders agree on all 3000 and the true pose is
+among the twin's within 1e-6 on all).  The six orders of a triple's correspondences (200 triples, gap >= 1e-2): equal pose counts,
+R 1.86e-7, t 2.82e-7 between the orders, inside the [1e-2, 5e-2) bounds.  Scaling the points by 2^-10, 4, 2^10: bit-exact (R equal,
+t = s t) on 300 triples.  Distance |R - R*|max + |t - t*|max to the true pose, 100 triples with gap >= 5e-2:
+    scene shifted by 1e3 / 1e6 along +-x, +-y, +-z    1.35e-7 / 4.15e-4          ->  TOL_P3P_SHIFT = 2.2e-6, 6.6e-3
+    third depth x 1/64, 1/8, 8, 64                    4.95e-11, 1.23e-11, 1.54e-11, 3.84e-11  ->  TOL_P3P_DEPTH = 7.9e-10, 2.0e-10, 2.5e-10, 6.1e-10
+(|t*| is the shift there: 1.35e-7 of 1e3 and 4.15e-4 of 1e6 are the rotation's error times the lever.)"""
 import os
 import sys
 
@@ -36,6 +50,10 @@ TOL_P3P_R, TOL_P3P_T = 4.1e-8, 3.8e-8
 TOL_R, TOL_T, TOL_RES, TOL_MEAN = 2.0e-14, 8.5e-14, 8.8e-12, 2.5e-13
 TOL_LOW_R, TOL_LOW_T, TOL_LOW_RES = 8.7e-13, 2.8e-12, 1.3e-9
 TRUTH_R, TRUTH_T = 16 * 1.85e-4, 16 * 6.8e-4
+TOL_P3P_DEC_R, TOL_P3P_DEC_T = (9.1e-4, 6.9e-6, 1.5e-7), (1.1e-3, 3.3e-6, 1.5e-7)     # per decade of gap, DECADES below
+TOL_P3P_BACK = (1.7e-5, 1.8e-7, 2.5e-9)
+TOL_P3P_SHIFT = (2.2e-6, 6.6e-3)
+TOL_P3P_DEPTH = (7.9e-10, 2.0e-10, 2.5e-10, 6.1e-10)
 CASES = [(77, tri.CAM), (5, tri.CAM), (77, tri.CAM_D), (5, tri.CAM_D)]
 
 
@@ -102,6 +120,200 @@ def test_p3p_against_the_reference_solver(host):
     print("p3p: worst twin - reference R %.2e t %.2e" % (worst_R, worst_t))
     assert worst_R <= TOL_P3P_R and worst_t <= TOL_P3P_T
 
+
+# ---- host_p3p off the easy cases ----------------------------------------------------------------------------------------------------
+DECADES = ((1e-3, 1e-2), (1e-2, 5e-2), (5e-2, np.inf))     # of the reference quartic's relative root gap
+N_TRIPLES, MAX_SKIPPED = 3000, 0.02
+
+
+def decade(gap):
+    return [k for k, (lo, hi) in enumerate(DECADES) if lo <= gap < hi][0]
+
+
+def random_triple(rng):
+    """test_p3p_against_the_reference_solver's draw -> (Q, t, X, u, v)"""
+    while True:
+        Q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+        Q *= np.sign(np.linalg.det(Q))
+        X = rng.uniform(-1.5, 1.5, (3, 3))
+        t = np.array([0.0, 0.0, 6.0]) + rng.normal(0, 0.3, 3)
+        Y = X @ Q.T + t
+        if (Y[:, 2] < 1).any():
+            continue
+        return Q, t, X, Y[:, 0] / Y[:, 2], Y[:, 1] / Y[:, 2]
+
+
+def truth_error(sols, Q, t):
+    return min([np.abs(R - Q).max() + np.abs(tt - t).max() for R, tt in sols] + [np.inf])
+
+
+def backward_error(sols, u, v, X):
+    """the largest distance (normalised units) between an observation and the projection of its point under any of the poses"""
+    worst = 0.0
+    for R, t in sols:
+        Y = X @ R.T + t
+        worst = max(worst, np.abs(Y[:, 0] / Y[:, 2] - u).max(), np.abs(Y[:, 1] / Y[:, 2] - v).max())
+    return worst
+
+
+_triples = []
+
+
+def triples(host):
+    """The first N_TRIPLES unfiltered draws (seed 11, the draws of test_p3p_against_the_reference_solver) whose reference gap is >=
+    1e-3, solved by both sides once -> (list of dicts Q t X u v gap want got, the number of draws skipped)"""
+    if not _triples:
+        rng = np.random.default_rng(11)
+        kept, skipped = [], 0
+        while len(kept) < N_TRIPLES:
+            Q, t, X, u, v = random_triple(rng)
+            want, gap = ref.p3p(u, v, X, with_condition=True)
+            if gap < DECADES[0][0]:
+                skipped += 1
+                continue
+            kept.append(dict(Q=Q, t=t, X=X, u=u, v=v, gap=gap, want=want, got=tw.p3p(host, u, v, X)))
+        _triples.extend([kept, skipped])
+    return _triples
+
+
+def test_p3p_down_to_a_root_gap_of_1e_3(host):
+    """3000 UNFILTERED triples but for a reference gap below 1e-3 (where two real roots merge and the solvers legitimately differ;
+    at most 2 % of the draws): the same number of poses in the same order, the true pose among the twin's, and the differences
+    within the bound of the triple's decade of gap."""
+    kept, skipped = triples(host)
+    assert skipped <= MAX_SKIPPED * (len(kept) + skipped), skipped
+    worst, count = np.zeros((3, 2)), [0, 0, 0]
+    for k, c in enumerate(kept):
+        d = decade(c["gap"])
+        count[d] += 1
+        assert len(c["got"]) == len(c["want"]) >= 1, (k, c["gap"], len(c["got"]), len(c["want"]))
+        for (R, t), (Rw, tw_) in zip(c["got"], c["want"]):
+            worst[d] = np.maximum(worst[d], [np.abs(R - Rw).max(), np.abs(t - tw_).max()])
+        assert truth_error(c["got"], c["Q"], c["t"]) < 1e-6, (k, c["gap"])
+    print("p3p: %d draws skipped; triples per decade of gap %s" % (skipped, count))
+    for d, (lo, hi) in enumerate(DECADES):
+        print("p3p gap [%g, %g): worst twin - reference R %.2e t %.2e" % (lo, hi, worst[d][0], worst[d][1]))
+    assert min(count) >= 100
+    for d in range(3):
+        assert worst[d][0] <= TOL_P3P_DEC_R[d] and worst[d][1] <= TOL_P3P_DEC_T[d], (d, worst[d])
+
+
+def test_p3p_backward_error(host):
+    """Every pose the twin returns puts its own three points onto their observations -- whatever the reference says."""
+    kept, _ = triples(host)
+    worst = np.zeros(3)
+    for c in kept:
+        d = decade(c["gap"])
+        worst[d] = max(worst[d], backward_error(c["got"], c["u"], c["v"], c["X"]))
+    for d, (lo, hi) in enumerate(DECADES):
+        print("p3p gap [%g, %g): worst backward error %.2e" % (lo, hi, worst[d]))
+    assert np.all(worst <= TOL_P3P_BACK), worst
+
+
+def test_p3p_scale_covariance_is_exact(host):
+    """s a power of two: every product, quotient and square root of the solver scales exactly (A = a2 / b2, C = c2 / b2 and the
+    quartic do not change at all) -> the same poses with R bit-equal and t exactly s t."""
+    kept, _ = triples(host)
+    for c in kept[:300]:
+        for s in (2.0 ** -10, 4.0, 2.0 ** 10):
+            got = tw.p3p(host, c["u"], c["v"], s * c["X"])
+            assert len(got) == len(c["got"])
+            for (R, t), (R1, t1) in zip(got, c["got"]):
+                assert R.tobytes() == R1.tobytes() and t.tobytes() == (s * t1).tobytes(), s
+
+
+def test_p3p_points_far_from_the_origin(host):
+    """The scene shifted by 1e3 and 1e6 along every axis, the camera with it (t' = t - R d): the cancellation in t = Y1 - R X1 and in
+    the point differences costs |d| x 2^-53 relative and no more."""
+    kept, _ = triples(host)
+    sel = [c for c in kept if c["gap"] >= 5e-2][:100]
+    for dist, bound in zip((1e3, 1e6), TOL_P3P_SHIFT):
+        worst = 0.0
+        for c in sel:
+            for axis in range(3):
+                for sign in (1.0, -1.0):
+                    d = np.zeros(3)
+                    d[axis] = sign * dist
+                    worst = max(worst, truth_error(tw.p3p(host, c["u"], c["v"], c["X"] + d), c["Q"], c["t"] - c["Q"] @ d))
+        print("p3p shifted by %g: worst distance to the true pose %.2e" % (dist, worst))
+        assert worst <= bound, (dist, worst)
+
+
+def test_p3p_extreme_depth_ratios(host):
+    """The third point at k times the first point's depth, k = 1/64 .. 64: the root q = s3 / s1 is tiny or large, so is the Cauchy
+    bound B and with it the bracket the bisection starts from."""
+    rng = np.random.default_rng(12)
+    for k, bound in zip((1 / 64, 1 / 8, 8.0, 64.0), TOL_P3P_DEPTH):
+        worst, done = 0.0, 0
+        while done < 100:
+            Q, t, X, u, v = random_triple(rng)
+            Y = X @ Q.T + t
+            Y[2] *= k * Y[0, 2] / Y[2, 2]          # along its own ray: the observation stays
+            X = (Y - t) @ Q
+            _, gap = ref.p3p(u, v, X, with_condition=True)
+            if gap < 5e-2:
+                continue
+            worst = max(worst, truth_error(tw.p3p(host, u, v, X), Q, t))
+            done += 1
+        print("p3p third depth x %g: worst distance to the true pose %.2e" % (k, worst))
+        assert worst <= bound, (k, worst)
+
+
+def test_p3p_is_invariant_under_permutation(host):
+    """All six orders of the three correspondences of 200 triples with gap >= 1e-2: the same set of poses (the order of the roots
+    changes with the roles of the points), within the bound of the [1e-2, 5e-2) decade."""
+    import itertools
+    kept, _ = triples(host)
+    sel = [c for c in kept if c["gap"] >= 1e-2][:200]
+    worst_R, worst_t = 0.0, 0.0
+    for k, c in enumerate(sel):
+        for perm in itertools.permutations(range(3)):
+            p = list(perm)
+            got = tw.p3p(host, c["u"][p], c["v"][p], c["X"][p])
+            assert len(got) == len(c["got"]), (k, perm, len(got), len(c["got"]))
+            for R, t in c["got"]:
+                j = int(np.argmin([np.abs(R - R1).max() + np.abs(t - t1).max() for R1, t1 in got]))
+                worst_R, worst_t = max(worst_R, np.abs(R - got[j][0]).max()), max(worst_t, np.abs(t - got[j][1]).max())
+    print("p3p permutations: worst difference between orders R %.2e t %.2e" % (worst_R, worst_t))
+    assert worst_R <= TOL_P3P_DEC_R[1] and worst_t <= TOL_P3P_DEC_T[1]
+
+
+def head_on(host, X, depth):
+    """the triangle X (z = 0) seen from the axis at `depth` -> (poses, distance to the true pose, backward error)"""
+    t = np.array([0.0, 0.0, depth])
+    u, v = X[:, 0] / depth, X[:, 1] / depth
+    got = tw.p3p(host, u, v, X)
+    return got, truth_error(got, np.eye(3), t), backward_error(got, u, v, X)
+
+
+def test_p3p_isosceles_triangle_seen_head_on(host):
+    """An isosceles triangle in a plane parallel to the image, the camera on its axis of symmetry: the mirror poses' roots come close
+    (gap 2e-2 at depth 3, 5e-3 at depth 6).  The true pose is among the twin's and every pose it returns reprojects its points; the
+    number of poses is not compared."""
+    X = np.array([[0.0, 1.3, 0], [-0.6, -0.4, 0], [0.6, -0.4, 0]])
+    for depth in (3.0, 6.0):
+        got, e, b = head_on(host, X, depth)
+        print("p3p isosceles at depth %g: %d poses, distance to the true pose %.2e, backward error %.2e" % (depth, len(got), e, b))
+        assert len(got) >= 1 and e < 1e-6 and b <= TOL_P3P_BACK[0]
+
+
+def test_p3p_equilateral_triangle_seen_head_on(host):
+    """An equilateral triangle in a plane parallel to the image, the camera on its axis: the true pose has p = q = 1, where cos_a =
+    cos_g makes the two quadratics in p the SAME -- their difference, the linear equation p is taken from, reads 0 p = 0 there and
+    q = 1 is a double root of the resultant (no sign change, or a pair split by rounding with p from 0 / 0).  p3p's coincidence
+    branch (kRegCoincide) takes both roots p of the quadratic there.  The true pose is among the twin's within 1e-6 and every pose
+    reprojects its points -- as drawn, turned about the axis and scaled.  (Before that branch: the nearest pose 0.22 .. 0.82 away,
+    as for the reference, and a pair of poses with backward error 7.4e-3.)"""
+    X0 = np.array([[1.0, 0, 0], [-0.5, np.sqrt(0.75), 0], [-0.5, -np.sqrt(0.75), 0]])
+    worst_e, worst_b = 0.0, 0.0
+    for depth in (3.0, 6.0, 5.3):
+        for a, scale in ((0.0, 1.0), (0.3, 1.0), (1.1, 0.77)):
+            turn = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+            got, e, b = head_on(host, scale * X0 @ turn.T, depth)
+            print("p3p equilateral at depth %g, turned %g, x %g: %d poses, distance to the true pose %.2e, backward error %.2e"
+                  % (depth, a, scale, len(got), e, b))
+            worst_e, worst_b = max(worst_e, e), max(worst_b, b)
+    assert worst_e < 1e-6 and worst_b <= TOL_P3P_BACK[0], (worst_e, worst_b)
 
 def test_p3p_degenerate_samples(host):
     X = np.array([[0.0, 0, 5], [1, 0, 5], [2, 0, 5]])
