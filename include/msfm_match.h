@@ -595,6 +595,46 @@ int msfm_triangulate_tracks(msfm_ctx* ctx, const msfm_camera* camera, const int3
                             const msfm_triangulation_params* params, msfm_triangulation_stats* stats);
 int msfm_fetch_points3d(msfm_ctx* ctx, msfm_point3d* out_points, double* out_residuals);
 
+/* ---- robust track triangulation: reject outlier observations per track (opt-in) ---------------
+ * msfm_triangulate_tracks is all or nothing: one observation beyond max_error clears ERROR_OK and the whole track is lost.  This
+ * second entry point takes the same inputs, writes the same session outputs (msfm_fetch_points3d, msfm_register_images work after it
+ * unchanged) and adds one inlier byte per kept observation.  The arithmetic is csrc/msfm_triangulate.h, bit-identical to the host twin
+ * TriangulateTracksRobust.  For a track with the used observations 0 .. m - 1, need = max(2, min_views):
+ *   plain pass   P0 = the record of msfm_triangulate_tracks.  Not ATTEMPTED, or POINT & ERROR_OK, or m < 3: the record is P0 bit for
+ *                bit, the inlier byte is 1 on every used observation, MSFM_TRI_ROBUST is clear.  Every other track is RETRIED:
+ *   hypotheses   H = min(m (m - 1) / 2, max_hypotheses) pairs of used observations: all pairs in the order for i: for j < i when they
+ *                fit, else distinct positions from the counter stream keyed by the track number.  X_h = the two-view DLT point; valid
+ *                iff it exists, lies in front of both views and subtends >= min_angle at their centres.  Its count: the used
+ *                observations with depth > DBL_EPSILON and err <= max_error.  Best = the largest count, the lowest h among equals.
+ *                None valid, or a best count < need: status = ATTEMPTED | ROBUST, every other field 0, residuals -1, inlier bytes 0.
+ *   refit, once  the DLT over the inliers of X_best stands iff it has a point and at least max(|inliers of X_best|, need) inliers
+ *                among all used observations (the rule of MSFM_REG_REFINED); else X_best stands with its inliers.
+ *   record       an error for EVERY used observation (the caller sees why one was dropped), n_views = the number of inliers,
+ *                mean_residual and the parallax scan over the inliers only, ERROR_OK set, DEPTH_OK over the inliers, ROBUST set.
+ * Inconsistent tracks stay unattempted.  params NULL = {2.0 px, 1.5 degrees, 2, 64}.  Errors: every check of msfm_triangulate_tracks
+ * with the same codes; MSFM_E_INVALID also for max_hypotheses outside 1 .. 1024.  The call invalidates earlier points and
+ * registrations like msfm_triangulate_tracks.  msfm_fetch_point_inliers copies observations_kept bytes aligned with the tracks'
+ * observations; MSFM_E_STATE unless the last successful triangulation of the session was the robust one (msfm_tracks_finish and
+ * msfm_triangulate_tracks invalidate the bytes, msfm_tracks_end frees them). */
+enum { MSFM_TRI_ROBUST = 32 };
+typedef struct msfm_robust_triangulation_params {   /* 24 bytes, no implicit padding */
+    double max_error;
+    double min_angle;
+    int32_t min_views;           /* values below 2 mean 2 */
+    int32_t max_hypotheses;      /* 1 .. 1024 */
+} msfm_robust_triangulation_params;
+typedef struct msfm_robust_stats {   /* 40 bytes, no implicit padding */
+    int64_t retried;                 /* tracks that went through the hypotheses */
+    int64_t rescued;                 /* ... of which end with POINT & ANGLE_OK */
+    int64_t observations_rejected;   /* used observations with inlier byte 0 on tracks that have a point */
+    int64_t hypotheses;              /* summed H of the retried tracks */
+    double robust_ms;                /* HIP events around all launches of the call (the wait for the retry list included) */
+} msfm_robust_stats;
+int msfm_triangulate_tracks_robust(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses,
+                                   int n_poses, const msfm_robust_triangulation_params* params, msfm_triangulation_stats* stats,
+                                   msfm_robust_stats* robust_stats);
+int msfm_fetch_point_inliers(msfm_ctx* ctx, uint8_t* out);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

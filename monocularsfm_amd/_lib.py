@@ -33,6 +33,7 @@ EXPORTS = [
     "msfm_tracks_begin", "msfm_tracks_add", "msfm_tracks_export_forest", "msfm_tracks_import_forest", "msfm_tracks_finish",
     "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
     "msfm_triangulate_tracks", "msfm_fetch_points3d", "msfm_register_images", "msfm_fetch_registrations",
+    "msfm_triangulate_tracks_robust", "msfm_fetch_point_inliers",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -76,6 +77,19 @@ class TriangulationStats(C.Structure):
     """msfm_triangulation_stats (include/msfm_match.h)."""
     _fields_ = [(k, C.c_int64) for k in ("tracks", "attempted", "with_point", "error_ok", "angle_ok", "depth_ok", "succeeded",
                                          "observations_used", "device_bytes")] + [("triangulate_ms", C.c_double)]
+
+
+# robust track triangulation (include/msfm_match.h): the record's extra status bit, the 24-byte parameters, the 40-byte stats
+TRI_ROBUST = 32
+
+
+class RobustTriangulationParams(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("min_angle", C.c_double), ("min_views", C.c_int32), ("max_hypotheses", C.c_int32)]
+
+
+class RobustStats(C.Structure):
+    """msfm_robust_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("retried", "rescued", "observations_rejected", "hypotheses")] + [("robust_ms", C.c_double)]
 
 
 def succeeded(points):
@@ -274,6 +288,9 @@ def load():
     L.msfm_triangulate_tracks.argtypes = [vp, C.POINTER(Camera), ip, C.c_void_p, C.c_int, C.POINTER(TriangulationParams),
                                           C.POINTER(TriangulationStats)]
     L.msfm_fetch_points3d.argtypes = [vp, C.c_void_p, C.POINTER(C.c_double)]
+    L.msfm_triangulate_tracks_robust.argtypes = [vp, C.POINTER(Camera), ip, C.c_void_p, C.c_int, C.POINTER(RobustTriangulationParams),
+                                                 C.POINTER(TriangulationStats), C.POINTER(RobustStats)]
+    L.msfm_fetch_point_inliers.argtypes = [vp, C.c_void_p]
     L.msfm_register_images.argtypes = [vp, C.POINTER(Camera), ip, C.c_int, C.POINTER(RegisterParams), C.POINTER(RegisterStats)]
     L.msfm_fetch_registrations.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
@@ -702,17 +719,37 @@ class Context:
         self._chk(self._L.msfm_tracks_end(self._h))
 
     # ---- track triangulation (include/msfm_match.h) ----
-    def triangulate_tracks(self, camera, poses, max_error=2.0, min_angle=1.5, min_views=2):
+    def triangulate_tracks(self, camera, poses, max_error=2.0, min_angle=1.5, min_views=2, robust=False, max_hypotheses=64):
         """3-D points of the kept tracks of the last tracks_finish under known poses: camera as set_verification_model takes it, poses a
         dict image id -> (R, t) with x_cam = R X + t (None: listed but unposed; declared images that are not listed are unposed too).
-        Defaults: the reference's Triangulator::Parameters.  -> stats dict.  The points are fetched with points3d()."""
+        Defaults: the reference's Triangulator::Parameters.  -> stats dict.  The points are fetched with points3d().
+        robust=True: msfm_triangulate_tracks_robust -- a track whose plain point fails the error test is retried over at most
+        max_hypotheses two-view hypotheses and keeps the observations that agree; the stats dict gains msfm_robust_stats' fields and
+        point_inliers() returns the inlier byte of every observation."""
         cam = camera_struct(camera) if camera is not None else None
         ids, tab = pose_table(poses)
-        prm = TriangulationParams(float(max_error), float(min_angle), int(min_views), 0)
         st = TriangulationStats()
+        if robust:
+            rprm = RobustTriangulationParams(float(max_error), float(min_angle), int(min_views), int(max_hypotheses))
+            rs = RobustStats()
+            self._chk(self._L.msfm_triangulate_tracks_robust(self._h, C.byref(cam) if cam is not None else None, _ip(ids), tab.ctypes.data,
+                                                             len(ids), C.byref(rprm), C.byref(st), C.byref(rs)))
+            out = {k: getattr(st, k) for k, _ in TriangulationStats._fields_}
+            out.update({k: getattr(rs, k) for k, _ in RobustStats._fields_})
+            return out
+        prm = TriangulationParams(float(max_error), float(min_angle), int(min_views), 0)
         self._chk(self._L.msfm_triangulate_tracks(self._h, C.byref(cam) if cam is not None else None, _ip(ids), tab.ctypes.data, len(ids),
                                                   C.byref(prm), C.byref(st)))
         return {k: getattr(st, k) for k, _ in TriangulationStats._fields_}
+
+    def point_inliers(self):
+        """-> uint8, one per kept observation in the tracks' order (aligned with points3d()'s residuals): 1 where the observation
+        supports its track's point.  Only after triangulate_tracks(..., robust=True)."""
+        st = getattr(self, "_track_stats", None) or {"tracks_kept": 0, "observations_kept": 0}
+        O = int(st["observations_kept"])
+        out = np.zeros(max(O, 1), np.uint8)
+        self._chk(self._L.msfm_fetch_point_inliers(self._h, out.ctypes.data))
+        return out[:O]
 
     def points3d(self):
         """-> (points: POINT3D array, one per kept track; residuals: float64, one per kept observation in the tracks' order, -1.0 where

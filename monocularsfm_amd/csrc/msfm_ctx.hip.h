@@ -647,6 +647,10 @@ struct TrackSession {
     // the current result (msfm_tracks_finish clears it)
     DevBuf t_points, t_resid;
     bool tri_valid = false;
+    // robust triangulation (msfm_triangulate_robust.hip.h): an inlier byte per kept observation; mask_valid: the current points are the
+    // robust call's (msfm_tracks_finish and msfm_triangulate_tracks clear it)
+    DevBuf t_mask;
+    bool mask_valid = false;
     // image registration (msfm_register.hip.h): a record per listed image, the CSR of (track number, inlier flag, residual) per
     // correspondence; reg_valid: they belong to the current points (msfm_tracks_finish and msfm_triangulate_tracks clear it)
     DevBuf g_records, g_offsets, g_tid, g_inl, g_res;
@@ -662,7 +666,7 @@ struct TrackSession {
         return s;
     }
     void release() {   // (the caller has drained the streams)
-        for (DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid, &t_points, &t_resid, &g_records, &g_offsets, &g_tid, &g_inl, &g_res}) b->release();
+        for (DevBuf* b : {&d_parent, &d_table, &d_base, &d_ids, &r_offsets, &r_img, &r_idx, &r_cons, &r_tid, &t_points, &t_resid, &t_mask, &g_records, &g_offsets, &g_tid, &g_inl, &g_res}) b->release();
         for (auto& e : ev_pending) {
             (void)hipEventDestroy(e.first);
             (void)hipEventDestroy(e.second);
@@ -673,7 +677,7 @@ struct TrackSession {
         rank_of.clear();
         nd = MsfmTrackNodes{};
         stats = msfm_track_stats{};
-        open = closed = finished = suppress = add_only = tri_valid = reg_valid = false;
+        open = closed = finished = suppress = add_only = tri_valid = mask_valid = reg_valid = false;
     }
 };
 

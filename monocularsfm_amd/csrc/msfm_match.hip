@@ -43,6 +43,7 @@ using namespace msfm;
 #include "msfm_batch.hip.h"
 #include "msfm_tracks.hip.h"
 #include "msfm_triangulate.hip.h"
+#include "msfm_triangulate_robust.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -861,6 +862,24 @@ int msfm_fetch_points3d(msfm_ctx* ctx, msfm_point3d* out_points, double* out_res
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return fetch_points3d_impl(ctx, out_points, out_residuals);
+    MSFM_API_END
+}
+
+// ---- robust track triangulation (msfm_triangulate_robust.hip.h) ---------------------------------------------------------------------
+
+int msfm_triangulate_tracks_robust(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses,
+                                   int n_poses, const msfm_robust_triangulation_params* params, msfm_triangulation_stats* stats,
+                                   msfm_robust_stats* robust_stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return triangulate_robust_impl(ctx, camera, image_ids, poses, n_poses, params, stats, robust_stats);
+    MSFM_API_END
+}
+
+int msfm_fetch_point_inliers(msfm_ctx* ctx, uint8_t* out) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return fetch_point_inliers_impl(ctx, out);
     MSFM_API_END
 }
 

@@ -477,6 +477,7 @@ int tracks_finish_impl(msfm_ctx* ctx, const msfm_track_filter* filter, msfm_trac
     ts.closed = true;      // the accumulation is closed whatever happens below ...
     ts.finished = false;   // ... and there is no result until this finish has succeeded
     ts.tri_valid = false;  // the points of an earlier result (msfm_triangulate_tracks) do not belong to the new one
+    ts.mask_valid = false; // ... nor do the inlier bytes of a robust one
     ts.reg_valid = false;  // ... nor do the registrations made from them (msfm_register_images)
     const int n = (int)ts.nd.nodes(), n_img = (int)ts.nd.ids.size();
     hipStream_t st = store_stream(ctx);

@@ -211,6 +211,230 @@ MSFM_UNROLL
     rec->tri_angle = angle;
 }
 
+// ---- robust triangulation: a per-track consensus over two-view hypotheses -------------------------------------
+// For one consistent track with the used observations 0 .. m - 1 (the posed elements, in element order), need = max(2, min_views):
+//   plain pass      P0 = triangulate_track.  Not ATTEMPTED, or POINT & ERROR_OK, or m < 3: the record is P0 bit for bit, the mask is 1
+//                   on every used observation, ROBUST is clear (retry() below is the test).
+//   hypotheses      H = min(m (m - 1) / 2, max_hypotheses).  All pairs fit: hypothesis h is the h-th pair of  for i: for j < i
+//                   (pair_of).  Otherwise two distinct positions from sample2 under tri_seed(track number), the larger one i.  X_h: the
+//                   DLT over the two observations alone (dlt_add of j, then of i; dlt_solve).  Valid iff it has a point, both depths
+//                   are > kDepthEps and parallax(X_h, O_i, O_j) >= min_angle.  count_h: the used observations with depth > kDepthEps
+//                   and err <= max_error (obs_error; a NaN fails).  Best: the largest count, the lowest h among equals.  No valid
+//                   hypothesis or a best count < need: status = ATTEMPTED | ROBUST, every other field 0, residuals -1, mask 0.
+//   refit, once     mask1 = the inliers of X_best;  R1 = the DLT over mask1 (dlt_point on Masked);  mask2 = the inliers of R1 among all
+//                   used observations;  R1 stands iff it has a point and |mask2| >= max(|mask1|, need), else X_best with mask1.
+//   record          evaluate_point: an error for EVERY used observation (-1 for unposed elements), n_views = |mask|, mean_residual =
+//                   the inliers' errors summed in element order from 0.0 / |mask|, the parallax scan for i: for j < i over the inliers
+//                   with triangulate_track's stop rule, ERROR_OK set, DEPTH_OK over the inliers, ROBUST set.
+constexpr unsigned long long kTriSeed = 0x547269616e67756cULL;
+
+struct RobustParams {
+    double max_error, min_angle;
+    int32_t min_views, max_hypotheses;
+};
+
+MSFM_FHD unsigned long long tri_seed(long long track) { return msfm_fmat::mix64(kTriSeed ^ (unsigned long long)track); }
+
+// the 2 distinct positions of hypothesis `it` (n >= 2): sample8's stream, k < 2
+MSFM_FHD void sample2(unsigned long long seed, int it, int n, int idx[2]) {
+    using msfm_fmat::mix64;
+    idx[0] = idx[1] = -1;
+MSFM_UNROLL
+    for (int k = 0; k < 2; ++k) {
+        int c = 0;
+        for (int attempt = 0;; ++attempt) {
+            c = attempt < 32 ? (int)(mix64(seed ^ mix64(((unsigned long long)it << 20) ^ ((unsigned long long)k << 8) ^ (unsigned long long)attempt)) % (unsigned long long)n)
+                             : (c + 1) % n;  // linear probe: terminates because n >= 2
+            if (!(idx[0] == c || idx[1] == c)) break;
+        }
+        idx[k] = c;
+    }
+}
+
+// the h-th pair (i, j), j < i, of the scan order  for i in 1 ..: for j < i
+MSFM_FHD void pair_of(int h, int* i, int* j) {
+    int a = 1;
+    while ((a + 1) * a / 2 <= h) ++a;
+    *i = a;
+    *j = h - a * (a - 1) / 2;
+}
+
+MSFM_FHD long long hypotheses_of(int m, int max_hypotheses) {
+    const long long pairs = (long long)m * (m - 1) / 2;
+    return pairs < max_hypotheses ? pairs : max_hypotheses;
+}
+
+// the two positions of hypothesis h of a track with m used observations: *j < *i
+MSFM_FHD void hypothesis_pair(unsigned long long seed, int h, int m, int max_hypotheses, int* i, int* j) {
+    if ((long long)m * (m - 1) / 2 <= max_hypotheses) {
+        pair_of(h, i, j);
+        return;
+    }
+    int idx[2];
+    sample2(seed, h, m, idx);
+    *i = idx[0] > idx[1] ? idx[0] : idx[1];
+    *j = idx[0] > idx[1] ? idx[1] : idx[0];
+}
+
+// step 1's verdict on the plain record of a track with m used observations
+MSFM_FHD bool retry(const msfm_point3d& p0, int m) {
+    const int done = MSFM_TRI_POINT | MSFM_TRI_ERROR_OK;
+    return (p0.status & MSFM_TRI_ATTEMPTED) && (p0.status & done) != done && m >= 3;
+}
+
+// triangulate_track's DLT in pieces: the normal matrix (m[j][i]: column j, row i) of no observation, one observation added, the point
+MSFM_FHD void dlt_clear(double m[4][4]) {
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j)
+MSFM_UNROLL
+        for (int i = 0; i < 4; ++i) m[j][i] = 0.0;
+}
+
+MSFM_FHD void dlt_add(double m[4][4], const double R[9], const double t[3], double u, double w) {
+    double r1[4], r2[4];
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        const double p0 = j < 3 ? R[j] : t[0], p1 = j < 3 ? R[3 + j] : t[1], p2 = j < 3 ? R[6 + j] : t[2];
+        r1[j] = u * p2 - p0;
+        r2[j] = w * p2 - p1;
+    }
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j)
+MSFM_UNROLL
+        for (int i = 0; i < 4; ++i) {
+            m[j][i] = m[j][i] + r1[i] * r1[j];
+            m[j][i] = m[j][i] + r2[i] * r2[j];
+        }
+}
+
+// (m is destroyed.)  False: no point.
+MSFM_FHD bool dlt_solve(double m[4][4], double X[3]) {
+    double v[4][4];
+    msfm_pose::onesided_jacobi<4, 4>(m, v);
+    double best = 0.0, h[4] = {0.0, 0.0, 0.0, 0.0};
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        const double nn = m[j][0] * m[j][0] + m[j][1] * m[j][1] + m[j][2] * m[j][2] + m[j][3] * m[j][3];
+        if (j == 0 || nn < best) {
+            best = nn;
+MSFM_UNROLL
+            for (int k = 0; k < 4; ++k) h[k] = v[j][k];
+        }
+    }
+    X[0] = X[1] = X[2] = 0.0;
+    if (!(h[3] > 0.0 || h[3] < 0.0)) return false;
+    X[0] = h[0] / h[3];
+    X[1] = h[1] / h[3];
+    X[2] = h[2] / h[3];
+    return msfm_pose::finite(X[0]) && msfm_pose::finite(X[1]) && msfm_pose::finite(X[2]);
+}
+
+// the reprojection error of X in one view, pixels (f = (fx + fy) / 2), and whether X lies in front of it
+MSFM_FHD double obs_error(const double R[9], const double t[3], double u, double w, const double X[3], double f, bool* depth) {
+    const double Y0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+    const double Y1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+    const double Y2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+    *depth = Y2 > msfm_pose::kDepthEps;
+    const double dx = Y0 / Y2 - u, dy = Y1 / Y2 - w;
+    return sqrt(dx * dx + dy * dy) * f;
+}
+
+MSFM_FHD bool obs_inlier(const double R[9], const double t[3], double u, double w, const double X[3], double f, double max_error) {
+    bool depth;
+    const double err = obs_error(R, t, u, w, X, f, &depth);
+    return depth && err <= max_error;   // (false for a NaN)
+}
+
+// the elements of `a` whose mask byte is set (the mask is element-aligned; a set byte belongs to a posed element)
+template <class A>
+struct Masked {
+    const A& a;
+    const uint8_t* mask;
+    MSFM_FHD const Pose* pose(int k) const { return mask[k] ? a.pose(k) : nullptr; }
+    MSFM_FHD void pixel(int k, double* x, double* y) const { a.pixel(k, x, y); }
+};
+
+// the DLT point over the posed elements of `a`, in element order
+template <class A>
+MSFM_FHD bool dlt_point(const A& a, int n, const msfm_emat::Camera& cam, double X[3]) {
+    double m[4][4];
+    dlt_clear(m);
+    for (int k = 0; k < n; ++k) {
+        const Pose* p = a.pose(k);
+        if (!p) continue;
+        double x, y, u, w;
+        a.pixel(k, &x, &y);
+        msfm_emat::undistort(cam, x, y, &u, &w);
+        dlt_add(m, p->R, p->t, u, w);
+    }
+    return dlt_solve(m, X);
+}
+
+// the record of a retried track without a consensus
+MSFM_FHD void robust_failed(int n, msfm_point3d* rec, double* residuals, uint8_t* mask) {
+    clear_point(rec);
+    rec->status = MSFM_TRI_ATTEMPTED | MSFM_TRI_ROBUST;
+    for (int k = 0; k < n; ++k) {
+        residuals[k] = -1.0;
+        mask[k] = 0;
+    }
+}
+
+// the record of X under the inlier mask (at least one byte set)
+template <class A>
+MSFM_FHD void evaluate_point(const A& a, int n, const double X[3], const uint8_t* mask, const msfm_emat::Camera& cam, double min_angle,
+                             msfm_point3d* rec, double* residuals) {
+    const double f = (cam.fx + cam.fy) / 2.0;
+    bool depth_ok = true;
+    double sum = 0.0;
+    int count = 0;
+    for (int k = 0; k < n; ++k) {
+        const Pose* p = a.pose(k);
+        if (!p) {
+            residuals[k] = -1.0;
+            continue;
+        }
+        double x, y, u, w;
+        a.pixel(k, &x, &y);
+        msfm_emat::undistort(cam, x, y, &u, &w);
+        bool depth;
+        const double err = obs_error(p->R, p->t, u, w, X, f, &depth);
+        residuals[k] = err;
+        if (mask[k]) {
+            depth_ok = depth_ok && depth;
+            sum = sum + err;
+            count += 1;
+        }
+    }
+    bool angle_ok = false;
+    double angle = 0.0;
+    for (int i = 1; i < n && !angle_ok; ++i) {
+        if (!mask[i]) continue;
+        const Pose* pi = a.pose(i);
+        const double Oi[3] = {pi->O[0], pi->O[1], pi->O[2]};
+        for (int j = 0; j < i; ++j) {
+            if (!mask[j]) continue;
+            const Pose* pj = a.pose(j);
+            const double Oj[3] = {pj->O[0], pj->O[1], pj->O[2]};
+            const double g = parallax(X, Oi, Oj);
+            if (g >= min_angle) {
+                angle = g;
+                angle_ok = true;
+                break;
+            }
+            if (g > angle) angle = g;
+        }
+    }
+    rec->status = MSFM_TRI_ATTEMPTED | MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | (angle_ok ? MSFM_TRI_ANGLE_OK : 0) |
+                  (depth_ok ? MSFM_TRI_DEPTH_OK : 0) | MSFM_TRI_ROBUST;
+    rec->n_views = count;
+    rec->X[0] = X[0];
+    rec->X[1] = X[1];
+    rec->X[2] = X[2];
+    rec->mean_residual = sum / (double)count;
+    rec->tri_angle = angle;
+}
+
 #if !defined(__HIP_DEVICE_COMPILE__)
 // ---- the host twin: TriangulateTracks over a finished track result ---------------------------------------------------------------
 // tracks as msfm_fetch_tracks returns them; kxy[rank]: the (x, y) fp32 pairs of the image of that rank (may be null for an image
@@ -239,6 +463,117 @@ inline void TriangulateTracks(const int64_t* offsets, const int32_t* image_ids, 
         const int64_t b = offsets[t], e = offsets[t + 1];
         const HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
         triangulate_track(a, (int)(e - b), consistent[t] != 0, cam, prm, out_points + t, out_residuals + b);
+    }
+}
+
+// the used observations of one track by position, as the hypotheses read them
+struct HostObs {
+    std::vector<int> elem;
+    std::vector<double> u, w;
+    std::vector<const Pose*> p;
+};
+
+struct RobustCounts {
+    long long retried, rescued, observations_rejected, hypotheses;
+};
+
+// One track, literally the definition above.  mask: n bytes, element-aligned.  `counts` (may be null) is added to.
+template <class A>
+inline void robust_track(const A& a, int n, bool consistent, long long track, const msfm_emat::Camera& cam, const RobustParams& prm,
+                         msfm_point3d* rec, double* residuals, uint8_t* mask, RobustCounts* counts) {
+    const Params plain = {prm.max_error, prm.min_angle, prm.min_views, 0};
+    triangulate_track(a, n, consistent, cam, plain, rec, residuals);
+    HostObs o;
+    const bool attempted = (rec->status & MSFM_TRI_ATTEMPTED) != 0;
+    for (int k = 0; k < n; ++k) {
+        const Pose* p = attempted ? a.pose(k) : nullptr;
+        mask[k] = p ? 1 : 0;
+        if (!p) continue;
+        double x, y, u, w;
+        a.pixel(k, &x, &y);
+        msfm_emat::undistort(cam, x, y, &u, &w);
+        o.elem.push_back(k);
+        o.u.push_back(u);
+        o.w.push_back(w);
+        o.p.push_back(p);
+    }
+    const int m = (int)o.elem.size();
+    if (!retry(*rec, m)) return;
+    const int need = prm.min_views > 2 ? prm.min_views : 2;
+    const double f = (cam.fx + cam.fy) / 2.0;
+    const int H = (int)hypotheses_of(m, prm.max_hypotheses);
+    const unsigned long long seed = tri_seed(track);
+    int best = -1;
+    double Xb[3] = {0.0, 0.0, 0.0};
+    for (int h = 0; h < H; ++h) {
+        int i, j;
+        hypothesis_pair(seed, h, m, prm.max_hypotheses, &i, &j);
+        double A4[4][4], X[3];
+        dlt_clear(A4);
+        dlt_add(A4, o.p[(size_t)j]->R, o.p[(size_t)j]->t, o.u[(size_t)j], o.w[(size_t)j]);
+        dlt_add(A4, o.p[(size_t)i]->R, o.p[(size_t)i]->t, o.u[(size_t)i], o.w[(size_t)i]);
+        bool valid = dlt_solve(A4, X);
+        int count = 0;
+        for (int k = 0; k < m && valid; ++k) {
+            const bool in = obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X, f, prm.max_error);
+            if (k == i || k == j) {
+                bool depth;
+                (void)obs_error(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X, f, &depth);
+                valid = depth;
+            }
+            count += in ? 1 : 0;
+        }
+        valid = valid && parallax(X, o.p[(size_t)i]->O, o.p[(size_t)j]->O) >= prm.min_angle;
+        if (valid && count > best) {
+            best = count;
+            Xb[0] = X[0];
+            Xb[1] = X[1];
+            Xb[2] = X[2];
+        }
+    }
+    if (counts) {
+        counts->retried += 1;
+        counts->hypotheses += H;
+    }
+    if (best < need) {
+        robust_failed(n, rec, residuals, mask);
+        return;
+    }
+    int n1 = 0;
+    for (int k = 0; k < m; ++k) {
+        const bool in = obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], Xb, f, prm.max_error);
+        mask[o.elem[(size_t)k]] = in ? 1 : 0;
+        n1 += in ? 1 : 0;
+    }
+    double X1[3];
+    const Masked<A> masked{a, mask};
+    if (dlt_point(masked, n, cam, X1)) {
+        int n2 = 0;
+        for (int k = 0; k < m; ++k) n2 += obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X1, f, prm.max_error) ? 1 : 0;
+        if (n2 >= (n1 > need ? n1 : need)) {
+            for (int k = 0; k < m; ++k)
+                mask[o.elem[(size_t)k]] = obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X1, f, prm.max_error) ? 1 : 0;
+            n1 = n2;
+            Xb[0] = X1[0];
+            Xb[1] = X1[1];
+            Xb[2] = X1[2];
+        }
+    }
+    evaluate_point(a, n, Xb, mask, cam, prm.min_angle, rec, residuals);
+    if (counts) {
+        counts->rescued += (rec->status & MSFM_TRI_ANGLE_OK) ? 1 : 0;
+        counts->observations_rejected += m - n1;
+    }
+}
+
+inline void TriangulateTracksRobust(const int64_t* offsets, const int32_t* image_ids, const int32_t* point_idx, const uint8_t* consistent,
+                                    int64_t first_track, int64_t n_tracks, const int* rank_of_id, const float* const* kxy,
+                                    const Pose* poses, const msfm_emat::Camera& cam, const RobustParams& prm, msfm_point3d* out_points,
+                                    double* out_residuals, uint8_t* out_mask, RobustCounts* counts) {
+    for (int64_t t = first_track; t < first_track + n_tracks; ++t) {
+        const int64_t b = offsets[t], e = offsets[t + 1];
+        const HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
+        robust_track(a, (int)(e - b), consistent[t] != 0, (long long)t, cam, prm, out_points + t, out_residuals + b, out_mask + b, counts);
     }
 }
 #endif

@@ -84,51 +84,67 @@ __global__ __launch_bounds__(256) void tri_track_kernel(const long long* __restr
 
 namespace {
 
-int triangulate_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
-                     const msfm_triangulation_params* params, msfm_triangulation_stats* stats) {
+// What msfm_triangulate_tracks and msfm_triangulate_tracks_robust (`who`) check before any device work, and the two tables they
+// upload: the caller's poses by declared-image rank, the per-image-id entry of the kernels.
+int tri_prepare(msfm_ctx* ctx, const std::string& who, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses,
+                int n_poses, const msfm_tri::Params& prm, std::vector<msfm_pose_rt>* by_rank_out, std::vector<TriImage>* table_out) {
     TrackSession& ts = ctx->tracks;
     ts.tri_valid = false;   // whatever happens below, the previous points are gone
+    ts.mask_valid = false;  // ... and the inlier bytes of a robust call (msfm_triangulate_robust.hip.h)
     ts.reg_valid = false;   // ... and the registrations made from them (msfm_register.hip.h)
-    if (!ts.open) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks without a track session (msfm_tracks_begin)");
-    if (!ts.finished) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks before a successful msfm_tracks_finish");
-    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "msfm_triangulate_tracks while a streaming series (msfm_match_pairs_begin .. _next) is open");
-    if (!camera) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: NULL camera");
+    if (!ts.open) return fail(ctx, MSFM_E_STATE, who + " without a track session (msfm_tracks_begin)");
+    if (!ts.finished) return fail(ctx, MSFM_E_STATE, who + " before a successful msfm_tracks_finish");
+    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, who + " while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (!camera) return fail(ctx, MSFM_E_INVALID, who + ": NULL camera");
     const msfm_camera c = *camera;
     for (double v : {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2})
-        if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: camera parameters must be finite");
-    if (!(c.fx > 0.0) || !(c.fy > 0.0)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: fx and fy must be positive");
-    msfm_tri::Params prm = {2.0, 1.5, 2, 0};   // Triangulator::Parameters
-    if (params) prm = msfm_tri::Params{params->max_error, params->min_angle, params->min_views, 0};
-    if (!std::isfinite(prm.max_error) || !std::isfinite(prm.min_angle)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: parameters must be finite");
-    if (prm.max_error < 0.0 || prm.min_angle < 0.0) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: max_error and min_angle must not be negative");
-    if (n_poses < 0 || (n_poses > 0 && (!image_ids || !poses))) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: bad pose list");
+        if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, who + ": camera parameters must be finite");
+    if (!(c.fx > 0.0) || !(c.fy > 0.0)) return fail(ctx, MSFM_E_INVALID, who + ": fx and fy must be positive");
+    if (!std::isfinite(prm.max_error) || !std::isfinite(prm.min_angle)) return fail(ctx, MSFM_E_INVALID, who + ": parameters must be finite");
+    if (prm.max_error < 0.0 || prm.min_angle < 0.0) return fail(ctx, MSFM_E_INVALID, who + ": max_error and min_angle must not be negative");
+    if (n_poses < 0 || (n_poses > 0 && (!image_ids || !poses))) return fail(ctx, MSFM_E_INVALID, who + ": bad pose list");
     const int n_img = (int)ts.nd.ids.size();
-    std::vector<msfm_pose_rt> by_rank((size_t)std::max(n_img, 1), msfm_pose_rt{});
+    std::vector<msfm_pose_rt>& by_rank = *by_rank_out;
+    by_rank.assign((size_t)std::max(n_img, 1), msfm_pose_rt{});
     std::vector<char> given((size_t)std::max(n_img, 1), 0);
     for (int k = 0; k < n_poses; ++k) {
         const int id = image_ids[k];
-        if (!ts.declares(id)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: image not declared in the session: " + std::to_string(id));
+        if (!ts.declares(id)) return fail(ctx, MSFM_E_INVALID, who + ": image not declared in the session: " + std::to_string(id));
         const int r = ts.rank_of[(size_t)id];
-        if (given[(size_t)r]) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: an image is given twice: " + std::to_string(id));
+        if (given[(size_t)r]) return fail(ctx, MSFM_E_INVALID, who + ": an image is given twice: " + std::to_string(id));
         given[(size_t)r] = 1;
         if (poses[k].valid) {
             for (double v : poses[k].R)
-                if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: non-finite R of image " + std::to_string(id));
+                if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, who + ": non-finite R of image " + std::to_string(id));
             for (double v : poses[k].t)
-                if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks: non-finite t of image " + std::to_string(id));
+                if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, who + ": non-finite t of image " + std::to_string(id));
         }
         by_rank[(size_t)r] = poses[k];
         by_rank[(size_t)r].valid = poses[k].valid ? 1 : 0;
         by_rank[(size_t)r].reserved = 0;
     }
-    std::vector<TriImage> table((size_t)MSFM_MAX_IMAGES, TriImage{nullptr, -1, 0});
+    std::vector<TriImage>& table = *table_out;
+    table.assign((size_t)MSFM_MAX_IMAGES, TriImage{nullptr, -1, 0});
     for (int r = 0; r < n_img; ++r) {
         const int id = ts.nd.ids[(size_t)r];
         const Image& im = ctx->images[(size_t)id];
         if (by_rank[(size_t)r].valid && im.nk < ts.nd.rows[(size_t)r])
-            return fail(ctx, MSFM_E_NOIMAGE, "msfm_triangulate_tracks: posed image without keypoints (msfm_upload_keypoints): " + std::to_string(id));
+            return fail(ctx, MSFM_E_NOIMAGE, who + ": posed image without keypoints (msfm_upload_keypoints): " + std::to_string(id));
         table[(size_t)id] = TriImage{im.kxy, r, 0};
     }
+    return MSFM_OK;
+}
+
+int triangulate_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
+                     const msfm_triangulation_params* params, msfm_triangulation_stats* stats) {
+    TrackSession& ts = ctx->tracks;
+    msfm_tri::Params prm = {2.0, 1.5, 2, 0};   // Triangulator::Parameters
+    if (params) prm = msfm_tri::Params{params->max_error, params->min_angle, params->min_views, 0};
+    std::vector<msfm_pose_rt> by_rank;
+    std::vector<TriImage> table;
+    if (const int rc = tri_prepare(ctx, "msfm_triangulate_tracks", camera, image_ids, poses, n_poses, prm, &by_rank, &table)) return rc;
+    const msfm_camera c = *camera;
+    const int n_img = (int)ts.nd.ids.size();
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
     struct Tmp {   // freed when the call returns, whatever it returns

@@ -629,6 +629,44 @@ int host_triangulate_tracks(const long long* offsets, const int* image_ids, cons
     return 0;
 }
 
+// The robust twin (TriangulateTracksRobust): the same inputs, max_hypotheses, and the inlier byte per observation.  counts4 (may be
+// NULL): retried, rescued, observations_rejected, hypotheses of the tracks computed by this call are ADDED to it.
+int host_triangulate_tracks_robust(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                                   const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
+                                   int n_poses, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses,
+                                   long long first, long long count, msfm_point3d* out_points, double* out_residuals,
+                                   unsigned char* out_mask, long long* counts4) {
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        rank_of[(size_t)ids[k]] = k;
+    }
+    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
+    }
+    if (max_hypotheses < 1 || max_hypotheses > 1024) return 3;
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    const msfm_tri::RobustParams prm = {max_error, min_angle, min_views, max_hypotheses};
+    msfm_tri::RobustCounts rc = {0, 0, 0, 0};
+    msfm_tri::TriangulateTracksRobust(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count,
+                                      rank_of.data(), kxy, table.data(), c, prm, out_points, out_residuals, out_mask, &rc);
+    if (counts4) {
+        counts4[0] += rc.retried;
+        counts4[1] += rc.rescued;
+        counts4[2] += rc.observations_rejected;
+        counts4[3] += rc.hypotheses;
+    }
+    return 0;
+}
+void host_tri_sample2(long long track, int h, int m, int* idx2) { msfm_tri::sample2(msfm_tri::tri_seed(track), h, m, idx2); }
+
 // pieces, for tests/test_triangulation_reference.py
 void host_tri_centre(const double* R, const double* t, double* O) { msfm_tri::centre(R, t, O); }
 double host_tri_parallax(const double* X, const double* Oi, const double* Oj) { return msfm_tri::parallax(X, Oi, Oj); }

@@ -166,6 +166,29 @@ def triangulation_job(n_images=1329, n_kp=8192, cam=(2500.0, 2500.0, 1536.0, 115
     return ids, kps, poses, lists
 
 
+def corrupt_observations(ids, kps, tracks, chosen, offset=(40.0, 0.0)):
+    """One wrong observation per chosen track, for the robust triangulation: tracks = (offsets, image_ids, point_idx, ...) as
+    Context.tracks() returns them over the images `ids` with the keypoints `kps` (by position in ids); chosen: (track number, element
+    position within the track) pairs; the keypoint of that element is moved by offset = (dx, dy) pixels.
+    -> (keypoints: copies of the arrays that changed, the others as given; moved: the observation numbers offsets[t] + position)."""
+    offsets, img, idx = tracks[0], tracks[1], tracks[2]
+    at = {int(i): k for k, i in enumerate(ids)}
+    out = list(kps)
+    copied = set()
+    moved = []
+    for t, pos in chosen:
+        o = int(offsets[int(t)]) + int(pos)
+        assert o < int(offsets[int(t) + 1]), "the position lies outside the track"
+        k = at[int(img[o])]
+        if k not in copied:
+            out[k] = np.array(out[k], copy=True)
+            copied.add(k)
+        out[k][int(idx[o]), 0] += F32(offset[0])
+        out[k][int(idx[o]), 1] += F32(offset[1])
+        moved.append(o)
+    return out, np.asarray(moved, np.int64)
+
+
 def _rotation(rng, scale):
     w = rng.normal(size=3) * scale
     th = np.linalg.norm(w)
