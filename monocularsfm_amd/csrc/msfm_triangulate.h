@@ -477,10 +477,32 @@ struct RobustCounts {
     long long retried, rescued, observations_rejected, hypotheses;
 };
 
-// One track, literally the definition above.  mask: n bytes, element-aligned.  `counts` (may be null) is added to.
+// Which route one track took through the definition above: what the tests assert before they trust a byte comparison to have met a
+// branch.  Twelve int32.  A track that is not retried: retried 0, m, everything else as set by trace_clear.
+struct RobustTrace {
+    int32_t retried;               // 1: the track went through the hypotheses
+    int32_t m;                     // used observations
+    int32_t hypotheses;            // H
+    int32_t winner;                // the winning hypothesis, -1: none was valid
+    int32_t best;                  // its count, -1: none was valid
+    int32_t valid;                 // hypotheses that were valid
+    int32_t depth_rejected;        // hypotheses with a point and parallax >= min_angle whose sampled views fail the depth test
+    int32_t depth_rejected_best;   // the largest count_h among those (over ALL used observations), -1: none
+    int32_t mask1;                 // |mask1|, -1: no consensus
+    int32_t mask2;                 // |mask2|, -1: no consensus or the refit had no point
+    int32_t refit_stood;           // 1: R1 stands
+    int32_t flipped;               // bytes that differ between mask1 and the final mask
+};
+
+inline void trace_clear(RobustTrace* tr, int m) {
+    *tr = RobustTrace{0, m, 0, -1, -1, 0, 0, -1, -1, -1, 0, 0};
+}
+
+// One track, literally the definition above.  mask: n bytes, element-aligned.  `counts` (may be null) is added to.  `trace` (may be
+// null) is filled; nothing the function computes depends on it.
 template <class A>
 inline void robust_track(const A& a, int n, bool consistent, long long track, const msfm_emat::Camera& cam, const RobustParams& prm,
-                         msfm_point3d* rec, double* residuals, uint8_t* mask, RobustCounts* counts) {
+                         msfm_point3d* rec, double* residuals, uint8_t* mask, RobustCounts* counts, RobustTrace* trace = nullptr) {
     const Params plain = {prm.max_error, prm.min_angle, prm.min_views, 0};
     triangulate_track(a, n, consistent, cam, plain, rec, residuals);
     HostObs o;
@@ -498,6 +520,7 @@ inline void robust_track(const A& a, int n, bool consistent, long long track, co
         o.p.push_back(p);
     }
     const int m = (int)o.elem.size();
+    if (trace) trace_clear(trace, m);
     if (!retry(*rec, m)) return;
     const int need = prm.min_views > 2 ? prm.min_views : 2;
     const double f = (cam.fx + cam.fy) / 2.0;
@@ -512,7 +535,8 @@ inline void robust_track(const A& a, int n, bool consistent, long long track, co
         dlt_clear(A4);
         dlt_add(A4, o.p[(size_t)j]->R, o.p[(size_t)j]->t, o.u[(size_t)j], o.w[(size_t)j]);
         dlt_add(A4, o.p[(size_t)i]->R, o.p[(size_t)i]->t, o.u[(size_t)i], o.w[(size_t)i]);
-        bool valid = dlt_solve(A4, X);
+        const bool point = dlt_solve(A4, X);
+        bool valid = point;
         int count = 0;
         for (int k = 0; k < m && valid; ++k) {
             const bool in = obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X, f, prm.max_error);
@@ -524,6 +548,20 @@ inline void robust_track(const A& a, int n, bool consistent, long long track, co
             count += in ? 1 : 0;
         }
         valid = valid && parallax(X, o.p[(size_t)i]->O, o.p[(size_t)j]->O) >= prm.min_angle;
+        if (trace) {
+            trace->valid += valid ? 1 : 0;
+            if (valid && count > best) trace->winner = h;
+            bool di, dj;
+            (void)obs_error(o.p[(size_t)i]->R, o.p[(size_t)i]->t, o.u[(size_t)i], o.w[(size_t)i], X, f, &di);
+            (void)obs_error(o.p[(size_t)j]->R, o.p[(size_t)j]->t, o.u[(size_t)j], o.w[(size_t)j], X, f, &dj);
+            if (point && !(di && dj) && parallax(X, o.p[(size_t)i]->O, o.p[(size_t)j]->O) >= prm.min_angle) {
+                int full = 0;
+                for (int k = 0; k < m; ++k)
+                    full += obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X, f, prm.max_error) ? 1 : 0;
+                trace->depth_rejected += 1;
+                if (full > trace->depth_rejected_best) trace->depth_rejected_best = full;
+            }
+        }
         if (valid && count > best) {
             best = count;
             Xb[0] = X[0];
@@ -535,6 +573,11 @@ inline void robust_track(const A& a, int n, bool consistent, long long track, co
         counts->retried += 1;
         counts->hypotheses += H;
     }
+    if (trace) {
+        trace->retried = 1;
+        trace->hypotheses = H;
+        trace->best = best;
+    }
     if (best < need) {
         robust_failed(n, rec, residuals, mask);
         return;
@@ -545,12 +588,19 @@ inline void robust_track(const A& a, int n, bool consistent, long long track, co
         mask[o.elem[(size_t)k]] = in ? 1 : 0;
         n1 += in ? 1 : 0;
     }
+    std::vector<uint8_t> first;
+    if (trace) {
+        trace->mask1 = n1;
+        first.assign(mask, mask + n);
+    }
     double X1[3];
     const Masked<A> masked{a, mask};
     if (dlt_point(masked, n, cam, X1)) {
         int n2 = 0;
         for (int k = 0; k < m; ++k) n2 += obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X1, f, prm.max_error) ? 1 : 0;
+        if (trace) trace->mask2 = n2;
         if (n2 >= (n1 > need ? n1 : need)) {
+            if (trace) trace->refit_stood = 1;
             for (int k = 0; k < m; ++k)
                 mask[o.elem[(size_t)k]] = obs_inlier(o.p[(size_t)k]->R, o.p[(size_t)k]->t, o.u[(size_t)k], o.w[(size_t)k], X1, f, prm.max_error) ? 1 : 0;
             n1 = n2;
@@ -559,6 +609,8 @@ inline void robust_track(const A& a, int n, bool consistent, long long track, co
             Xb[2] = X1[2];
         }
     }
+    if (trace)
+        for (int k = 0; k < n; ++k) trace->flipped += first[(size_t)k] != mask[k] ? 1 : 0;
     evaluate_point(a, n, Xb, mask, cam, prm.min_angle, rec, residuals);
     if (counts) {
         counts->rescued += (rec->status & MSFM_TRI_ANGLE_OK) ? 1 : 0;
@@ -569,11 +621,12 @@ inline void robust_track(const A& a, int n, bool consistent, long long track, co
 inline void TriangulateTracksRobust(const int64_t* offsets, const int32_t* image_ids, const int32_t* point_idx, const uint8_t* consistent,
                                     int64_t first_track, int64_t n_tracks, const int* rank_of_id, const float* const* kxy,
                                     const Pose* poses, const msfm_emat::Camera& cam, const RobustParams& prm, msfm_point3d* out_points,
-                                    double* out_residuals, uint8_t* out_mask, RobustCounts* counts) {
+                                    double* out_residuals, uint8_t* out_mask, RobustCounts* counts, RobustTrace* out_trace = nullptr) {
     for (int64_t t = first_track; t < first_track + n_tracks; ++t) {
         const int64_t b = offsets[t], e = offsets[t + 1];
         const HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
-        robust_track(a, (int)(e - b), consistent[t] != 0, (long long)t, cam, prm, out_points + t, out_residuals + b, out_mask + b, counts);
+        robust_track(a, (int)(e - b), consistent[t] != 0, (long long)t, cam, prm, out_points + t, out_residuals + b, out_mask + b, counts,
+                     out_trace ? out_trace + t : nullptr);
     }
 }
 #endif

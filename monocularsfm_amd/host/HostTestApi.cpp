@@ -624,6 +624,7 @@ int host_triangulate_tracks(const long long* offsets, const int* image_ids, cons
     const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
     const msfm_tri::Params prm = {max_error, min_angle, min_views, 0};
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are int64");
+    static_assert(sizeof(msfm_tri::RobustTrace) == 12 * sizeof(int), "the trace is twelve int32");
     msfm_tri::TriangulateTracks(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(),
                                 kxy, table.data(), c, prm, out_points, out_residuals);
     return 0;
@@ -631,11 +632,13 @@ int host_triangulate_tracks(const long long* offsets, const int* image_ids, cons
 
 // The robust twin (TriangulateTracksRobust): the same inputs, max_hypotheses, and the inlier byte per observation.  counts4 (may be
 // NULL): retried, rescued, observations_rejected, hypotheses of the tracks computed by this call are ADDED to it.
-int host_triangulate_tracks_robust(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
-                                   const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
-                                   int n_poses, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses,
-                                   long long first, long long count, msfm_point3d* out_points, double* out_residuals,
-                                   unsigned char* out_mask, long long* counts4) {
+// host_triangulate_tracks_robust_trace: the same, and out_trace (may be NULL) receives msfm_tri::RobustTrace (12 int32) per computed
+// track at the track's own position: the route it took.
+int host_triangulate_tracks_robust_trace(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                                         const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
+                                         int n_poses, const double* cam, double max_error, double min_angle, int min_views,
+                                         int max_hypotheses, long long first, long long count, msfm_point3d* out_points,
+                                         double* out_residuals, unsigned char* out_mask, long long* counts4, int* out_trace) {
     std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
     for (int k = 0; k < n_images; ++k) {
         if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
@@ -656,7 +659,8 @@ int host_triangulate_tracks_robust(const long long* offsets, const int* image_id
     const msfm_tri::RobustParams prm = {max_error, min_angle, min_views, max_hypotheses};
     msfm_tri::RobustCounts rc = {0, 0, 0, 0};
     msfm_tri::TriangulateTracksRobust(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count,
-                                      rank_of.data(), kxy, table.data(), c, prm, out_points, out_residuals, out_mask, &rc);
+                                      rank_of.data(), kxy, table.data(), c, prm, out_points, out_residuals, out_mask, &rc,
+                                      reinterpret_cast<msfm_tri::RobustTrace*>(out_trace));
     if (counts4) {
         counts4[0] += rc.retried;
         counts4[1] += rc.rescued;
@@ -664,6 +668,15 @@ int host_triangulate_tracks_robust(const long long* offsets, const int* image_id
         counts4[3] += rc.hypotheses;
     }
     return 0;
+}
+int host_triangulate_tracks_robust(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                                   const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
+                                   int n_poses, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses,
+                                   long long first, long long count, msfm_point3d* out_points, double* out_residuals,
+                                   unsigned char* out_mask, long long* counts4) {
+    return host_triangulate_tracks_robust_trace(offsets, image_ids, point_idx, consistent, ids, n_images, kxy, pose_ids, poses, n_poses, cam,
+                                                max_error, min_angle, min_views, max_hypotheses, first, count, out_points, out_residuals,
+                                                out_mask, counts4, nullptr);
 }
 void host_tri_sample2(long long track, int h, int m, int* idx2) { msfm_tri::sample2(msfm_tri::tri_seed(track), h, m, idx2); }
 

@@ -54,26 +54,36 @@ def svd_point(obs):
 
 
 def errors(X, obs, f):
-    """-> (errors float [m], depth > eps bool [m])"""
-    e, d = [], []
-    for u, v, P in obs:
-        Y = P[:, :3].astype(LD) @ np.asarray(X, np.float64).astype(LD) + P[:, 3].astype(LD)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            e.append(float(np.sqrt((Y[0] / Y[2] - u) ** 2 + (Y[1] / Y[2] - v) ** 2) * f))
-        d.append(bool(float(Y[2]) > ref.EPS))
-    return np.asarray(e), np.asarray(d)
+    """-> (errors float [m], depth > eps bool [m]); the views at once, every sum in long double and in the order of the definition"""
+    P = np.asarray([o[2] for o in obs], np.float64).astype(LD)
+    u, v = np.asarray([o[0] for o in obs], LD), np.asarray([o[1] for o in obs], LD)
+    Xl = np.asarray(X, np.float64).astype(LD)
+    Y = P[:, :, 0] * Xl[0] + P[:, :, 1] * Xl[1] + P[:, :, 2] * Xl[2] + P[:, :, 3]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        e = (np.sqrt((Y[:, 0] / Y[:, 2] - u) ** 2 + (Y[:, 1] / Y[:, 2] - v) ** 2) * f).astype(np.float64)
+    return e, Y[:, 2].astype(np.float64) > ref.EPS
 
 
-def track(img, idx, consistent, kps, poses, cam, track_no, max_error=2.0, min_angle=1.5, min_views=2, max_hypotheses=64):
+TRACE_KEYS = ("retried", "m", "hypotheses", "winner", "best", "valid", "depth_rejected", "depth_rejected_best", "mask1", "mask2",
+              "refit_stood", "flipped")
+
+
+def track(img, idx, consistent, kps, poses, cam, track_no, max_error=2.0, min_angle=1.5, min_views=2, max_hypotheses=64, depth_check=True):
     """One track -> triangulation_ref.track's dict plus mask (element-aligned uint8), retried, hypotheses (H), literal_tie (the two
-    best valid counts are equal), and the margins taken over EVERY error and angle a decision of the definition looked at."""
+    best valid counts are equal), the margins taken over EVERY error and angle a decision of the definition looked at, and trace: the
+    route the track took, from this function's own decisions (TRACE_KEYS, the fields of the twin's msfm_tri::RobustTrace).
+    depth_check=False leaves the depth test out of a hypothesis' validity (NOT the definition: the tests use it to show that a track's
+    answer hangs on that test)."""
     n = len(img)
     out = ref.track(img, idx, consistent, kps, poses, cam, max_error, min_angle, min_views)
     used = [k for k in range(n) if poses.get(int(img[k])) is not None]
     mask = np.zeros(n, np.uint8)
     if out["status"] & ref.ATTEMPTED:
         mask[used] = 1
-    out.update(mask=mask, retried=False, hypotheses=0, literal_tie=False)
+    m = len(used) if out["status"] & ref.ATTEMPTED else 0
+    tr = dict(retried=0, m=m, hypotheses=0, winner=-1, best=-1, valid=0, depth_rejected=0, depth_rejected_best=-1, mask1=-1, mask2=-1,
+              refit_stood=0, flipped=0)
+    out.update(mask=mask, retried=False, hypotheses=0, literal_tie=False, trace=tr)
     m = len(used)
     done = ref.POINT | ref.ERROR_OK
     if not out["status"] & ref.ATTEMPTED or (out["status"] & done) == done or m < 3:
@@ -90,7 +100,7 @@ def track(img, idx, consistent, kps, poses, cam, track_no, max_error=2.0, min_an
     em, am = [out["error_margin"]], [out["angle_margin"]]
     hyp = hypotheses(m, max_hypotheses, track_no)
     best, best_X, counts = -1, None, []
-    for i, j in hyp:
+    for h, (i, j) in enumerate(hyp):
         X = svd_point([obs[j], obs[i]])
         if X is None:
             continue
@@ -98,13 +108,19 @@ def track(img, idx, consistent, kps, poses, cam, track_no, max_error=2.0, min_an
         a = ref.angle(X, centres[i], centres[j])
         em.append(float(np.min(np.abs(e - max_error))))
         am.append(abs(a - min_angle))
-        if not (d[i] and d[j] and a >= min_angle):
-            continue
         c = int(np.sum(d & (e <= max_error)))
+        if a >= min_angle and not (d[i] and d[j]):
+            tr["depth_rejected"] += 1
+            tr["depth_rejected_best"] = max(tr["depth_rejected_best"], c)
+        if not (((d[i] and d[j]) or not depth_check) and a >= min_angle):
+            continue
+        tr["valid"] += 1
         counts.append(c)
         if c > best:
             best, best_X = c, X
+            tr["winner"] = h
     counts.sort()
+    tr.update(retried=1, hypotheses=len(hyp), best=best)
     out.update(retried=True, hypotheses=len(hyp), literal_tie=len(counts) >= 2 and counts[-1] == counts[-2])
     out.update(status=ref.ATTEMPTED | ROBUST, n_views=0, X=np.zeros(3), mean_residual=0.0, tri_angle=0.0, residuals=np.full(n, -1.0),
                mask=np.zeros(n, np.uint8), error_margin=min(em), angle_margin=min(am))
@@ -114,13 +130,17 @@ def track(img, idx, consistent, kps, poses, cam, track_no, max_error=2.0, min_an
     m1 = d & (e <= max_error)
     X = best_X
     inl = m1
+    tr["mask1"] = int(m1.sum())
     X1 = svd_point([o for o, keep in zip(obs, m1) if keep])
     if X1 is not None:
         e1, d1 = errors(X1, obs, f)
         em.append(float(np.min(np.abs(e1 - max_error))))
         m2 = d1 & (e1 <= max_error)
+        tr["mask2"] = int(m2.sum())
         if m2.sum() >= max(m1.sum(), need):
             X, inl = X1, m2
+            tr["refit_stood"] = 1
+    tr["flipped"] = int(np.sum(m1 != inl))
     e, d = errors(X, obs, f)
     status = ref.ATTEMPTED | ref.POINT | ref.ERROR_OK | ROBUST | (ref.DEPTH_OK if np.all(d[inl]) else 0)
     res = np.full(n, -1.0)
@@ -144,8 +164,8 @@ def track(img, idx, consistent, kps, poses, cam, track_no, max_error=2.0, min_an
     return out
 
 
-def run(tracks, kps, poses, cam, max_error=2.0, min_angle=1.5, min_views=2, max_hypotheses=64, select=None):
+def run(tracks, kps, poses, cam, max_error=2.0, min_angle=1.5, min_views=2, max_hypotheses=64, select=None, depth_check=True):
     offsets, img, idx, cons = tracks[:4]
     todo = range(len(offsets) - 1) if select is None else select
     return [track(img[offsets[t]:offsets[t + 1]], idx[offsets[t]:offsets[t + 1]], bool(cons[t]), kps, poses, cam, t, max_error, min_angle,
-                  min_views, max_hypotheses) for t in todo]
+                  min_views, max_hypotheses, depth_check) for t in todo]

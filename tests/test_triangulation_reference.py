@@ -48,7 +48,7 @@ def host():
 
 def capture(seed=77, noise_px=0.7, cam=CAM, n_images=24, n_desc=600, n_proto=1500):
     """fx.scene_job's capture with what it does not return: the prototype of every row, the cameras, the true points.  With a distorted
-    camera the keypoints are re-made through the Brown model.  -> dict"""
+    camera, or one whose focal lengths or centre are not CAM's, the keypoints are re-made through the Brown model.  -> dict"""
     from monocularsfm_amd import synth
     _, protos = synth.rootsift_images(n_images, n_desc, seed=seed, n_proto=n_proto, return_proto=True)
     cams = synth.scene_cameras(n_images, seed=seed)
@@ -56,13 +56,13 @@ def capture(seed=77, noise_px=0.7, cam=CAM, n_images=24, n_desc=600, n_proto=150
     ids = np.asarray([3 * i + 1 for i in range(n_images)], np.int32)
     rng = np.random.default_rng(seed)
     X = np.stack([rng.uniform(-1.6, 1.6, n_proto), rng.uniform(-1.1, 1.1, n_proto), rng.uniform(-1.0, 1.0, n_proto)], 1)
-    if any(cam[4:]):
+    if any(cam[4:]) or tuple(cam[:4]) != CAM:
         nrng = np.random.default_rng(seed + 9)
         for i, k in enumerate(kps):
             sel = np.nonzero(np.asarray(protos[i]) >= 0)[0]
             R, t = cams[i][0], cams[i][1]
             Y = X[np.asarray(protos[i])[sel]] @ R.T + t
-            xd, yd = emat_ref.distort(cam, Y[:, 0] / Y[:, 2], Y[:, 1] / Y[:, 2])
+            xd, yd = emat_ref.distort(tuple(cam) + (0.0,) * (8 - len(cam)), Y[:, 0] / Y[:, 2], Y[:, 1] / Y[:, 2])
             k[sel, 0] = (cam[0] * xd + cam[2] + nrng.normal(0, noise_px, len(sel))).astype(np.float32)
             k[sel, 1] = (cam[1] * yd + cam[3] + nrng.normal(0, noise_px, len(sel))).astype(np.float32)
     tracks, track_proto = ref.proto_tracks(ids, protos)
@@ -216,6 +216,176 @@ def test_edge_cases(host):
     within(worst(w, (p, r)))
 
 
+def identical_tracks():
+    """Tracks whose cameras AND pixels are all the same (2, 3 and 5 views, two poses): every row of the DLT is one of two rows, the
+    normal matrix has rank 2 and the point is whatever the Jacobi sweep leaves in the null space.  As (poses per element, pixels
+    float32 [n, 2]) per track, the layout of tests/test_gpu_robust_triangulation.py's laid_out."""
+    c, s = np.cos(0.3), np.sin(0.3)
+    poses = [(np.eye(3), np.asarray([0.0, 0.0, 6.5])), (np.asarray([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]]), np.asarray([0.2, -0.1, 6.0]))]
+    return [([p] * m, np.tile(np.asarray([[1600.25, 1100.5]], np.float32), (m, 1))) for p in poses for m in (2, 3, 5)]
+
+
+def laid_job(laid):
+    """identical_tracks' layout -> (tracks, ids, kps, poses) for the twins: every element an image of its own, its keypoint row 0"""
+    n = [len(p) for p, _ in laid]
+    ids = np.arange(sum(n), dtype=np.int32) * 3 + 1
+    kps = {int(i): np.asarray([xy], np.float32) for i, xy in zip(ids, np.concatenate([xy for _, xy in laid]))}
+    poses = {int(i): p for i, p in zip(ids, [p for ps, _ in laid for p in ps]) if p is not None}
+    tracks = (np.concatenate([[0], np.cumsum(n)]).astype(np.int64), ids.copy(), np.zeros(len(ids), np.int32), np.ones(len(n), np.uint8))
+    return tracks, ids, kps, poses
+
+
+def test_identical_cameras_and_pixels(host):
+    """What the definition fixes on a rank-2 normal matrix: ATTEMPTED, no ANGLE_OK (the centres coincide), and either no POINT or a
+    finite X -- in the plain twin and in the robust one (which retries the tracks of three and five views that have no ERROR_OK)."""
+    import robust_triangulation_twin as rtw
+    tracks, ids, kps, poses = laid_job(identical_tracks())
+    pts, res = tw.run(host, tracks, ids, kps, poses, CAM)
+    rp = rtw.run(rtw.load_host(), tracks, ids, kps, poses, CAM)[0]
+    for p in list(pts) + list(rp):
+        s = int(p["status"])
+        assert s & ref.ATTEMPTED and not s & ref.ANGLE_OK and (not s & ref.POINT or np.all(np.isfinite(p["X"])))
+    print("identical cameras and pixels: status %s (plain), %s (robust)" % (pts["status"].tolist(), rp["status"].tolist()))
+
+
+# ---- the plain DLT where the conditioning is bad: against mpmath at 50 digits (triangulation_ref.mp_point) --------------------------------
+# Worst |X_twin - X_mp| measured on the CPU over the 1439 tracks of the seed-5 capture (0.3 px), python tests/test_triangulation_reference.py
+# prints them; the bounds are 16 x the measured values.  (For orientation only: twin - float64 SVD reference is 6.2e-11, 6.9e-8 and 9.9e-4
+# at the three shifts, and at 1e6 the SVD reference is the side that drifts.)
+#     scene shifted by (mag, -0.7 mag, 0.4 mag)   mag 1e2: 4.7e-11    1e4: 7.6e-9    1e6: 2.9e-7   (the float64 SVD reference: 1.6e-11, 7.0e-8, 9.9e-4)
+#     world scaled                                   1e-3: 1.4e-16     1e6: 3.5e-7 (of |X| ~ 6e6)     (the float64 SVD reference: 9.0e-15, 1.2e-3)
+MP_BOUNDS = {"shift 1e2": 7.5e-10, "shift 1e4": 1.2e-7, "shift 1e6": 4.6e-6, "scale 1e-3": 2.3e-15, "scale 1e6": 5.6e-6}
+
+
+def shifted(poses, mag):
+    """the scene moved by s = (mag, -0.7 mag, 0.4 mag): X' = X + s, t' = t - R s"""
+    s = np.asarray([mag, -0.7 * mag, 0.4 * mag])
+    return {i: (R, t - R @ s) for i, (R, t) in poses.items()}
+
+
+def scaled(poses, k):
+    """the world scaled by k: X' = k X, t' = k t"""
+    return {i: (R, k * t) for i, (R, t) in poses.items()}
+
+
+MP_CASES = [("shift 1e2", shifted, 1e2), ("shift 1e4", shifted, 1e4), ("shift 1e6", shifted, 1e6), ("scale 1e-3", scaled, 1e-3), ("scale 1e6", scaled, 1e6)]
+_MP = {}
+
+
+def mp_case(host, name):
+    """the twin, the float64 reference and mp_point on the seed-5 capture under one of MP_CASES -> (twin points, reference list, X_mp)"""
+    if name not in _MP:
+        from concurrent.futures import ProcessPoolExecutor
+        import multiprocessing
+        _, fn, mag = [m for m in MP_CASES if m[0] == name][0]
+        c = capture(5, noise_px=0.3)
+        poses = fn(c["poses"], mag)
+        pts, _ = tw.run(host, c["tracks"], c["ids"], c["kps"], poses, c["cam"])
+        want = ref.run(c["tracks"], c["kps"], poses, c["cam"])
+        o, img, idx, _ = c["tracks"]
+        jobs = [[ref.observation(c["cam"], c["kps"][int(img[e])][int(idx[e]), :2]) + (np.c_[poses[int(img[e])][0], poses[int(img[e])][1]],)
+                 for e in range(int(o[t]), int(o[t + 1]))] for t in range(len(o) - 1)]
+        step = 48
+        with ProcessPoolExecutor(max_workers=min(16, os.cpu_count() or 1), mp_context=multiprocessing.get_context("fork")) as pool:
+            X = np.concatenate(list(pool.map(ref.mp_points, [jobs[a:a + step] for a in range(0, len(jobs), step)])))
+        _MP[name] = (pts, want, X)
+    return _MP[name]
+
+
+@pytest.mark.parametrize("name", [m[0] for m in MP_CASES])
+def test_shifted_and_scaled_scene_against_mpmath(host, name):
+    """Status and n_views equal the reference's on EVERY track; the twin's point within the bound of the 50-digit solution of the same
+    stacked rows on every track."""
+    pts, want, X = mp_case(host, name)
+    for t, r in enumerate(want):
+        assert int(pts[t]["status"]) == r["status"] and int(pts[t]["n_views"]) == r["n_views"], (t, int(pts[t]["status"]), r["status"])
+    assert np.all(pts["status"] & ref.POINT) and np.all(np.isfinite(X))
+    d = float(np.abs(pts["X"] - X).max())
+    print("%s: worst |X_twin - X_mp| %.3g, worst |X_ref - X_mp| %.3g" % (name, d, float(np.abs(np.asarray([r["X"] for r in want]) - X).max())))
+    assert d <= MP_BOUNDS[name], (d, MP_BOUNDS[name])
+
+
+def parallax_tracks(thetas, depth=6.5):
+    """Two views per track whose rays meet exactly: camera 1 at the origin looks along z, camera 2 is camera 1 turned by theta degrees
+    about y around the point (0, 0, depth); both observe the point at the principal point (an exact fp32 pixel), so the angle between
+    the rays is theta whatever the pixels' rounding.  -> laid_job's layout"""
+    out = []
+    xy = np.asarray([[CAM[2], CAM[3]]] * 2, np.float32)
+    for th in thetas:
+        a = np.deg2rad(th)
+        R = np.asarray([[np.cos(a), 0.0, -np.sin(a)], [0.0, 1.0, 0.0], [np.sin(a), 0.0, np.cos(a)]])
+        X = np.asarray([0.0, 0.0, depth])
+        out.append(([(np.eye(3), np.zeros(3)), (R, np.asarray([0.0, 0.0, depth]) - R @ X)], xy))
+    return out
+
+
+def small_parallax_tracks():
+    """two and three views with unit baselines, depth 1e1 .. 1e5, noise-free fp32 pixels"""
+    out, depths = [], []
+    O = [np.zeros(3), np.asarray([1.0, 0.0, 0.0]), np.asarray([0.0, 1.0, 0.0])]
+    for z in (1e1, 1e2, 1e3, 1e4, 1e5):
+        X = np.asarray([0.3, 0.2, z])
+        for n in (2, 3):
+            xy = np.asarray([[CAM[0] * (X - o)[0] / z + CAM[2], CAM[1] * (X - o)[1] / z + CAM[3]] for o in O[:n]], np.float32)
+            out.append(([(np.eye(3), -o) for o in O[:n]], xy))
+            depths.append(z)
+    return out, depths
+
+
+# Measured on the CPU (test_small_parallax_against_mpmath prints them):
+#     depth 1e1 .. 1e5 over unit baselines: relative depth error against mp_point at most 5.8e-16 -> the bound 16 x that
+#     tri_angle - the law of cosines in mpmath at the twin's point = tri_angle - the true angle (atan2) in every case: the law of cosines
+#     itself is exact to 50 digits there, the loss is the twin's fp64 evaluation of it (the cancellation r1^2 + r2^2 - b^2 under acos):
+#     3.6e-15 degrees at 5.7 degrees, 1.2e-13 at 0.57, 2.5e-13 at 0.057, 6.8e-12 at 5.7e-3, 8.9e-10 at 5.7e-4 degrees of parallax
+#     at min_angle = 1.5 degrees: |tri_angle - true angle| at most 5.2e-13 degrees over the 240 tracks
+ANGLE_ERR = 5.2e-13
+DEPTH_REL = 16 * 5.8e-16
+
+
+def laid_obs(laid):
+    return [[ref.observation(CAM, xy[k]) + (np.c_[ps[k][0], ps[k][1]],) for k in range(len(ps))] for ps, xy in laid]
+
+
+def test_small_parallax_against_mpmath(host):
+    """Depth 1e1 .. 1e5 over unit baselines (parallax 5.7 degrees .. 5.7e-4 degrees), min_angle = 0: the twin's depth against mp_point's
+    within 16 x the measured relative error; tri_angle against the mpmath evaluation of the SAME law of cosines at the twin's point
+    (what the arithmetic loses) and against the true angle by atan2 of cross and dot products (what the definition loses): recorded.
+    Then the verdict: 240 two-view tracks whose true angle lies within 1e-6 degrees of min_angle = 1.5 and farther than 16 x the
+    measured angle error from it -- ANGLE_OK equals the mpmath verdict on every one."""
+    laid, depths = small_parallax_tracks()
+    tracks, ids, kps, poses = laid_job(laid)
+    pts, _ = tw.run(host, tracks, ids, kps, poses, CAM, (2.0, 0.0, 2))
+    Xm = ref.mp_points(laid_obs(laid))
+    for t, (ps, _) in enumerate(laid):
+        assert int(pts[t]["status"]) & ref.SUCCESS == ref.SUCCESS
+        rel = abs(float(pts[t]["X"][2]) - Xm[t][2]) / Xm[t][2]
+        cen = [-(R.T @ tt) for R, tt in ps]
+        law = float(ref.mp_angle(pts[t]["X"], cen[1], cen[0], True))
+        true = float(ref.mp_angle(pts[t]["X"], cen[1], cen[0], False))
+        got = float(pts[t]["tri_angle"])
+        print("depth %.0e, %d views: relative depth error %.3g, tri_angle %.6g, - law of cosines in mpmath %.3g, - true angle %.3g" % (
+            depths[t], len(ps), rel, got, abs(got - law), abs(got - true)))
+        assert rel <= DEPTH_REL, rel
+    rng = np.random.default_rng(11)
+    d = rng.uniform(16 * ANGLE_ERR, 1e-6, 240) * np.where(np.arange(240) % 2, 1.0, -1.0)
+    assert len(d) >= 200 and np.all(np.abs(d) > 16 * ANGLE_ERR) and np.all(np.abs(d) <= 1e-6)
+    laid = parallax_tracks(1.5 + d)
+    tracks, ids, kps, poses = laid_job(laid)
+    pts, _ = tw.run(host, tracks, ids, kps, poses, CAM)
+    Xm = ref.mp_points(laid_obs(laid))
+    worst_err, verdicts = 0.0, [0, 0]
+    for t, (ps, _) in enumerate(laid):
+        cen = [-(R.T @ tt) for R, tt in ps]
+        true = ref.mp_angle(Xm[t], cen[1], cen[0], False)
+        assert abs(float(true) - 1.5) <= 1e-6 + 1e-9 and abs(float(true - 1.5)) > 16 * ANGLE_ERR, (t, float(true - 1.5))
+        worst_err = max(worst_err, abs(float(pts[t]["tri_angle"] - true)))
+        ok = bool(true >= 1.5)
+        verdicts[ok] += 1
+        assert bool(int(pts[t]["status"]) & ref.ANGLE_OK) == ok, (t, float(true - 1.5), float(pts[t]["tri_angle"]) - 1.5)
+    print("at min_angle: worst |tri_angle - true angle| %.3g degrees over %d tracks, verdicts %s" % (worst_err, len(laid), verdicts))
+    assert min(verdicts) >= 100
+
+
 def test_mean_residual_is_the_sum_in_observation_order(host):
     c = capture(77)
     pts, res = tw.run(host, c["tracks"], c["ids"], c["kps"], c["poses"], c["cam"])
@@ -264,3 +434,8 @@ if __name__ == "__main__":   # the figures of the module docstring
               "margins", min(r["error_margin"] for r in want), min(r["angle_margin"] for r in want),
               "truth", max(float(np.linalg.norm(r["X"] - x)) for r, x in zip(want, c["X"])),
               "succeeded", sum((r["status"] & ref.SUCCESS) == ref.SUCCESS for r in want), "of", len(want))
+    for name, _, _ in MP_CASES:   # against mpmath: the figures next to MP_BOUNDS
+        pts, want, X = mp_case(h, name)
+        print(name, "worst |X_twin - X_mp|", float(np.abs(pts["X"] - X).max()), "worst |X_ref - X_mp|",
+              float(np.abs(np.asarray([r["X"] for r in want]) - X).max()))
+    test_small_parallax_against_mpmath(h)

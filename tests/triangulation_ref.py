@@ -37,6 +37,51 @@ def angle(X, Oi, Oj):
     return float(min(a, LD(np.pi) - a) * 180 / LD(np.pi))
 
 
+def mp_point(obs, dps=50):
+    """The same algebraic problem as track()'s point -- the stacked rows u P[2] - P[0], v P[2] - P[1] (u, v rounded to fp64 as
+    there), the right singular vector of the smallest singular value -- solved with mpmath at `dps` digits.  obs: [(u, v, P [3, 4])].
+    -> X as three mpmath numbers, or None (h[3] == 0)"""
+    import mpmath as mp
+    with mp.workdps(dps):
+        rows = []
+        for u, v, P in obs:
+            P = [[mp.mpf(float(x)) for x in row] for row in np.asarray(P, np.float64)]
+            rows.append([mp.mpf(float(u)) * P[2][k] - P[0][k] for k in range(4)])
+            rows.append([mp.mpf(float(v)) * P[2][k] - P[1][k] for k in range(4)])
+        _, S, V = mp.svd_r(mp.matrix(rows))
+        k = min(range(4), key=lambda i: S[i])
+        if V[k, 3] == 0:
+            return None
+        return [V[k, j] / V[k, 3] for j in range(3)]
+
+
+def mp_points(jobs):
+    """mp_point over a list of observation lists, as float64 [n, 3] (NaN where there is no point): the unit of work of a process pool"""
+    out = np.full((len(jobs), 3), np.nan)
+    for n, obs in enumerate(jobs):
+        X = mp_point(obs)
+        if X is not None:
+            out[n] = [float(x) for x in X]
+    return out
+
+
+def mp_angle(X, Oi, Oj, law_of_cosines, dps=50):
+    """the parallax angle at X between the centres, degrees, with mpmath: by the definition's law of cosines, or (the true angle) by
+    atan2 of the cross and dot products of the two rays"""
+    import mpmath as mp
+    with mp.workdps(dps):
+        X, Oi, Oj = ([mp.mpf(x) for x in a] for a in (X, Oi, Oj))
+        a, b = [x - o for x, o in zip(X, Oi)], [x - o for x, o in zip(X, Oj)]
+        if law_of_cosines:
+            base2 = sum((p - q) ** 2 for p, q in zip(Oi, Oj))
+            r1, r2 = mp.sqrt(sum(x * x for x in a)), mp.sqrt(sum(x * x for x in b))
+            ang = abs(mp.acos((r1 * r1 + r2 * r2 - base2) / (2 * r1 * r2)))
+        else:
+            cr = [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+            ang = mp.atan2(mp.sqrt(sum(x * x for x in cr)), sum(p * q for p, q in zip(a, b)))
+        return min(ang, mp.pi - ang) * 180 / mp.pi
+
+
 def track(img, idx, consistent, kps, poses, cam, max_error=2.0, min_angle=1.5, min_views=2):
     """One track (image ids, keypoint indices in element order) -> dict(status, n_views, X, mean_residual, tri_angle, residuals
     (element-aligned, -1 where none), error_margin = min |err - max_error|, angle_margin = min |a - min_angle| over the scanned pairs)."""
