@@ -635,6 +635,55 @@ int msfm_triangulate_tracks_robust(msfm_ctx* ctx, const msfm_camera* camera, con
                                    msfm_robust_stats* robust_stats);
 int msfm_fetch_point_inliers(msfm_ctx* ctx, uint8_t* out);
 
+/* ---- point refinement: per-track Levenberg-Marquardt on the reprojection error (opt-in) ---------------
+ * The triangulation calls return the DLT point, which minimises an algebraic error.  msfm_refine_points moves every point of the
+ * session's last successful triangulation to the minimum of its reprojection error under the FIXED poses of that call: one 3 x 3
+ * system per point, nothing shared between tracks, no pose is ever changed.  The arithmetic is csrc/msfm_refine.h, bit-identical to
+ * the host twin RefinePoints.
+ *   inputs       none besides the context: the session keeps a host copy of the camera, the thresholds and the (image id, pose) list
+ *                of the last successful msfm_triangulate_tracks / _robust; the call rebuilds its device tables from them (keypoint
+ *                pointers are looked up fresh) and frees them when it returns.
+ *   eligible     a track whose record has ATTEMPTED | POINT.  Its fitting set: its used observations -- after the robust call those
+ *                whose inlier byte is 1.
+ *   cost         the sum over the fitting set of |proj(R X + t) - (u, v)|^2 f^2, (u, v) and f as msfm_triangulate_tracks defines them.
+ *   LM           H = sum J^T J, g = sum J^T r in observation order; (H + lambda diag H) delta = -g by a 3 x 3 Cholesky (a pivot that
+ *                is not > 0 or a non-finite delta is a rejected step); a step is accepted iff its cost is finite, strictly lower and
+ *                every fitting view keeps depth > DBL_EPSILON; accept: lambda / 10 (floor 1e-12), reject: 10 lambda; lambda starts
+ *                at 1e-3.  A track stops after max_iters evaluated steps, after an accepted step with
+ *                |delta|^2 <= step_tol^2 (|X|^2 + step_tol), or when a rejected step raises lambda past 1e4.
+ *   verdict      recomputed at the refined point with the triangulation's code and thresholds: an error for EVERY used observation;
+ *                mean_residual, the parallax scan, ERROR_OK and DEPTH_OK over the fitting set.  The refined point STANDS iff a step
+ *                was accepted (its cost is strictly lower) and none of ERROR_OK, ANGLE_OK, DEPTH_OK that the record had is cleared.
+ *                Then the record gets the new X, errors, mean_residual, tri_angle and bits plus MSFM_TRI_REFINED (ROBUST is kept).
+ *                Otherwise the record and its residuals stay bit for bit what they were, an earlier REFINED bit included.
+ * n_views, the inlier bytes, the tracks and the match lists never change; the succeeded set can only grow; max_iters = 0 changes
+ * nothing.  The call may be repeated: it refines from the current records.  It invalidates registrations like a triangulation call
+ * (msfm_fetch_registrations returns MSFM_E_STATE until msfm_register_images has run again); points and inlier bytes stay valid.
+ * params NULL = {1e-10, 10}.  Errors: MSFM_E_STATE -- no track session, no successful msfm_triangulate_tracks / _robust since the last
+ * msfm_tracks_finish, a streaming series open.  MSFM_E_INVALID -- max_iters outside 0 .. 100, a non-finite or negative step_tol.
+ * MSFM_E_NOIMAGE -- a posed image whose keypoints have been replaced by fewer than its rows.
+ * cost_before / cost_after: the eligible tracks' costs at the records' points before and after the call, information only (each
+ * wave's tracks are summed in a fixed order, the waves' sums in wave order on the host: reproducible on one device, not bit-equal to
+ * the twin's sum in track order). */
+enum { MSFM_TRI_REFINED = 64 };
+typedef struct msfm_refine_params {   /* 16 bytes, no implicit padding */
+    double step_tol;
+    int32_t max_iters;               /* 0 .. 100 evaluated steps per track */
+    int32_t reserved;
+} msfm_refine_params;
+typedef struct msfm_refine_stats {   /* 72 bytes, no implicit padding */
+    int64_t eligible;                /* tracks with ATTEMPTED | POINT */
+    int64_t refined;                 /* ... whose refined point stands */
+    int64_t gained_error_ok;         /* ... of which gain ERROR_OK */
+    int64_t rejected_by_verdict;     /* tracks with an accepted step whose refined point would clear a status bit */
+    int64_t iterations;              /* evaluated steps, summed */
+    double cost_before;
+    double cost_after;
+    double refine_ms;                /* HIP events around all launches of the call */
+    double prepare_ms;               /* ... of which the pose table and the per-observation array */
+} msfm_refine_stats;
+int msfm_refine_points(msfm_ctx* ctx, const msfm_refine_params* params, msfm_refine_stats* stats);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

@@ -33,7 +33,7 @@ EXPORTS = [
     "msfm_tracks_begin", "msfm_tracks_add", "msfm_tracks_export_forest", "msfm_tracks_import_forest", "msfm_tracks_finish",
     "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
     "msfm_triangulate_tracks", "msfm_fetch_points3d", "msfm_register_images", "msfm_fetch_registrations",
-    "msfm_triangulate_tracks_robust", "msfm_fetch_point_inliers",
+    "msfm_triangulate_tracks_robust", "msfm_fetch_point_inliers", "msfm_refine_points",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -90,6 +90,25 @@ class RobustTriangulationParams(C.Structure):
 class RobustStats(C.Structure):
     """msfm_robust_stats (include/msfm_match.h)."""
     _fields_ = [(k, C.c_int64) for k in ("retried", "rescued", "observations_rejected", "hypotheses")] + [("robust_ms", C.c_double)]
+
+
+# point refinement (include/msfm_match.h): the record's extra status bit, the 16-byte parameters, the 72-byte stats
+TRI_REFINED = 64
+
+
+class RefineParams(C.Structure):
+    _fields_ = [("step_tol", C.c_double), ("max_iters", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RefineStats(C.Structure):
+    """msfm_refine_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("eligible", "refined", "gained_error_ok", "rejected_by_verdict", "iterations")] + \
+               [(k, C.c_double) for k in ("cost_before", "cost_after", "refine_ms", "prepare_ms")]
+
+
+def refined(points):
+    """The records of a POINT3D array whose point is a refined one (MSFM_TRI_REFINED)."""
+    return (np.asarray(points)["status"] & TRI_REFINED) != 0
 
 
 def succeeded(points):
@@ -291,6 +310,7 @@ def load():
     L.msfm_triangulate_tracks_robust.argtypes = [vp, C.POINTER(Camera), ip, C.c_void_p, C.c_int, C.POINTER(RobustTriangulationParams),
                                                  C.POINTER(TriangulationStats), C.POINTER(RobustStats)]
     L.msfm_fetch_point_inliers.argtypes = [vp, C.c_void_p]
+    L.msfm_refine_points.argtypes = [vp, C.POINTER(RefineParams), C.POINTER(RefineStats)]
     L.msfm_register_images.argtypes = [vp, C.POINTER(Camera), ip, C.c_int, C.POINTER(RegisterParams), C.POINTER(RegisterStats)]
     L.msfm_fetch_registrations.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
@@ -750,6 +770,16 @@ class Context:
         out = np.zeros(max(O, 1), np.uint8)
         self._chk(self._L.msfm_fetch_point_inliers(self._h, out.ctypes.data))
         return out[:O]
+
+    def refine_points(self, max_iters=10, step_tol=1e-10):
+        """Moves every point of the last triangulate_tracks to the minimum of its reprojection error under that call's poses (per-track
+        Levenberg-Marquardt, msfm_refine_points); a refined point replaces its record only where it costs strictly less and clears no
+        status bit.  -> stats dict.  points3d() and point_inliers() work after it unchanged; refined(points) is the mask of the
+        records it rewrote.  Registrations are invalidated as by triangulate_tracks."""
+        prm = RefineParams(float(step_tol), int(max_iters), 0)
+        st = RefineStats()
+        self._chk(self._L.msfm_refine_points(self._h, C.byref(prm), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in RefineStats._fields_}
 
     def points3d(self):
         """-> (points: POINT3D array, one per kept track; residuals: float64, one per kept observation in the tracks' order, -1.0 where

@@ -651,6 +651,12 @@ struct TrackSession {
     // robust call's (msfm_tracks_finish and msfm_triangulate_tracks clear it)
     DevBuf t_mask;
     bool mask_valid = false;
+    // point refinement (msfm_refine.hip.h): the host copy of the inputs of the triangulation call that made the current points (read
+    // only while tri_valid)
+    msfm_camera tri_camera = {};
+    msfm_triangulation_params tri_prm = {};
+    std::vector<int32_t> tri_ids;
+    std::vector<msfm_pose_rt> tri_poses;
     // image registration (msfm_register.hip.h): a record per listed image, the CSR of (track number, inlier flag, residual) per
     // correspondence; reg_valid: they belong to the current points (msfm_tracks_finish and msfm_triangulate_tracks clear it)
     DevBuf g_records, g_offsets, g_tid, g_inl, g_res;
@@ -675,6 +681,8 @@ struct TrackSession {
         ev_pending.clear();
         ev_free.clear();
         rank_of.clear();
+        tri_ids.clear();
+        tri_poses.clear();
         nd = MsfmTrackNodes{};
         stats = msfm_track_stats{};
         open = closed = finished = suppress = add_only = tri_valid = mask_valid = reg_valid = false;

@@ -44,6 +44,7 @@ using namespace msfm;
 #include "msfm_tracks.hip.h"
 #include "msfm_triangulate.hip.h"
 #include "msfm_triangulate_robust.hip.h"
+#include "msfm_refine.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -880,6 +881,15 @@ int msfm_fetch_point_inliers(msfm_ctx* ctx, uint8_t* out) {
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return fetch_point_inliers_impl(ctx, out);
+    MSFM_API_END
+}
+
+// ---- point refinement (msfm_refine.hip.h) ---------------------------------------------------------------------------------------------
+
+int msfm_refine_points(msfm_ctx* ctx, const msfm_refine_params* params, msfm_refine_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return refine_impl(ctx, params, stats);
     MSFM_API_END
 }
 

@@ -135,6 +135,15 @@ int tri_prepare(msfm_ctx* ctx, const std::string& who, const msfm_camera* camera
     return MSFM_OK;
 }
 
+// what a successful msfm_triangulate_tracks / _robust leaves behind for msfm_refine_points (msfm_refine.hip.h): a host copy of its inputs
+void tri_keep_inputs(TrackSession& ts, const msfm_camera& camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
+                     const msfm_tri::Params& prm) {
+    ts.tri_camera = camera;
+    ts.tri_prm = msfm_triangulation_params{prm.max_error, prm.min_angle, prm.min_views, 0};
+    ts.tri_ids.assign(image_ids, image_ids + (n_poses > 0 ? n_poses : 0));
+    ts.tri_poses.assign(poses, poses + (n_poses > 0 ? n_poses : 0));
+}
+
 int triangulate_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
                      const msfm_triangulation_params* params, msfm_triangulation_stats* stats) {
     TrackSession& ts = ctx->tracks;
@@ -200,6 +209,7 @@ int triangulate_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* im
     s.observations_used = (int64_t)hc.observations_used;
     s.device_bytes = (int64_t)(ts.t_points.cap + ts.t_resid.cap);
     s.triangulate_ms = ms;
+    tri_keep_inputs(ts, c, image_ids, poses, n_poses, prm);
     ts.tri_valid = true;
     if (stats) *stats = s;
     return MSFM_OK;

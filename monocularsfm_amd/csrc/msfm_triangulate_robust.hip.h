@@ -385,6 +385,7 @@ int triangulate_robust_impl(msfm_ctx* ctx, const msfm_camera* camera, const int3
     rs.observations_rejected = (int64_t)hc.observations_rejected;
     rs.hypotheses = (int64_t)hc.hypotheses;
     rs.robust_ms = all_ms;
+    tri_keep_inputs(ts, c, image_ids, poses, n_poses, prm);
     ts.tri_valid = true;
     ts.mask_valid = true;
     if (stats) *stats = s;

@@ -16,6 +16,7 @@
 #include "../csrc/msfm_pose.h"
 #include "../csrc/msfm_tracks.h"
 #include "../csrc/msfm_triangulate.h"
+#include "../csrc/msfm_refine.h"
 #include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
@@ -679,6 +680,54 @@ int host_triangulate_tracks_robust(const long long* offsets, const int* image_id
                                                 out_mask, counts4, nullptr);
 }
 void host_tri_sample2(long long track, int h, int m, int* idx2) { msfm_tri::sample2(msfm_tri::tri_seed(track), h, m, idx2); }
+
+// ---- point refinement: the host twin of the device kernels (csrc/msfm_refine.h, RefinePoints) ---------------------------------------
+// The inputs of host_triangulate_tracks[_robust] with the thresholds that call ran with (the verdict's), and its OUTPUTS: points and
+// residuals are read and rewritten in place, mask (may be NULL: the points are the plain call's) is read.  Tracks [first, first +
+// count) are refined.  counts5 (may be NULL): eligible, refined, gained_error_ok, rejected_by_verdict, iterations of those tracks are
+// ADDED to it; costs2 (may be NULL): their cost_before and cost_after, summed in track order, are ADDED to it.  out_trace (may be
+// NULL) receives msfm_ref::Trace (40 bytes) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3: max_iters
+// outside 0 .. 100 or a bad step_tol.
+int host_refine_points(const long long* offsets, const int* image_ids, const int* point_idx, const int* ids, int n_images,
+                       const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const double* cam,
+                       double max_error, double min_angle, double step_tol, int max_iters, long long first, long long count,
+                       msfm_point3d* points, double* residuals, const unsigned char* mask, long long* counts5, double* costs2,
+                       void* out_trace) {
+    static_assert(sizeof(msfm_ref::Trace) == 40 && sizeof(msfm_ref::Obs) == 24, "the trace is six int32 and two doubles");
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        rank_of[(size_t)ids[k]] = k;
+    }
+    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
+    }
+    if (max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol)) return 3;
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    msfm_ref::Counts rc = {0, 0, 0, 0, 0, 0.0, 0.0};
+    msfm_ref::RefinePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, first, count, rank_of.data(), kxy, table.data(),
+                           mask, c, msfm_ref::Verdict{max_error, min_angle}, msfm_ref::Params{step_tol, max_iters, 0}, points, residuals,
+                           &rc, static_cast<msfm_ref::Trace*>(out_trace));
+    if (counts5) {
+        counts5[0] += rc.eligible;
+        counts5[1] += rc.refined;
+        counts5[2] += rc.gained_error_ok;
+        counts5[3] += rc.rejected_by_verdict;
+        counts5[4] += rc.iterations;
+    }
+    if (costs2) {
+        costs2[0] += rc.cost_before;
+        costs2[1] += rc.cost_after;
+    }
+    return 0;
+}
 
 // pieces, for tests/test_triangulation_reference.py
 void host_tri_centre(const double* R, const double* t, double* O) { msfm_tri::centre(R, t, O); }
