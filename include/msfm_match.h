@@ -684,6 +684,84 @@ typedef struct msfm_refine_stats {   /* 72 bytes, no implicit padding */
 } msfm_refine_stats;
 int msfm_refine_points(msfm_ctx* ctx, const msfm_refine_params* params, msfm_refine_stats* stats);
 
+/* ---- pose refinement: per-image Levenberg-Marquardt on the reprojection error (opt-in) ---------------
+ * The other block of the alternation: msfm_refine_poses moves every posed image of the session's last successful triangulation to
+ * the minimum of the SAME pixel cost under FIXED points: one 6 x 6 system per image, nothing shared between images, no point's X is
+ * ever changed.  The arithmetic is csrc/msfm_refine_poses.h, bit-identical to the host twin RefinePoses.
+ *   inputs       none besides the context and the images to hold fixed: like msfm_refine_points the call works on what the last
+ *                successful msfm_triangulate_tracks / _robust left in the session (camera, thresholds, pose list, records, residuals,
+ *                inlier bytes), with the poses as earlier msfm_refine_poses calls left them.
+ *   fitting set  of a listed image with a valid pose that is not fixed: its observations (after the robust call those whose inlier
+ *                byte is 1) of tracks whose record has ATTEMPTED | POINT | ERROR_OK | ANGLE_OK, by ascending track number.
+ *   eligible     such an image with at least min_observations entries.
+ *   cost         the sum over the fitting set of |proj(R X + t) - (u, v)|^2 f^2: msfm_refine_points' cost.
+ *   LM           27 sums (J^T J, J^T r of the unknowns (a, dt):  R <- C(a) R,  t <- C(a) t + dt,  C Cayley's rotation), 64 partials by
+ *                list position modulo 64, then a butterfly;  (H + lambda diag H) delta = -g by a 6 x 6 Cholesky (a pivot that is not
+ *                > 0, a non-finite delta or pose is a rejected step); a step is accepted iff its cost is finite, strictly lower and
+ *                every fitting observation keeps depth > DBL_EPSILON; accept: lambda / 10 (floor 1e-12), reject: 10 lambda; lambda
+ *                starts at 1e-3.  An image stops after max_iters evaluated steps, after an accepted step with
+ *                |delta|^2 <= step_tol^2 (1 + |t|^2), or when a rejected step raises lambda past 1e4.
+ *   standing     the refined pose STANDS iff a step was accepted and it has at least as many fitting observations with positive depth
+ *                and err <= the triangulation's max_error as the old pose (the rule of MSFM_REG_REFINED).  It then replaces the
+ *                session's pose of that image; otherwise not one byte of that pose changes.
+ *   re-verdict   every track with ATTEMPTED | POINT and a used observation in an image whose pose changed is evaluated again at its
+ *                unchanged X under the new poses (camera centres included) with the triangulation's code and thresholds: an error for
+ *                every used observation, mean_residual, tri_angle, ERROR_OK, ANGLE_OK, DEPTH_OK over the fitting set, plus
+ *                MSFM_TRI_REPOSED.  ROBUST, REFINED, n_views, X and the inlier bytes are kept; the succeeded set may shrink or grow
+ *                (points_lost / points_gained).  Tracks that touch no changed image stay bit for bit.
+ * max_iters = 0 changes nothing.  The call may be repeated.  It invalidates registrations like msfm_refine_points; points and inlier
+ * bytes stay valid; a following msfm_refine_points / msfm_register_images sees the new poses and records.
+ * params NULL = {1e-6, 10, 15}.  Errors: MSFM_E_STATE -- as msfm_refine_points.  MSFM_E_INVALID -- max_iters outside 0 .. 100, a
+ * non-finite or negative step_tol, min_observations < 3, n_fixed < 0 or a NULL list with n_fixed > 0, a fixed id that is not declared
+ * in the session or given twice.  MSFM_E_NOIMAGE -- as msfm_refine_points.
+ * cost_before / cost_after: the records' costs added in list order (a record that was not attempted adds 0): bit-equal to the twin's.
+ * msfm_fetch_poses: the session's current pose list in the triangulation call's order; *n receives its length, NULL arrays return it
+ * alone.  Valid after any successful triangulation (it then returns the caller's poses bit for bit); MSFM_E_STATE otherwise.
+ * msfm_fetch_pose_refinements: one record per listed image in that order; MSFM_E_STATE unless msfm_refine_poses was the last
+ * successful call that rebuilt the session's pose tables (a triangulation or msfm_refine_points after it invalidates the records).
+ *   record       status MSFM_POSE_FIXED: the image is in the fixed list; _ATTEMPTED: eligible; _REFINED: its refined pose stands.
+ *                n_observations: the fitting set (0 for an image that is fixed or has no valid pose); iterations: evaluated steps;
+ *                stop: 0 not attempted, 1 step criterion, 2 max_iters, 3 lambda ceiling; inliers_before / _after: the standing
+ *                rule's counts; cost_before / cost_after: the cost at the old pose and at the pose that stands. */
+enum { MSFM_TRI_REPOSED = 128 };
+enum { MSFM_POSE_ATTEMPTED = 1, MSFM_POSE_REFINED = 2, MSFM_POSE_FIXED = 4 };
+typedef struct msfm_pose_refine_params {   /* 16 bytes, no implicit padding */
+    double step_tol;
+    int32_t max_iters;               /* 0 .. 100 evaluated steps per image */
+    int32_t min_observations;        /* >= 3 */
+} msfm_pose_refine_params;
+typedef struct msfm_pose_refine_stats {   /* 104 bytes, no implicit padding */
+    int64_t images;                  /* listed images */
+    int64_t eligible;
+    int64_t refined;                 /* ... whose refined pose stands */
+    int64_t rejected_by_inliers;     /* images with an accepted step whose refined pose would lose an inlier */
+    int64_t iterations;              /* evaluated steps, summed */
+    int64_t observations;            /* the fitting sets, summed */
+    int64_t points_reposed;          /* tracks that went through the re-verdict */
+    int64_t points_lost;             /* ... of which had POINT & ERROR_OK & ANGLE_OK and lost it */
+    int64_t points_gained;           /* ... of which gained it */
+    double cost_before;
+    double cost_after;
+    double refine_ms;                /* HIP events around all launches of the call */
+    double prepare_ms;               /* ... of which the pose table, the per-observation array and the image-major list */
+} msfm_pose_refine_stats;
+typedef struct msfm_pose_refinement {   /* 48 bytes, no implicit padding */
+    int32_t image_id;
+    int32_t status;
+    int32_t n_observations;
+    int32_t iterations;
+    int32_t stop;
+    int32_t inliers_before;
+    int32_t inliers_after;
+    int32_t reserved;
+    double cost_before;
+    double cost_after;
+} msfm_pose_refinement;
+int msfm_refine_poses(msfm_ctx* ctx, const msfm_pose_refine_params* params, const int32_t* fixed_image_ids, int n_fixed,
+                      msfm_pose_refine_stats* stats);
+int msfm_fetch_poses(msfm_ctx* ctx, int32_t* out_ids, msfm_pose_rt* out_poses, int* n);
+int msfm_fetch_pose_refinements(msfm_ctx* ctx, msfm_pose_refinement* out);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

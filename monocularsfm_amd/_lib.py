@@ -34,6 +34,7 @@ EXPORTS = [
     "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
     "msfm_triangulate_tracks", "msfm_fetch_points3d", "msfm_register_images", "msfm_fetch_registrations",
     "msfm_triangulate_tracks_robust", "msfm_fetch_point_inliers", "msfm_refine_points",
+    "msfm_refine_poses", "msfm_fetch_poses", "msfm_fetch_pose_refinements",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -109,6 +110,30 @@ class RefineStats(C.Structure):
 def refined(points):
     """The records of a POINT3D array whose point is a refined one (MSFM_TRI_REFINED)."""
     return (np.asarray(points)["status"] & TRI_REFINED) != 0
+
+
+# pose refinement (include/msfm_match.h): the record's extra status bit, the 16-byte parameters, the 104-byte stats, the 48-byte record
+TRI_REPOSED = 128
+POSE_ATTEMPTED, POSE_REFINED, POSE_FIXED = 1, 2, 4
+POSE_REFINEMENT = np.dtype([("image_id", "<i4"), ("status", "<i4"), ("n_observations", "<i4"), ("iterations", "<i4"), ("stop", "<i4"),
+                            ("inliers_before", "<i4"), ("inliers_after", "<i4"), ("reserved", "<i4"), ("cost_before", "<f8"),
+                            ("cost_after", "<f8")])
+
+
+class PoseRefineParams(C.Structure):
+    _fields_ = [("step_tol", C.c_double), ("max_iters", C.c_int32), ("min_observations", C.c_int32)]
+
+
+class PoseRefineStats(C.Structure):
+    """msfm_pose_refine_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("images", "eligible", "refined", "rejected_by_inliers", "iterations", "observations",
+                                         "points_reposed", "points_lost", "points_gained")] + \
+               [(k, C.c_double) for k in ("cost_before", "cost_after", "refine_ms", "prepare_ms")]
+
+
+def reposed(points):
+    """The records of a POINT3D array that a pose refinement evaluated again under changed poses (MSFM_TRI_REPOSED)."""
+    return (np.asarray(points)["status"] & TRI_REPOSED) != 0
 
 
 def succeeded(points):
@@ -311,6 +336,9 @@ def load():
                                                  C.POINTER(TriangulationStats), C.POINTER(RobustStats)]
     L.msfm_fetch_point_inliers.argtypes = [vp, C.c_void_p]
     L.msfm_refine_points.argtypes = [vp, C.POINTER(RefineParams), C.POINTER(RefineStats)]
+    L.msfm_refine_poses.argtypes = [vp, C.POINTER(PoseRefineParams), ip, C.c_int, C.POINTER(PoseRefineStats)]
+    L.msfm_fetch_poses.argtypes = [vp, ip, C.c_void_p, C.POINTER(C.c_int)]
+    L.msfm_fetch_pose_refinements.argtypes = [vp, C.c_void_p]
     L.msfm_register_images.argtypes = [vp, C.POINTER(Camera), ip, C.c_int, C.POINTER(RegisterParams), C.POINTER(RegisterStats)]
     L.msfm_fetch_registrations.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
@@ -780,6 +808,52 @@ class Context:
         st = RefineStats()
         self._chk(self._L.msfm_refine_points(self._h, C.byref(prm), C.byref(st)))
         return {k: getattr(st, k) for k, _ in RefineStats._fields_}
+
+    def refine_poses(self, max_iters=10, step_tol=1e-6, min_observations=15, fixed=()):
+        """Moves every posed image of the last triangulate_tracks to the minimum of its reprojection error under the current points
+        (per-image Levenberg-Marquardt, msfm_refine_poses); `fixed`: image ids whose pose is held.  A refined pose replaces the
+        session's only where it costs strictly less and loses no inlier; the records of the tracks it touches are evaluated again
+        (reposed(points)).  -> stats dict.  poses() returns the current poses, pose_refinements() the per-image records.
+        Registrations are invalidated as by refine_points."""
+        prm = PoseRefineParams(float(step_tol), int(max_iters), int(min_observations))
+        st = PoseRefineStats()
+        fx = np.ascontiguousarray(list(fixed), dtype=np.int32).reshape(-1)
+        self._chk(self._L.msfm_refine_poses(self._h, C.byref(prm), _ip(fx) if len(fx) else None, len(fx), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in PoseRefineStats._fields_}
+
+    def pose_list(self):
+        """-> (ids int32, POSE_RT array) of the session's current pose list, in the order of the triangulation call."""
+        n = C.c_int(0)
+        self._chk(self._L.msfm_fetch_poses(self._h, None, None, C.byref(n)))
+        ids, tab = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), POSE_RT)
+        self._chk(self._L.msfm_fetch_poses(self._h, _ip(ids), tab.ctypes.data, C.byref(n)))
+        return ids[:n.value], tab[:n.value]
+
+    def poses(self):
+        """-> {image id: (R, t)} of the session's valid poses: what triangulate_tracks was given, with every pose that a refine_poses
+        call has replaced since.  The form triangulate_tracks takes."""
+        ids, tab = self.pose_list()
+        return {int(i): (p["R"].reshape(3, 3).copy(), p["t"].copy()) for i, p in zip(ids, tab) if p["valid"]}
+
+    def pose_refinements(self):
+        """-> POSE_REFINEMENT array, one record per listed image, of the last refine_poses."""
+        n = C.c_int(0)
+        self._chk(self._L.msfm_fetch_poses(self._h, None, None, C.byref(n)))
+        rec = np.zeros(max(n.value, 1), POSE_REFINEMENT)
+        self._chk(self._L.msfm_fetch_pose_refinements(self._h, rec.ctypes.data))
+        return rec[:n.value]
+
+    def alternate(self, rounds, fixed=(), point_params=None, pose_params=None):
+        """`rounds` times refine_points(**point_params) then refine_poses(fixed=fixed, **pose_params); stops early after a round that
+        refined neither a point nor a pose.  -> [(point stats, pose stats)] per round run."""
+        out = []
+        for _ in range(int(rounds)):
+            a = self.refine_points(**(point_params or {}))
+            b = self.refine_poses(fixed=fixed, **(pose_params or {}))
+            out.append((a, b))
+            if a["refined"] == 0 and b["refined"] == 0:
+                break
+        return out
 
     def points3d(self):
         """-> (points: POINT3D array, one per kept track; residuals: float64, one per kept observation in the tracks' order, -1.0 where

@@ -657,6 +657,10 @@ struct TrackSession {
     msfm_triangulation_params tri_prm = {};
     std::vector<int32_t> tri_ids;
     std::vector<msfm_pose_rt> tri_poses;
+    // pose refinement (msfm_refine_poses.hip.h): it rewrites tri_poses where a refined pose stands; a record per listed image, on the
+    // host; rp_valid: they describe the current poses and points (every call that rebuilds the pose tables clears it)
+    std::vector<msfm_pose_refinement> rp_records;
+    bool rp_valid = false;
     // image registration (msfm_register.hip.h): a record per listed image, the CSR of (track number, inlier flag, residual) per
     // correspondence; reg_valid: they belong to the current points (msfm_tracks_finish and msfm_triangulate_tracks clear it)
     DevBuf g_records, g_offsets, g_tid, g_inl, g_res;
@@ -683,6 +687,8 @@ struct TrackSession {
         rank_of.clear();
         tri_ids.clear();
         tri_poses.clear();
+        rp_records.clear();
+        rp_valid = false;
         nd = MsfmTrackNodes{};
         stats = msfm_track_stats{};
         open = closed = finished = suppress = add_only = tri_valid = mask_valid = reg_valid = false;

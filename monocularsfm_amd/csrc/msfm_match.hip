@@ -45,6 +45,7 @@ using namespace msfm;
 #include "msfm_triangulate.hip.h"
 #include "msfm_triangulate_robust.hip.h"
 #include "msfm_refine.hip.h"
+#include "msfm_refine_poses.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -890,6 +891,30 @@ int msfm_refine_points(msfm_ctx* ctx, const msfm_refine_params* params, msfm_ref
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return refine_impl(ctx, params, stats);
+    MSFM_API_END
+}
+
+// ---- pose refinement (msfm_refine_poses.hip.h) -----------------------------------------------------------------------------------------
+
+int msfm_refine_poses(msfm_ctx* ctx, const msfm_pose_refine_params* params, const int32_t* fixed_image_ids, int n_fixed,
+                      msfm_pose_refine_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return refine_poses_impl(ctx, params, fixed_image_ids, n_fixed, stats);
+    MSFM_API_END
+}
+
+int msfm_fetch_poses(msfm_ctx* ctx, int32_t* out_ids, msfm_pose_rt* out_poses, int* n) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return fetch_poses_impl(ctx, out_ids, out_poses, n);
+    MSFM_API_END
+}
+
+int msfm_fetch_pose_refinements(msfm_ctx* ctx, msfm_pose_refinement* out) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return fetch_pose_refinements_impl(ctx, out);
     MSFM_API_END
 }
 

@@ -92,6 +92,7 @@ int tri_prepare(msfm_ctx* ctx, const std::string& who, const msfm_camera* camera
     ts.tri_valid = false;   // whatever happens below, the previous points are gone
     ts.mask_valid = false;  // ... and the inlier bytes of a robust call (msfm_triangulate_robust.hip.h)
     ts.reg_valid = false;   // ... and the registrations made from them (msfm_register.hip.h)
+    ts.rp_valid = false;    // ... and the pose refinement's records (msfm_refine_poses.hip.h)
     if (!ts.open) return fail(ctx, MSFM_E_STATE, who + " without a track session (msfm_tracks_begin)");
     if (!ts.finished) return fail(ctx, MSFM_E_STATE, who + " before a successful msfm_tracks_finish");
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, who + " while a streaming series (msfm_match_pairs_begin .. _next) is open");

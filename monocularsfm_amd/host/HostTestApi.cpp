@@ -17,6 +17,7 @@
 #include "../csrc/msfm_tracks.h"
 #include "../csrc/msfm_triangulate.h"
 #include "../csrc/msfm_refine.h"
+#include "../csrc/msfm_refine_poses.h"
 #include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
@@ -721,6 +722,67 @@ int host_refine_points(const long long* offsets, const int* image_ids, const int
         counts5[2] += rc.gained_error_ok;
         counts5[3] += rc.rejected_by_verdict;
         counts5[4] += rc.iterations;
+    }
+    if (costs2) {
+        costs2[0] += rc.cost_before;
+        costs2[1] += rc.cost_after;
+    }
+    return 0;
+}
+
+// ---- pose refinement: the host twin of the device kernels (csrc/msfm_refine_poses.h, RefinePoses) -------------------------------------
+// The inputs of host_refine_points (all tracks: an image's fitting set runs through every track), min_observations and the ids to hold
+// fixed.  `poses` is read AND rewritten: where a refined pose stands its R and t replace the entry.  points and residuals are read and
+// rewritten by the re-verdict.  out_records: one msfm_pose_refinement per entry of the pose list.  counts9 (may be NULL): images,
+// eligible, refined, rejected_by_inliers, iterations, observations, points_reposed, points_lost, points_gained are ADDED to it; costs2
+// (may be NULL): cost_before and cost_after, summed in list order, are ADDED to it.  out_trace (may be NULL) receives msfm_rp::Trace
+// (40 bytes) per entry of the pose list.  Returns 0; 1, 2 as above; 3: a bad parameter; 4: a fixed id that is not declared or given twice.
+int host_refine_poses(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks, const int* ids, int n_images,
+                      const float* const* kxy, const int* pose_ids, msfm_pose_rt* poses, int n_poses, const double* cam, double max_error,
+                      double min_angle, double step_tol, int max_iters, int min_observations, const int* fixed_ids, int n_fixed,
+                      msfm_point3d* points, double* residuals, const unsigned char* mask, msfm_pose_refinement* out_records,
+                      long long* counts9, double* costs2, void* out_trace) {
+    static_assert(sizeof(msfm_rp::Trace) == 40 && sizeof(msfm_pose_refinement) == 48, "the trace is six int32 and two doubles");
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        rank_of[(size_t)ids[k]] = k;
+    }
+    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    std::vector<int> list_rank((size_t)std::max(n_poses, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        list_rank[(size_t)k] = r;
+        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
+    }
+    if (max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol) || min_observations < 3 || n_fixed < 0) return 3;
+    std::vector<uint8_t> fixed((size_t)std::max(n_images, 1), 0), changed((size_t)std::max(n_images, 1), 0);
+    for (int k = 0; k < n_fixed; ++k) {
+        const int r = (fixed_ids[k] >= 0 && fixed_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)fixed_ids[k]] : -1;
+        if (r < 0 || fixed[(size_t)r]) return 4;
+        fixed[(size_t)r] = 1;
+    }
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    msfm_rp::Counts rc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
+    msfm_rp::RefinePoses(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, rank_of.data(), kxy, table.data(),
+                         n_images, mask, c, msfm_ref::Verdict{max_error, min_angle}, msfm_rp::Params{step_tol, max_iters, min_observations},
+                         list_rank.data(), pose_ids, n_poses, fixed.data(), points, residuals, out_records, changed.data(), &rc,
+                         static_cast<msfm_rp::Trace*>(out_trace));
+    for (int k = 0; k < n_poses; ++k) {
+        const size_t r = (size_t)list_rank[(size_t)k];
+        if (!changed[r]) continue;
+        for (int q = 0; q < 9; ++q) poses[k].R[q] = table[r].R[q];
+        for (int q = 0; q < 3; ++q) poses[k].t[q] = table[r].t[q];
+    }
+    if (counts9) {
+        const long long v[9] = {rc.images, rc.eligible, rc.refined, rc.rejected_by_inliers, rc.iterations, rc.observations, rc.points_reposed,
+                                rc.points_lost, rc.points_gained};
+        for (int k = 0; k < 9; ++k) counts9[k] += v[k];
     }
     if (costs2) {
         costs2[0] += rc.cost_before;
