@@ -180,7 +180,16 @@ def camera_struct(camera):
 
 
 def pose_table(poses):
-    """dict image id -> (R 3 x 3, t 3) [or None: listed but not valid] -> (ids int32, POSE_RT array), by ascending id."""
+    """dict image id -> (R 3 x 3, t 3) [or None: listed but not valid] -> (ids int32, POSE_RT array), by ascending id.  A pair (ids,
+    POSE_RT array), the form Context.pose_list() returns, is passed on IN THE GIVEN ORDER (a copy; the C API takes the list in any
+    order)."""
+    if not isinstance(poses, dict):
+        ids, tab = poses
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        tab = np.array(tab, POSE_RT).reshape(-1)
+        if len(ids) != len(tab):
+            raise ValueError("pose list: %d ids for %d poses" % (len(ids), len(tab)))
+        return ids, tab
     ids = np.asarray(sorted(int(i) for i in poses), np.int32)
     tab = np.zeros(max(len(ids), 1), POSE_RT)
     for k, i in enumerate(ids):
@@ -769,7 +778,9 @@ class Context:
     # ---- track triangulation (include/msfm_match.h) ----
     def triangulate_tracks(self, camera, poses, max_error=2.0, min_angle=1.5, min_views=2, robust=False, max_hypotheses=64):
         """3-D points of the kept tracks of the last tracks_finish under known poses: camera as set_verification_model takes it, poses a
-        dict image id -> (R, t) with x_cam = R X + t (None: listed but unposed; declared images that are not listed are unposed too).
+        dict image id -> (R, t) with x_cam = R X + t (None: listed but unposed; declared images that are not listed are unposed too),
+        listed by ascending id, or a pair (ids, POSE_RT array) as pose_list() returns it, listed in the given order (pose_list(),
+        pose_refinements() and the cost sums of refine_poses follow the list's order; nothing else depends on it).
         Defaults: the reference's Triangulator::Parameters.  -> stats dict.  The points are fetched with points3d().
         robust=True: msfm_triangulate_tracks_robust -- a track whose plain point fails the error test is retried over at most
         max_hypotheses two-view hypotheses and keeps the observations that agree; the stats dict gains msfm_robust_stats' fields and

@@ -4,6 +4,8 @@ residuals, every integer counter and both cost sums (bit-equal by the fixed summ
 triangulation outputs and the session's own pose list.  Where a test is about a route of the LM loop the twin's trace is asserted next
 to the byte comparison: the routes are found on the CPU (tests/refine_poses_fixtures.py, tests/test_refine_poses_reference.py).  The
 twin itself is checked against the independent numpy reference in tests/test_refine_poses_reference.py."""
+import time
+
 import numpy as np
 import pytest
 
@@ -12,7 +14,7 @@ import refine_poses_fixtures as pfx
 import refine_poses_twin as ptw
 import registration_twin as regtw
 from monocularsfm_amd import _lib
-from test_gpu_robust_triangulation import open_ring
+from test_gpu_robust_triangulation import open_ring, second_pass_job
 
 pytestmark = pytest.mark.gpu
 CAM = pfx.CAM
@@ -69,7 +71,8 @@ def poses_same(ctx, host, ids, kps, tracks, params=ptw.DEFAULTS, fixed=(), thres
     assert np.array_equal(pts["status"] & keep, p0["status"] & keep)
     changed_ids = set(int(i) for i in l1[0][moved])
     o, img = tracks[0], tracks[1]
-    touched = np.asarray([bool(changed_ids & set(int(i) for i in img[o[t]:o[t + 1]])) for t in range(len(o) - 1)], bool) & ((p0["status"] & 3) == 3)
+    in_changed = np.isin(img, sorted(changed_ids)).astype(np.int64)                          # (every kept track has observations)
+    touched = (np.add.reduceat(in_changed, o[:-1]) > 0 if len(o) > 1 else np.zeros(0, bool)) & ((p0["status"] & 3) == 3)
     if not moved.any():
         touched[:] = False
     now = _lib.reposed(pts) & ~(_lib.reposed(p0) & ~touched)
@@ -244,6 +247,187 @@ def test_alternate_three_rounds_equals_the_twins_in_turn(tctx, host):
     assert tctx.pose_refinements().tobytes() == rec.tobytes()
     assert rounds[2][1]["cost_after"] < 0.05 * rounds[0][1]["cost_before"]
     tctx.tracks_end()
+
+
+# ---- the pose list in other orders than the ranks' -------------------------------------------------------------------------------------
+def order_job(which):
+    if which == "sizes":
+        ids, kps, poses, seen = pfx.ring(SIZES, 200)
+        return ids, kps, pfx.perturbed(poses, 7, keep=(int(ids[0]),)), seen, [int(ids[0])], THR, (10, 1e-6, 3)
+    ids, kps, bad, seen, fixed, thr, _ = pfx.route_case("lost_inliers")
+    return ids, kps, bad, seen, fixed, thr, pfx.ROUTE_PARAMS
+
+
+@pytest.mark.parametrize("which", ["sizes", "lost_inliers"])
+def test_pose_list_in_other_orders_than_the_ranks(tctx, host, which):
+    """The pose list as an (ids, table) pair in a seeded permutation, with the first, a middle and the last declared image dropped
+    (permuted) and with the fixed image last: list position k and pose rank differ, so a mix-up of the two in rp_image_kernel or in
+    the host's write-back shows.  Device against twin byte for byte; per image id the device's records and pose entries equal the
+    device's own run from the ascending list of the same images; pose_list() returns the caller's order; from the permuted list a
+    repeated call and a following refine_points against their twins."""
+    t0 = time.perf_counter()
+    ids, kps, bad, seen, fixed, thr, params = order_job(which)
+    tracks = opened(tctx, ids, kps, seen)
+    full = ptw.as_pose_list(bad)
+    orders = pfx.list_orders(full[0], fixed[0])
+    got = {}
+    for name in ("sorted", "dropped_sorted", "fixed_last", "dropped", "permuted"):
+        lst = pfx.relisted(full, orders[name])
+        tctx.triangulate_tracks(CAM, lst, *thr)
+        l0 = tctx.pose_list()
+        assert np.array_equal(l0[0], lst[0]) and l0[1].tobytes() == lst[1].tobytes()          # the caller's order, the caller's bytes
+        st, pts, res, l1, rec, tr = poses_same(tctx, host, ids, kps, tracks, params, fixed=fixed, thresholds=thr)
+        assert list(rec["image_id"]) == list(lst[0]) and st["refined"] >= 3
+        assert (st["cost_before"], st["cost_after"]) == pfx.summed_in_list_order(rec)
+        got[name] = (st, pts, res, l1, rec)
+    for name, base in (("permuted", "sorted"), ("fixed_last", "sorted"), ("dropped", "dropped_sorted")):
+        st, pts, res, l1, rec = got[name]
+        wst, wpts, wres, wl, wrec = got[base]
+        assert list(l1[0]) != list(wl[0])
+        assert pfx.by_id(l1[0], rec) == pfx.by_id(wl[0], wrec) and pfx.by_id(l1[0], l1[1]) == pfx.by_id(wl[0], wl[1])
+        assert pts.tobytes() == wpts.tobytes() and res.tobytes() == wres.tobytes()
+        assert {k: st[k] for k in ptw.COUNT_KEYS} == {k: wst[k] for k in ptw.COUNT_KEYS}
+    if which == "lost_inliers":
+        assert got["permuted"][0]["rejected_by_inliers"] == 1
+    # (the permuted list ran last) a repeated call, then the point refinement under the new poses
+    st2, pts, res, lst, rec, tr = poses_same(tctx, host, ids, kps, tracks, params, fixed=fixed, thresholds=thr)
+    assert np.array_equal(lst[0], full[0][orders["permuted"]])
+    s3 = tctx.refine_points(10, 1e-4)
+    p3, r3 = tctx.points3d()
+    wp, wr, wc = rtw.run(host, tracks, ids, kps, ptw.poses_dict(*lst), CAM, pts, res, None, thr, (10, 1e-4))
+    assert p3.tobytes() == wp.tobytes() and r3.tobytes() == wr.tobytes() and s3["refined"] == wc["refined"] > 0
+    after = tctx.pose_list()
+    assert np.array_equal(after[0], lst[0]) and after[1].tobytes() == lst[1].tobytes()
+    tctx.tracks_end()
+    print("list orders (%s): %.2f s" % (which, time.perf_counter() - t0))
+
+
+def test_alternate_two_rounds_on_a_permuted_list(tctx, host):
+    t0 = time.perf_counter()
+    ids, kps, poses, seen = pfx.ring([120] * 8, 120)
+    tracks = opened(tctx, ids, kps, seen)
+    full = ptw.as_pose_list(pfx.perturbed(poses, 3, keep=(int(ids[0]),)))
+    given = pfx.relisted(full, pfx.list_orders(full[0], int(ids[0]))["permuted"])
+    tctx.triangulate_tracks(CAM, given, *THR)
+    pts, res, _, lst = state(tctx, False)
+    assert np.array_equal(lst[0], given[0])
+    rounds = tctx.alternate(2, fixed=[int(ids[0])], point_params=dict(max_iters=5, step_tol=1e-6), pose_params=dict(max_iters=10, step_tol=1e-6))
+    assert len(rounds) == 2
+    for a, b in rounds:
+        pts, res, wa = rtw.run(host, tracks, ids, kps, ptw.poses_dict(*lst), CAM, pts, res, None, THR, (5, 1e-6))
+        pts, res, lst, rec, wb = ptw.run(host, tracks, ids, kps, lst, CAM, pts, res, None, THR, (10, 1e-6, 15), [int(ids[0])])
+        assert {k: a[k] for k in rtw.COUNT_KEYS} == {k: wa[k] for k in rtw.COUNT_KEYS}
+        assert {k: b[k] for k in ptw.COUNT_KEYS + ptw.COST_KEYS} == {k: wb[k] for k in ptw.COUNT_KEYS + ptw.COST_KEYS}
+        assert b["cost_after"] <= b["cost_before"] and b["refined"] == 7
+    got = state(tctx, False)
+    assert got[0].tobytes() == pts.tobytes() and got[1].tobytes() == res.tobytes()
+    assert np.array_equal(got[3][0], given[0]) and got[3][1].tobytes() == lst[1].tobytes()
+    assert tctx.pose_refinements().tobytes() == rec.tobytes()
+    tctx.tracks_end()
+    print("alternate on a permuted list: %.2f s" % (time.perf_counter() - t0))
+
+
+# ---- the second pass of every grid-stride loop ----------------------------------------------------------------------------------------
+def test_image_kernel_second_stride_pass(tctx, host):
+    """rp_image_kernel's grid holds at most 8 x CUs workgroups of four waves: with 32 x CUs + 5 listed images the first five waves walk
+    to a second image and add its counters to the first one's in registers.  The list is not in rank order; behind the first pass lie
+    an eligible image that stands, a fixed one, an unposed one, one below min_observations and a second eligible one, and position
+    0 -- the same wave as position 32 x CUs -- is eligible (tests/refine_poses_fixtures.listed_images_case; the placement is asserted
+    on the twin's trace, here and in tests/test_refine_poses_reference.py)."""
+    t0 = time.perf_counter()
+    cus = tctx.device_info()["cu_count"]
+    L = 32 * cus + 5
+    assert L <= _lib.MAX_IMAGES, "a device of %d CUs needs %d listed images for a second pass: more than MSFM_MAX_IMAGES" % (cus, L)
+    ids, kps, lst, matches, want_tracks, fixed, at = pfx.listed_images_case(L, 32 * cus)
+    d = np.random.default_rng(1).integers(0, 256, (kps[0].shape[0], 128), dtype=np.uint8)
+    for k, i in enumerate(ids):
+        tctx.upload_image(int(i), d)
+        tctx.upload_keypoints(int(i), kps[k])
+    tctx.tracks_begin(ids, add_only=True)
+    tctx.tracks_add(*matches)
+    tctx.tracks_finish()
+    tracks = tctx.tracks()
+    assert all(np.array_equal(a, b) for a, b in zip(tracks, want_tracks))
+    t1 = time.perf_counter()
+    tctx.triangulate_tracks(CAM, lst, *THR)
+    st, pts, res, l1, rec, tr = poses_same(tctx, host, ids, kps, tracks, pfx.LISTED_PARAMS, fixed=fixed)
+    pfx.assert_placed(at, rec, tr)
+    assert st["images"] == L and np.array_equal(l1[0], lst[0]) and not np.array_equal(lst[0], np.sort(lst[0]))
+    assert st["eligible"] == (tr["verdict"] != ptw.NOT_ELIGIBLE).sum() > L - 100 and st["iterations"] == tr["steps"].sum()
+    tctx.tracks_end()
+    print("image kernel's second pass: %d CUs, %d listed images (32 x CUs + 5), %d eligible, refine_ms %.3f; uploads and tracks %.2f s, test %.2f s"
+          % (cus, L, st["eligible"], st["refine_ms"], t1 - t0, time.perf_counter() - t0))
+
+
+def test_key_fill_and_verdict_kernels_second_pass_and_long_partials(tctx, host):
+    """rp_key_kernel, rp_fill_kernel and rp_verdict_kernel walk their inputs with a grid of 8 x CUs x 256 lanes: second_pass_job's
+    8 x 256 x CUs + 8192 three-view tracks give more observations in the fitting sets, and more tracks, than that; its images hold
+    8192 keypoints, so a fitting set runs through 64 and more rounds of the stride-64 partials.  After the robust call, every pose but
+    the first of each group turned by 0.2 mrad and moved by 1e-3 units (chosen on the CPU with the twins: every track still succeeds
+    under the default 2 px and some images lose an inlier), the first image of each group fixed, default parameters."""
+    t0 = time.perf_counter()
+    cus = tctx.device_info()["cu_count"]
+    lanes = 8 * 256 * cus
+    T = lanes + 8192
+    ids, kps, poses, lists = second_pass_job(T)
+    d = np.random.default_rng(1).integers(0, 256, (8192, 128), dtype=np.uint8)
+    for k, i in enumerate(ids):
+        tctx.upload_image(int(i), d)
+        tctx.upload_keypoints(int(i), kps[k])
+    tctx.tracks_begin(ids, add_only=True)
+    for l in lists:
+        tctx.tracks_add(*l)
+    assert tctx.tracks_finish()["tracks_kept"] == T
+    tracks = tctx.tracks()
+    fixed = [int(i) for i in ids[0::3]]
+    tctx.triangulate_tracks(CAM, pfx.perturbed(poses, 23, rot=2e-4, trans=1e-3, keep=tuple(fixed)), robust=True)
+    st, pts, res, lst, rec, tr = poses_same(tctx, host, ids, kps, tracks, fixed=fixed, thresholds=(2.0, 1.5), robust=True)
+    longest = int(rec["n_observations"][(rec["status"] & _lib.POSE_REFINED) != 0].max())
+    print("second pass: %d CUs, T %d, observations in the fitting sets %d (grid %d lanes), re-verdicted behind the grid %d, longest refined "
+          "fitting set %d, refined %d of %d, refine_ms %.3f of which prepare %.3f; test %.2f s"
+          % (cus, T, st["observations"], lanes, int(_lib.reposed(pts)[lanes:].sum()), longest, st["refined"], st["eligible"], st["refine_ms"],
+             st["prepare_ms"], time.perf_counter() - t0))
+    assert st["observations"] > lanes                                                        # rp_key's and rp_fill's second pass
+    assert _lib.reposed(pts)[lanes:].any()                                                   # rp_verdict's second pass
+    assert longest >= 4096                                                                   # 64 and more rounds per partial
+    assert st["eligible"] == 2 * len(fixed) and st["refined"] > st["eligible"] // 2
+    tctx.tracks_end()
+
+
+# ---- routes decided by rounding, and the chosen scenes of the reference tests -----------------------------------------------------------
+@pytest.mark.parametrize("params", pfx.ILL_PARAMS)
+@pytest.mark.parametrize("name", sorted(pfx.ILL_CASES))
+def test_ill_conditioned_routes(tctx, host, name, params):
+    """Collinear and nearly coincident points (tests/refine_poses_fixtures.ILL_CASES; found and asserted on the twin in
+    tests/test_refine_poses_reference.py): 30 and up to 100 evaluated steps per image, a dozen and more accepts directly after a
+    reject, each decided in the last bits of a cost -- one ulp of difference between the device's and the twin's arithmetic changes
+    the route and every byte after it."""
+    t0 = time.perf_counter()
+    ids, kps, bad, seen, fixed, thr = pfx.ill_case(name)
+    tracks = opened(tctx, ids, kps, seen)
+    tctx.triangulate_tracks(CAM, bad, *thr)
+    st, pts, res, lst, rec, tr = poses_same(tctx, host, ids, kps, tracks, params, fixed=fixed, thresholds=thr)
+    pfx.assert_ill_routes(rec, tr, params[0])
+    assert st["eligible"] == 6 and st["iterations"] == tr["steps"].sum() >= 6 * 30
+    tctx.tracks_end()
+    print("ill-conditioned %s %s: steps %s, accepted after rejected %s; %.2f s"
+          % (name, params, tr["steps"].tolist(), tr["accepted_after_rejected"].tolist(), time.perf_counter() - t0))
+
+
+@pytest.mark.parametrize("name", sorted(pfx.REF_CASES))
+def test_chosen_scenes_of_the_reference_tests(tctx, host, name):
+    """Fitting sets of 3, 4, 5 and 6 entries, a planar scene, a free camera at the origin and a world of 1e3 units
+    (tests/refine_poses_fixtures.REF_CASES): where tests/test_refine_poses_reference.py holds the twin to the reference."""
+    t0 = time.perf_counter()
+    ids, kps, bad, seen, fixed, thr, params = pfx.ref_case(name)
+    tracks = opened(tctx, ids, kps, seen)
+    tctx.triangulate_tracks(CAM, bad, *thr)
+    st, pts, res, lst, rec, tr = poses_same(tctx, host, ids, kps, tracks, params, fixed=fixed, thresholds=thr)
+    assert st["eligible"] == st["refined"] == 6 and np.all(tr["stop"][2:] == ptw.STOP_STEP) and st["points_reposed"] == pfx.REF_T
+    if name == "minimal_sets":
+        assert list(rec["n_observations"][4:]) == [3, 4, 5, 6]
+    tctx.tracks_end()
+    print("chosen scene %s: steps %s; %.2f s" % (name, tr["steps"].tolist(), time.perf_counter() - t0))
 
 
 def test_errors_and_state(tctx):

@@ -2,7 +2,10 @@
 // ring scene of refine_points_sanitize.cpp with 2 px of noise -- tracks of 3 .. 130 views, every third with one observation moved by
 // 40 px, every seventh image unposed, some tracks inconsistent -- with every posed image but the first turned by 1 mrad; the poses are
 // refined after the plain and after the robust triangulation with max_iters 0, 1, 10 and 100, min_observations 3 and 15, one image
-// fixed, alternating with the point refinement, with the trace.  Prints the counters; exits 1 if nothing was refined or a cost rose.
+// fixed, alternating with the point refinement, with the trace.  The pose list is NOT in rank order and shorter than the declared set
+// (position k holds image (37 k + 11) mod 130, every 13th position left out), and the records and the trace hold exactly one entry per
+// listed image: an index by rank where the list position is meant runs off their end.  A second scene has nearly coincident points
+// (1e-9 apart): ill-conditioned systems, LM runs to max_iters.  Prints the counters; exits 1 if nothing was refined or a cost rose.
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
 //       tools/refine_poses_sanitize.cpp -o refine_poses_sanitize && ./refine_poses_sanitize
 #include <cmath>
@@ -12,7 +15,7 @@
 
 #include "../monocularsfm_amd/csrc/msfm_refine_poses.h"
 
-int main() {
+static int scene(bool coincident, long long* refined_out) {
     const int n_img = 130, n_tr = 240;
     const msfm_emat::Camera cam{2500.0, 2400.0, 1536.0, 1152.0, -0.1, 0.02, 1e-3, -5e-4};
     std::mt19937_64 rng(7);
@@ -37,7 +40,8 @@ int main() {
     std::vector<uint8_t> cons;
     for (int j = 0; j < n_tr; ++j) {
         const int len = j % 40 == 0 ? n_img : 3 + j % 9;
-        const double X[3] = {box(rng), box(rng), box(rng)};
+        const double X[3] = {coincident ? 0.1 + 1e-9 * box(rng) : box(rng), coincident ? -0.2 + 1e-9 * box(rng) : box(rng),
+                             coincident ? 0.05 + 1e-9 * box(rng) : box(rng)};
         for (int i = 0; i < len; ++i) {
             const msfm_tri::Pose& p = poses[(size_t)i];
             const double Y0 = p.R[0] * X[0] + p.R[1] * X[1] + p.R[2] * X[2] + p.t[0], Y1 = p.R[3] * X[0] + p.R[4] * X[1] + p.R[5] * X[2] + p.t[1],
@@ -67,10 +71,13 @@ int main() {
     }
     std::vector<int> list_rank;
     std::vector<int32_t> list_ids;
-    for (int i = 0; i < n_img; ++i) {
+    for (int k = 0; k < n_img; ++k) {
+        if (k % 13 == 12) continue;
+        const int i = (37 * k + 11) % n_img;   // (37 and 130 are coprime: every image at most once)
         list_rank.push_back(i);
         list_ids.push_back(3 * i + 1);
     }
+    const int n_list = (int)list_rank.size();
     std::vector<uint8_t> fixed((size_t)n_img, 0), changed((size_t)n_img, 0);
     fixed[0] = 1;
     long long refined = 0;
@@ -91,18 +98,18 @@ int main() {
         int round = 0;
         for (int max_iters : {0, 1, 10, 10, 100}) {   // (each call refines from what the one before left)
             const int min_obs = round++ % 2 ? 3 : 15;
-            std::vector<msfm_rp::Trace> trace((size_t)n_img);
-            std::vector<msfm_pose_refinement> rec((size_t)n_img);
+            std::vector<msfm_rp::Trace> trace((size_t)n_list);
+            std::vector<msfm_pose_refinement> rec((size_t)n_list);
             msfm_rp::Counts c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
             msfm_rp::RefinePoses(offsets.data(), img.data(), idx.data(), n_tr, rank_of.data(), ptr.data(), cur.data(), n_img,
                                  robust ? mask.data() : nullptr, cam, msfm_ref::Verdict{12.0, 1.5}, msfm_rp::Params{1e-6, max_iters, min_obs},
-                                 list_rank.data(), list_ids.data(), n_img, fixed.data(), pts.data(), res.data(), rec.data(), changed.data(), &c,
+                                 list_rank.data(), list_ids.data(), n_list, fixed.data(), pts.data(), res.data(), rec.data(), changed.data(), &c,
                                  trace.data());
             long long steps = 0;
             for (const auto& t : trace) steps += t.steps;
-            std::printf("robust %d max_iters %3d min_observations %2d: eligible %lld refined %lld rejected_by_inliers %lld iterations %lld observations %lld "
+            std::printf("coincident %d robust %d max_iters %3d min_observations %2d: eligible %lld refined %lld rejected_by_inliers %lld iterations %lld observations %lld "
                         "reposed %lld lost %lld gained %lld cost %.6f -> %.6f\n",
-                        robust, max_iters, min_obs, c.eligible, c.refined, c.rejected_by_inliers, c.iterations, c.observations, c.points_reposed,
+                        (int)coincident, robust, max_iters, min_obs, c.eligible, c.refined, c.rejected_by_inliers, c.iterations, c.observations, c.points_reposed,
                         c.points_lost, c.points_gained, c.cost_before, c.cost_after);
             refined += c.refined;
             rose = rose || !(c.cost_after <= c.cost_before) || steps != c.iterations;
@@ -112,5 +119,12 @@ int main() {
                                    res.data(), &pc);
         }
     }
+    *refined_out += refined;
+    return rose ? 1 : 0;
+}
+
+int main() {
+    long long refined = 0;
+    const int rose = scene(false, &refined) + scene(true, &refined);
     return refined > 0 && !rose ? 0 : 1;
 }
