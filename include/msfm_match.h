@@ -762,6 +762,69 @@ int msfm_refine_poses(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
 int msfm_fetch_poses(msfm_ctx* ctx, int32_t* out_ids, msfm_pose_rt* out_poses, int* n);
 int msfm_fetch_pose_refinements(msfm_ctx* ctx, msfm_pose_refinement* out);
 
+/* ---- map extension: continue and create points under new poses (opt-in) ---------------
+ * The step that makes the blocks above an INCREMENTAL reconstruction (the reference's MapBuilder::TryRegisterNextImage after the
+ * pose is found: AddObservation, Map::CompletePoint3D, MapBuilder::Triangulate).  msfm_extend_points takes the poses of newly
+ * registered images, continues the session's standing points into those images WITHOUT moving them, and triangulates the tracks that
+ * only now have enough posed views.  A track that sees none of the new images stays bit for bit.  The arithmetic is
+ * csrc/msfm_extend.h, bit-identical to the host twin ExtendPoints.
+ *   inputs       the (image id, pose) list of the NEW images only; no camera and no thresholds: like msfm_refine_points the call
+ *                works on what the last successful msfm_triangulate_tracks / _robust left in the session (camera, thresholds, pose
+ *                list, records, residuals, inlier bytes), with the poses as msfm_refine_poses left them.
+ *   new images   every listed id is declared in the session, listed once, and UNPOSED in the session's pose list (absent, or present
+ *                with valid == 0).  An entry with valid == 0 is accepted and changes nothing.  On success an absent image with a
+ *                valid pose is appended to the session's pose list in the call's order, a valid == 0 entry of the session's list is
+ *                replaced in place; msfm_fetch_poses returns the enlarged list.
+ *   inlier bytes the call needs one byte per kept observation.  A session whose points are the plain call's gets them first: 1 on
+ *                every used observation of an attempted track, else 0 (what the robust call gives a track that passes its plain
+ *                test).  After a successful call the bytes are valid whatever the triangulation was: msfm_fetch_point_inliers works
+ *                and msfm_refine_points / msfm_refine_poses take their fitting sets from them (on a plain session this changes none
+ *                of their results: every used observation has byte 1).
+ *   new observation   an element of a kept track in an image that gained a valid pose in this call.
+ *   untouched    a track without a new observation, an inconsistent track, every track at n_poses == 0: record, residual slots and
+ *                inlier bytes stay bit for bit.
+ *   continue     the record has POINT | ERROR_OK | ANGLE_OK.  X never changes.  Per new observation: err = the reprojection error
+ *                at X under the new pose (pixels, f = (fx + fy) / 2); its residual slot = err; its inlier byte = 1 iff depth >
+ *                DBL_EPSILON and err <= the SESSION'S max_error, else 0.  (The reference's complete_max_reproj_error is a looser
+ *                4 px; the session's own threshold is used so that a continued point never fails the test it was admitted by.  The
+ *                registration's inlier flags are not consulted: the poses may come from any source.)  At least one accepted:
+ *                n_views = the byte-1 observations; mean_residual = their residual slots summed in element order / n_views (old
+ *                slots are read, not recomputed, and never rewritten); tri_angle = the parallax scan over them in element order;
+ *                status = every bit it had | MSFM_TRI_EXTENDED (ERROR_OK, DEPTH_OK and ANGLE_OK cannot be lost).  None accepted:
+ *                the record stays bit for bit, only the new slots and bytes are written.
+ *   create       every other consistent track with a new observation is triangulated afresh over all its elements in posed images
+ *                under the enlarged pose list: max_hypotheses == 0 by msfm_triangulate_tracks' rule, 1 .. 1024 by
+ *                msfm_triangulate_tracks_robust's.  Record, residual slots and inlier bytes are replaced by that result |
+ *                MSFM_TRI_EXTENDED (an earlier REFINED / REPOSED bit goes with the old record): apart from that one bit a created
+ *                track is byte for byte what the full triangulation call gives it under the enlarged pose list.
+ * The call invalidates registrations and pose-refinement records like msfm_refine_points.  params NULL = {0}.
+ * Errors, after each of which the session is exactly what it was: MSFM_E_STATE -- as msfm_refine_points.  MSFM_E_INVALID --
+ * max_hypotheses outside 0 .. 1024, n_poses < 0 or a NULL list with n_poses > 0, an id that is not declared in the session, given
+ * twice or already posed in the session (changing a pose is msfm_refine_poses' or a full triangulation's job), non-finite R or t of a
+ * valid pose.  MSFM_E_NOIMAGE -- a posed image with fewer keypoints than rows.
+ * The counters only count: no order reaches an output. */
+enum { MSFM_TRI_EXTENDED = 256 };
+typedef struct msfm_extend_params {   /* 8 bytes, no implicit padding */
+    int32_t max_hypotheses;          /* 0: created tracks take the plain route; 1 .. 1024: the robust one */
+    int32_t reserved;
+} msfm_extend_params;
+typedef struct msfm_extend_stats {   /* 96 bytes, no implicit padding */
+    int64_t images_added;            /* listed images that gained a valid pose */
+    int64_t tracks_touched;          /* consistent tracks with a new observation */
+    int64_t continued;               /* ... whose standing point accepted at least one */
+    int64_t observations_added;      /* new observations accepted by standing points */
+    int64_t observations_rejected;   /* ... and rejected by them (by error or depth) */
+    int64_t created_attempted;       /* touched tracks that were triangulated afresh */
+    int64_t created;                 /* ... of which end with POINT & ERROR_OK & ANGLE_OK */
+    int64_t retried;                 /* ... of which went through the robust hypotheses */
+    int64_t succeeded;               /* POINT & ERROR_OK & ANGLE_OK over all tracks after the call */
+    int64_t observations_used;       /* n_views summed over all tracks after the call */
+    double extend_ms;                /* HIP events around all launches of the call (the wait for the retry list included) */
+    double prepare_ms;               /* ... of which the pose table, the inlier bytes and the per-observation array */
+} msfm_extend_stats;
+int msfm_extend_points(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
+                       const msfm_extend_params* params, msfm_extend_stats* stats);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

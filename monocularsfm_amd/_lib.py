@@ -34,7 +34,7 @@ EXPORTS = [
     "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
     "msfm_triangulate_tracks", "msfm_fetch_points3d", "msfm_register_images", "msfm_fetch_registrations",
     "msfm_triangulate_tracks_robust", "msfm_fetch_point_inliers", "msfm_refine_points",
-    "msfm_refine_poses", "msfm_fetch_poses", "msfm_fetch_pose_refinements",
+    "msfm_refine_poses", "msfm_fetch_poses", "msfm_fetch_pose_refinements", "msfm_extend_points",
 ]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
@@ -134,6 +134,26 @@ class PoseRefineStats(C.Structure):
 def reposed(points):
     """The records of a POINT3D array that a pose refinement evaluated again under changed poses (MSFM_TRI_REPOSED)."""
     return (np.asarray(points)["status"] & TRI_REPOSED) != 0
+
+
+# map extension (include/msfm_match.h): the record's extra status bit, the 8-byte parameters, the 96-byte stats
+TRI_EXTENDED = 256
+
+
+class ExtendParams(C.Structure):
+    _fields_ = [("max_hypotheses", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ExtendStats(C.Structure):
+    """msfm_extend_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("images_added", "tracks_touched", "continued", "observations_added", "observations_rejected",
+                                         "created_attempted", "created", "retried", "succeeded", "observations_used")] + \
+               [(k, C.c_double) for k in ("extend_ms", "prepare_ms")]
+
+
+def extended(points):
+    """The records of a POINT3D array that a map extension continued into new images or created (MSFM_TRI_EXTENDED)."""
+    return (np.asarray(points)["status"] & TRI_EXTENDED) != 0
 
 
 def succeeded(points):
@@ -348,6 +368,7 @@ def load():
     L.msfm_refine_poses.argtypes = [vp, C.POINTER(PoseRefineParams), ip, C.c_int, C.POINTER(PoseRefineStats)]
     L.msfm_fetch_poses.argtypes = [vp, ip, C.c_void_p, C.POINTER(C.c_int)]
     L.msfm_fetch_pose_refinements.argtypes = [vp, C.c_void_p]
+    L.msfm_extend_points.argtypes = [vp, ip, C.c_void_p, C.c_int, C.POINTER(ExtendParams), C.POINTER(ExtendStats)]
     L.msfm_register_images.argtypes = [vp, C.POINTER(Camera), ip, C.c_int, C.POINTER(RegisterParams), C.POINTER(RegisterStats)]
     L.msfm_fetch_registrations.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
@@ -716,6 +737,7 @@ class Context:
         prm = TrackParams(int(min_pair_matches), int(bool(add_only)))
         self._chk(self._L.msfm_tracks_begin(self._h, _ip(ids), len(ids), C.byref(prm)))
         self._track_nodes = int(sum(self.image_rows(int(i)) for i in ids))
+        self._track_ids = [int(i) for i in ids]   # (grow()'s default list)
 
     def tracks_add(self, pairs, offsets, qt):
         """Fold host lists in (CSR as match_pairs returns them: pairs P x 2, offsets P + 1, qt M x 2).  An index outside its image's
@@ -788,6 +810,7 @@ class Context:
         cam = camera_struct(camera) if camera is not None else None
         ids, tab = pose_table(poses)
         st = TriangulationStats()
+        self._tri_route = int(max_hypotheses) if robust else 0   # (what extend_points(max_hypotheses=None) follows)
         if robust:
             rprm = RobustTriangulationParams(float(max_error), float(min_angle), int(min_views), int(max_hypotheses))
             rs = RobustStats()
@@ -865,6 +888,42 @@ class Context:
             if a["refined"] == 0 and b["refined"] == 0:
                 break
         return out
+
+    def extend_points(self, poses, max_hypotheses=None):
+        """Brings newly posed images into the map without a full triangulation (msfm_extend_points): `poses` -- a dict or an (ids,
+        POSE_RT) pair as triangulate_tracks takes them -- lists ONLY images that have no valid pose in the session yet.  Standing points
+        (POINT & ERROR_OK & ANGLE_OK) are continued into the new images without moving; every other consistent track that sees a new
+        image is triangulated afresh under the enlarged pose list; tracks that see none stay bit for bit.  max_hypotheses: 0 = the
+        plain route for the created tracks, 1 .. 1024 = the robust one, None = the route of this context's last triangulate_tracks.
+        -> stats dict.  extended(points) is the mask of the records it continued or created; pose_list() returns the enlarged list and
+        point_inliers() works after it whatever the triangulation was.  Registrations and pose refinements are invalidated."""
+        ids, tab = pose_table(poses)
+        if max_hypotheses is None:
+            max_hypotheses = getattr(self, "_tri_route", 0)
+        prm = ExtendParams(int(max_hypotheses), 0)
+        st = ExtendStats()
+        self._chk(self._L.msfm_extend_points(self._h, _ip(ids) if len(ids) else None, tab.ctypes.data if len(ids) else None, len(ids),
+                                             C.byref(prm), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in ExtendStats._fields_}
+
+    def grow(self, camera, image_ids=None, register_params=None, rounds=1, fixed=(), point_params=None, pose_params=None):
+        """One increment of the reconstruction: register_images(camera, image_ids, **register_params) -- image_ids None: every declared
+        image without a valid pose in the session -- then extend_points(the registered poses), then alternate(rounds, fixed=...).
+        -> (register stats, extend stats or None, alternate's list, the ids that registered).  When no image registers nothing but the
+        registrations has changed and the call returns early."""
+        if image_ids is None:
+            posed = set(self.poses())
+            image_ids = [int(i) for i in sorted(getattr(self, "_track_ids", ())) if int(i) not in posed]
+        image_ids = [int(i) for i in image_ids]
+        if not image_ids:
+            return None, None, [], []
+        reg = self.register_images(camera, image_ids, **(register_params or {}))
+        new = registered_poses(self.registrations()[0])
+        if not new:
+            return reg, None, [], []
+        ext = self.extend_points(new)
+        alt = self.alternate(rounds, fixed=fixed, point_params=point_params, pose_params=pose_params)
+        return reg, ext, alt, sorted(new)
 
     def points3d(self):
         """-> (points: POINT3D array, one per kept track; residuals: float64, one per kept observation in the tracks' order, -1.0 where

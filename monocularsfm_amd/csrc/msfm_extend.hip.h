@@ -1,0 +1,306 @@
+// msfm_extend.hip.h -- map extension on the device (include/msfm_match.h "map extension"): the three kernels and
+// the host side of msfm_extend_points (defined in msfm_match.hip).  The arithmetic is msfm_extend.h, shared with the host twin
+// ExtendPoints: the same bits.  Included by msfm_match.hip behind msfm_refine.hip.h, whose ref_obs_kernel it launches unchanged, and
+// behind msfm_triangulate_robust.hip.h, whose trr_retry_kernel it launches unchanged.
+//
+// Everything runs on the library's stream between HIP events; the host waits once for the length of the retry list (robust route
+// only) and once at the end.
+//   ext_mask_kernel    one lane per kept track, grid-stride; launched only on a session without inlier bytes: the byte of every
+//                      element (msfm_ext::plain_byte).  Per track, not per observation: the byte needs the record's ATTEMPTED bit
+//                      and the session keeps no observation -> track map.
+//   ref_obs_kernel     (msfm_refine.hip.h) under the enlarged pose table and the current bytes.
+//   ext_track_kernel   one lane per kept track, grid-stride, 256 threads, no LDS, the shape of trr_first_kernel.  A lane scans its
+//                      track's Obs for new observations; untouched lanes only count.  Continue lanes run msfm_ext::extend_track,
+//                      create lanes msfm_tri::triangulate_track through TriDevTrack and write the track's bytes.  On the robust route
+//                      the tracks that msfm_tri::retry selects are appended to a list: a ballot per wave, one atomic per wave for the
+//                      list position; no output depends on its order.  The counters are reduced per wave by shuffles and added with one
+//                      vector atomic per wave and counter.
+//   trr_retry_kernel   (msfm_triangulate_robust.hip.h) over that list with its own `positions` scratch; not launched for an empty list.
+//   ext_mark_kernel    one lane per listed track: the record the retry left | MSFM_TRI_EXTENDED.
+// Plain vector loads and stores only; no floating-point atomics.
+#pragma once
+#include "msfm_extend.h"
+#include "msfm_refine.hip.h"
+
+namespace msfm {
+
+struct ExtCounters {
+    unsigned long long tracks_touched, continued, observations_added, observations_rejected, created_attempted, created, succeeded,
+        observations_used;
+};
+constexpr int kExtCounters = 8;
+
+__global__ __launch_bounds__(256) void ext_mask_kernel(const long long* __restrict__ offsets, const int* __restrict__ img, int T,
+                                                       const TriImage* __restrict__ table, const msfm_tri::Pose* __restrict__ poses,
+                                                       const unsigned char* __restrict__ gained, const msfm_point3d* __restrict__ points,
+                                                       unsigned char* __restrict__ mask) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += stride) {
+        const long long b = offsets[t], e = offsets[t + 1];
+        const msfm_point3d r = points[t];
+        for (long long o = b; o < e; ++o) {
+            const int rank = table[img[o]].rank;   // (a track's images are declared: rank >= 0)
+            mask[o] = msfm_ext::plain_byte(r, poses[rank].valid ? poses + rank : nullptr, rank, gained);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ext_track_kernel(const long long* __restrict__ offsets, const int* __restrict__ img,
+                                                        const int* __restrict__ idx, const unsigned char* __restrict__ cons, int T,
+                                                        const msfm_ref::Obs* __restrict__ obs, const TriImage* __restrict__ table,
+                                                        const msfm_tri::Pose* __restrict__ poses, const unsigned char* __restrict__ gained,
+                                                        msfm_emat::Camera cam, msfm_tri::Params prm, int robust, msfm_point3d* points,
+                                                        double* residuals, unsigned char* mask, int* __restrict__ list,
+                                                        int* __restrict__ list_count, ExtCounters* __restrict__ counters) {
+    unsigned long long c[kExtCounters] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int lane = threadIdx.x & 63;
+    const int ok = MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK;
+    const double f = (cam.fx + cam.fy) / 2.0;
+    const msfm_ref::Verdict vd = {prm.max_error, prm.min_angle};
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long t0 = (long long)blockIdx.x * blockDim.x + (threadIdx.x - lane); t0 < T; t0 += stride) {   // (uniform over the wave)
+        const long long t = t0 + lane;
+        bool again = false;
+        if (t < T) {
+            const long long b = offsets[t], e = offsets[t + 1];
+            const int n = (int)(e - b);
+            msfm_point3d r = points[t];
+            const int fresh = cons[t] ? msfm_ext::new_observations(obs + b, n, gained) : 0;
+            if (fresh > 0) {
+                c[0] += 1;
+                if (msfm_ext::continues(r)) {
+                    msfm_ext::Tally tl;
+                    msfm_ext::extend_track(obs + b, n, poses, gained, f, vd, &r, residuals + b, mask + b, &tl);
+                    if (tl.accepted > 0) points[t] = r;
+                    c[1] += tl.accepted > 0 ? 1 : 0;
+                    c[2] += (unsigned long long)tl.accepted;
+                    c[3] += (unsigned long long)tl.rejected;
+                } else {
+                    const TriDevTrack a{img + b, idx + b, table, poses};
+                    msfm_tri::triangulate_track(a, n, true, cam, prm, &r, residuals + b);
+                    const bool attempted = (r.status & MSFM_TRI_ATTEMPTED) != 0;
+                    for (int k = 0; k < n; ++k) mask[b + k] = (attempted && a.pose(k)) ? 1 : 0;
+                    again = robust && msfm_tri::retry(r, r.n_views);
+                    if (!again) r.status |= MSFM_TRI_EXTENDED;   // (a retried track gets the bit from ext_mark_kernel)
+                    points[t] = r;
+                    c[4] += 1;
+                    c[5] += (!again && (r.status & ok) == ok) ? 1 : 0;
+                }
+            }
+            if (!again) {   // (trr_retry_kernel counts the tracks it rewrites)
+                c[6] += ((r.status & ok) == ok) ? 1 : 0;
+                c[7] += (unsigned long long)r.n_views;
+            }
+        }
+        const unsigned long long bal = __ballot(again);
+        if (bal) {
+            const int leader = __ffsll((long long)bal) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(list_count, __popcll(bal));
+            base = __shfl(base, leader, 64);
+            if (again) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = (int)t;
+        }
+    }
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(counters);
+#pragma unroll
+    for (int k = 0; k < kExtCounters; ++k) {
+        unsigned long long v = c[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+        if (lane == 0 && v) atomicAdd(out + k, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void ext_mark_kernel(const int* __restrict__ list, int listed, msfm_point3d* __restrict__ points) {
+    const int at = blockIdx.x * blockDim.x + threadIdx.x;
+    if (at < listed) points[list[at]].status |= MSFM_TRI_EXTENDED;
+}
+
+}  // namespace msfm
+
+namespace {
+
+int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses, const msfm_extend_params* params,
+                msfm_extend_stats* stats) {
+    TrackSession& ts = ctx->tracks;
+    const std::string who = "msfm_extend_points";
+    if (!ts.open) return fail(ctx, MSFM_E_STATE, who + " without a track session (msfm_tracks_begin)");
+    if (!ts.finished || !ts.tri_valid)
+        return fail(ctx, MSFM_E_STATE, who + " without points: msfm_triangulate_tracks has not run since the last msfm_tracks_finish");
+    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, who + " while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    const int max_hyp = params ? params->max_hypotheses : 0;
+    if (max_hyp < 0 || max_hyp > 1024) return fail(ctx, MSFM_E_INVALID, who + ": max_hypotheses must lie in 0 .. 1024");
+    if (n_poses < 0 || (n_poses > 0 && (!image_ids || !poses))) return fail(ctx, MSFM_E_INVALID, who + ": bad pose list");
+    // the enlarged pose list: nothing of the session is touched before every check has passed
+    const int n_img = (int)ts.nd.ids.size();
+    std::vector<int> at_of((size_t)std::max(n_img, 1), -1);   // rank -> position in the session's pose list
+    for (size_t k = 0; k < ts.tri_ids.size(); ++k) at_of[(size_t)ts.rank_of[(size_t)ts.tri_ids[k]]] = (int)k;
+    std::vector<int32_t> ids = ts.tri_ids;
+    std::vector<msfm_pose_rt> list = ts.tri_poses;
+    std::vector<unsigned char> gained((size_t)std::max(n_img, 1), 0), given((size_t)std::max(n_img, 1), 0);
+    long long added = 0;
+    for (int k = 0; k < n_poses; ++k) {
+        const int id = image_ids[k];
+        if (!ts.declares(id)) return fail(ctx, MSFM_E_INVALID, who + ": image not declared in the session: " + std::to_string(id));
+        const int r = ts.rank_of[(size_t)id];
+        if (given[(size_t)r]) return fail(ctx, MSFM_E_INVALID, who + ": an image is given twice: " + std::to_string(id));
+        given[(size_t)r] = 1;
+        const int at = at_of[(size_t)r];
+        if (at >= 0 && ts.tri_poses[(size_t)at].valid)
+            return fail(ctx, MSFM_E_INVALID, who + ": the image already has a pose in the session (msfm_refine_poses or a full triangulation changes one): " + std::to_string(id));
+        if (!poses[k].valid) continue;
+        for (double v : poses[k].R)
+            if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, who + ": non-finite R of image " + std::to_string(id));
+        for (double v : poses[k].t)
+            if (!std::isfinite(v)) return fail(ctx, MSFM_E_INVALID, who + ": non-finite t of image " + std::to_string(id));
+        if (ctx->images[(size_t)id].nk < ts.nd.rows[(size_t)r])
+            return fail(ctx, MSFM_E_NOIMAGE, who + ": posed image without keypoints (msfm_upload_keypoints): " + std::to_string(id));
+        msfm_pose_rt p = poses[k];
+        p.valid = 1;
+        p.reserved = 0;
+        if (at >= 0) {
+            list[(size_t)at] = p;
+        } else {
+            ids.push_back(id);
+            list.push_back(p);
+        }
+        gained[(size_t)r] = 1;
+        added += 1;
+    }
+    // the device tables through the triangulation's own host path; it drops the session's validity flags before it checks anything:
+    // after an error of its own (an OLD posed image lost its keypoints) they come back
+    const bool had_mask = ts.mask_valid, had_reg = ts.reg_valid, had_rp = ts.rp_valid;
+    const msfm_tri::Params prm = {ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0};
+    std::vector<msfm_pose_rt> by_rank;
+    std::vector<TriImage> table;
+    const int rc = tri_prepare(ctx, who, &ts.tri_camera, ids.data(), list.data(), (int)ids.size(), prm, &by_rank, &table);
+    ts.tri_valid = true;
+    ts.mask_valid = had_mask;
+    if (rc) {
+        ts.reg_valid = had_reg;
+        ts.rp_valid = had_rp;
+        return rc;
+    }
+    const msfm_camera c = ts.tri_camera;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
+    struct Tmp {   // freed when the call returns, whatever it returns
+        DevBuf in, poses, table, gained, counters, obs, list, positions;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        ~Tmp() {
+            for (DevBuf* b : {&in, &poses, &table, &gained, &counters, &obs, &list, &positions}) b->release();
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } t;
+    hipStream_t st = store_stream(ctx);
+    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
+    HIPCHK(ctx, t.in.ensure(by_rank.size() * sizeof(msfm_pose_rt)));
+    HIPCHK(ctx, t.poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose)));
+    HIPCHK(ctx, t.table.ensure(table.size() * sizeof(TriImage)));
+    HIPCHK(ctx, t.gained.ensure(gained.size()));
+    HIPCHK(ctx, t.counters.ensure(sizeof(ExtCounters) + sizeof(TrrCounters)));   // this file's | the retry kernel's
+    HIPCHK(ctx, t.obs.ensure((size_t)std::max<long long>(1, O) * sizeof(msfm_ref::Obs)));
+    HIPCHK(ctx, t.list.ensure((size_t)(std::max<long long>(1, T) + 1) * sizeof(int)));   // the list | its length
+    HIPCHK(ctx, ts.t_mask.ensure((size_t)std::max<long long>(1, O)));
+    // (synchronous copies of the small tables: nothing queued reads host memory that an early return below would free)
+    HIPCHK(ctx, hipMemcpy(t.in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(t.table.p, table.data(), table.size() * sizeof(TriImage), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(t.gained.p, gained.data(), gained.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(ExtCounters) + sizeof(TrrCounters), st));
+    ExtCounters* d_ext = t.counters.as<ExtCounters>();
+    TrrCounters* d_trr = reinterpret_cast<TrrCounters*>(d_ext + 1);
+    int* d_list = t.list.as<int>();
+    int* d_listed = d_list + std::max<long long>(1, T);
+    HIPCHK(ctx, hipMemsetAsync(d_listed, 0, sizeof(int), st));
+    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
+    if (n_img > 0) {
+        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)t.in.as<msfm_pose_rt>(), n_img,
+                           t.poses.as<msfm_tri::Pose>());
+        HIPCHK(ctx, hipGetLastError());
+    }
+    const msfm_emat::Camera cam{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+    const unsigned grid = tk_grid(ctx, T);
+    hipError_t queued = hipSuccess;   // from the first kernel that writes session memory on, an error drops the session's points
+    auto wrote = [&](hipError_t e) {
+        if (e != hipSuccess && queued == hipSuccess) queued = e;
+        return e == hipSuccess;
+    };
+    int listed = 0;
+    if (T > 0 && O > 0) {
+        if (!had_mask) {
+            hipLaunchKernelGGL(ext_mask_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
+                               (const int*)ts.r_img.as<int>(), (int)T, (const TriImage*)t.table.as<TriImage>(),
+                               (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), (const unsigned char*)t.gained.as<unsigned char>(),
+                               (const msfm_point3d*)ts.t_points.as<msfm_point3d>(), ts.t_mask.as<unsigned char>());
+            wrote(hipGetLastError());
+        }
+        if (queued == hipSuccess) {
+            hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
+                               (const TriImage*)t.table.as<TriImage>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(),
+                               (const unsigned char*)ts.t_mask.as<unsigned char>(), cam, t.obs.as<msfm_ref::Obs>());
+            wrote(hipGetLastError());
+        }
+    }
+    if (queued == hipSuccess) wrote(hipEventRecord(t.ev[1], st));
+    if (T > 0 && O > 0 && queued == hipSuccess) {
+        hipLaunchKernelGGL(ext_track_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
+                           (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)T,
+                           (const msfm_ref::Obs*)t.obs.as<msfm_ref::Obs>(), (const TriImage*)t.table.as<TriImage>(),
+                           (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), (const unsigned char*)t.gained.as<unsigned char>(), cam, prm,
+                           max_hyp > 0 ? 1 : 0, ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), d_list,
+                           d_listed, d_ext);
+        wrote(hipGetLastError());
+        if (max_hyp > 0 && queued == hipSuccess) {
+            if (wrote(hipMemcpyAsync(&listed, d_listed, sizeof(int), hipMemcpyDeviceToHost, st)))
+                wrote(hipStreamSynchronize(st));   // the first wait: the length of the retry list
+            if (queued != hipSuccess) listed = 0;
+        }
+    }
+    if (listed > 0 && wrote(t.positions.ensure((size_t)O * sizeof(int)))) {
+        const msfm_tri::RobustParams rp = {prm.max_error, prm.min_angle, prm.min_views, max_hyp};
+        const unsigned groups = (unsigned)((listed + kTrrWaves - 1) / kTrrWaves);
+        const unsigned rgrid = std::min<unsigned>(groups, (unsigned)(kTrrGroupsPerCU * std::max(1, ctx->cu_count)));
+        hipLaunchKernelGGL(trr_retry_kernel, dim3(rgrid), dim3(64 * kTrrWaves), 0, st, (const long long*)ts.r_offsets.as<long long>(),
+                           (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const TriImage*)t.table.as<TriImage>(),
+                           (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), cam, rp, (const int*)d_list, listed, t.positions.as<int>(),
+                           ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), d_trr);
+        if (wrote(hipGetLastError())) {
+            hipLaunchKernelGGL(ext_mark_kernel, dim3((unsigned)((listed + 255) / 256)), dim3(256), 0, st, (const int*)d_list, listed,
+                               ts.t_points.as<msfm_point3d>());
+            wrote(hipGetLastError());
+        }
+    }
+    if (queued == hipSuccess) wrote(hipEventRecord(t.ev[2], st));
+    const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
+    wrote(done);
+    if (queued != hipSuccess) ts.tri_valid = ts.mask_valid = false;   // (the records and the bytes may be half rewritten)
+    HIPCHK(ctx, queued);
+    ts.tri_ids.swap(ids);   // (the records describe the enlarged list from here on, whatever the copies below return)
+    ts.tri_poses.swap(list);
+    ts.mask_valid = true;
+    ExtCounters hc = {};
+    TrrCounters hr = {};
+    HIPCHK(ctx, hipMemcpy(&hc, d_ext, sizeof(hc), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(&hr, d_trr, sizeof(hr), hipMemcpyDeviceToHost));
+    float prep_ms = 0.f, all_ms = 0.f;
+    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, t.ev[0], t.ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&all_ms, t.ev[0], t.ev[2]));
+    msfm_extend_stats s = {};
+    s.images_added = added;
+    s.tracks_touched = (int64_t)hc.tracks_touched;
+    s.continued = (int64_t)hc.continued;
+    s.observations_added = (int64_t)hc.observations_added;
+    s.observations_rejected = (int64_t)hc.observations_rejected;
+    s.created_attempted = (int64_t)hc.created_attempted;
+    s.created = (int64_t)(hc.created + hr.tri[5]);   // (every track the retry kernel rewrites is a created one)
+    s.retried = (int64_t)hr.retried;
+    s.succeeded = (int64_t)(hc.succeeded + hr.tri[5]);
+    s.observations_used = (int64_t)(hc.observations_used + hr.tri[6]);
+    s.extend_ms = all_ms;
+    s.prepare_ms = prep_ms;
+    if (stats) *stats = s;
+    return MSFM_OK;
+}
+
+}  // namespace

@@ -46,6 +46,7 @@ using namespace msfm;
 #include "msfm_triangulate_robust.hip.h"
 #include "msfm_refine.hip.h"
 #include "msfm_refine_poses.hip.h"
+#include "msfm_extend.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -915,6 +916,16 @@ int msfm_fetch_pose_refinements(msfm_ctx* ctx, msfm_pose_refinement* out) {
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return fetch_pose_refinements_impl(ctx, out);
+    MSFM_API_END
+}
+
+// ---- map extension (msfm_extend.hip.h) -------------------------------------------------------------------------------------------------
+
+int msfm_extend_points(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses, const msfm_extend_params* params,
+                       msfm_extend_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return extend_impl(ctx, image_ids, poses, n_poses, params, stats);
     MSFM_API_END
 }
 

@@ -18,6 +18,7 @@
 #include "../csrc/msfm_triangulate.h"
 #include "../csrc/msfm_refine.h"
 #include "../csrc/msfm_refine_poses.h"
+#include "../csrc/msfm_extend.h"
 #include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
@@ -787,6 +788,56 @@ int host_refine_poses(const long long* offsets, const int* image_ids, const int*
     if (costs2) {
         costs2[0] += rc.cost_before;
         costs2[1] += rc.cost_after;
+    }
+    return 0;
+}
+
+// ---- map extension: the host twin of the device kernels (csrc/msfm_extend.h, ExtendPoints) --------------------------------------------
+// The inputs of host_refine_points with `consistent`, the ENLARGED pose list (the session's list with the new images appended or
+// replaced in place, as msfm_extend_points leaves it) and new_ids: the images that gained their valid pose in this call (each must be
+// in the enlarged list with a valid pose).  min_views is the triangulation's; max_hypotheses 0 = plain route for created tracks.
+// points, residuals and mask are read and rewritten in place; have_mask 0: the points are the plain call's and the bytes of the
+// computed tracks are created first.  Tracks [first, first + count) are computed.  counts7 (may be NULL): tracks_touched, continued,
+// observations_added, observations_rejected, created_attempted, created, retried of those tracks are ADDED to it.  out_trace (may be
+// NULL) receives msfm_ext::Trace (four int32) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3:
+// max_hypotheses outside 0 .. 1024; 4: a new id that is not in the enlarged list with a valid pose, or given twice.
+int host_extend_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent, const int* ids,
+                       int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const int* new_ids,
+                       int n_new, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses, long long first,
+                       long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask, long long* counts7,
+                       int* out_trace) {
+    static_assert(sizeof(msfm_ext::Trace) == 4 * sizeof(int), "the trace is four int32");
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        rank_of[(size_t)ids[k]] = k;
+    }
+    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
+    }
+    if (max_hypotheses < 0 || max_hypotheses > 1024) return 3;
+    std::vector<uint8_t> gained((size_t)std::max(n_images, 1), 0);
+    for (int k = 0; k < n_new; ++k) {
+        const int r = (new_ids[k] >= 0 && new_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)new_ids[k]] : -1;
+        if (r < 0 || gained[(size_t)r] || !table[(size_t)r].valid) return 4;
+        gained[(size_t)r] = 1;
+    }
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    msfm_ext::Counts ec = {0, 0, 0, 0, 0, 0, 0};
+    msfm_ext::ExtendPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(), kxy,
+                           table.data(), gained.data(), c, msfm_tri::Params{max_error, min_angle, min_views, 0}, max_hypotheses,
+                           have_mask != 0, points, residuals, mask, &ec, reinterpret_cast<msfm_ext::Trace*>(out_trace));
+    if (counts7) {
+        const long long v[7] = {ec.tracks_touched, ec.continued, ec.observations_added, ec.observations_rejected, ec.created_attempted,
+                                ec.created, ec.retried};
+        for (int k = 0; k < 7; ++k) counts7[k] += v[k];
     }
     return 0;
 }
