@@ -5,7 +5,7 @@
 //
 // The contract of msfm_pose.h holds: fp64 with +, -, *, /, sqrt only, static loop structure, -ffp-contract=off on both sides, every
 // sum in element order -> the host twin and the device produce the SAME bits.  Obs and prepare_obs are msfm_refine.h's, Pose,
-// parallax, obs_error, triangulate_track, retry and robust_track are msfm_triangulate.h's, kDepthEps is msfm_pose.h's.
+// parallax_scan, obs_error, triangulate_track, retry and robust_track are msfm_triangulate.h's, kDepthEps is msfm_pose.h's.
 //
 //   gained          one byte per pose rank: the image got its valid pose in this call.  A NEW OBSERVATION of a track is an element
 //                   that is OBS_USED under the enlarged pose table and whose image has the byte set.
@@ -17,8 +17,8 @@
 //                   order: err = obs_error at X under the new pose, f = (fx + fy) / 2; its residual slot = err; its inlier byte = 1
 //                   iff depth > kDepthEps and err <= max_error (a NaN fails), else 0.  None accepted: the record stays bit for bit.
 //                   Otherwise, over the byte-1 observations in element order: n_views = their number; mean_residual = their residual
-//                   SLOTS (old ones are read, never recomputed or rewritten) summed from 0.0 / n_views; tri_angle = the parallax scan
-//                   for i: for j < i with triangulate_track's stop rule (reverdict_track's); status = every bit it had | EXTENDED.
+//                   SLOTS (old ones are read, never recomputed or rewritten) summed from 0.0 / n_views; tri_angle =
+//                   msfm_tri::parallax_scan over them; status = every bit it had | EXTENDED.
 //                   The old pairs are still scanned, so ANGLE_OK stays; every accepted observation passed the error and the depth
 //                   test, so ERROR_OK and DEPTH_OK cannot be lost.
 //   create          every other consistent track with a new observation: triangulate_track over all its posed elements under the
@@ -98,27 +98,11 @@ MSFM_FHD void extend_track(const msfm_ref::Obs* obs, int n, const msfm_tri::Pose
         sum = sum + residuals[k];
         count += 1;
     }
-    bool angle_ok = false;
-    double angle = 0.0;
-    for (int i = 1; i < n && !angle_ok; ++i) {
-        const Obs oi = obs[i];
-        if (!((oi.flags & OBS_FIT) || (is_new(oi, gained) && mask[i]))) continue;
-        const msfm_tri::Pose* pi = poses + oi.rank;
-        const double Oi[3] = {pi->O[0], pi->O[1], pi->O[2]};
-        for (int j = 0; j < i; ++j) {
-            const Obs oj = obs[j];
-            if (!((oj.flags & OBS_FIT) || (is_new(oj, gained) && mask[j]))) continue;
-            const msfm_tri::Pose* pj = poses + oj.rank;
-            const double Oj[3] = {pj->O[0], pj->O[1], pj->O[2]};
-            const double a = msfm_tri::parallax(X, Oi, Oj);
-            if (a >= vd.min_angle) {
-                angle = a;
-                angle_ok = true;
-                break;
-            }
-            if (a > angle) angle = a;
-        }
-    }
+    double angle;
+    (void)msfm_tri::parallax_scan(X, n, vd.min_angle, [&](int k) -> const double* {
+        const Obs o = obs[k];
+        return ((o.flags & OBS_FIT) || (is_new(o, gained) && mask[k])) ? poses[o.rank].O : nullptr;
+    }, &angle);
     msfm_point3d r = old;
     r.status = old.status | MSFM_TRI_EXTENDED;
     r.n_views = count;
@@ -156,12 +140,7 @@ inline void ExtendPoints(const int64_t* offsets, const int32_t* image_ids, const
                 mask[b + k] = plain_byte(points[t], p, p ? (int)(p - poses) : -1, gained);
             }
         obs.resize((size_t)n);
-        for (int k = 0; k < n; ++k) {
-            const msfm_tri::Pose* p = a.pose(k);
-            double x = 0.0, y = 0.0;
-            if (p) a.pixel(k, &x, &y);
-            msfm_ref::prepare_obs(p, p ? (int)(p - poses) : -1, x, y, mask[b + k] != 0, cam, &obs[(size_t)k]);
-        }
+        msfm_ref::host_obs(a, n, mask + b, cam, obs.data());
         const int fresh = consistent[t] ? new_observations(obs.data(), n, gained) : 0;
         Trace tr = {KIND_UNTOUCHED, fresh, 0, ROUTE_NONE};
         if (fresh > 0 && continues(points[t])) {

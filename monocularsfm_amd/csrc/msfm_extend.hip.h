@@ -13,8 +13,7 @@
 //                      track's Obs for new observations; untouched lanes only count.  Continue lanes run msfm_ext::extend_track,
 //                      create lanes msfm_tri::triangulate_track through TriDevTrack and write the track's bytes.  On the robust route
 //                      the tracks that msfm_tri::retry selects are appended to a list: a ballot per wave, one atomic per wave for the
-//                      list position; no output depends on its order.  The counters are reduced per wave by shuffles and added with one
-//                      vector atomic per wave and counter.
+//                      list position; no output depends on its order.  The counters go through wave_add_counters.
 //   trr_retry_kernel   (msfm_triangulate_robust.hip.h) over that list with its own `positions` scratch; not launched for an empty list.
 //   ext_mark_kernel    one lane per listed track: the record the retry left | MSFM_TRI_EXTENDED.
 // Plain vector loads and stores only; no floating-point atomics.
@@ -92,23 +91,9 @@ __global__ __launch_bounds__(256) void ext_track_kernel(const long long* __restr
                 c[7] += (unsigned long long)r.n_views;
             }
         }
-        const unsigned long long bal = __ballot(again);
-        if (bal) {
-            const int leader = __ffsll((long long)bal) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(list_count, __popcll(bal));
-            base = __shfl(base, leader, 64);
-            if (again) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = (int)t;
-        }
+        wave_list_append(again, (int)t, list, list_count);
     }
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(counters);
-#pragma unroll
-    for (int k = 0; k < kExtCounters; ++k) {
-        unsigned long long v = c[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-        if (lane == 0 && v) atomicAdd(out + k, v);
-    }
+    wave_add_counters(c, reinterpret_cast<unsigned long long*>(counters));
 }
 
 __global__ __launch_bounds__(256) void ext_mark_kernel(const int* __restrict__ list, int listed, msfm_point3d* __restrict__ points) {
@@ -124,10 +109,7 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
                 msfm_extend_stats* stats) {
     TrackSession& ts = ctx->tracks;
     const std::string who = "msfm_extend_points";
-    if (!ts.open) return fail(ctx, MSFM_E_STATE, who + " without a track session (msfm_tracks_begin)");
-    if (!ts.finished || !ts.tri_valid)
-        return fail(ctx, MSFM_E_STATE, who + " without points: msfm_triangulate_tracks has not run since the last msfm_tracks_finish");
-    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, who + " while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (const int rc = tri_session_check(ctx, who, true)) return rc;
     const int max_hyp = params ? params->max_hypotheses : 0;
     if (max_hyp < 0 || max_hyp > 1024) return fail(ctx, MSFM_E_INVALID, who + ": max_hypotheses must lie in 0 .. 1024");
     if (n_poses < 0 || (n_poses > 0 && (!image_ids || !poses))) return fail(ctx, MSFM_E_INVALID, who + ": bad pose list");
@@ -167,45 +149,30 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
         gained[(size_t)r] = 1;
         added += 1;
     }
-    // the device tables through the triangulation's own host path; it drops the session's validity flags before it checks anything:
-    // after an error of its own (an OLD posed image lost its keypoints) they come back
-    const bool had_mask = ts.mask_valid, had_reg = ts.reg_valid, had_rp = ts.rp_valid;
+    const bool had_mask = ts.mask_valid;
     const msfm_tri::Params prm = {ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0};
     std::vector<msfm_pose_rt> by_rank;
     std::vector<TriImage> table;
-    const int rc = tri_prepare(ctx, who, &ts.tri_camera, ids.data(), list.data(), (int)ids.size(), prm, &by_rank, &table);
-    ts.tri_valid = true;
-    ts.mask_valid = had_mask;
-    if (rc) {
-        ts.reg_valid = had_reg;
-        ts.rp_valid = had_rp;
-        return rc;
-    }
-    const msfm_camera c = ts.tri_camera;
+    if (const int rc = tri_tables(ctx, who, &ts.tri_camera, ids.data(), list.data(), (int)ids.size(), prm, &by_rank, &table))
+        return rc;   // (an OLD posed image lost its keypoints: still nothing of the session is touched)
+    // every check has passed: the registrations and the pose refinement's records are gone, they describe the map as it was
+    ts.reg_valid = ts.rp_valid = false;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
-    struct Tmp {   // freed when the call returns, whatever it returns
-        DevBuf in, poses, table, gained, counters, obs, list, positions;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        ~Tmp() {
-            for (DevBuf* b : {&in, &poses, &table, &gained, &counters, &obs, &list, &positions}) b->release();
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
+    PoseTables pt;   // (the temporaries are freed when the call returns, whatever it returns)
+    struct {
+        TmpBuf gained, counters, obs, list, positions;
     } t;
+    TmpEvents<3> ev;
     hipStream_t st = store_stream(ctx);
-    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
-    HIPCHK(ctx, t.in.ensure(by_rank.size() * sizeof(msfm_pose_rt)));
-    HIPCHK(ctx, t.poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose)));
-    HIPCHK(ctx, t.table.ensure(table.size() * sizeof(TriImage)));
+    HIPCHK(ctx, ev.create());
     HIPCHK(ctx, t.gained.ensure(gained.size()));
     HIPCHK(ctx, t.counters.ensure(sizeof(ExtCounters) + sizeof(TrrCounters)));   // this file's | the retry kernel's
     HIPCHK(ctx, t.obs.ensure((size_t)std::max<long long>(1, O) * sizeof(msfm_ref::Obs)));
     HIPCHK(ctx, t.list.ensure((size_t)(std::max<long long>(1, T) + 1) * sizeof(int)));   // the list | its length
     HIPCHK(ctx, ts.t_mask.ensure((size_t)std::max<long long>(1, O)));
+    HIPCHK(ctx, pt.upload(ts.tri_camera, by_rank, table, n_img));
     // (synchronous copies of the small tables: nothing queued reads host memory that an early return below would free)
-    HIPCHK(ctx, hipMemcpy(t.in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(t.table.p, table.data(), table.size() * sizeof(TriImage), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(t.gained.p, gained.data(), gained.size(), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(ExtCounters) + sizeof(TrrCounters), st));
     ExtCounters* d_ext = t.counters.as<ExtCounters>();
@@ -213,13 +180,9 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
     int* d_list = t.list.as<int>();
     int* d_listed = d_list + std::max<long long>(1, T);
     HIPCHK(ctx, hipMemsetAsync(d_listed, 0, sizeof(int), st));
-    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
-    if (n_img > 0) {
-        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)t.in.as<msfm_pose_rt>(), n_img,
-                           t.poses.as<msfm_tri::Pose>());
-        HIPCHK(ctx, hipGetLastError());
-    }
-    const msfm_emat::Camera cam{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+    HIPCHK(ctx, hipEventRecord(ev[0], st));
+    HIPCHK(ctx, pt.prepare(st));
+    const msfm_emat::Camera cam = pt.cam;
     const unsigned grid = tk_grid(ctx, T);
     hipError_t queued = hipSuccess;   // from the first kernel that writes session memory on, an error drops the session's points
     auto wrote = [&](hipError_t e) {
@@ -230,24 +193,24 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
     if (T > 0 && O > 0) {
         if (!had_mask) {
             hipLaunchKernelGGL(ext_mask_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
-                               (const int*)ts.r_img.as<int>(), (int)T, (const TriImage*)t.table.as<TriImage>(),
-                               (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), (const unsigned char*)t.gained.as<unsigned char>(),
+                               (const int*)ts.r_img.as<int>(), (int)T, pt.d_table(),
+                               pt.d_poses(), (const unsigned char*)t.gained.as<unsigned char>(),
                                (const msfm_point3d*)ts.t_points.as<msfm_point3d>(), ts.t_mask.as<unsigned char>());
             wrote(hipGetLastError());
         }
         if (queued == hipSuccess) {
             hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
-                               (const TriImage*)t.table.as<TriImage>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(),
+                               pt.d_table(), pt.d_poses(),
                                (const unsigned char*)ts.t_mask.as<unsigned char>(), cam, t.obs.as<msfm_ref::Obs>());
             wrote(hipGetLastError());
         }
     }
-    if (queued == hipSuccess) wrote(hipEventRecord(t.ev[1], st));
+    if (queued == hipSuccess) wrote(hipEventRecord(ev[1], st));
     if (T > 0 && O > 0 && queued == hipSuccess) {
         hipLaunchKernelGGL(ext_track_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
                            (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)T,
-                           (const msfm_ref::Obs*)t.obs.as<msfm_ref::Obs>(), (const TriImage*)t.table.as<TriImage>(),
-                           (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), (const unsigned char*)t.gained.as<unsigned char>(), cam, prm,
+                           (const msfm_ref::Obs*)t.obs.as<msfm_ref::Obs>(), pt.d_table(),
+                           pt.d_poses(), (const unsigned char*)t.gained.as<unsigned char>(), cam, prm,
                            max_hyp > 0 ? 1 : 0, ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), d_list,
                            d_listed, d_ext);
         wrote(hipGetLastError());
@@ -262,8 +225,8 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
         const unsigned groups = (unsigned)((listed + kTrrWaves - 1) / kTrrWaves);
         const unsigned rgrid = std::min<unsigned>(groups, (unsigned)(kTrrGroupsPerCU * std::max(1, ctx->cu_count)));
         hipLaunchKernelGGL(trr_retry_kernel, dim3(rgrid), dim3(64 * kTrrWaves), 0, st, (const long long*)ts.r_offsets.as<long long>(),
-                           (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const TriImage*)t.table.as<TriImage>(),
-                           (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), cam, rp, (const int*)d_list, listed, t.positions.as<int>(),
+                           (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), pt.d_table(),
+                           pt.d_poses(), cam, rp, (const int*)d_list, listed, t.positions.as<int>(),
                            ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), d_trr);
         if (wrote(hipGetLastError())) {
             hipLaunchKernelGGL(ext_mark_kernel, dim3((unsigned)((listed + 255) / 256)), dim3(256), 0, st, (const int*)d_list, listed,
@@ -271,7 +234,7 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
             wrote(hipGetLastError());
         }
     }
-    if (queued == hipSuccess) wrote(hipEventRecord(t.ev[2], st));
+    if (queued == hipSuccess) wrote(hipEventRecord(ev[2], st));
     const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
     wrote(done);
     if (queued != hipSuccess) ts.tri_valid = ts.mask_valid = false;   // (the records and the bytes may be half rewritten)
@@ -284,8 +247,8 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
     HIPCHK(ctx, hipMemcpy(&hc, d_ext, sizeof(hc), hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(&hr, d_trr, sizeof(hr), hipMemcpyDeviceToHost));
     float prep_ms = 0.f, all_ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, t.ev[0], t.ev[1]));
-    HIPCHK(ctx, hipEventElapsedTime(&all_ms, t.ev[0], t.ev[2]));
+    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, ev[0], ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&all_ms, ev[0], ev[2]));
     msfm_extend_stats s = {};
     s.images_added = added;
     s.tracks_touched = (int64_t)hc.tracks_touched;

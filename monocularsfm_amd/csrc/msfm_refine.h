@@ -3,8 +3,8 @@
 // poses by Levenberg-Marquardt, one 3 x 3 system per point.  Poses, tracks and inlier bytes never change.
 //
 // The contract of msfm_pose.h holds: fp64 with +, -, *, /, sqrt only, static loop structure, -ffp-contract=off on both sides, every
-// sum in observation order -> the host twin and the device produce the SAME bits.  Pose, parallax, obs_error are msfm_triangulate.h's,
-// undistort is msfm_emat.h's, kDepthEps is msfm_pose.h's.
+// sum in observation order -> the host twin and the device produce the SAME bits.  Pose, parallax_scan, transform, obs_error are
+// msfm_triangulate.h's, undistort is msfm_emat.h's, kDepthEps is msfm_pose.h's.
 //
 //   observations    one Obs per kept observation, aligned with the track CSR (prepare_obs): the undistorted (u, v) of
 //                   msfm_triangulate.h, the rank of the image's pose, USED (the image has a valid pose) and FIT (USED, and the inlier
@@ -16,7 +16,8 @@
 //                   H += J^T J (upper triangle, the row of rx before the row of ry), g += J^T r, in observation order from 0.0.
 //   step            A = H + lambda diag(H);  A = L L^T by a 3 x 3 Cholesky;  L y = -g;  L^T delta = y.  A pivot that is not > 0 or a
 //                   non-finite delta: the step is rejected without a cost evaluation.
-//   LM              lambda = kLambda0; c = c(X) at the record's X.  While fewer than max_iters steps have been evaluated:
+//   LM              lm_minimise below over PointProblem:  lambda = kLambda0; c = c(X) at the record's X.  While fewer than max_iters
+//                   steps have been evaluated:
 //                     (H, g at X are recomputed only after X changed.)  One step is evaluated:  Xn = X + delta.
 //                     ACCEPTED iff c(Xn) is finite, c(Xn) < c, and every fitting view has Y.z > kDepthEps at Xn:
 //                       X = Xn, c = c(Xn), lambda = max(lambda / 10, kLambdaFloor);
@@ -25,9 +26,9 @@
 //                   Leaving the loop at max_iters evaluated steps: MAX_ITERS (also for max_iters = 0).
 //   verdict         nothing accepted: the record stays.  Otherwise, at the final X with the thresholds of the triangulation that made
 //                   the points: err (obs_error) of every USED observation; over the fitting set, in observation order: the errors'
-//                   sum, ERROR_OK iff every err <= max_error (a NaN fails), DEPTH_OK iff every Y.z > kDepthEps, the parallax scan
-//                   for i: for j < i with triangulate_track's stop rule.  The refined point STANDS iff none of ERROR_OK, ANGLE_OK,
-//                   DEPTH_OK that the record had is cleared (its cost is strictly lower: a step was accepted).
+//                   sum, ERROR_OK iff every err <= max_error (a NaN fails), DEPTH_OK iff every Y.z > kDepthEps, ANGLE_OK and the
+//                   angle by msfm_tri::parallax_scan over the fitting set (point_verdict below).  The refined point STANDS iff none
+//                   of ERROR_OK, ANGLE_OK, DEPTH_OK that the record had is cleared (its cost is strictly lower: a step was accepted).
 //   record          stands: X, mean_residual = sum / |fitting set|, tri_angle, status = ATTEMPTED | POINT | the three bits | the
 //                   record's ROBUST bit | REFINED; the residual slot of every USED observation gets its new error.  n_views and the
 //                   slots of unposed elements are not written.  Does not stand: nothing is written.
@@ -104,11 +105,10 @@ MSFM_FHD double cost(const Obs* obs, int n, const msfm_tri::Pose* poses, double 
         const Obs o = obs[k];
         if (!(o.flags & OBS_FIT)) continue;
         const msfm_tri::Pose* p = poses + o.rank;
-        const double Y0 = p->R[0] * X[0] + p->R[1] * X[1] + p->R[2] * X[2] + p->t[0];
-        const double Y1 = p->R[3] * X[0] + p->R[4] * X[1] + p->R[5] * X[2] + p->t[1];
-        const double Y2 = p->R[6] * X[0] + p->R[7] * X[1] + p->R[8] * X[2] + p->t[2];
-        d = d && Y2 > msfm_pose::kDepthEps;
-        const double rx = (Y0 / Y2 - o.u) * f, ry = (Y1 / Y2 - o.w) * f;
+        double Y[3];
+        msfm_tri::transform(p->R, p->t, X, Y);
+        d = d && Y[2] > msfm_pose::kDepthEps;
+        const double rx = (Y[0] / Y[2] - o.u) * f, ry = (Y[1] / Y[2] - o.w) * f;
         c = c + rx * rx;
         c = c + ry * ry;
     }
@@ -123,10 +123,9 @@ MSFM_FHD void normal_system(const Obs* obs, int n, const msfm_tri::Pose* poses, 
         const Obs o = obs[k];
         if (!(o.flags & OBS_FIT)) continue;
         const msfm_tri::Pose* p = poses + o.rank;
-        const double Y0 = p->R[0] * X[0] + p->R[1] * X[1] + p->R[2] * X[2] + p->t[0];
-        const double Y1 = p->R[3] * X[0] + p->R[4] * X[1] + p->R[5] * X[2] + p->t[1];
-        const double Y2 = p->R[6] * X[0] + p->R[7] * X[1] + p->R[8] * X[2] + p->t[2];
-        const double x = Y0 / Y2, y = Y1 / Y2, s = f / Y2;
+        double Y[3];
+        msfm_tri::transform(p->R, p->t, X, Y);
+        const double x = Y[0] / Y[2], y = Y[1] / Y[2], s = f / Y[2];
         const double rx = (x - o.u) * f, ry = (y - o.w) * f;
         const double a0 = (p->R[0] - x * p->R[6]) * s, a1 = (p->R[1] - x * p->R[7]) * s, a2 = (p->R[2] - x * p->R[8]) * s;
         const double b0 = (p->R[3] - y * p->R[6]) * s, b1 = (p->R[4] - y * p->R[7]) * s, b2 = (p->R[5] - y * p->R[8]) * s;
@@ -185,53 +184,54 @@ MSFM_FHD bool solve_step(const double H[6], const double g[3], double lambda, do
     return msfm_pose::finite(z0) && msfm_pose::finite(z1) && msfm_pose::finite(z2);
 }
 
-// One track: obs, residuals: its n element-aligned slots; rec: its record (read, and rewritten iff the refined point stands).
-// tally is always filled; trace may be null and changes nothing.
-MSFM_FHD void refine_track(const Obs* obs, int n, const msfm_tri::Pose* poses, double f, const Verdict& vd, const Params& prm,
-                           msfm_point3d* rec, double* residuals, Tally* tally, Trace* trace) {
-    *tally = Tally{0, 0, 0, 0, 0, 0.0, 0.0};
-    if (trace) *trace = Trace{0, 0, STOP_NONE, NOT_ELIGIBLE, 0, 0, 0.0, 0.0};
-    const msfm_point3d old = *rec;
-    if (!eligible(old)) return;
-    double X[3] = {old.X[0], old.X[1], old.X[2]};
+// ---- the Levenberg-Marquardt loop (the LM paragraphs above and of msfm_refine_poses.h) ------------------------------------------------
+// What one run leaves; the two trace counters are dead code where nobody reads them.
+struct LmRun {
+    int32_t steps, accepted, stop, accepted_after_rejected, depth_rejected;
+    double lambda, cost_before, cost;   // the final damping, c at the start, c at the final state
+};
+
+// `pb` is the problem:  typename P::State (copyable), typename P::System;
+//   pb.cost(s, &depth) -> c at the state s, depth: every fitting view has Y.z > kDepthEps;
+//   pb.linearise(s, &sys): the normal system at s;
+//   pb.step(sys, lambda, s, &sn, &d2) -> the damped step from s to the candidate sn, d2 = |delta|^2; false: no step;
+//   pb.stop_scale(s): an accepted step ends the run (STEP) iff d2 <= step_tol^2 stop_scale(s), s the new state.
+// s: the start, and the final state of the loop.
+template <class P>
+MSFM_FHD void lm_minimise(const P& pb, int max_iters, double step_tol, typename P::State* s, LmRun* run) {
     bool depth;
-    double c = cost(obs, n, poses, f, X, &depth);
+    double c = pb.cost(*s, &depth);
     const double c0 = c;
-    double lambda = kLambda0, H[6], g[3];
+    double lambda = kLambda0;
+    typename P::System sys;
     bool fresh = false, last_rejected = false;
-    int steps = 0, accepted = 0, stop = STOP_MAX_ITERS;
-    while (steps < prm.max_iters) {
+    int steps = 0, accepted = 0, stop = STOP_MAX_ITERS, after_rejected = 0, depth_rejected = 0;
+    while (steps < max_iters) {
         if (!fresh) {
-            normal_system(obs, n, poses, f, X, H, g);
+            pb.linearise(*s, &sys);
             fresh = true;
         }
         steps += 1;
-        double delta[3], Xn[3] = {X[0], X[1], X[2]};
-        bool accept = solve_step(H, g, lambda, delta);
+        typename P::State sn;
+        double d2;
+        bool accept = pb.step(sys, lambda, *s, &sn, &d2);
         if (accept) {
-            Xn[0] = X[0] + delta[0];
-            Xn[1] = X[1] + delta[1];
-            Xn[2] = X[2] + delta[2];
             bool dn;
-            const double cn = cost(obs, n, poses, f, Xn, &dn);
+            const double cn = pb.cost(sn, &dn);
             const bool lower = msfm_pose::finite(cn) && cn < c;
-            if (trace && lower && !dn) trace->depth_rejected += 1;
+            depth_rejected += (lower && !dn) ? 1 : 0;
             accept = lower && dn;
             if (accept) c = cn;
         }
         if (accept) {
-            X[0] = Xn[0];
-            X[1] = Xn[1];
-            X[2] = Xn[2];
+            *s = sn;
             fresh = false;
             accepted += 1;
-            if (trace && last_rejected) trace->accepted_after_rejected += 1;
+            after_rejected += last_rejected ? 1 : 0;
             last_rejected = false;
             lambda = lambda / 10.0;
             if (lambda < kLambdaFloor) lambda = kLambdaFloor;
-            const double d2 = delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2];
-            const double x2 = X[0] * X[0] + X[1] * X[1] + X[2] * X[2];
-            if (d2 <= prm.step_tol * prm.step_tol * (x2 + prm.step_tol)) {
+            if (d2 <= step_tol * step_tol * pb.stop_scale(*s)) {
                 stop = STOP_STEP;
                 break;
             }
@@ -244,57 +244,101 @@ MSFM_FHD void refine_track(const Obs* obs, int n, const msfm_tri::Pose* poses, d
             }
         }
     }
-    tally->eligible = 1;
-    tally->iterations = steps;
-    tally->cost_before = c0;
-    tally->cost_after = c0;
-    if (trace) {
-        trace->steps = steps;
-        trace->accepted = accepted;
-        trace->stop = stop;
-        trace->lambda = lambda;
-        trace->cost = c;
-        trace->verdict = NO_ACCEPTED_STEP;
+    *run = LmRun{steps, accepted, stop, after_rejected, depth_rejected, lambda, c0, c};
+}
+
+MSFM_FHD void trace_of(const LmRun& run, int verdict, Trace* trace) {
+    *trace = Trace{run.steps, run.accepted, run.stop, verdict, run.accepted_after_rejected, run.depth_rejected, run.lambda, run.cost};
+}
+
+// one point under fixed poses: the 3 x 3 problem of lm_minimise
+struct PointProblem {
+    struct State {
+        double X[3];
+    };
+    struct System {
+        double H[6], g[3];
+    };
+    const Obs* obs;
+    int n;
+    const msfm_tri::Pose* poses;
+    double f, step_tol;
+    MSFM_FHD double cost(const State& s, bool* depth) const { return msfm_ref::cost(obs, n, poses, f, s.X, depth); }
+    MSFM_FHD void linearise(const State& s, System* sys) const { normal_system(obs, n, poses, f, s.X, sys->H, sys->g); }
+    MSFM_FHD bool step(const System& sys, double lambda, const State& s, State* sn, double* d2) const {
+        double delta[3];
+        if (!solve_step(sys.H, sys.g, lambda, delta)) return false;
+        sn->X[0] = s.X[0] + delta[0];
+        sn->X[1] = s.X[1] + delta[1];
+        sn->X[2] = s.X[2] + delta[2];
+        *d2 = delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2];
+        return true;
     }
-    if (accepted == 0) return;
-    // the verdict at X over the fitting set
+    MSFM_FHD double stop_scale(const State& s) const { return (s.X[0] * s.X[0] + s.X[1] * s.X[1] + s.X[2] * s.X[2]) + step_tol; }
+};
+
+// ---- the verdict of a point at X over its Obs ----------------------------------------------------------------------------------------
+struct PointVerdict {
+    int32_t bits, count;   // ERROR_OK | ANGLE_OK | DEPTH_OK as they hold over the fitting set; |fitting set|
+    double sum, angle;     // the fitting set's errors summed in observation order from 0.0; the parallax scan's angle
+};
+
+// err (obs_error) over the fitting set, in observation order: the sum, ERROR_OK iff every err <= max_error (a NaN fails), DEPTH_OK iff
+// every Y.z > kDepthEps; ANGLE_OK and the angle by msfm_tri::parallax_scan over the fitting set.  Two modes, the same sums in both:
+//   residuals != nullptr  the loop visits every USED observation, writes its error to its slot, and lets only the FIT ones (the second
+//                         filter) into the sums: reverdict_track.
+//   residuals == nullptr  the loop visits the FIT observations alone and NO slot is written: refine_track, which may not touch a slot
+//                         before it knows that the point stands, and then writes the USED observations' errors in a loop of its own.
+MSFM_FHD void point_verdict(const Obs* obs, int n, const msfm_tri::Pose* poses, double f, const Verdict& vd, const double X[3],
+                            double* residuals, PointVerdict* out) {
     bool error_ok = true, depth_ok = true;
     double sum = 0.0;
     int count = 0;
     for (int k = 0; k < n; ++k) {
         const Obs o = obs[k];
-        if (!(o.flags & OBS_FIT)) continue;
+        if (!(o.flags & (residuals ? OBS_USED : OBS_FIT))) continue;
         const msfm_tri::Pose* p = poses + o.rank;
         bool d;
         const double err = msfm_tri::obs_error(p->R, p->t, o.u, o.w, X, f, &d);
+        if (residuals) residuals[k] = err;
+        if (!(o.flags & OBS_FIT)) continue;
         depth_ok = depth_ok && d;
         error_ok = error_ok && err <= vd.max_error;   // (false for a NaN)
         sum = sum + err;
         count += 1;
     }
-    bool angle_ok = false;
-    double angle = 0.0;
-    for (int i = 1; i < n && !angle_ok; ++i) {
-        const Obs oi = obs[i];
-        if (!(oi.flags & OBS_FIT)) continue;
-        const msfm_tri::Pose* pi = poses + oi.rank;
-        const double Oi[3] = {pi->O[0], pi->O[1], pi->O[2]};
-        for (int j = 0; j < i; ++j) {
-            const Obs oj = obs[j];
-            if (!(oj.flags & OBS_FIT)) continue;
-            const msfm_tri::Pose* pj = poses + oj.rank;
-            const double Oj[3] = {pj->O[0], pj->O[1], pj->O[2]};
-            const double a = msfm_tri::parallax(X, Oi, Oj);
-            if (a >= vd.min_angle) {
-                angle = a;
-                angle_ok = true;
-                break;
-            }
-            if (a > angle) angle = a;
-        }
-    }
-    const int bits = (error_ok ? MSFM_TRI_ERROR_OK : 0) | (angle_ok ? MSFM_TRI_ANGLE_OK : 0) | (depth_ok ? MSFM_TRI_DEPTH_OK : 0);
-    const int cleared = old.status & ~bits & (MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK | MSFM_TRI_DEPTH_OK);
+    double angle;
+    const bool angle_ok = msfm_tri::parallax_scan(X, n, vd.min_angle, [&](int k) -> const double* {
+        const Obs o = obs[k];
+        return (o.flags & OBS_FIT) ? poses[o.rank].O : nullptr;
+    }, &angle);
+    out->bits = (error_ok ? MSFM_TRI_ERROR_OK : 0) | (angle_ok ? MSFM_TRI_ANGLE_OK : 0) | (depth_ok ? MSFM_TRI_DEPTH_OK : 0);
+    out->count = count;
+    out->sum = sum;
+    out->angle = angle;
+}
+
+// One track: obs, residuals: its n element-aligned slots; rec: its record (read, and rewritten iff the refined point stands).
+// tally is always filled; trace may be null and changes nothing.
+MSFM_FHD void refine_track(const Obs* obs, int n, const msfm_tri::Pose* poses, double f, const Verdict& vd, const Params& prm,
+                           msfm_point3d* rec, double* residuals, Tally* tally, Trace* trace) {
+    *tally = Tally{0, 0, 0, 0, 0, 0.0, 0.0};
+    if (trace) *trace = Trace{0, 0, STOP_NONE, NOT_ELIGIBLE, 0, 0, 0.0, 0.0};
+    const msfm_point3d old = *rec;
+    if (!eligible(old)) return;
+    const PointProblem pb{obs, n, poses, f, prm.step_tol};
+    PointProblem::State s = {{old.X[0], old.X[1], old.X[2]}};
+    LmRun run;
+    lm_minimise(pb, prm.max_iters, prm.step_tol, &s, &run);
+    tally->eligible = 1;
+    tally->iterations = run.steps;
+    tally->cost_before = run.cost_before;
+    tally->cost_after = run.cost_before;
+    if (trace) trace_of(run, NO_ACCEPTED_STEP, trace);
+    if (run.accepted == 0) return;
+    PointVerdict v;
+    point_verdict(obs, n, poses, f, vd, s.X, nullptr, &v);
+    const int cleared = old.status & ~v.bits & (MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK | MSFM_TRI_DEPTH_OK);
     if (trace) trace->verdict = cleared;
     if (cleared) {
         tally->rejected_by_verdict = 1;
@@ -305,19 +349,19 @@ MSFM_FHD void refine_track(const Obs* obs, int n, const msfm_tri::Pose* poses, d
         if (!(o.flags & OBS_USED)) continue;
         const msfm_tri::Pose* p = poses + o.rank;
         bool d;
-        residuals[k] = msfm_tri::obs_error(p->R, p->t, o.u, o.w, X, f, &d);
+        residuals[k] = msfm_tri::obs_error(p->R, p->t, o.u, o.w, s.X, f, &d);
     }
     msfm_point3d r = old;
-    r.status = MSFM_TRI_ATTEMPTED | MSFM_TRI_POINT | bits | (old.status & MSFM_TRI_ROBUST) | MSFM_TRI_REFINED;
-    r.X[0] = X[0];
-    r.X[1] = X[1];
-    r.X[2] = X[2];
-    r.mean_residual = sum / (double)count;
-    r.tri_angle = angle;
+    r.status = MSFM_TRI_ATTEMPTED | MSFM_TRI_POINT | v.bits | (old.status & MSFM_TRI_ROBUST) | MSFM_TRI_REFINED;
+    r.X[0] = s.X[0];
+    r.X[1] = s.X[1];
+    r.X[2] = s.X[2];
+    r.mean_residual = v.sum / (double)v.count;
+    r.tri_angle = v.angle;
     *rec = r;
     tally->refined = 1;
-    tally->gained_error_ok = (error_ok && !(old.status & MSFM_TRI_ERROR_OK)) ? 1 : 0;
-    tally->cost_after = c;
+    tally->gained_error_ok = ((v.bits & MSFM_TRI_ERROR_OK) && !(old.status & MSFM_TRI_ERROR_OK)) ? 1 : 0;
+    tally->cost_after = run.cost;
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -326,6 +370,16 @@ struct Counts {
     long long eligible, refined, gained_error_ok, rejected_by_verdict, iterations;
     double cost_before, cost_after;   // summed in track order
 };
+
+// the n Obs of one track: mask: the track's inlier bytes (element-aligned), or null = every byte 1
+inline void host_obs(const msfm_tri::HostTrack& a, int n, const uint8_t* mask, const msfm_emat::Camera& cam, Obs* out) {
+    for (int k = 0; k < n; ++k) {
+        const msfm_tri::Pose* p = a.pose(k);
+        double x = 0.0, y = 0.0;
+        if (p) a.pixel(k, &x, &y);
+        prepare_obs(p, p ? (int)(p - a.poses) : -1, x, y, mask ? mask[k] != 0 : true, cam, out + k);
+    }
+}
 
 // tracks, rank_of_id, kxy, poses as TriangulateTracks takes them; mask: the robust call's inlier bytes, or null after the plain call;
 // points / residuals: read and rewritten in place.  `counts` (may be null) is added to; out_trace (may be null): one Trace per track
@@ -341,12 +395,7 @@ inline void RefinePoints(const int64_t* offsets, const int32_t* image_ids, const
         const int n = (int)(e - b);
         const msfm_tri::HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
         obs.resize((size_t)n);
-        for (int k = 0; k < n; ++k) {
-            const msfm_tri::Pose* p = a.pose(k);
-            double x = 0.0, y = 0.0;
-            if (p) a.pixel(k, &x, &y);
-            prepare_obs(p, p ? (int)(p - poses) : -1, x, y, mask ? mask[b + k] != 0 : true, cam, &obs[(size_t)k]);
-        }
+        host_obs(a, n, mask ? mask + b : nullptr, cam, obs.data());
         Tally tl;
         refine_track(obs.data(), n, poses, f, vd, prm, points + t, residuals + b, &tl, out_trace ? out_trace + t : nullptr);
         if (counts) {

@@ -1,7 +1,7 @@
 // msfm_refine.hip.h -- point refinement on the device (include/msfm_match.h "point refinement"): the two kernels
 // and the host side of msfm_refine_points (defined in msfm_match.hip).  The arithmetic is msfm_refine.h, shared with the host twin
-// RefinePoints: the same bits.  Included by msfm_match.hip behind msfm_triangulate_robust.hip.h, whose tri_pose_kernel, TriImage and
-// tri_prepare it reuses.
+// RefinePoints: the same bits.  Included by msfm_match.hip behind msfm_triangulate_robust.hip.h, whose PoseTables, tri_tables and
+// wave_add_counters it reuses.
 //
 // Everything runs on the library's stream between HIP events; the host waits once, at the end.
 //   ref_obs_kernel     one lane per kept OBSERVATION, grid-stride: the dependent gather of tri_track_kernel (CSR element -> image table
@@ -10,8 +10,8 @@
 //                      the records: observations of tracks that are not eligible are resolved too and never read.
 //   ref_track_kernel   one lane per kept track, grid-stride, 256 threads, no LDS; lanes of tracks that are not eligible fall through.
 //                      A lane reads only its track's Obs and the prepared poses; H, g, the Cholesky factor and X live in registers
-//                      (every index is a compile-time constant), lanes leave the LM loop individually.  The five counters are reduced
-//                      per wave by shuffles and added with one vector atomic per wave and counter; the two cost sums are reduced per
+//                      (every index is a compile-time constant), lanes leave the LM loop individually.  The five counters go through
+//                      wave_add_counters; the two cost sums are reduced per
 //                      wave by the same fixed shuffle tree and STORED per wave (no floating-point atomics: the host adds the waves'
 //                      sums in wave order).
 // Plain vector loads and stores only.
@@ -67,16 +67,9 @@ __global__ __launch_bounds__(256) void ref_track_kernel(const long long* __restr
         before = before + tl.cost_before;
         after = after + tl.cost_after;
     }
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(counters);
+    wave_add_counters(c, reinterpret_cast<unsigned long long*>(counters));
 #pragma unroll
-    for (int k = 0; k < kRefCounters; ++k) {
-        unsigned long long v = c[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(out + k, v);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
+    for (int d = 32; d >= 1; d >>= 1) {   // (the cost sums: a fixed tree and a store per wave, no floating-point atomics)
         before = before + __shfl_down(before, d, 64);
         after = after + __shfl_down(after, d, 64);
     }
@@ -94,84 +87,63 @@ namespace {
 int refine_impl(msfm_ctx* ctx, const msfm_refine_params* params, msfm_refine_stats* stats) {
     TrackSession& ts = ctx->tracks;
     const std::string who = "msfm_refine_points";
-    if (!ts.open) return fail(ctx, MSFM_E_STATE, who + " without a track session (msfm_tracks_begin)");
-    if (!ts.finished || !ts.tri_valid)
-        return fail(ctx, MSFM_E_STATE, who + " without points: msfm_triangulate_tracks has not run since the last msfm_tracks_finish");
-    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, who + " while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (const int rc = tri_session_check(ctx, who, true)) return rc;
     msfm_ref::Params prm = {1e-10, 10, 0};
     if (params) prm = msfm_ref::Params{params->step_tol, params->max_iters, 0};
     if (prm.max_iters < 0 || prm.max_iters > 100) return fail(ctx, MSFM_E_INVALID, who + ": max_iters must lie in 0 .. 100");
     if (!std::isfinite(prm.step_tol) || prm.step_tol < 0.0) return fail(ctx, MSFM_E_INVALID, who + ": step_tol must be finite and not negative");
-    // the device tables through the triangulation's own host path; it drops the session's validity flags "whatever happens below":
-    // the points and the inlier bytes are not touched by it, so theirs come back
+    // from here on the registrations and the pose refinement's records are gone: they describe the points as they were (DESIGN.md,
+    // the flag table of section 15)
+    ts.reg_valid = ts.rp_valid = false;
     const bool had_mask = ts.mask_valid;
     std::vector<msfm_pose_rt> by_rank;
     std::vector<TriImage> table;
-    const int rc = tri_prepare(ctx, who, &ts.tri_camera, ts.tri_ids.data(), ts.tri_poses.data(), (int)ts.tri_ids.size(),
-                               msfm_tri::Params{ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0}, &by_rank, &table);
-    ts.tri_valid = true;
-    ts.mask_valid = had_mask;
-    if (rc) return rc;
-    const msfm_camera c = ts.tri_camera;
-    const int n_img = (int)ts.nd.ids.size();
+    if (const int rc = tri_tables(ctx, who, &ts.tri_camera, ts.tri_ids.data(), ts.tri_poses.data(), (int)ts.tri_ids.size(),
+                                  msfm_tri::Params{ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0}, &by_rank, &table))
+        return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
-    struct Tmp {   // freed when the call returns, whatever it returns
-        DevBuf in, poses, table, counters, obs, costs;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        ~Tmp() {
-            for (DevBuf* b : {&in, &poses, &table, &counters, &obs, &costs}) b->release();
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } t;
+    PoseTables pt;   // (the temporaries are freed when the call returns, whatever it returns)
+    TmpBuf counters, obs, wave_costs;
+    TmpEvents<3> ev;
     hipStream_t st = store_stream(ctx);
     const unsigned grid = tk_grid(ctx, T);
     const size_t waves = (size_t)grid * 4;
-    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
-    HIPCHK(ctx, t.in.ensure(by_rank.size() * sizeof(msfm_pose_rt)));
-    HIPCHK(ctx, t.poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose)));
-    HIPCHK(ctx, t.table.ensure(table.size() * sizeof(TriImage)));
-    HIPCHK(ctx, t.counters.ensure(sizeof(RefCounters)));
-    HIPCHK(ctx, t.obs.ensure((size_t)std::max<long long>(1, O) * sizeof(msfm_ref::Obs)));
-    HIPCHK(ctx, t.costs.ensure(2 * waves * sizeof(double)));
-    // (synchronous copies of the two small tables: nothing queued reads host memory that an early return below would free)
-    HIPCHK(ctx, hipMemcpy(t.in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(t.table.p, table.data(), table.size() * sizeof(TriImage), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(RefCounters), st));
-    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
-    if (n_img > 0) {
-        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)t.in.as<msfm_pose_rt>(), n_img,
-                           t.poses.as<msfm_tri::Pose>());
-        HIPCHK(ctx, hipGetLastError());
-    }
-    const msfm_emat::Camera cam{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+    HIPCHK(ctx, ev.create());
+    HIPCHK(ctx, counters.ensure(sizeof(RefCounters)));
+    HIPCHK(ctx, obs.ensure((size_t)std::max<long long>(1, O) * sizeof(msfm_ref::Obs)));
+    HIPCHK(ctx, wave_costs.ensure(2 * waves * sizeof(double)));
+    HIPCHK(ctx, pt.upload(ts.tri_camera, by_rank, table, (int)ts.nd.ids.size()));
+    HIPCHK(ctx, hipMemsetAsync(counters.p, 0, sizeof(RefCounters), st));
+    HIPCHK(ctx, hipEventRecord(ev[0], st));
+    HIPCHK(ctx, pt.prepare(st));
+    const msfm_emat::Camera cam = pt.cam;
     if (T > 0 && O > 0) {
         hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
-                           (const TriImage*)t.table.as<TriImage>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(),
+                           pt.d_table(), pt.d_poses(),
                            had_mask ? (const unsigned char*)ts.t_mask.as<unsigned char>() : (const unsigned char*)nullptr, cam,
-                           t.obs.as<msfm_ref::Obs>());
+                           obs.as<msfm_ref::Obs>());
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(t.ev[1], st));
+    HIPCHK(ctx, hipEventRecord(ev[1], st));
     if (T > 0) {
         hipLaunchKernelGGL(ref_track_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(), (int)T,
-                           (const msfm_ref::Obs*)t.obs.as<msfm_ref::Obs>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(),
+                           (const msfm_ref::Obs*)obs.as<msfm_ref::Obs>(), pt.d_poses(),
                            (cam.fx + cam.fy) / 2.0, msfm_ref::Verdict{ts.tri_prm.max_error, ts.tri_prm.min_angle}, prm,
-                           ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), t.counters.as<RefCounters>(), t.costs.as<double>());
+                           ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), counters.as<RefCounters>(), wave_costs.as<double>());
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(t.ev[2], st));
+    HIPCHK(ctx, hipEventRecord(ev[2], st));
     const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
     if (done != hipSuccess) ts.tri_valid = ts.mask_valid = false;   // (the records may be half rewritten)
     HIPCHK(ctx, done);
     RefCounters hc = {};
-    HIPCHK(ctx, hipMemcpy(&hc, t.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(&hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost));
     std::vector<double> costs(2 * waves, 0.0);
-    if (T > 0) HIPCHK(ctx, hipMemcpy(costs.data(), t.costs.p, costs.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (T > 0) HIPCHK(ctx, hipMemcpy(costs.data(), wave_costs.p, costs.size() * sizeof(double), hipMemcpyDeviceToHost));
     float prep_ms = 0.f, all_ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, t.ev[0], t.ev[1]));
-    HIPCHK(ctx, hipEventElapsedTime(&all_ms, t.ev[0], t.ev[2]));
+    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, ev[0], ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&all_ms, ev[0], ev[2]));
     msfm_refine_stats s = {};
     s.eligible = (int64_t)hc.eligible;
     s.refined = (int64_t)hc.refined;

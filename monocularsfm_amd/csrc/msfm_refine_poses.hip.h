@@ -1,7 +1,7 @@
 // msfm_refine_poses.hip.h -- pose refinement on the device (include/msfm_match.h "pose refinement"): the kernels and
 // the host side of msfm_refine_poses / msfm_fetch_poses / msfm_fetch_pose_refinements (defined in msfm_match.hip).  The arithmetic is
 // msfm_refine_poses.h, shared with the host twin RefinePoses: the same bits.  Included by msfm_match.hip behind msfm_refine.hip.h, whose
-// ref_obs_kernel it reuses beside tri_pose_kernel, TriImage and tri_prepare.
+// ref_obs_kernel it reuses beside PoseTables, tri_tables and wave_add_counters.
 //
 // Everything runs on the library's stream between HIP events; the host waits once for the size of the image-major list and once at the
 // end.
@@ -18,8 +18,8 @@
 //                      the record and the rank's `changed` byte.  The four counters are wave-uniform: lane 0 adds each with one vector
 //                      atomic per wave.  The costs are stored in the records; the host adds them in list order.
 //   rp_verdict_kernel  one lane per kept track, grid-stride: a lane scans its track's Obs for a changed rank and falls through if
-//                      there is none; otherwise the re-verdict under the new pose table.  Its three counters are reduced per wave by
-//                      shuffles and added with one vector atomic each.
+//                      there is none; otherwise the re-verdict under the new pose table.  Its three counters go through
+//                      wave_add_counters.
 // Plain vector loads and stores only; no LDS; no floating-point atomics.
 #pragma once
 #include "msfm_refine_poses.h"
@@ -194,14 +194,7 @@ __global__ __launch_bounds__(256) void rp_verdict_kernel(const long long* __rest
         c[1] += (unsigned long long)tl.lost;
         c[2] += (unsigned long long)tl.gained;
     }
-    unsigned long long* out = &counters->points_reposed;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        unsigned long long v = c[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(out + k, v);
-    }
+    wave_add_counters(c, &counters->points_reposed);
 }
 
 }  // namespace msfm
@@ -212,10 +205,7 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
                       msfm_pose_refine_stats* stats) {
     TrackSession& ts = ctx->tracks;
     const std::string who = "msfm_refine_poses";
-    if (!ts.open) return fail(ctx, MSFM_E_STATE, who + " without a track session (msfm_tracks_begin)");
-    if (!ts.finished || !ts.tri_valid)
-        return fail(ctx, MSFM_E_STATE, who + " without points: msfm_triangulate_tracks has not run since the last msfm_tracks_finish");
-    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, who + " while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (const int rc = tri_session_check(ctx, who, true)) return rc;
     msfm_rp::Params prm = {1e-6, 10, 15};
     if (params) prm = msfm_rp::Params{params->step_tol, params->max_iters, params->min_observations};
     if (prm.max_iters < 0 || prm.max_iters > 100) return fail(ctx, MSFM_E_INVALID, who + ": max_iters must lie in 0 .. 100");
@@ -231,17 +221,14 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
         if (fixed[(size_t)r]) return fail(ctx, MSFM_E_INVALID, who + ": a fixed image is given twice: " + std::to_string(id));
         fixed[(size_t)r] = 1;
     }
-    // the device tables through the triangulation's own host path, as msfm_refine_points does: the points and the inlier bytes are not
-    // touched by it, so their validity comes back
+    // from here on the registrations and the previous records are gone, as after msfm_refine_points
+    ts.reg_valid = ts.rp_valid = false;
     const bool had_mask = ts.mask_valid;
     std::vector<msfm_pose_rt> by_rank;
     std::vector<TriImage> table;
-    const int rc = tri_prepare(ctx, who, &ts.tri_camera, ts.tri_ids.data(), ts.tri_poses.data(), (int)ts.tri_ids.size(),
-                               msfm_tri::Params{ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0}, &by_rank, &table);
-    ts.tri_valid = true;
-    ts.mask_valid = had_mask;
-    if (rc) return rc;
-    const msfm_camera c = ts.tri_camera;
+    if (const int rc = tri_tables(ctx, who, &ts.tri_camera, ts.tri_ids.data(), ts.tri_poses.data(), (int)ts.tri_ids.size(),
+                                  msfm_tri::Params{ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0}, &by_rank, &table))
+        return rc;
     const int n_list = (int)ts.tri_ids.size();
     std::vector<RpImage> list((size_t)std::max(n_list, 1), RpImage{0, 0, 0, 0});
     std::vector<unsigned char> candidate((size_t)std::max(n_img, 1), 0);
@@ -254,23 +241,14 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
     if (O > 0x7fffffffLL) return fail(ctx, MSFM_E_CAPACITY, who + ": more than 2^31 - 1 kept observations");
-    struct Tmp {   // freed when the call returns, whatever it returns
-        DevBuf in, poses, table, counters, obs, list, candidate, changed, records, keys, keys2, vals, vals2, sort_tmp, offsets, cu, cw, cX, cY, cZ;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        ~Tmp() {
-            for (DevBuf* b : {&in, &poses, &table, &counters, &obs, &list, &candidate, &changed, &records, &keys, &keys2, &vals, &vals2, &sort_tmp,
-                              &offsets, &cu, &cw, &cX, &cY, &cZ})
-                b->release();
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
+    PoseTables pt;   // (the temporaries are freed when the call returns, whatever it returns)
+    struct {
+        TmpBuf counters, obs, list, candidate, changed, records, keys, keys2, vals, vals2, sort_tmp, offsets, cu, cw, cX, cY, cZ;
     } t;
+    TmpEvents<3> ev;
     hipStream_t st = store_stream(ctx);
-    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
+    HIPCHK(ctx, ev.create());
     const size_t N = (size_t)std::max(n_img, 1), L = (size_t)std::max(n_list, 1), Oz = (size_t)std::max<long long>(1, O);
-    HIPCHK(ctx, t.in.ensure(by_rank.size() * sizeof(msfm_pose_rt)));
-    HIPCHK(ctx, t.poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose)));
-    HIPCHK(ctx, t.table.ensure(table.size() * sizeof(TriImage)));
     HIPCHK(ctx, t.counters.ensure(sizeof(RpCounters)));
     HIPCHK(ctx, t.obs.ensure(Oz * sizeof(msfm_ref::Obs)));
     HIPCHK(ctx, t.list.ensure(L * sizeof(RpImage)));
@@ -282,21 +260,16 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
     HIPCHK(ctx, t.vals.ensure(Oz * 4));
     HIPCHK(ctx, t.vals2.ensure(Oz * 4));
     HIPCHK(ctx, t.offsets.ensure((N + 1) * 8));
+    HIPCHK(ctx, pt.upload(ts.tri_camera, by_rank, table, n_img));
     // (synchronous copies of the small tables: nothing queued reads host memory that an early return below would free)
-    HIPCHK(ctx, hipMemcpy(t.in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(t.table.p, table.data(), table.size() * sizeof(TriImage), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(t.list.p, list.data(), L * sizeof(RpImage), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(t.candidate.p, candidate.data(), N, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(RpCounters), st));
     HIPCHK(ctx, hipMemsetAsync(t.changed.p, 0, N, st));
     HIPCHK(ctx, hipMemsetAsync(t.offsets.p, 0, (N + 1) * 8, st));
-    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
-    if (n_img > 0) {
-        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)t.in.as<msfm_pose_rt>(), n_img,
-                           t.poses.as<msfm_tri::Pose>());
-        HIPCHK(ctx, hipGetLastError());
-    }
-    const msfm_emat::Camera cam{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+    HIPCHK(ctx, hipEventRecord(ev[0], st));
+    HIPCHK(ctx, pt.prepare(st));
+    const msfm_emat::Camera cam = pt.cam;
     const double f = (cam.fx + cam.fy) / 2.0;
     const msfm_ref::Obs* d_obs = t.obs.as<msfm_ref::Obs>();
     const msfm_point3d* d_points = ts.t_points.as<msfm_point3d>();
@@ -304,7 +277,7 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
     long long M = 0;
     if (T > 0 && O > 0) {
         hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
-                           (const TriImage*)t.table.as<TriImage>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(),
+                           pt.d_table(), pt.d_poses(),
                            had_mask ? (const unsigned char*)ts.t_mask.as<unsigned char>() : (const unsigned char*)nullptr, cam,
                            t.obs.as<msfm_ref::Obs>());
         HIPCHK(ctx, hipGetLastError());
@@ -325,31 +298,31 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
         HIPCHK(ctx, hipStreamSynchronize(st));   // the first wait: the size of the image-major list
     }
     const size_t Mz = (size_t)std::max<long long>(1, M);
-    for (DevBuf* b : {&t.cu, &t.cw, &t.cX, &t.cY, &t.cZ}) HIPCHK(ctx, b->ensure(Mz * 8));
+    for (TmpBuf* b : {&t.cu, &t.cw, &t.cX, &t.cY, &t.cZ}) HIPCHK(ctx, b->ensure(Mz * 8));
     if (M > 0) {
         hipLaunchKernelGGL(rp_fill_kernel, dim3(tk_grid(ctx, M)), dim3(256), 0, st, keys2, (const int*)t.vals2.as<int>(), M, d_obs, d_points,
                            t.cu.as<double>(), t.cw.as<double>(), t.cX.as<double>(), t.cY.as<double>(), t.cZ.as<double>());
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(t.ev[1], st));
+    HIPCHK(ctx, hipEventRecord(ev[1], st));
     if (n_list > 0) {
         const unsigned groups = (unsigned)((n_list + 3) / 4);
         const unsigned grid = std::min<unsigned>(groups, 8u * (unsigned)std::max(1, ctx->cu_count));
         hipLaunchKernelGGL(rp_image_kernel, dim3(grid), dim3(256), 0, st, (const RpImage*)t.list.as<RpImage>(), n_list,
                            (const long long*)t.offsets.as<long long>(), (const double*)t.cu.as<double>(), (const double*)t.cw.as<double>(),
                            (const double*)t.cX.as<double>(), (const double*)t.cY.as<double>(), (const double*)t.cZ.as<double>(), f,
-                           ts.tri_prm.max_error, prm, t.poses.as<msfm_tri::Pose>(), t.records.as<msfm_pose_refinement>(),
+                           ts.tri_prm.max_error, prm, pt.poses.as<msfm_tri::Pose>(), t.records.as<msfm_pose_refinement>(),
                            t.changed.as<unsigned char>(), t.counters.as<RpCounters>());
         HIPCHK(ctx, hipGetLastError());
     }
     if (T > 0 && O > 0 && n_list > 0) {
         hipLaunchKernelGGL(rp_verdict_kernel, dim3(tk_grid(ctx, T)), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(), (int)T, d_obs,
-                           (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), (const unsigned char*)t.changed.as<unsigned char>(), f,
+                           pt.d_poses(), (const unsigned char*)t.changed.as<unsigned char>(), f,
                            msfm_ref::Verdict{ts.tri_prm.max_error, ts.tri_prm.min_angle}, ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(),
                            t.counters.as<RpCounters>());
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(t.ev[2], st));
+    HIPCHK(ctx, hipEventRecord(ev[2], st));
     const hipError_t done = hipStreamSynchronize(st);   // the second wait (before anything returns: the temporaries die with this function)
     if (done != hipSuccess) ts.tri_valid = ts.mask_valid = false;   // (the records may be half rewritten)
     HIPCHK(ctx, done);
@@ -359,13 +332,13 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
     std::vector<unsigned char> changed(N, 0);
     hipError_t back = hipMemcpy(&hc, t.counters.p, sizeof(hc), hipMemcpyDeviceToHost);
     if (back == hipSuccess && n_list > 0) back = hipMemcpy(records.data(), t.records.p, L * sizeof(msfm_pose_refinement), hipMemcpyDeviceToHost);
-    if (back == hipSuccess && n_img > 0) back = hipMemcpy(poses.data(), t.poses.p, N * sizeof(msfm_tri::Pose), hipMemcpyDeviceToHost);
+    if (back == hipSuccess && n_img > 0) back = hipMemcpy(poses.data(), pt.poses.p, N * sizeof(msfm_tri::Pose), hipMemcpyDeviceToHost);
     if (back == hipSuccess) back = hipMemcpy(changed.data(), t.changed.p, N, hipMemcpyDeviceToHost);
     if (back != hipSuccess) ts.tri_valid = ts.mask_valid = false;   // (the points may describe poses the session does not have)
     HIPCHK(ctx, back);
     float prep_ms = 0.f, all_ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, t.ev[0], t.ev[1]));
-    HIPCHK(ctx, hipEventElapsedTime(&all_ms, t.ev[0], t.ev[2]));
+    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, ev[0], ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&all_ms, ev[0], ev[2]));
     msfm_pose_refine_stats s = {};
     s.images = n_list;
     s.eligible = (int64_t)hc.eligible;

@@ -4,7 +4,8 @@
 // over the image's correspondences with the triangulated tracks, and a Gauss-Newton refinement of the winner.
 //
 // The contract of msfm_pose.h holds: fp64 with +, -, *, /, sqrt only, static loop structure, -ffp-contract=off on both sides -> the host
-// twin and the device produce the SAME bits.  undistort is msfm_emat.h's, kDepthEps msfm_pose.h's, mix64 / replay_adaptive msfm_fmat.h's.
+// twin and the device produce the SAME bits.  undistort is msfm_emat.h's, kDepthEps msfm_pose.h's, transform msfm_triangulate.h's,
+// mix64 / replay_adaptive msfm_fmat.h's.
 //
 //   correspondences the kept tracks with POINT & ERROR_OK & ANGLE_OK that have an element (I, k), by ascending track number (a
 //                   triangulated track is consistent: at most one element per image).  (u, v) = undistort(pixel of keypoint k),
@@ -40,7 +41,7 @@
 //                   sqrt(dx^2 + dy^2) f; mean_residual = (the inliers' residuals summed in list order from 0.0) / n_inliers.
 #pragma once
 
-#include "msfm_pose.h"
+#include "msfm_triangulate.h"
 
 #if !defined(__HIPCC__)
 #include <algorithm>
@@ -276,12 +277,12 @@ MSFM_UNROLL
 
 // the squared normalised error of one correspondence under (R, t); false: behind the camera (err2 is then not meaningful)
 MSFM_FHD bool project_error(const double R[9], const double t[3], double u, double v, double X, double Y, double Z, double* err2) {
-    const double y0 = R[0] * X + R[1] * Y + R[2] * Z + t[0];
-    const double y1 = R[3] * X + R[4] * Y + R[5] * Z + t[1];
-    const double y2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
-    const double dx = y0 / y2 - u, dy = y1 / y2 - v;
+    const double P[3] = {X, Y, Z};
+    double y[3];
+    msfm_tri::transform(R, t, P, y);
+    const double dx = y[0] / y[2] - u, dy = y[1] / y[2] - v;
     *err2 = dx * dx + dy * dy;
-    return y2 > msfm_pose::kDepthEps;
+    return y[2] > msfm_pose::kDepthEps;
 }
 
 MSFM_FHD bool inlier(const double R[9], const double t[3], double u, double v, double X, double Y, double Z, double f2, double thr2) {
@@ -301,16 +302,15 @@ constexpr int kRegSums = 27;   // 21 of J^T J (upper triangle, row by row), then
 
 // one inlier's terms added to a partial sum
 MSFM_FHD void gn_add(const double R[9], const double t[3], double u, double v, double X, double Y, double Z, double acc[kRegSums]) {
-    const double y0 = R[0] * X + R[1] * Y + R[2] * Z + t[0];
-    const double y1 = R[3] * X + R[4] * Y + R[5] * Z + t[1];
-    const double y2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
-    const double iz = 1.0 / y2, px = y0 * iz, py = y1 * iz;
+    const double P[3] = {X, Y, Z};
+    double Yv[3];
+    msfm_tri::transform(R, t, P, Yv);
+    const double iz = 1.0 / Yv[2], px = Yv[0] * iz, py = Yv[1] * iz;
     const double rx = px - u, ry = py - v;
     // d(pi)/dY = [iz 0 -px iz; 0 iz -py iz];  dY/da = -2 [Y]x,  dY/d(dt) = I
     const double a0[3] = {iz, 0.0, -px * iz}, a1[3] = {0.0, iz, -py * iz};
     double J0[6], J1[6];
     // (row) . (-2 [Y]x):  columns  -2 (row x ... ) = 2 (Y x row)^T ... written out: row . (a x Y) = a . (Y x row)
-    const double Yv[3] = {y0, y1, y2};
     double w0[3], w1[3];
     cross3(Yv, a0, w0);
     cross3(Yv, a1, w1);
@@ -333,14 +333,9 @@ MSFM_UNROLL
     for (int r = 0; r < 6; ++r) acc[21 + r] = acc[21 + r] + (J0[r] * rx + J1[r] * ry);
 }
 
-// the step from the 27 sums (H x = -g by Cholesky), applied to (R, t) in place; false: no step (R, t unchanged)
-MSFM_FHD bool gn_step(const double acc[kRegSums], double R[9], double t[3]) {
-    double L[6][6], x[6];
-    int at = 0;
-MSFM_UNROLL
-    for (int r = 0; r < 6; ++r)
-MSFM_UNROLL
-        for (int c = r; c < 6; ++c) L[c][r] = acc[at++];   // lower triangle
+// A x = -g by a 6 x 6 Cholesky: L holds the lower triangle of A (L[r][c], c <= r) and is overwritten by its factor; then L y = -g,
+// L^T x = y.  False: a pivot is not > 0 or x is not finite.
+MSFM_FHD bool cholesky6_solve(double L[6][6], const double g[6], double x[6]) {
 MSFM_UNROLL
     for (int k = 0; k < 6; ++k) {
         double dd = L[k][k];
@@ -359,7 +354,7 @@ MSFM_UNROLL
     }
 MSFM_UNROLL
     for (int k = 0; k < 6; ++k) {   // L y = -g
-        double s = -acc[21 + k];
+        double s = -g[k];
 MSFM_UNROLL
         for (int m = 0; m < k; ++m) s = s - L[k][m] * x[m];
         x[k] = s / L[k][k];
@@ -374,13 +369,17 @@ MSFM_UNROLL
     bool ok = true;
 MSFM_UNROLL
     for (int k = 0; k < 6; ++k) ok = ok && msfm_pose::finite(x[k]);
-    if (!ok) return false;
+    return ok;
+}
+
+// the step x = (a, dt) applied to (R, t):  Rn = C(a) R,  tn = C(a) t + dt  with Cayley's C.  False: the new pose is not finite.
+MSFM_FHD bool cayley_update(const double x[6], const double R[9], const double t[3], double Rn[9], double tn[3]) {
     const double a0 = x[0], a1 = x[1], a2 = x[2];
     const double aa = a0 * a0 + a1 * a1 + a2 * a2, inv = 1.0 / (1.0 + aa), dg = 1.0 - aa;
     const double C[9] = {(dg + 2.0 * a0 * a0) * inv,       (2.0 * a0 * a1 - 2.0 * a2) * inv, (2.0 * a0 * a2 + 2.0 * a1) * inv,
                          (2.0 * a0 * a1 + 2.0 * a2) * inv, (dg + 2.0 * a1 * a1) * inv,       (2.0 * a1 * a2 - 2.0 * a0) * inv,
                          (2.0 * a0 * a2 - 2.0 * a1) * inv, (2.0 * a1 * a2 + 2.0 * a0) * inv, (dg + 2.0 * a2 * a2) * inv};
-    double Rn[9], tn[3];
+    bool ok = true;
 MSFM_UNROLL
     for (int r = 0; r < 3; ++r) {
 MSFM_UNROLL
@@ -391,7 +390,19 @@ MSFM_UNROLL
         tn[r] = (C[3 * r] * t[0] + C[3 * r + 1] * t[1] + C[3 * r + 2] * t[2]) + x[3 + r];
         ok = ok && msfm_pose::finite(tn[r]);
     }
-    if (!ok) return false;
+    return ok;
+}
+
+// the step from the 27 sums (H x = -g, H as summed: undamped), applied to (R, t) in place; false: no step (R, t unchanged)
+MSFM_FHD bool gn_step(const double acc[kRegSums], double R[9], double t[3]) {
+    double L[6][6], x[6];
+    int at = 0;
+MSFM_UNROLL
+    for (int r = 0; r < 6; ++r)
+MSFM_UNROLL
+        for (int c = r; c < 6; ++c) L[c][r] = acc[at++];   // lower triangle
+    double Rn[9], tn[3];
+    if (!cholesky6_solve(L, acc + 21, x) || !cayley_update(x, R, t, Rn, tn)) return false;
 MSFM_UNROLL
     for (int k = 0; k < 9; ++k) R[k] = Rn[k];
 MSFM_UNROLL

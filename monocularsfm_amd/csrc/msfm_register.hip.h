@@ -27,6 +27,7 @@
 // Plain vector loads and stores; the stats' counters are reduced per wave and added with one vector atomic each.
 #pragma once
 #include "msfm_register.h"
+#include "msfm_triangulate.hip.h"
 #include "msfm_verify_staged.hip.h"
 
 namespace msfm {
@@ -184,9 +185,8 @@ __global__ __launch_bounds__(msfm_reg::kRegRound) void reg_round_kernel(
         solved += live ? 1 : 0;
         __syncthreads();   // (the next image's staging overwrites the tile)
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) solved += __shfl_down(solved, d, 64);
-    if (t == 0 && solved) atomicAdd(&stats->solved, solved);
+    const unsigned long long c[1] = {solved};
+    wave_add_counters(c, &stats->solved);
 }
 
 // the number of set flags over the wave, the same in every lane
@@ -368,9 +368,7 @@ int register_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image
                   msfm_register_stats* stats) {
     TrackSession& ts = ctx->tracks;
     ts.reg_valid = false;   // whatever happens below, the previous registrations are gone
-    if (!ts.open) return fail(ctx, MSFM_E_STATE, "msfm_register_images without a track session (msfm_tracks_begin)");
-    if (!ts.finished || !ts.tri_valid) return fail(ctx, MSFM_E_STATE, "msfm_register_images without points: msfm_triangulate_tracks has not run since the last msfm_tracks_finish");
-    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "msfm_register_images while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    if (const int rc = tri_session_check(ctx, "msfm_register_images", true)) return rc;
     if (!camera) return fail(ctx, MSFM_E_INVALID, "msfm_register_images: NULL camera");
     const msfm_camera c = *camera;
     for (double v : {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2})
@@ -400,19 +398,12 @@ int register_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image
         n_slots += rows;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    struct Tmp {   // freed when the call returns, whatever it returns
-        DevBuf imgs, keys, vals, keys2, vals2, sort_tmp, counts, cu, cv, cX, cY, cZ, hyp, state, best_it, best_count, sstats, inl, counters;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        ~Tmp() {
-            for (DevBuf* b : {&imgs, &keys, &vals, &keys2, &vals2, &sort_tmp, &counts, &cu, &cv, &cX, &cY, &cZ, &hyp, &state, &best_it, &best_count,
-                              &sstats, &inl, &counters})
-                b->release();
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
+    struct {   // (the temporaries are freed when the call returns, whatever it returns)
+        TmpBuf imgs, keys, vals, keys2, vals2, sort_tmp, counts, cu, cv, cX, cY, cZ, hyp, state, best_it, best_count, sstats, inl, counters;
     } t;
+    TmpEvents<2> ev;
     hipStream_t st = store_stream(ctx);
-    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
+    HIPCHK(ctx, ev.create());
     const size_t N = (size_t)std::max(n_images, 1), S = (size_t)std::max<long long>(1, n_slots);
     HIPCHK(ctx, t.imgs.ensure(N * sizeof(RegImage)));
     HIPCHK(ctx, t.keys.ensure(S * 8));
@@ -429,7 +420,7 @@ int register_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image
     HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(RegCounters), st));
     HIPCHK(ctx, hipMemsetAsync(t.sstats.p, 0, sizeof(StagedStats), st));
     HIPCHK(ctx, hipMemsetAsync(ts.g_offsets.p, 0, (N + 1) * 8, st));
-    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
+    HIPCHK(ctx, hipEventRecord(ev[0], st));
     const RegImage* d_imgs = t.imgs.as<RegImage>();
     const msfm_point3d* d_points = ts.t_points.as<msfm_point3d>();
     unsigned long long *keys = t.keys.as<unsigned long long>(), *keys2 = t.keys2.as<unsigned long long>();
@@ -453,7 +444,7 @@ int register_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image
         HIPCHK(ctx, hipMemsetAsync(t.counts.p, 0, N * 4, st));
     }
     const size_t Mz = (size_t)std::max<long long>(1, M);
-    for (DevBuf* b : {&t.cu, &t.cv, &t.cX, &t.cY, &t.cZ}) HIPCHK(ctx, b->ensure(Mz * 8));
+    for (TmpBuf* b : {&t.cu, &t.cv, &t.cX, &t.cY, &t.cZ}) HIPCHK(ctx, b->ensure(Mz * 8));
     HIPCHK(ctx, t.inl.ensure(Mz * 4));
     HIPCHK(ctx, ts.g_tid.ensure(Mz * 4));
     HIPCHK(ctx, ts.g_inl.ensure(Mz));
@@ -500,7 +491,7 @@ int register_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image
                            ts.g_records.as<msfm_registration>(), ts.g_inl.as<unsigned char>(), ts.g_res.as<double>(), t.counters.as<RegCounters>());
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(t.ev[1], st));
+    HIPCHK(ctx, hipEventRecord(ev[1], st));
     const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
     HIPCHK(ctx, done);
     RegCounters hc = {};
@@ -508,7 +499,7 @@ int register_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* image
     HIPCHK(ctx, hipMemcpy(&hc, t.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(&hs, t.sstats.p, sizeof(hs), hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
     msfm_register_stats s = {};
     s.images = n_images;
     s.attempted = hc.attempted;

@@ -23,10 +23,11 @@
 //                   computed and reported (the reference stops at the first failure: the same verdict).  ERROR_OK iff err <= max_error
 //                   holds for every used observation (a NaN fails).  mean_residual = (the errors summed in observation order from 0.0)
 //                   / count, reported whenever a point exists.
-//   parallax        camera centres O = -R^T t, once per pose, by centre() below (Projection.cpp:149-194).  Pairs in the reference's loop
-//                   order, for i: for j < i over the used observations; the scan stops at the first pair with angle >= min_angle and
-//                   tri_angle is that pair's angle (ANGLE_OK set); if none reaches it tri_angle is the largest angle seen (ANGLE_OK
-//                   clear).  Angle as msfm_pose::evaluate: law of cosines, |acos|, NaN -> 0, min(a, pi - a), degrees.
+//   parallax        camera centres O = -R^T t, once per pose, by centre() below (Projection.cpp:149-194).  parallax_scan() below, THE
+//                   scan of this stage: pairs in the reference's loop order, for i: for j < i over the used observations; the scan
+//                   stops at the first pair with angle >= min_angle and tri_angle is that pair's angle (ANGLE_OK set); if none
+//                   reaches it tri_angle is the largest angle seen (ANGLE_OK clear).  Angle as msfm_pose::evaluate: law of cosines,
+//                   |acos|, NaN -> 0, min(a, pi - a), degrees.
 //   status bits     MSFM_TRI_ATTEMPTED 1, _POINT 2, _ERROR_OK 4, _ANGLE_OK 8, _DEPTH_OK 16 (every used view in front).  The
 //                   reference's is_succeed is POINT & ERROR_OK & ANGLE_OK.  THE REFERENCE HAS NO DEPTH TEST: DEPTH_OK is extra
 //                   information and not part of the verdict.
@@ -94,6 +95,131 @@ MSFM_FHD void clear_point(msfm_point3d* r) {
     r->tri_angle = 0.0;
 }
 
+// The parallax scan at X over the elements k = 0 .. n - 1.  centre_of(k) -> the camera centre of element k (const double*), nullptr:
+// the element takes no part.  Pairs in the order  for i: for j < i;  the scan stops at the first pair whose angle is >= min_angle:
+// true, *angle = that pair's angle.  No such pair: false, *angle = the largest angle seen (0.0 without a pair).
+template <class C>
+MSFM_FHD bool parallax_scan(const double X[3], int n, double min_angle, C centre_of, double* angle_out) {
+    bool angle_ok = false;
+    double angle = 0.0;
+    for (int i = 1; i < n && !angle_ok; ++i) {
+        const double* ci = centre_of(i);
+        if (!ci) continue;
+        const double Oi[3] = {ci[0], ci[1], ci[2]};
+        for (int j = 0; j < i; ++j) {
+            const double* cj = centre_of(j);
+            if (!cj) continue;
+            const double Oj[3] = {cj[0], cj[1], cj[2]};
+            const double g = parallax(X, Oi, Oj);
+            if (g >= min_angle) {
+                angle = g;
+                angle_ok = true;
+                break;
+            }
+            if (g > angle) angle = g;
+        }
+    }
+    *angle_out = angle;
+    return angle_ok;
+}
+
+// Y = R X + t
+MSFM_FHD void transform(const double R[9], const double t[3], const double X[3], double Y[3]) {
+    Y[0] = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+    Y[1] = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+    Y[2] = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+}
+
+// triangulate_track's DLT in pieces: the normal matrix (m[j][i]: column j, row i) of no observation, one observation added, the point
+MSFM_FHD void dlt_clear(double m[4][4]) {
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j)
+MSFM_UNROLL
+        for (int i = 0; i < 4; ++i) m[j][i] = 0.0;
+}
+
+MSFM_FHD void dlt_add(double m[4][4], const double R[9], const double t[3], double u, double w) {
+    double r1[4], r2[4];
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        const double p0 = j < 3 ? R[j] : t[0], p1 = j < 3 ? R[3 + j] : t[1], p2 = j < 3 ? R[6 + j] : t[2];
+        r1[j] = u * p2 - p0;
+        r2[j] = w * p2 - p1;
+    }
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j)
+MSFM_UNROLL
+        for (int i = 0; i < 4; ++i) {
+            m[j][i] = m[j][i] + r1[i] * r1[j];
+            m[j][i] = m[j][i] + r2[i] * r2[j];
+        }
+}
+
+// (m is destroyed.)  False: no point.
+MSFM_FHD bool dlt_solve(double m[4][4], double X[3]) {
+    double v[4][4];
+    msfm_pose::onesided_jacobi<4, 4>(m, v);
+    double best = 0.0, h[4] = {0.0, 0.0, 0.0, 0.0};
+MSFM_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        const double nn = m[j][0] * m[j][0] + m[j][1] * m[j][1] + m[j][2] * m[j][2] + m[j][3] * m[j][3];
+        if (j == 0 || nn < best) {
+            best = nn;
+MSFM_UNROLL
+            for (int k = 0; k < 4; ++k) h[k] = v[j][k];
+        }
+    }
+    X[0] = X[1] = X[2] = 0.0;
+    if (!(h[3] > 0.0 || h[3] < 0.0)) return false;
+    X[0] = h[0] / h[3];
+    X[1] = h[1] / h[3];
+    X[2] = h[2] / h[3];
+    return msfm_pose::finite(X[0]) && msfm_pose::finite(X[1]) && msfm_pose::finite(X[2]);
+}
+
+// the reprojection error of X in one view, pixels (f = (fx + fy) / 2), and whether X lies in front of it
+MSFM_FHD double obs_error(const double R[9], const double t[3], double u, double w, const double X[3], double f, bool* depth) {
+    double Y[3];
+    transform(R, t, X, Y);
+    *depth = Y[2] > msfm_pose::kDepthEps;
+    const double dx = Y[0] / Y[2] - u, dy = Y[1] / Y[2] - w;
+    return sqrt(dx * dx + dy * dy) * f;
+}
+
+MSFM_FHD bool obs_inlier(const double R[9], const double t[3], double u, double w, const double X[3], double f, double max_error) {
+    bool depth;
+    const double err = obs_error(R, t, u, w, X, f, &depth);
+    return depth && err <= max_error;   // (false for a NaN)
+}
+
+// the elements of `a` whose mask byte is set (the mask is element-aligned; a set byte belongs to a posed element)
+template <class A>
+struct Masked {
+    const A& a;
+    const uint8_t* mask;
+    MSFM_FHD const Pose* pose(int k) const { return mask[k] ? a.pose(k) : nullptr; }
+    MSFM_FHD void pixel(int k, double* x, double* y) const { a.pixel(k, x, y); }
+};
+
+// the DLT point over the posed elements of `a`, in element order
+template <class A>
+MSFM_FHD bool dlt_point(const A& a, int n, const msfm_emat::Camera& cam, double X[3]) {
+    double m[4][4];
+    dlt_clear(m);
+    for (int k = 0; k < n; ++k) {
+        const Pose* p = a.pose(k);
+        if (!p) continue;
+        double x, y, u, w;
+        a.pixel(k, &x, &y);
+        msfm_emat::undistort(cam, x, y, &u, &w);
+        dlt_add(m, p->R, p->t, u, w);
+    }
+    return dlt_solve(m, X);
+}
+
+// (The DLT, the error pass and the scan are written out here, not called: tri_track_kernel measured 1 .. 1.5 % slower at the bench's
+// default setting with this function built from dlt_clear / dlt_add / dlt_solve, obs_error and parallax_scan, which are the same
+// arithmetic and what every other site calls -- DESIGN.md section 15.)
 // One track.  `a` gives the track's elements k = 0 .. n - 1:  a.pose(k) -> const Pose* (nullptr: the element's image has no valid
 // pose),  a.pixel(k, &x, &y) -> the keypoint's pixel as fp64 (asked for posed elements only).  residuals: n slots, element-aligned;
 // -1.0 where no error was computed.  The arithmetic does not depend on where `a` reads from.
@@ -224,8 +350,8 @@ MSFM_UNROLL
 //   refit, once     mask1 = the inliers of X_best;  R1 = the DLT over mask1 (dlt_point on Masked);  mask2 = the inliers of R1 among all
 //                   used observations;  R1 stands iff it has a point and |mask2| >= max(|mask1|, need), else X_best with mask1.
 //   record          evaluate_point: an error for EVERY used observation (-1 for unposed elements), n_views = |mask|, mean_residual =
-//                   the inliers' errors summed in element order from 0.0 / |mask|, the parallax scan for i: for j < i over the inliers
-//                   with triangulate_track's stop rule, ERROR_OK set, DEPTH_OK over the inliers, ROBUST set.
+//                   the inliers' errors summed in element order from 0.0 / |mask|, parallax_scan over the inliers, ERROR_OK set,
+//                   DEPTH_OK over the inliers, ROBUST set.
 constexpr unsigned long long kTriSeed = 0x547269616e67756cULL;
 
 struct RobustParams {
@@ -282,94 +408,6 @@ MSFM_FHD bool retry(const msfm_point3d& p0, int m) {
     return (p0.status & MSFM_TRI_ATTEMPTED) && (p0.status & done) != done && m >= 3;
 }
 
-// triangulate_track's DLT in pieces: the normal matrix (m[j][i]: column j, row i) of no observation, one observation added, the point
-MSFM_FHD void dlt_clear(double m[4][4]) {
-MSFM_UNROLL
-    for (int j = 0; j < 4; ++j)
-MSFM_UNROLL
-        for (int i = 0; i < 4; ++i) m[j][i] = 0.0;
-}
-
-MSFM_FHD void dlt_add(double m[4][4], const double R[9], const double t[3], double u, double w) {
-    double r1[4], r2[4];
-MSFM_UNROLL
-    for (int j = 0; j < 4; ++j) {
-        const double p0 = j < 3 ? R[j] : t[0], p1 = j < 3 ? R[3 + j] : t[1], p2 = j < 3 ? R[6 + j] : t[2];
-        r1[j] = u * p2 - p0;
-        r2[j] = w * p2 - p1;
-    }
-MSFM_UNROLL
-    for (int j = 0; j < 4; ++j)
-MSFM_UNROLL
-        for (int i = 0; i < 4; ++i) {
-            m[j][i] = m[j][i] + r1[i] * r1[j];
-            m[j][i] = m[j][i] + r2[i] * r2[j];
-        }
-}
-
-// (m is destroyed.)  False: no point.
-MSFM_FHD bool dlt_solve(double m[4][4], double X[3]) {
-    double v[4][4];
-    msfm_pose::onesided_jacobi<4, 4>(m, v);
-    double best = 0.0, h[4] = {0.0, 0.0, 0.0, 0.0};
-MSFM_UNROLL
-    for (int j = 0; j < 4; ++j) {
-        const double nn = m[j][0] * m[j][0] + m[j][1] * m[j][1] + m[j][2] * m[j][2] + m[j][3] * m[j][3];
-        if (j == 0 || nn < best) {
-            best = nn;
-MSFM_UNROLL
-            for (int k = 0; k < 4; ++k) h[k] = v[j][k];
-        }
-    }
-    X[0] = X[1] = X[2] = 0.0;
-    if (!(h[3] > 0.0 || h[3] < 0.0)) return false;
-    X[0] = h[0] / h[3];
-    X[1] = h[1] / h[3];
-    X[2] = h[2] / h[3];
-    return msfm_pose::finite(X[0]) && msfm_pose::finite(X[1]) && msfm_pose::finite(X[2]);
-}
-
-// the reprojection error of X in one view, pixels (f = (fx + fy) / 2), and whether X lies in front of it
-MSFM_FHD double obs_error(const double R[9], const double t[3], double u, double w, const double X[3], double f, bool* depth) {
-    const double Y0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
-    const double Y1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
-    const double Y2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
-    *depth = Y2 > msfm_pose::kDepthEps;
-    const double dx = Y0 / Y2 - u, dy = Y1 / Y2 - w;
-    return sqrt(dx * dx + dy * dy) * f;
-}
-
-MSFM_FHD bool obs_inlier(const double R[9], const double t[3], double u, double w, const double X[3], double f, double max_error) {
-    bool depth;
-    const double err = obs_error(R, t, u, w, X, f, &depth);
-    return depth && err <= max_error;   // (false for a NaN)
-}
-
-// the elements of `a` whose mask byte is set (the mask is element-aligned; a set byte belongs to a posed element)
-template <class A>
-struct Masked {
-    const A& a;
-    const uint8_t* mask;
-    MSFM_FHD const Pose* pose(int k) const { return mask[k] ? a.pose(k) : nullptr; }
-    MSFM_FHD void pixel(int k, double* x, double* y) const { a.pixel(k, x, y); }
-};
-
-// the DLT point over the posed elements of `a`, in element order
-template <class A>
-MSFM_FHD bool dlt_point(const A& a, int n, const msfm_emat::Camera& cam, double X[3]) {
-    double m[4][4];
-    dlt_clear(m);
-    for (int k = 0; k < n; ++k) {
-        const Pose* p = a.pose(k);
-        if (!p) continue;
-        double x, y, u, w;
-        a.pixel(k, &x, &y);
-        msfm_emat::undistort(cam, x, y, &u, &w);
-        dlt_add(m, p->R, p->t, u, w);
-    }
-    return dlt_solve(m, X);
-}
-
 // the record of a retried track without a consensus
 MSFM_FHD void robust_failed(int n, msfm_point3d* rec, double* residuals, uint8_t* mask) {
     clear_point(rec);
@@ -406,25 +444,8 @@ MSFM_FHD void evaluate_point(const A& a, int n, const double X[3], const uint8_t
             count += 1;
         }
     }
-    bool angle_ok = false;
-    double angle = 0.0;
-    for (int i = 1; i < n && !angle_ok; ++i) {
-        if (!mask[i]) continue;
-        const Pose* pi = a.pose(i);
-        const double Oi[3] = {pi->O[0], pi->O[1], pi->O[2]};
-        for (int j = 0; j < i; ++j) {
-            if (!mask[j]) continue;
-            const Pose* pj = a.pose(j);
-            const double Oj[3] = {pj->O[0], pj->O[1], pj->O[2]};
-            const double g = parallax(X, Oi, Oj);
-            if (g >= min_angle) {
-                angle = g;
-                angle_ok = true;
-                break;
-            }
-            if (g > angle) angle = g;
-        }
-    }
+    double angle;
+    const bool angle_ok = parallax_scan(X, n, min_angle, [&](int k) -> const double* { return mask[k] ? a.pose(k)->O : nullptr; }, &angle);
     rec->status = MSFM_TRI_ATTEMPTED | MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | (angle_ok ? MSFM_TRI_ANGLE_OK : 0) |
                   (depth_ok ? MSFM_TRI_DEPTH_OK : 0) | MSFM_TRI_ROBUST;
     rec->n_views = count;

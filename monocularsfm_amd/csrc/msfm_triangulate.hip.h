@@ -8,8 +8,7 @@
 //                     keypoint, the 128-byte pose.  The 4 x 4 normal matrix and the Jacobi state stay in registers (every index is a
 //                     compile-time constant); the track's elements are re-read in the error pass and the parallax scan instead of
 //                     being kept, so the register need does not depend on the track's length.  Plain vector loads and stores; the
-//                     counters of the stats are reduced per wave by shuffles and added with one atomic per wave and counter (they
-//                     only COUNT: no order reaches the output).
+//                     counters of the stats go through wave_add_counters (they only COUNT: no order reaches the output).
 #pragma once
 #include "msfm_triangulate.h"
 
@@ -25,6 +24,45 @@ struct TriCounters {
     unsigned long long attempted, with_point, error_ok, angle_ok, depth_ok, succeeded, observations_used;
 };
 constexpr int kTriCounters = 7;
+
+// Integer counters of a kernel, one set per lane: reduced over the wave by a shuffle tree, then one vector atomic per wave and non-zero
+// counter (they only COUNT: no order reaches the output).  Every lane of the wave must call it.
+template <int N>
+__device__ __forceinline__ void wave_add_counters(const unsigned long long (&c)[N], unsigned long long* out) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        unsigned long long v = c[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(out + k, v);
+    }
+}
+
+// The lanes of a wave with `add` set append `value` to a list: a ballot, one atomic per wave for the position.  The list's order
+// differs from run to run.  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_list_append(bool add, int value, int* __restrict__ list, int* __restrict__ list_count) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long bal = __ballot(add);
+    if (bal) {
+        const int leader = __ffsll((long long)bal) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(list_count, __popcll(bal));
+        base = __shfl(base, leader, 64);
+        if (add) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = value;
+    }
+}
+
+// one record added to the seven counters of TriCounters, in its order
+__device__ __forceinline__ void tri_count(unsigned long long* c, const msfm_point3d& r) {
+    const int s = r.status, ok = MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK;
+    c[0] += (s & MSFM_TRI_ATTEMPTED) ? 1 : 0;
+    c[1] += (s & MSFM_TRI_POINT) ? 1 : 0;
+    c[2] += (s & MSFM_TRI_ERROR_OK) ? 1 : 0;
+    c[3] += (s & MSFM_TRI_ANGLE_OK) ? 1 : 0;
+    c[4] += (s & MSFM_TRI_DEPTH_OK) ? 1 : 0;
+    c[5] += ((s & ok) == ok) ? 1 : 0;
+    c[6] += (unsigned long long)r.n_views;
+}
 
 __global__ __launch_bounds__(256) void tri_pose_kernel(const msfm_pose_rt* __restrict__ in, int n, msfm_tri::Pose* __restrict__ out) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,41 +99,60 @@ __global__ __launch_bounds__(256) void tri_track_kernel(const long long* __restr
         msfm_point3d r;
         msfm_tri::triangulate_track(a, (int)(e - b), cons[t] != 0, cam, prm, &r, residuals + b);
         points[t] = r;
-        const int s = r.status;
-        c[0] += (s & MSFM_TRI_ATTEMPTED) ? 1 : 0;
-        c[1] += (s & MSFM_TRI_POINT) ? 1 : 0;
-        c[2] += (s & MSFM_TRI_ERROR_OK) ? 1 : 0;
-        c[3] += (s & MSFM_TRI_ANGLE_OK) ? 1 : 0;
-        c[4] += (s & MSFM_TRI_DEPTH_OK) ? 1 : 0;
-        c[5] += ((s & (MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK)) == (MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK)) ? 1 : 0;
-        c[6] += (unsigned long long)r.n_views;
+        tri_count(c, r);
     }
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(counters);
-#pragma unroll
-    for (int k = 0; k < kTriCounters; ++k) {
-        unsigned long long v = c[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(out + k, v);
-    }
+    wave_add_counters(c, reinterpret_cast<unsigned long long*>(counters));
 }
 
 }  // namespace msfm
 
 namespace {
 
-// What msfm_triangulate_tracks and msfm_triangulate_tracks_robust (`who`) check before any device work, and the two tables they
-// upload: the caller's poses by declared-image rank, the per-image-id entry of the kernels.
-int tri_prepare(msfm_ctx* ctx, const std::string& who, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses,
-                int n_poses, const msfm_tri::Params& prm, std::vector<msfm_pose_rt>* by_rank_out, std::vector<TriImage>* table_out) {
-    TrackSession& ts = ctx->tracks;
-    ts.tri_valid = false;   // whatever happens below, the previous points are gone
-    ts.mask_valid = false;  // ... and the inlier bytes of a robust call (msfm_triangulate_robust.hip.h)
-    ts.reg_valid = false;   // ... and the registrations made from them (msfm_register.hip.h)
-    ts.rp_valid = false;    // ... and the pose refinement's records (msfm_refine_poses.hip.h)
+// A device buffer that lives as long as the call that declares it: DevBuf (which never frees by itself: the session's long-lived
+// buffers rely on that) plus the release when it goes out of scope, whatever the call returns.
+struct TmpBuf : DevBuf {
+    TmpBuf() = default;
+    TmpBuf(const TmpBuf&) = delete;
+    TmpBuf& operator=(const TmpBuf&) = delete;
+    ~TmpBuf() { release(); }
+};
+
+// the N events a call times itself with, destroyed with it
+template <int N>
+struct TmpEvents {
+    hipEvent_t ev[N] = {};
+    TmpEvents() = default;
+    TmpEvents(const TmpEvents&) = delete;
+    TmpEvents& operator=(const TmpEvents&) = delete;
+    ~TmpEvents() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() {
+        for (hipEvent_t& e : ev)
+            if (const hipError_t rc = hipEventCreate(&e)) return rc;
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int k) const { return ev[k]; }
+};
+
+// The session state every call of the reconstruction stage (`who`) needs: an open, finished track session and no open series; the
+// calls that work on points (needs_points) need the points of a triangulation as well.
+int tri_session_check(msfm_ctx* ctx, const std::string& who, bool needs_points) {
+    const TrackSession& ts = ctx->tracks;
     if (!ts.open) return fail(ctx, MSFM_E_STATE, who + " without a track session (msfm_tracks_begin)");
+    if (needs_points && (!ts.finished || !ts.tri_valid))
+        return fail(ctx, MSFM_E_STATE, who + " without points: msfm_triangulate_tracks has not run since the last msfm_tracks_finish");
     if (!ts.finished) return fail(ctx, MSFM_E_STATE, who + " before a successful msfm_tracks_finish");
     if (ctx->series_open) return fail(ctx, MSFM_E_STATE, who + " while a streaming series (msfm_match_pairs_begin .. _next) is open");
+    return MSFM_OK;
+}
+
+// What a call (`who`) checks of a camera, thresholds and a pose list before any device work, and the two tables it uploads: the
+// caller's poses by declared-image rank, the per-image-id entry of the kernels.  It reads the session and changes nothing of it.
+int tri_tables(msfm_ctx* ctx, const std::string& who, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses,
+               int n_poses, const msfm_tri::Params& prm, std::vector<msfm_pose_rt>* by_rank_out, std::vector<TriImage>* table_out) {
+    const TrackSession& ts = ctx->tracks;
     if (!camera) return fail(ctx, MSFM_E_INVALID, who + ": NULL camera");
     const msfm_camera c = *camera;
     for (double v : {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2})
@@ -136,6 +193,34 @@ int tri_prepare(msfm_ctx* ctx, const std::string& who, const msfm_camera* camera
     return MSFM_OK;
 }
 
+// The pose tables of one call on the device: tri_tables' two tables, the prepared poses the kernels read, and the camera in the
+// kernels' form.
+struct PoseTables {
+    TmpBuf in, poses, table;
+    msfm_emat::Camera cam;
+    int n_ranks = 0;
+    const msfm_tri::Pose* d_poses() const { return poses.as<msfm_tri::Pose>(); }
+    const TriImage* d_table() const { return table.as<TriImage>(); }
+    // (synchronous copies of the two small tables: nothing queued reads host memory that an early return of the caller would free)
+    hipError_t upload(const msfm_camera& c, const std::vector<msfm_pose_rt>& by_rank, const std::vector<TriImage>& tab, int n_img) {
+        cam = msfm_emat::Camera{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+        n_ranks = n_img;
+        hipError_t e = in.ensure(by_rank.size() * sizeof(msfm_pose_rt));
+        if (e == hipSuccess) e = poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose));
+        if (e == hipSuccess) e = table.ensure(tab.size() * sizeof(TriImage));
+        if (e == hipSuccess) e = hipMemcpy(in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(table.p, tab.data(), tab.size() * sizeof(TriImage), hipMemcpyHostToDevice);
+        return e;
+    }
+    // tri_pose_kernel over the declared images
+    hipError_t prepare(hipStream_t st) {
+        if (n_ranks <= 0) return hipSuccess;
+        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_ranks + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)in.as<msfm_pose_rt>(),
+                           n_ranks, poses.as<msfm_tri::Pose>());
+        return hipGetLastError();
+    }
+};
+
 // what a successful msfm_triangulate_tracks / _robust leaves behind for msfm_refine_points (msfm_refine.hip.h): a host copy of its inputs
 void tri_keep_inputs(TrackSession& ts, const msfm_camera& camera, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
                      const msfm_tri::Params& prm) {
@@ -150,55 +235,43 @@ int triangulate_impl(msfm_ctx* ctx, const msfm_camera* camera, const int32_t* im
     TrackSession& ts = ctx->tracks;
     msfm_tri::Params prm = {2.0, 1.5, 2, 0};   // Triangulator::Parameters
     if (params) prm = msfm_tri::Params{params->max_error, params->min_angle, params->min_views, 0};
+    // whatever happens below, the previous points are gone, and with them the inlier bytes of a robust call, the registrations made
+    // from them and the pose refinement's records
+    ts.tri_valid = ts.mask_valid = ts.reg_valid = ts.rp_valid = false;
+    const std::string who = "msfm_triangulate_tracks";
+    if (const int rc = tri_session_check(ctx, who, false)) return rc;
     std::vector<msfm_pose_rt> by_rank;
     std::vector<TriImage> table;
-    if (const int rc = tri_prepare(ctx, "msfm_triangulate_tracks", camera, image_ids, poses, n_poses, prm, &by_rank, &table)) return rc;
+    if (const int rc = tri_tables(ctx, who, camera, image_ids, poses, n_poses, prm, &by_rank, &table)) return rc;
     const msfm_camera c = *camera;
-    const int n_img = (int)ts.nd.ids.size();
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
-    struct Tmp {   // freed when the call returns, whatever it returns
-        DevBuf in, poses, table, counters;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        ~Tmp() {
-            for (DevBuf* b : {&in, &poses, &table, &counters}) b->release();
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } t;
+    PoseTables pt;   // (the temporaries are freed when the call returns, whatever it returns)
+    TmpBuf counters;
+    TmpEvents<2> ev;
     hipStream_t st = store_stream(ctx);
-    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
-    HIPCHK(ctx, t.in.ensure(by_rank.size() * sizeof(msfm_pose_rt)));
-    HIPCHK(ctx, t.poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose)));
-    HIPCHK(ctx, t.table.ensure(table.size() * sizeof(TriImage)));
-    HIPCHK(ctx, t.counters.ensure(sizeof(TriCounters)));
+    HIPCHK(ctx, ev.create());
+    HIPCHK(ctx, counters.ensure(sizeof(TriCounters)));
     HIPCHK(ctx, ts.t_points.ensure((size_t)std::max<long long>(1, T) * sizeof(msfm_point3d)));
     HIPCHK(ctx, ts.t_resid.ensure((size_t)std::max<long long>(1, O) * sizeof(double)));
-    // (synchronous copies of the two small tables: nothing queued reads host memory that an early return below would free)
-    HIPCHK(ctx, hipMemcpy(t.in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(t.table.p, table.data(), table.size() * sizeof(TriImage), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(TriCounters), st));
-    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
-    if (n_img > 0) {
-        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)t.in.as<msfm_pose_rt>(), n_img,
-                           t.poses.as<msfm_tri::Pose>());
-        HIPCHK(ctx, hipGetLastError());
-    }
+    HIPCHK(ctx, pt.upload(c, by_rank, table, (int)ts.nd.ids.size()));
+    HIPCHK(ctx, hipMemsetAsync(counters.p, 0, sizeof(TriCounters), st));
+    HIPCHK(ctx, hipEventRecord(ev[0], st));
+    HIPCHK(ctx, pt.prepare(st));
     if (T > 0) {
         hipLaunchKernelGGL(tri_track_kernel, dim3(tk_grid(ctx, T)), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
                            (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)T,
-                           (const TriImage*)t.table.as<TriImage>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(),
-                           msfm_emat::Camera{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2}, prm, ts.t_points.as<msfm_point3d>(),
-                           ts.t_resid.as<double>(), t.counters.as<TriCounters>());
+                           pt.d_table(), pt.d_poses(), pt.cam, prm, ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(),
+                           counters.as<TriCounters>());
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(t.ev[1], st));
+    HIPCHK(ctx, hipEventRecord(ev[1], st));
     const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
     HIPCHK(ctx, done);
     TriCounters hc = {};
-    HIPCHK(ctx, hipMemcpy(&hc, t.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(&hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
     msfm_triangulation_stats s = {};
     s.tracks = T;
     s.attempted = (int64_t)hc.attempted;

@@ -1,7 +1,7 @@
 // msfm_triangulate_robust.hip.h -- robust track triangulation on the device (include/msfm_match.h "robust track triangulation",
 // DESIGN.md section 17): the two kernels and the host side of msfm_triangulate_tracks_robust / msfm_fetch_point_inliers (defined in
 // msfm_match.hip).  The arithmetic is msfm_triangulate.h's robust part, shared with the host twin TriangulateTracksRobust: the same
-// bits.  Included by msfm_match.hip behind msfm_triangulate.hip.h, whose tri_pose_kernel, TriDevTrack and tri_prepare it reuses.
+// bits.  Included by msfm_match.hip behind msfm_triangulate.hip.h, whose TriDevTrack, PoseTables, tri_tables and wave helpers it reuses.
 //
 // Everything runs on the library's stream between HIP events; the host waits once, for the length of the retry list.
 //   trr_first_kernel   one lane per kept track, grid-stride, the shape of tri_track_kernel: the plain record (triangulate_track), the
@@ -35,18 +35,6 @@ struct TrrCounters {
 };
 constexpr int kTrrCounters = kTriCounters + 4;
 
-// the seven counters of TriCounters, in its order
-__device__ __forceinline__ void trr_count(unsigned long long* c, const msfm_point3d& r) {
-    const int s = r.status, ok = MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK;
-    c[0] += (s & MSFM_TRI_ATTEMPTED) ? 1 : 0;
-    c[1] += (s & MSFM_TRI_POINT) ? 1 : 0;
-    c[2] += (s & MSFM_TRI_ERROR_OK) ? 1 : 0;
-    c[3] += (s & MSFM_TRI_ANGLE_OK) ? 1 : 0;
-    c[4] += (s & MSFM_TRI_DEPTH_OK) ? 1 : 0;
-    c[5] += ((s & ok) == ok) ? 1 : 0;
-    c[6] += (unsigned long long)r.n_views;
-}
-
 // what one wave wrote (LDS, or memory its own lanes read back) is visible to all of its lanes
 __device__ __forceinline__ void trr_wave_sync() {
     __threadfence_block();
@@ -76,25 +64,11 @@ __global__ __launch_bounds__(256) void trr_first_kernel(const long long* __restr
             const bool attempted = (r.status & MSFM_TRI_ATTEMPTED) != 0;
             for (int k = 0; k < n; ++k) mask[b + k] = (attempted && a.pose(k)) ? 1 : 0;
             again = msfm_tri::retry(r, r.n_views);
-            if (!again) trr_count(c, r);
+            if (!again) tri_count(c, r);
         }
-        const unsigned long long bal = __ballot(again);
-        if (bal) {
-            const int leader = __ffsll((long long)bal) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(list_count, __popcll(bal));
-            base = __shfl(base, leader, 64);
-            if (again) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = (int)t;
-        }
+        wave_list_append(again, (int)t, list, list_count);
     }
-    unsigned long long* out = counters->tri;
-#pragma unroll
-    for (int k = 0; k < kTriCounters; ++k) {
-        unsigned long long v = c[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-        if (lane == 0 && v) atomicAdd(out + k, v);
-    }
+    wave_add_counters(c, counters->tri);
 }
 
 // the staged observation at slot q of the wave's tile
@@ -267,7 +241,7 @@ __global__ __launch_bounds__(64 * kTrrWaves) void trr_retry_kernel(const long lo
         }
         if (lane == 0) {
             points[t] = r;
-            trr_count(c, r);
+            tri_count(c, r);
             c[kTriCounters] += 1;
             c[kTriCounters + 1] += ((r.status & (MSFM_TRI_POINT | MSFM_TRI_ANGLE_OK)) == (MSFM_TRI_POINT | MSFM_TRI_ANGLE_OK)) ? 1 : 0;
             c[kTriCounters + 2] += (r.status & MSFM_TRI_POINT) ? (unsigned long long)(m - kept) : 0;
@@ -294,80 +268,68 @@ int triangulate_robust_impl(msfm_ctx* ctx, const msfm_camera* camera, const int3
     msfm_tri::RobustParams rp = {2.0, 1.5, 2, 64};
     if (params) rp = msfm_tri::RobustParams{params->max_error, params->min_angle, params->min_views, params->max_hypotheses};
     const msfm_tri::Params prm = {rp.max_error, rp.min_angle, rp.min_views, 0};
+    // whatever happens below, the previous points are gone, and with them the inlier bytes of a robust call, the registrations made
+    // from them and the pose refinement's records
+    ts.tri_valid = ts.mask_valid = ts.reg_valid = ts.rp_valid = false;
+    const std::string who = "msfm_triangulate_tracks_robust";
+    if (const int rc = tri_session_check(ctx, who, false)) return rc;
     std::vector<msfm_pose_rt> by_rank;
     std::vector<TriImage> table;
-    if (const int rc = tri_prepare(ctx, "msfm_triangulate_tracks_robust", camera, image_ids, poses, n_poses, prm, &by_rank, &table)) return rc;
-    if (rp.max_hypotheses < 1 || rp.max_hypotheses > 1024)
-        return fail(ctx, MSFM_E_INVALID, "msfm_triangulate_tracks_robust: max_hypotheses must lie in 1 .. 1024");
+    if (const int rc = tri_tables(ctx, who, camera, image_ids, poses, n_poses, prm, &by_rank, &table)) return rc;
+    if (rp.max_hypotheses < 1 || rp.max_hypotheses > 1024) return fail(ctx, MSFM_E_INVALID, who + ": max_hypotheses must lie in 1 .. 1024");
     const msfm_camera c = *camera;
-    const int n_img = (int)ts.nd.ids.size();
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
-    struct Tmp {   // freed when the call returns, whatever it returns
-        DevBuf in, poses, table, counters, list, positions;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        ~Tmp() {
-            for (DevBuf* b : {&in, &poses, &table, &counters, &list, &positions}) b->release();
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } t;
+    PoseTables pt;   // (the temporaries are freed when the call returns, whatever it returns)
+    TmpBuf counters, list, positions;
+    TmpEvents<3> ev;
     hipStream_t st = store_stream(ctx);
-    for (hipEvent_t& e : t.ev) HIPCHK(ctx, hipEventCreate(&e));
-    HIPCHK(ctx, t.in.ensure(by_rank.size() * sizeof(msfm_pose_rt)));
-    HIPCHK(ctx, t.poses.ensure(by_rank.size() * sizeof(msfm_tri::Pose)));
-    HIPCHK(ctx, t.table.ensure(table.size() * sizeof(TriImage)));
-    HIPCHK(ctx, t.counters.ensure(sizeof(TrrCounters)));
-    HIPCHK(ctx, t.list.ensure((size_t)(std::max<long long>(1, T) + 1) * sizeof(int)));   // the list | its length
+    HIPCHK(ctx, ev.create());
+    HIPCHK(ctx, counters.ensure(sizeof(TrrCounters)));
+    HIPCHK(ctx, list.ensure((size_t)(std::max<long long>(1, T) + 1) * sizeof(int)));   // the list | its length
     HIPCHK(ctx, ts.t_points.ensure((size_t)std::max<long long>(1, T) * sizeof(msfm_point3d)));
     HIPCHK(ctx, ts.t_resid.ensure((size_t)std::max<long long>(1, O) * sizeof(double)));
     HIPCHK(ctx, ts.t_mask.ensure((size_t)std::max<long long>(1, O)));
-    // (synchronous copies of the two small tables: nothing queued reads host memory that an early return below would free)
-    HIPCHK(ctx, hipMemcpy(t.in.p, by_rank.data(), by_rank.size() * sizeof(msfm_pose_rt), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(t.table.p, table.data(), table.size() * sizeof(TriImage), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(TrrCounters), st));
-    int* d_list = t.list.as<int>();
+    HIPCHK(ctx, pt.upload(c, by_rank, table, (int)ts.nd.ids.size()));
+    HIPCHK(ctx, hipMemsetAsync(counters.p, 0, sizeof(TrrCounters), st));
+    int* d_list = list.as<int>();
     int* d_listed = d_list + std::max<long long>(1, T);
     HIPCHK(ctx, hipMemsetAsync(d_listed, 0, sizeof(int), st));
-    HIPCHK(ctx, hipEventRecord(t.ev[0], st));
-    if (n_img > 0) {
-        hipLaunchKernelGGL(tri_pose_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, (const msfm_pose_rt*)t.in.as<msfm_pose_rt>(), n_img,
-                           t.poses.as<msfm_tri::Pose>());
-        HIPCHK(ctx, hipGetLastError());
-    }
-    const msfm_emat::Camera cam{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2};
+    HIPCHK(ctx, hipEventRecord(ev[0], st));
+    HIPCHK(ctx, pt.prepare(st));
+    const msfm_emat::Camera cam = pt.cam;
     int listed = 0;
     if (T > 0) {
         hipLaunchKernelGGL(trr_first_kernel, dim3(tk_grid(ctx, T)), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
                            (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)T,
-                           (const TriImage*)t.table.as<TriImage>(), (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), cam, prm,
+                           pt.d_table(), pt.d_poses(), cam, prm,
                            ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), d_list, d_listed,
-                           t.counters.as<TrrCounters>());
+                           counters.as<TrrCounters>());
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(t.ev[1], st));
+        HIPCHK(ctx, hipEventRecord(ev[1], st));
         HIPCHK(ctx, hipMemcpyAsync(&listed, d_listed, sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));   // the one wait: the length of the retry list
     } else {
-        HIPCHK(ctx, hipEventRecord(t.ev[1], st));
+        HIPCHK(ctx, hipEventRecord(ev[1], st));
     }
     if (listed > 0) {
-        HIPCHK(ctx, t.positions.ensure((size_t)O * sizeof(int)));
+        HIPCHK(ctx, positions.ensure((size_t)O * sizeof(int)));
         const unsigned groups = (unsigned)((listed + kTrrWaves - 1) / kTrrWaves);
         const unsigned grid = std::min<unsigned>(groups, (unsigned)(kTrrGroupsPerCU * std::max(1, ctx->cu_count)));
         hipLaunchKernelGGL(trr_retry_kernel, dim3(grid), dim3(64 * kTrrWaves), 0, st, (const long long*)ts.r_offsets.as<long long>(),
-                           (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const TriImage*)t.table.as<TriImage>(),
-                           (const msfm_tri::Pose*)t.poses.as<msfm_tri::Pose>(), cam, rp, (const int*)d_list, listed, t.positions.as<int>(),
-                           ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), t.counters.as<TrrCounters>());
+                           (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), pt.d_table(),
+                           pt.d_poses(), cam, rp, (const int*)d_list, listed, positions.as<int>(),
+                           ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), counters.as<TrrCounters>());
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(t.ev[2], st));
+    HIPCHK(ctx, hipEventRecord(ev[2], st));
     const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
     HIPCHK(ctx, done);
     TrrCounters hc = {};
-    HIPCHK(ctx, hipMemcpy(&hc, t.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(&hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost));
     float first_ms = 0.f, all_ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&first_ms, t.ev[0], t.ev[1]));
-    HIPCHK(ctx, hipEventElapsedTime(&all_ms, t.ev[0], t.ev[2]));
+    HIPCHK(ctx, hipEventElapsedTime(&first_ms, ev[0], ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&all_ms, ev[0], ev[2]));
     msfm_triangulation_stats s = {};
     s.tracks = T;
     s.attempted = (int64_t)hc.tri[0];

@@ -736,14 +736,14 @@ int host_refine_points(const long long* offsets, const int* image_ids, const int
 // fixed.  `poses` is read AND rewritten: where a refined pose stands its R and t replace the entry.  points and residuals are read and
 // rewritten by the re-verdict.  out_records: one msfm_pose_refinement per entry of the pose list.  counts9 (may be NULL): images,
 // eligible, refined, rejected_by_inliers, iterations, observations, points_reposed, points_lost, points_gained are ADDED to it; costs2
-// (may be NULL): cost_before and cost_after, summed in list order, are ADDED to it.  out_trace (may be NULL) receives msfm_rp::Trace
+// (may be NULL): cost_before and cost_after, summed in list order, are ADDED to it.  out_trace (may be NULL) receives msfm_ref::Trace
 // (40 bytes) per entry of the pose list.  Returns 0; 1, 2 as above; 3: a bad parameter; 4: a fixed id that is not declared or given twice.
 int host_refine_poses(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks, const int* ids, int n_images,
                       const float* const* kxy, const int* pose_ids, msfm_pose_rt* poses, int n_poses, const double* cam, double max_error,
                       double min_angle, double step_tol, int max_iters, int min_observations, const int* fixed_ids, int n_fixed,
                       msfm_point3d* points, double* residuals, const unsigned char* mask, msfm_pose_refinement* out_records,
                       long long* counts9, double* costs2, void* out_trace) {
-    static_assert(sizeof(msfm_rp::Trace) == 40 && sizeof(msfm_pose_refinement) == 48, "the trace is six int32 and two doubles");
+    static_assert(sizeof(msfm_ref::Trace) == 40 && sizeof(msfm_pose_refinement) == 48, "the trace is six int32 and two doubles");
     std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
     for (int k = 0; k < n_images; ++k) {
         if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
@@ -773,7 +773,7 @@ int host_refine_poses(const long long* offsets, const int* image_ids, const int*
     msfm_rp::RefinePoses(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, rank_of.data(), kxy, table.data(),
                          n_images, mask, c, msfm_ref::Verdict{max_error, min_angle}, msfm_rp::Params{step_tol, max_iters, min_observations},
                          list_rank.data(), pose_ids, n_poses, fixed.data(), points, residuals, out_records, changed.data(), &rc,
-                         static_cast<msfm_rp::Trace*>(out_trace));
+                         static_cast<msfm_ref::Trace*>(out_trace));
     for (int k = 0; k < n_poses; ++k) {
         const size_t r = (size_t)list_rank[(size_t)k];
         if (!changed[r]) continue;

@@ -2,7 +2,7 @@
 definitions in plain numpy on top of tests/triangulation_ref.py: the residuals and the Jacobian of the parametrisation R <- C(a) R,
 t <- C(a) t + dt STACKED in long double (2n rows, pixel units), H = J^T J and g = J^T r as matrix products, the damped system by
 numpy.linalg.solve after numpy.linalg.cholesky has shown it positive definite, Cayley's rotation and the errors in long double, angles
-by np.arccos; the same Levenberg-Marquardt, stop and standing rules and the same trace fields as the twin's msfm_rp::Trace.  No
+by np.arccos; the same Levenberg-Marquardt, stop and standing rules and the same trace fields as the twin's msfm_ref::Trace.  No
 partial sums, no butterfly, no 27 sums.  Test infrastructure only."""
 import numpy as np
 

@@ -17,7 +17,7 @@ COUNT_KEYS = ("images", "eligible", "refined", "rejected_by_inliers", "iteration
 COST_KEYS = ("cost_before", "cost_after")
 STOP_NONE, STOP_STEP, STOP_MAX_ITERS, STOP_CEILING = 0, 1, 2, 3
 NOT_ELIGIBLE, NO_ACCEPTED_STEP, LOST_INLIERS = 1, 2, 3          # verdict: 0 stands, else why not
-# msfm_rp::Trace: the route an image took (csrc/msfm_refine_poses.h)
+# msfm_ref::Trace, as msfm_rp::refine_image fills it: the route an image took (csrc/msfm_refine.h)
 TRACE = np.dtype([("steps", np.int32), ("accepted", np.int32), ("stop", np.int32), ("verdict", np.int32),
                   ("accepted_after_rejected", np.int32), ("depth_rejected", np.int32), ("lambda", np.float64), ("cost", np.float64)])
 assert TRACE.itemsize == 40

@@ -98,7 +98,7 @@ static int scene(bool coincident, long long* refined_out) {
         int round = 0;
         for (int max_iters : {0, 1, 10, 10, 100}) {   // (each call refines from what the one before left)
             const int min_obs = round++ % 2 ? 3 : 15;
-            std::vector<msfm_rp::Trace> trace((size_t)n_list);
+            std::vector<msfm_ref::Trace> trace((size_t)n_list);
             std::vector<msfm_pose_refinement> rec((size_t)n_list);
             msfm_rp::Counts c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
             msfm_rp::RefinePoses(offsets.data(), img.data(), idx.data(), n_tr, rank_of.data(), ptr.data(), cur.data(), n_img,
