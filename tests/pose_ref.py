@@ -128,6 +128,10 @@ def _null_refine_general(A, x, dtype):
     for _ in range(4):
         s = x @ M @ x
         y = _solve(M - (s * (1 - dtype(1e-6))) * np.eye(4, dtype=dtype), x)
+        if not np.all(np.isfinite(y)):
+            # near-exact data (s ~ 0): the matrix shifted that closely is singular to working precision.  The step again with the
+            # shift a safe distance below s (still 1e-12 of the other singular values: one step converges)
+            y = _solve(M - (s - dtype(1e-12) * np.trace(M)) * np.eye(4, dtype=dtype), x)
         x = y / np.sqrt(y @ y)
     return x
 

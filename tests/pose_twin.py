@@ -33,6 +33,7 @@ def load_host():
     L.host_two_view_geometry.argtypes = [FP, FP, C.c_int, DP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
                                          C.c_ulonglong, UP, C.c_void_p]
     L.host_essential_ransac.argtypes = [FP, FP, C.c_int, DP, C.c_double, C.c_double, C.c_int, C.c_ulonglong, UP]
+    L.host_emat_undistort.argtypes = [DP, DP, C.c_int, DP]
     return L
 
 
@@ -67,6 +68,30 @@ def acos(host, x):
     out = np.zeros_like(x)
     host.host_pose_acos(_dp(x), len(x), _dp(out))
     return out
+
+
+def normalise(host, cam, p):
+    """The twin's own normalised coordinates (msfm_emat::undistort) of the float32 pixel points p (n x 2) -> n x 2 doubles"""
+    cam = np.asarray(tuple(cam) + (0.0,) * (8 - len(cam)), np.float64)
+    uv = np.ascontiguousarray(np.asarray(p, np.float32).reshape(-1, 2), np.float64)
+    xy = np.zeros_like(uv)
+    host.host_emat_undistort(_dp(cam), _dp(uv), len(uv), _dp(xy))
+    return xy
+
+
+def kept_angles(host, rec, p1, p2, cam):
+    """The per-match angles (degrees) of the kept pixel matches p1, p2 under the pose of the record `rec`, as the record's own
+    statistics saw them: the twin's normalisation, msfm_pose::evaluate, the focal length (fx + fy) / 2."""
+    q1, q2 = normalise(host, cam, p1), normalise(host, cam, p2)
+    f = (cam[0] + cam[1]) * 0.5
+    return [evaluate(host, rec["R"], rec["t"], f, *a, *b)[2] for a, b in zip(q1, q2)]
+
+
+def median_rule(values):
+    """The record's median: the middle entry of the sorted values, or the mean of the two middle ones."""
+    v = sorted(values)
+    n = len(v)
+    return v[n // 2] if n % 2 else (v[(n - 1) // 2] + v[n // 2]) / 2
 
 
 def record(host, E, q1, q2, f, params=DEFAULTS):

@@ -7,11 +7,15 @@
   * with the feature on, the match lists, verification_stats() and the selection records equal those with it off;
   * a production-shaped call: thousands of pairs in one call (the persistent grid walks its list several times), one of them with
     thousands of kept matches (the selection always runs over global memory: there is no LDS-capacity fallback to miss);
+  * the kernel's structural edges (tests/two_view_fixtures.py): staged and kept counts at the ballot's 64 and the passes' 256, rejected
+    matches on both sides of those boundaries, tied and widely spread angles under the median's radix selection, tri_max_error = 0,
+    and a grid that walks through valid, invalid and H-kept pairs in one sub-batch;
   * the errors of the two entry points, and the records' lifetime across _next / _end."""
 import numpy as np
 import pytest
 
 import pose_twin
+import two_view_fixtures
 from monocularsfm_amd import _lib, synth
 from test_gpu_verify_homography import load, same, two_view
 
@@ -219,3 +223,138 @@ def test_errors_and_lifetime(tctx):
     assert code(0) == _lib.OK
     tctx.match_pairs_verified(pairs)
     assert L.msfm_fetch_two_view_geometry(h, None) == _lib.E_STATE
+
+
+# ---- the edges of tv_pose_kernel (tests/two_view_fixtures.py; tests/test_pose_reference.py checks without a GPU that every scene
+# reaches the edge it is named for) ------------------------------------------------------------------------------------------------
+
+def load_cases(ctx, cases):
+    kps, _ = load(ctx, [c["scene"] + (None,) for c in cases])
+    return kps, np.asarray([(2 * s, 2 * s + 1) for s in range(len(cases))], np.int32)
+
+
+def removed(raw, cases):
+    """The raw lists without the cases' rejected staged positions, in order: what the verified call must return."""
+    offs, qt, d = raw
+    keep = np.ones(len(qt), bool)
+    for p, c in enumerate(cases):
+        keep[offs[p] + c["rejected"]] = False
+    new = np.r_[0, np.cumsum([c["n"] - len(c["rejected"]) for c in cases])].astype(np.int64)
+    return new, qt[keep], d[keep]
+
+
+def test_kept_list_and_strides_at_their_edges(tctx, host):
+    """Staged and kept counts at 63 / 64 / 65, 127 / 128 / 129 (the ballot of 64 that writes the kept list), 255 / 256 / 257, 511 /
+    512 / 513 and 769 (the passes strided by 256: a tail of dead lanes, none, one live lane, a third and a fourth stride), with the
+    rejected matches on both sides of the 64-boundaries, a whole rejected chunk and the last staged match rejected."""
+    cases = two_view_fixtures.exact_sizes() + two_view_fixtures.staged_vs_kept()
+    kps, pairs = load_cases(tctx, cases)
+    raw = tctx.match_pairs(pairs)
+    assert np.diff(raw[0]).tolist() == [c["n"] for c in cases]                      # the staged counts
+    assert np.array_equal(raw[1], np.concatenate([c["qt"] for c in cases]))         # and lists: the planted ones
+    want = pose_twin.run(host, raw, pairs, kps, CAM)
+    lists = removed(raw, cases)
+    tctx.set_two_view_geometry(True)
+
+    def check(on, got):
+        assert same_records(got, want)
+        assert got["n_kept"].tolist() == [c["nk"] for c in cases] and got["valid"].all() and no_nan(got)
+        assert got["n_triangulated"].tolist() == [c["nk"] for c in cases]
+        assert same(on, lists)
+
+    check(tctx.match_pairs_verified(pairs), tctx.two_view_geometry(len(pairs)))
+    tctx.set_limits(max_pairs_per_batch=1)
+    check(tctx.match_pairs_verified(pairs), tctx.two_view_geometry(len(pairs)))
+    recs, qts, ds, offs = [], [], [], [0]
+    for ch in tctx.match_pairs_stream(pairs, verified=True):
+        assert ch["n_pairs"] == 1
+        recs.append(ch["two_view_geometry"].copy())
+        qts.append(ch["qt"])
+        ds.append(ch["dist"])
+        offs += (offs[-1] + ch["offsets"][1:]).tolist()
+    check((np.asarray(offs, np.int64), np.concatenate(qts), np.concatenate(ds)), np.concatenate(recs))
+    tctx.set_limits()
+
+
+def test_median_with_ties_and_spread(tctx, host):
+    """The radix selection on runs of equal keys (the remaining rank lands inside a bin on every pass; both middle ranks of an even
+    list in one run, and in two), on keys that differ in their exponent bytes, and with tri_max_error = 0: nothing triangulated,
+    both means exactly 0, the median what it was."""
+    cases = two_view_fixtures.tied_angles() + [two_view_fixtures.depth_spread()]
+    kps, pairs = load_cases(tctx, cases)
+    raw = tctx.match_pairs(pairs)
+    assert np.array_equal(raw[1], np.concatenate([c["qt"] for c in cases]))
+    want = pose_twin.run(host, raw, pairs, kps, CAM)
+    tctx.set_two_view_geometry(True)
+    tctx.match_pairs_verified(pairs)
+    got = tctx.two_view_geometry(len(pairs)).copy()
+    assert same_records(got, want) and got["valid"].all() and no_nan(got)
+    assert got["n_kept"].tolist() == [c["nk"] for c in cases]
+    assert {int(n) % 2 for n in got["n_kept"]} == {0, 1}
+    for p, c in enumerate(cases):
+        p1, p2 = kps[2 * p][c["qt"][:, 0], :2], kps[2 * p + 1][c["qt"][:, 1], :2]
+        mask, _ = pose_twin.geometry(host, p1, p2, CAM)
+        angles = pose_twin.kept_angles(host, got[p], p1[mask], p2[mask], CAM)
+        assert len(set(angles)) == c.get("distinct", c["nk"])
+        assert got["median_tri_angle"][p] == pose_twin.median_rule(angles), c["name"]
+    assert got["is_initial_candidate"].any() and (got["n_triangulated"] > 0).all()
+    tctx.set_two_view_geometry(True, tri_max_error=0.0)
+    tctx.match_pairs_verified(pairs)
+    got0 = tctx.two_view_geometry(len(pairs))
+    assert same_records(got0, pose_twin.run(host, raw, pairs, kps, CAM, params=(100, 0.0, 4.0)))
+    assert got0["valid"].all() and not got0["n_triangulated"].any() and not got0["is_initial_candidate"].any()
+    assert got0["mean_tri_angle"].tobytes() == got0["mean_residual"].tobytes() == np.zeros(len(pairs)).tobytes()
+    assert got0["median_tri_angle"].tobytes() == got["median_tri_angle"].tobytes() and (got0["median_tri_angle"] > 0).all()
+    assert got0["R"].tobytes() == got["R"].tobytes() and np.array_equal(got0["n_positive_depth"], got["n_positive_depth"])
+
+
+def test_grid_walks_through_invalid_and_valid_pairs(tctx, host):
+    """One sub-batch of 3 * CUs + 7 pairs, most of them cross pairs that leave the kernel early, the valid own-scene pairs spread over
+    the three thirds: workgroups walk valid, invalid, valid and invalid, valid, invalid (the LDS state of one pair must not reach the
+    next).  Then with planar scenes under the model selection: H-kept pairs (a third early exit) between E-kept ones."""
+    cu = tctx.device_info()["cu_count"]
+    zero = np.zeros(1, pose_twin.RECORD).tobytes()
+    plain = {}
+    for planar_every in (0, 3):
+        job = two_view_fixtures.walk_job(cu, planar_every)
+        pairs, own = job["pairs"], job["own"]
+        tctx.clear_images()
+        kps, _ = load(tctx, job["scenes"])
+        tctx.set_pipeline(1)
+        tctx.set_limits(max_pairs_per_batch=len(pairs))
+        tctx.set_model_selection(False)
+        raw = tctx.match_pairs(pairs)
+        assert sorted(set(np.diff(raw[0])[job["staged_only"]].tolist())) == [3, 4]     # staged, but fewer than an E needs
+        want = pose_twin.run(host, raw, pairs, kps, CAM)
+        tctx.set_two_view_geometry(True)
+        tctx.match_pairs_verified(pairs)
+        assert tctx.profile()["sub_batches"] == 1
+        got = tctx.two_view_geometry(len(pairs)).copy()
+        assert same_records(got, want) and no_nan(got)
+        valid = got["valid"] == 1
+        assert all(valid[k * cu:(k + 1) * cu].any() for k in range(3)) and valid[3 * cu:].sum() == 0
+        assert all(got[p:p + 1].tobytes() == zero for p in np.nonzero(~valid)[0])
+        is_own = np.zeros(len(pairs), bool)
+        is_own[own] = True
+        assert int(valid.sum()) == int(want["valid"][is_own].sum()) >= 40 and not valid[~is_own].any()
+        walks = {tuple(valid[b::cu][:3]) for b in range(cu)}
+        assert {(True, False, True), (False, True, False)} <= walks
+        plain[planar_every] = (got, valid, pairs, job)
+    # the planar variant under the selection
+    got, valid, pairs, job = plain[3]
+    tctx.set_model_selection(True, 0.7)
+    tctx.match_pairs_verified(pairs)
+    assert tctx.profile()["sub_batches"] == 1
+    sel = tctx.two_view_geometry(len(pairs))
+    h_kept = tctx.model_selection(len(pairs))[0] == _lib.VERIFY_HOMOGRAPHY
+    assert h_kept[job["planar"]].sum() >= 8 and not h_kept[job["own"]][~job["planar"][job["own"]]].any()
+    assert not sel["valid"][h_kept].any() and sel[h_kept].tobytes() == zero * int(h_kept.sum())
+    assert same_records(sel[~h_kept], got[~h_kept])
+    e_own = np.nonzero(sel["valid"] == 1)[0]
+    h_own = np.nonzero(h_kept & valid)[0]                      # valid without the selection, H-kept (cleared) with it
+    assert len(h_own) >= 8 and any(e_own[0] < p < e_own[-1] for p in h_own)
+    walks = {tuple(sel["valid"][b::cu][:3].tolist()) for b in range(cu) if h_kept[b::cu][:3].any()}
+    assert any(sum(w) >= 1 for w in walks)                     # a workgroup meets an H-kept pair and an E-kept one
+    tctx.set_model_selection(False)
+    tctx.set_pipeline()
+    tctx.set_limits()
