@@ -279,7 +279,17 @@ int msfm_read_device(msfm_ctx* ctx, void* host_dst, const void* device_src, int6
  * point is OUTSIDE the bit-parity claim; it is bit-identical to the host twin
  * monocularsfm_amd/host/GeometricVerification.cpp (shared arithmetic, csrc/msfm_fmat.h).
  * Cases as in findFundamentalMat: no matches -> none; < 7 -> none; exactly 7 -> all; otherwise RANSAC with
- * the adaptive iteration bound, and a consensus set below 8 keeps none. */
+ * the adaptive iteration bound, and a consensus set below 8 keeps none.
+ * THE COORDINATES ARE NOT VALIDATED: msfm_upload_keypoints checks the row count and nothing else (the reference does not validate
+ * them either, and dropping rows would change the row indices).  A NaN, an infinity or a huge coordinate reaches the verification, the
+ * two-view records, the triangulations, the registration, the refinements and the map extension, and there it makes ITS OWN
+ * OBSERVATION FAIL every test it takes part in -- it is never a kept match of a sample-based model's consensus, never an inlier of a
+ * point or of a pose, no loop's bound depends on it, and the tests (tests/test_nonfinite_reference.py, tests/test_gpu_nonfinite.py) hold the calls to
+ * treating it byte for byte as they treat the same coordinate at 1e6 px.  (A plain,
+ * non-robust triangulation whose DLT takes such an observation in gives ATTEMPTED without ERROR_OK -- without a point for a
+ * non-finite coordinate -- as for any gross outlier.)  The only doubles of an output that can be NaN are that observation's own
+ * error slots (msfm_fetch_points3d's and msfm_fetch_registrations' residuals), and a NaN there is always 0x7ff8000000000000
+ * (csrc/msfm_pose.h, "THE NaN RULE").  The denormals and -0.0 are the pixel coordinate 0. */
 typedef struct msfm_verify_params {
     double threshold;            /* pixels (reference: 3.0) */
     double confidence;           /* (reference: 0.99) */

@@ -81,7 +81,7 @@ MSFM_FHD void extend_track(const msfm_ref::Obs* obs, int n, const msfm_tri::Pose
         bool d;
         const double err = msfm_tri::obs_error(p->R, p->t, o.u, o.w, X, f, &d);
         const bool in = d && err <= vd.max_error;   // (false for a NaN)
-        residuals[k] = err;
+        residuals[k] = msfm_pose::canonical(err);
         mask[k] = in ? 1 : 0;
         accepted += in ? 1 : 0;
         rejected += in ? 0 : 1;

@@ -6,7 +6,9 @@
 // selection gets an invalid record.
 //
 // The contract of msfm_fmat.h / msfm_emat.h holds: fp64 with +, -, *, /, sqrt only, static loop structure, -ffp-contract=off on
-// both sides -> the host twin and the device produce the SAME bits.
+// both sides -> the host twin and the device produce the SAME bits.  The one exception is the bits of a NaN, which belong to the
+// processor: every double that can be NaN where it is stored to an output goes through canonical() below ("THE NaN RULE"), so the
+// outputs agree there too.
 //
 //   decomposition    one-sided (Hestenes) Jacobi on the columns of E, kSvdSweeps fixed cyclic sweeps: E V = U S.  The columns are
 //                    ordered by norm with a fixed compare-and-swap network; u1, u2 are the two largest ones normalised,
@@ -58,6 +60,22 @@ constexpr double kDepthEps = 2.220446049250313e-16;   // std::numeric_limits<dou
 constexpr double kMaxFinite = 1.7976931348623157e308;
 
 MSFM_FHD bool finite(double v) { return v >= -kMaxFinite && v <= kMaxFinite; }   // (false for NaN)
+
+// THE NaN RULE of everything this stage hands out.  Keypoint coordinates are not validated (msfm_upload_keypoints): a NaN, an
+// infinity or a huge coordinate reaches the arithmetic, and every decision on it is written so that a NaN FAILS (err <= max_error,
+// depth > kDepthEps, h[3] != 0, finite(X) are all false for one), which makes its observation a gross outlier.  The only doubles that
+// can then be NaN in an output are the per-observation error slots (residuals), and "the same bits" cannot be asked of a NaN as it
+// falls out of the arithmetic: which operand's payload survives an operation, and the sign of a NaN that an operation generates
+// (inf - inf, 0 * inf, sqrt(-1)), belong to the processor -- x86 generates 0xfff8000000000000, the GPU 0x7ff8000000000000.  So every
+// double that can be NaN goes through canonical() where it is stored to an output: v itself when v == v (infinities included), else
+// THE NaN 0x7ff8000000000000, built from these bits and not from arithmetic.
+constexpr unsigned long long kCanonicalNaN = 0x7ff8000000000000ULL;
+MSFM_FHD double canonical(double v) {
+    double q;
+    const unsigned long long bits = kCanonicalNaN;
+    __builtin_memcpy(&q, &bits, sizeof q);
+    return v == v ? v : q;
+}
 
 // asin(z) = z * sum_k c_k z^2k for |z| <= 1/2: c_0 = 1, c_k = c_{k-1} (2k - 1)^2 / (2k (2k + 1)), k < 22 (the first term left out is
 // below 1e-16 there)

@@ -300,7 +300,7 @@ MSFM_FHD void point_verdict(const Obs* obs, int n, const msfm_tri::Pose* poses, 
         const msfm_tri::Pose* p = poses + o.rank;
         bool d;
         const double err = msfm_tri::obs_error(p->R, p->t, o.u, o.w, X, f, &d);
-        if (residuals) residuals[k] = err;
+        if (residuals) residuals[k] = msfm_pose::canonical(err);
         if (!(o.flags & OBS_FIT)) continue;
         depth_ok = depth_ok && d;
         error_ok = error_ok && err <= vd.max_error;   // (false for a NaN)
@@ -349,7 +349,7 @@ MSFM_FHD void refine_track(const Obs* obs, int n, const msfm_tri::Pose* poses, d
         if (!(o.flags & OBS_USED)) continue;
         const msfm_tri::Pose* p = poses + o.rank;
         bool d;
-        residuals[k] = msfm_tri::obs_error(p->R, p->t, o.u, o.w, s.X, f, &d);
+        residuals[k] = msfm_pose::canonical(msfm_tri::obs_error(p->R, p->t, o.u, o.w, s.X, f, &d));
     }
     msfm_point3d r = old;
     r.status = MSFM_TRI_ATTEMPTED | MSFM_TRI_POINT | v.bits | (old.status & MSFM_TRI_ROBUST) | MSFM_TRI_REFINED;

@@ -543,7 +543,7 @@ inline void RegisterImage(int image_id, const double* cu, const double* cv, cons
         const bool in = inlier(R, t, cu[i], cv[i], cX[i], cY[i], cZ[i], f2, thr2);
         const double e = residual(R, t, cu[i], cv[i], cX[i], cY[i], cZ[i], f);
         flags[i] = in ? 1 : 0;
-        residuals[i] = e;
+        residuals[i] = msfm_pose::canonical(e);
         if (in) {
             ni += 1;
             sum = sum + e;

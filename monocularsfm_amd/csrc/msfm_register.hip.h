@@ -335,7 +335,7 @@ __global__ __launch_bounds__(64) void reg_finish_kernel(const long long* __restr
             in = inlier(R, t, cu[i], cv[i], cX[i], cY[i], cZ[i], f2, thr2);
             e = residual(R, t, cu[i], cv[i], cX[i], cY[i], cZ[i], f);
             flags[base + i] = in ? 1 : 0;
-            residuals[base + i] = e;
+            residuals[base + i] = msfm_pose::canonical(e);
         }
         unsigned long long bal = __ballot(in);
         nf += __popcll(bal);

@@ -306,7 +306,7 @@ MSFM_UNROLL
         const double err = sqrt(dx * dx + dy * dy) * f;
         error_ok = error_ok && err <= prm.max_error;   // (false for a NaN)
         sum = sum + err;
-        residuals[k] = err;
+        residuals[k] = msfm_pose::canonical(err);
     }
     // the parallax scan: for i: for j < i over the used observations, to the first pair that reaches min_angle
     bool angle_ok = false;
@@ -437,7 +437,7 @@ MSFM_FHD void evaluate_point(const A& a, int n, const double X[3], const uint8_t
         msfm_emat::undistort(cam, x, y, &u, &w);
         bool depth;
         const double err = obs_error(p->R, p->t, u, w, X, f, &depth);
-        residuals[k] = err;
+        residuals[k] = msfm_pose::canonical(err);
         if (mask[k]) {
             depth_ok = depth_ok && depth;
             sum = sum + err;

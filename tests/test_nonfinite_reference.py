@@ -1,0 +1,518 @@
+"""Non-finite and huge keypoint coordinates through the host twins of the reconstruction and verification stages (DESIGN.md section
+21).  CPU only.  msfm_upload_keypoints validates nothing, so a NaN (plain, signed, with a payload), +-inf, +-3e38, 1e30, the smallest
+denormal and -0.0 reach every function that reads a keypoint; the shared headers promise that "a NaN fails" every test it takes part
+in.  These tests hold the twins -- and through the byte comparisons of tests/test_gpu_nonfinite.py the kernels -- to that, for every
+entry of nonfinite_fixtures.CASES, under CAM and the distorted CAM_D, on the placements of tests/nonfinite_fixtures.py.  That every
+case returns at all is the proof that no shared loop needs a finite value to end.
+
+WHICH PLACEMENT IS COMPARED WHICH WAY
+  first form    GROSS-OUTLIER EQUIVALENCE: the chain on the scene equals, byte for byte, the chain on the twin scene whose bad coordinates
+                are 1e6 -- records, inlier bytes, pose lists, registration and pose-refinement records, every counter and every residual
+                slot outside the bad mask.  Every track whose record comes from a consensus or from a continuation: every track of the
+                robust session; the tracks the extension creates with max_hypotheses 8 (robust or plain session); every clean track
+                anywhere.
+  second form   a PLAIN track whose DLT takes the bad observation in: the bad tracks of the plain triangulation and of the point
+                refinement that follows it (plain session), and the bad 3-view tracks that the extension creates with max_hypotheses 0
+                (either session).  The DLT over a NaN is not the DLT over 1e6, so there the documented result is asserted instead:
+                ATTEMPTED and never ERROR_OK (so the track supports nothing downstream); for a non-finite value ATTEMPTED alone, every
+                other field 0, every slot -1, n_views = the posed elements (msfm_triangulate.h, "DLT").  The counters and cost sums of
+                a step that has such tracks follow them (eligible, iterations, points_reposed, the costs) and are not compared there.
+The 1e6 scene itself is anchored: test_the_gross_scene_against_the_references holds its twins to the independent numpy references
+with those modules' own comparisons, margins and tolerances."""
+import numpy as np
+import pytest
+
+import extend_twin as etw
+import nonfinite_fixtures as nf
+import refine_poses_twin as ptw
+import triangulation_twin as tw
+from monocularsfm_amd import _lib
+
+CANONICAL = 0x7ff8000000000000
+PLACEMENTS = {"lanes": nf.lanes, "wave": nf.whole_wave, "images": nf.images}
+CAMS = {"cam": nf.CAM, "cam_d": nf.CAM_D}
+STEPS = ("plain", "robust", "refine1", "register", "extend", "poses", "refine2")
+
+
+@pytest.fixture(scope="module")
+def host():
+    return nf.load_host()
+
+
+_GROSS = {}
+
+
+def gross_chain(host, place, case, cam, mh, robust):
+    """the chain on the twin scene: the same for every value that sits in the same coordinates"""
+    key = (place, case[2], cam, mh, robust)
+    if key not in _GROSS:
+        _GROSS[key] = nf.chain(host, PLACEMENTS[place](case)[2], CAMS[cam], mh=mh, robust=robust)
+    return _GROSS[key]
+
+
+def posed_after(step, sc):
+    """the image positions that have a pose when `step` has run"""
+    return set(nf.OLD) | (set(nf.NEW) | {nf.REG} if step in ("extend", "poses", "refine2") else set())
+
+
+def loose_tracks(step, sc, out, mh, robust):
+    """the second form's tracks at `step` (module docstring): bad tracks whose record is a plain DLT over a bad observation"""
+    o = sc.tracks[0]
+    bad_posed = np.asarray([any(sc.bad[o[t] + k] for k in range(n) if k in posed_after(step, sc)) for t, n in enumerate(sc.lengths)])
+    if step in ("plain",) or (not robust and step in ("refine1",)):
+        return bad_posed
+    if step in ("extend", "poses", "refine2") and mh == 0:
+        return bad_posed & (out["extend"][5]["kind"] == etw.KIND_CREATE)
+    return np.zeros(len(sc.lengths), bool)
+
+
+def arrays_of(step, o):
+    """(records per track, residuals per slot, bytes per slot or None, everything else that must be byte-equal, counters) of a step"""
+    if o is None:
+        return None
+    if step == "plain":
+        return o[0], o[1], None, [], None
+    if step == "robust":
+        return o[0], o[1], o[2], [], o[3]
+    if step in ("refine1", "refine2"):
+        return o[0], o[1], None, [], o[2]
+    if step == "extend":
+        return o[0], o[1], o[2], list(o[4]), o[3]
+    if step == "poses":
+        return o[0], o[1], None, list(o[2]) + [o[3]], o[4]
+    raise AssertionError(step)
+
+
+def nan_bits(a):
+    a = np.ascontiguousarray(a, np.float64)
+    return set(int(v) for v in a.view(np.uint64)[np.isnan(a)])
+
+
+def float_fields_finite(rec):
+    for name in rec.dtype.names:
+        if rec.dtype[name].base.kind == "f":
+            assert np.all(np.isfinite(rec[name])), name
+
+
+def same_number(a, b):
+    return a == b or (a != a and b != b)
+
+
+def compare(sc, case, a, b, mh, robust, canonical=True):
+    """the chain outputs `a` (the scene) against `b` (the twin scene): the first form wherever it applies, the second form elsewhere;
+    every float field of every record finite; NaNs only inside the bad mask and, with `canonical`, only THE NaN"""
+    o = sc.tracks[0]
+    per_slot = np.repeat(np.arange(len(sc.lengths)), np.diff(o))
+    for step in STEPS:
+        if a.get(step) is None:
+            assert b.get(step) is None
+            continue
+        if step == "register":
+            ra, rb = a[step], b[step]
+            badc = nf.registration_bad(sc, ra)
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(ra[:4], rb[:4])), (case[0], step)     # records, offsets, track ids, flags
+            assert ra[4][~badc].tobytes() == rb[4][~badc].tobytes() and not np.isnan(ra[4][~badc]).any(), (case[0], step)
+            assert not ra[3][badc].any()                                  # a bad correspondence is never an inlier
+            float_fields_finite(ra[0])
+            if canonical:
+                assert nan_bits(ra[4]) <= {CANONICAL}, (case[0], step, [hex(v) for v in nan_bits(ra[4])])
+            continue
+        pa, sa, ma, xa, ca = arrays_of(step, a[step])
+        pb, sb, mb, xb, cb = arrays_of(step, b[step])
+        loose = loose_tracks(step, sc, a, mh, robust)
+        tight = ~loose
+        slot_ok = tight[per_slot] & ~sc.bad
+        assert pa[tight].tobytes() == pb[tight].tobytes(), (case[0], step, np.nonzero(pa != pb)[0][:8])
+        assert sa[slot_ok].tobytes() == sb[slot_ok].tobytes(), (case[0], step)
+        if ma is not None:
+            assert ma[tight[per_slot]].tobytes() == mb[tight[per_slot]].tobytes(), (case[0], step)
+            assert not ma[sc.bad & tight[per_slot]].any(), (case[0], step)     # a bad observation never supports a consensus point
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(xa, xb)), (case[0], step)
+        if ca is not None and not loose.any():
+            assert all(same_number(ca[k], cb[k]) for k in ca), (case[0], step, ca, cb)
+            # which cost sums are finite (tests/test_gpu_nonfinite.py asserts the same of the device): all of them where no track is
+            # of the second form
+            assert all(np.isfinite(ca[k]) for k in ca if k.startswith("cost_")), (case[0], step, ca)
+        elif ca is not None and (nf.non_finite(case) or case[0].startswith(("denormal", "minus_zero"))):
+            # ... and where the second-form tracks have no point (a non-finite value) or an error that does not overflow (0 px)
+            assert all(np.isfinite(ca[k]) for k in ca if k.startswith("cost_")), (case[0], step, ca)
+        # the second form
+        for t in np.nonzero(loose)[0]:
+            s = int(pa[t]["status"])
+            assert s & _lib.TRI_ATTEMPTED and not s & _lib.TRI_ERROR_OK, (case[0], step, t, s)
+            if nf.non_finite(case):
+                posed = sum(1 for k in range(sc.lengths[t]) if k in posed_after(step, sc))
+                assert (s & ~_lib.TRI_EXTENDED) == _lib.TRI_ATTEMPTED and pa[t]["n_views"] == posed, (case[0], step, t, pa[t])
+                assert pa[t].tobytes()[8:] == bytes(40) and np.all(sa[o[t]:o[t + 1]] == -1.0), (case[0], step, t, pa[t])
+        # finiteness and THE NaN (a second-form track under 3e38 or 1e30 has a finite X whose errors overflow: mean_residual = +inf)
+        float_fields_finite(pa[tight])
+        assert not any(np.isnan(pa[n]).any() for n in ("X", "mean_residual", "tri_angle")), (case[0], step)
+        for x in xa:
+            if x.dtype.names:
+                float_fields_finite(x)
+        assert not np.isnan(sa[~sc.bad]).any(), (case[0], step)
+        if canonical:
+            assert nan_bits(sa) <= {CANONICAL}, (case[0], step, [hex(v) for v in nan_bits(sa)])
+
+
+@pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
+@pytest.mark.parametrize("cam", sorted(CAMS))
+@pytest.mark.parametrize("place", sorted(PLACEMENTS))
+def test_the_chain_equals_the_gross_outlier_scene(host, place, cam, case):
+    """robust and plain session, the extension with max_hypotheses 8 and 0: the module docstring says what is compared which way"""
+    sc = PLACEMENTS[place](case)[0]
+    for robust in (True, False):
+        for mh in (8, 0):
+            a = nf.chain(host, sc, CAMS[cam], mh=mh, robust=robust)
+            compare(sc, case, a, gross_chain(host, place, case, cam, mh, robust), mh, robust)
+
+
+@pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
+@pytest.mark.parametrize("cam", sorted(CAMS))
+def test_tile_elements_equal_the_gross_outlier_scene(host, cam, case):
+    """the elements placement (tracks of 2 .. 130 views, the bad observation at element 0, 63, 64 and last) through the plain and the
+    robust triangulation and the point refinement: the robust session in the first form -- but for the 2-view tracks, which are not
+    retried (m < 3) and keep the plain record: second form -- the plain session in the second"""
+    sc, bad, gr = nf.elements(case)
+    poses = sc.poses
+    o = sc.tracks[0]
+    per_slot = np.repeat(np.arange(len(sc.lengths)), np.diff(o))
+    badt = np.zeros(len(sc.lengths), bool)
+    badt[sc.bad_tracks()] = True
+    two = badt & (np.asarray(sc.lengths) == 2)
+    outs = []
+    for s in (sc, gr):
+        pp, pr = tw.run(host, s.tracks, s.ids, s.kps, poses, CAMS[cam], nf.THR)
+        rp, rr, rm, rc, tr = nf.robtw.run(host, s.tracks, s.ids, s.kps, poses, CAMS[cam], nf.THR + (64,), trace=True)
+        fp, fr, fc = nf.rtw.run(host, s.tracks, s.ids, s.kps, poses, CAMS[cam], rp, rr, rm, nf.THR[:2])
+        qp, qr, qc = nf.rtw.run(host, s.tracks, s.ids, s.kps, poses, CAMS[cam], pp, pr, None, nf.THR[:2])
+        outs.append(dict(plain=(pp, pr), robust=(rp, rr, rm, rc), refined=(fp, fr, fc), plain_refined=(qp, qr, qc), trace=tr))
+    a, b = outs
+    tight = ~two
+    for step in ("robust", "refined"):
+        assert a[step][0][tight].tobytes() == b[step][0][tight].tobytes(), (case[0], step)
+        ok = tight[per_slot] & ~bad
+        assert a[step][1][ok].tobytes() == b[step][1][ok].tobytes(), (case[0], step)
+        assert not np.isnan(a[step][1][~bad]).any() and nan_bits(a[step][1]) <= {CANONICAL}, (case[0], step)
+        float_fields_finite(a[step][0][tight])
+    assert a["robust"][2].tobytes() == b["robust"][2].tobytes() and a["robust"][3] == b["robust"][3]
+    assert not a["robust"][2][bad & tight[per_slot]].any()
+    # (the refinement's counters and cost sums follow the 2-view tracks' plain records and are not compared here)
+    # every bad track of 3 and more views went through the hypotheses; those of 64 and more lost the bad observation and nothing else
+    # and kept a point; a 3-view track is left with two views 1.2 degrees apart (elements 1, 2 or 0, 1: below min_angle, no consensus)
+    # or 2.4 degrees apart (elements 0, 2)
+    lengths = np.asarray(sc.lengths)
+    tr = a["trace"]
+    assert np.all(tr["retried"][badt & ~two] == 1)
+    long_bad = badt & (lengths >= 64)
+    assert long_bad.sum() == 9 and np.all(tr["mask1"][long_bad] == lengths[long_bad] - 1) and np.all(_lib.succeeded(a["robust"][0])[long_bad])
+    three = np.nonzero(badt & (lengths == 3))[0]
+    assert [int(tr["mask1"][t]) for t in three] == [-1, -1] and np.all(a["robust"][0]["status"][three] == _lib.TRI_ATTEMPTED | _lib.TRI_ROBUST)
+    # the plain records: clean tracks equal, bad ones in the second form
+    for step in ("plain", "plain_refined"):
+        assert a[step][0][~badt].tobytes() == b[step][0][~badt].tobytes()
+        assert a[step][1][~badt[per_slot]].tobytes() == b[step][1][~badt[per_slot]].tobytes()
+        float_fields_finite(a[step][0][~badt])
+        assert not any(np.isnan(a[step][0][n]).any() for n in ("X", "mean_residual", "tri_angle"))
+        assert not np.isnan(a[step][1][~bad]).any() and nan_bits(a[step][1]) <= {CANONICAL}
+        for t in np.nonzero(badt)[0]:
+            s = int(a[step][0][t]["status"])
+            assert s & _lib.TRI_ATTEMPTED and not s & _lib.TRI_ERROR_OK
+            if nf.non_finite(case):
+                assert s == _lib.TRI_ATTEMPTED and a[step][0][t]["n_views"] == sc.lengths[t] and np.all(a[step][1][o[t]:o[t + 1]] == -1.0)
+    for t in np.nonzero(two)[0]:                                  # never retried: the plain record stands in the robust call
+        assert a["robust"][0][t].tobytes() == a["plain"][0][t].tobytes()
+
+
+@pytest.mark.parametrize("case", [c for c in nf.CASES if c[2] == "x" or c[0] == "nan_xy"], ids=lambda c: c[0])
+def test_the_routes_are_reached(host, case):
+    """On the twins' traces, under CAM, on the images placement: a fixture that quietly misses a route proves nothing."""
+    sc = nf.images(case)[0]
+    ids, o = sc.ids, sc.tracks[0]
+    a = nf.chain(host, sc, nf.CAM, mh=8, robust=True)
+    lengths = np.asarray(sc.lengths)
+    badt = np.zeros(len(lengths), bool)
+    badt[sc.bad_tracks()] = True
+    long_bad, short_bad = np.nonzero(badt & (lengths == 8))[0], np.nonzero(badt & (lengths == 3))[0]
+    assert len(long_bad) >= 16 and len(short_bad) >= 8
+    # the consensus rejected the bad observation of the OLD image: retried, mask 0 there, rescued
+    rp, rr, rm, rc, tr = a["robust"]
+    assert np.all(tr["retried"][long_bad] == 1) and not rm[o[long_bad] + 4].any() and np.all(rm[o[long_bad] + 3] == 1)
+    assert np.all(_lib.succeeded(rp)[long_bad]) and np.all(rp["status"][long_bad] & _lib.TRI_ROBUST)
+    assert rc["retried"] == rc["rescued"] == rc["observations_rejected"] == len(long_bad)
+    plain = a["plain"][0]
+    assert not (plain["status"][long_bad] & _lib.TRI_ERROR_OK).any()
+    if nf.non_finite(case):
+        assert np.all(plain["status"][long_bad] == _lib.TRI_ATTEMPTED) and not np.isfinite(rr[o[long_bad] + 4]).any()
+    # a continued track rejected its bad new observations (images 1 and REG), accepted the clean one (image 0)
+    ep, er, em, ec, el, et = a["extend"]
+    assert np.all(et["kind"][long_bad] == etw.KIND_CONTINUE) and np.all(et["new_observations"][long_bad] == 3)
+    assert np.all(et["accepted"][long_bad] == 1) and not em[o[long_bad] + 1].any() and not em[o[long_bad] + 7].any()
+    if nf.non_finite(case):
+        assert not np.isfinite(er[o[long_bad] + 1]).any() and not np.isfinite(er[o[long_bad] + 7]).any()
+    # a created track: the plain DLT over its three views fails, it is retried, and rescued from the two clean views
+    assert np.all(et["kind"][short_bad] == etw.KIND_CREATE) and np.all(et["route"][short_bad] == etw.ROUTE_ROBUST)
+    assert np.all(_lib.succeeded(ep)[short_bad]) and np.all(ep["n_views"][short_bad] == 2) and not em[o[short_bad] + 1].any()
+    full = tw.run(host, sc.tracks, ids, sc.kps, el, nf.CAM, nf.THR, select=short_bad)[0]
+    assert not (full["status"][short_bad] & _lib.TRI_ERROR_OK).any()
+    if nf.non_finite(case):
+        assert np.all(full["status"][short_bad] == _lib.TRI_ATTEMPTED)
+    # the registration drew samples with bad correspondences and succeeded all the same
+    reg = a["register"]
+    drew = nf.samples_with_bad(host, sc, reg)
+    assert drew >= 1 and _lib.registered(reg[0]).all() and nf.registration_bad(sc, reg).sum() >= 16
+    # the pose refinement of the images with bad observations stood
+    pid, tab = a["poses"][2]
+    rec, trc = a["poses"][3], a["poses"][5]
+    for pos in nf.BAD_AT:
+        k = pid.tolist().index(int(ids[pos]))
+        assert trc[k]["verdict"] == 0 and trc[k]["accepted"] >= 1, (pos, trc[k])
+    print("%s: retried %d, samples with a bad correspondence %d of %d" % (case[0], rc["retried"], drew, int(reg[0][0]["hypotheses"])))
+
+
+# ---- the verification stage ---------------------------------------------------------------------------------------------------------------
+N_MATCHES, N_BAD = 300, 20
+
+
+def verify_pair(kind, case):
+    """300 matches of a general (or planar) two-view scene with 0.5 px of noise; the value sits in 20 of them, alternately in image 1
+    and in image 2 -> (p1, p2, bad [300], the twin pair with 1e6 there)"""
+    from monocularsfm_amd import synth
+    make = synth.planar_view_pair if kind == "planar" else synth.general_view_pair
+    k1, k2, _, _ = make(N_MATCHES, 0, seed=11, noise_px=0.5)
+    p = [np.array(k1[:, :2], np.float32), np.array(k2[:, :2], np.float32)]
+    g = [a.copy() for a in p]
+    bad = np.zeros(N_MATCHES, bool)
+    for n, row in enumerate(range(7, N_MATCHES, N_MATCHES // N_BAD)[:N_BAD]):
+        bad[row] = True
+        if case is not None:
+            for ax in case[2]:
+                p[n % 2][row, "xy".index(ax)] = nf.value(case[1])
+                g[n % 2][row, "xy".index(ax)] = nf.GROSS
+    return p[0], p[1], bad, (g[0], g[1])
+
+
+def verify_all(vhost, phost, p1, p2, cam):
+    """every verification twin on one pair -> {name: (kept mask, record or None, schedule or None)}"""
+    import pose_twin
+    import verify_twin as vt
+    camv = np.asarray(tuple(cam) + (0.0,) * (8 - len(cam)), np.float64)
+    out = {}
+    m = np.zeros(len(p1), np.uint8)
+    a, b = np.ascontiguousarray(p1, np.float32), np.ascontiguousarray(p2, np.float32)
+    k = vhost.host_fundamental_ransac_ex(a.ctypes.data_as(vt.FP), b.ctypes.data_as(vt.FP), len(a), 3.0, 0.99, 1000, 0x5eed5eed,
+                                         m.ctypes.data_as(vt.UP))
+    out["F"] = (m[:k].astype(bool) if k else np.zeros(len(a), bool), None, None)
+    for name, model, select in (("E", 1, False), ("H", 2, False), ("select_F", 0, True), ("select_E", 1, True)):
+        out[name] = vt._pair(vhost, model, select, camv, 0.7, 3.0, 0.99, 1000, 0x5eed5eed, a, b)
+    mask, rec = pose_twin.geometry(phost, a, b, cam)
+    out["pose"] = (mask, rec, None)
+    return out
+
+
+@pytest.fixture(scope="module")
+def vhosts():
+    import ctypes as C
+
+    import pose_twin
+    import verify_twin as vt
+    v = vt.load_host()
+    v.host_fundamental_ransac_ex.argtypes = [vt.FP, vt.FP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_ulonglong, vt.UP]
+    return v, pose_twin.load_host()
+
+
+@pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
+@pytest.mark.parametrize("cam", sorted(CAMS))
+@pytest.mark.parametrize("kind", ["general", "planar"])
+def test_verification_twins(vhosts, kind, cam, case):
+    """The F, E and H RANSAC twins, the model selection under both epipolar models and pose_twin.geometry on a 300-match pair with
+    the value planted in 20 matches (10 in either image).  The gross-outlier equivalence holds here as well and is asserted: kept
+    lists, selection records, staged schedules and the two-view record are those of the pair with 1e6 in the same coordinates.  A
+    sample that draws a bad match gives a model that is not finite or that nothing agrees with; a bad match fails every error test.
+    THE DENORMAL AND -0.0 ARE COMPARED ANOTHER WAY: they are the pixel coordinate 0, a place inside the image, and an epipolar test
+    has one degree of freedom -- on the planar pair the F twin keeps match 67 with x = 0 px, as it must (0 px lies within 3 px of
+    its epipolar line), and does not keep it with 1e6.  What the code owes these two values is that they count as the number they
+    are: every output equals, byte for byte, that of the pair with +0.0 in the same coordinates (x - cx is the same double for all
+    three)."""
+    p1, p2, bad, gross = verify_pair(kind, case)
+    zero_like = case[0].startswith(("denormal", "minus_zero"))
+    if zero_like:                                           # the twin pair: +0.0 there
+        gross = tuple(np.where(g == nf.GROSS, np.float32(0.0), g) for g in gross)
+    got = verify_all(*vhosts, p1, p2, CAMS[cam])
+    want = verify_all(*vhosts, *gross, CAMS[cam])
+    for name, (keep, rec, sched) in got.items():
+        if not zero_like:
+            assert not keep[bad].any(), (name, np.nonzero(keep & bad)[0])                   # no bad match is kept
+        if (name == "H") == (kind == "planar") or name.startswith("select"):
+            assert keep.sum() >= 250, (name, int(keep.sum()))                               # ... and the pair is not lost to them
+        gk, grec, gsched = want[name]
+        assert np.array_equal(keep, gk), (name, np.nonzero(keep != gk)[0])                  # the equivalence
+        if name == "pose":
+            assert rec["valid"] == 1 and rec["n_kept"] == keep.sum() and rec.tobytes() == grec.tobytes(), (rec, grec)
+            assert all(np.all(np.isfinite(rec[f])) for f in ("R", "t", "median_tri_angle", "mean_tri_angle", "mean_residual"))
+        else:
+            assert rec == grec and sched == gsched, (name, rec, grec, sched, gsched)
+            assert sched is None or all(0 < s <= 1000 and 0 < r <= 32 for s, r in sched), sched   # (solved, rounds): finite, in range
+
+
+# ---- the oracle's anchor: the 1e6 scene against the independent references -----------------------------------------------------------------
+@pytest.mark.parametrize("axes", ["x", "y", "xy"])
+@pytest.mark.parametrize("cam", sorted(CAMS))
+def test_the_gross_scene_against_the_references(host, cam, axes):
+    """The twin scene (1e6 in the bad coordinates) of the images placement is finite, so the independent numpy references process it:
+    every twin of the chain against its reference, fed the same state, with the comparison functions, guards and tolerances of that
+    twin's own reference test (tests/test_*_reference.py); the point and pose refinements with those modules' step_tol 1e-4."""
+    import extend_ref
+    import refine_points_ref
+    import refine_poses_ref
+    import registration_ref
+    import robust_triangulation_ref
+    import test_extend_points_reference as xe
+    import test_refine_points_reference as xr
+    import test_refine_poses_reference as xp
+    import test_registration_reference as xg
+    import test_robust_triangulation_reference as xb
+    import test_triangulation_reference as xt
+    import triangulation_ref
+    case = next(c for c in nf.CASES if c[0] == "nan_" + axes)
+    gr = nf.images(case)[2]
+    o = gr.tracks[0]
+
+    def bad_slots_apart(res, want, tol):
+        """The bad observations' errors are ~1e6 px, where one ulp (1.2e-10) is of the size of the modules' ABSOLUTE tolerances, which
+        were measured on errors of a few px: they are held to `tol` RELATIVE to the error here and then handed to the module's
+        comparison as the reference's own numbers.  Under CAM_D not even that: 1e6 px lies 400 focal lengths off the axis, where the
+        undistortion's fixed-point iteration does not converge and its result depends on the number of steps (the twin's
+        kUndistortIters, the references' own): there both must call the observation gross (> 100 x max_error), and every decision
+        that the modules' comparisons check -- statuses, inlier bytes, counters -- must still agree.  -> a copy of res"""
+        res = np.array(res, copy=True)
+        for t, r in enumerate(want):
+            for k in np.nonzero(gr.bad[o[t]:o[t + 1]])[0]:
+                e = r["residuals"][k]
+                if e >= 0:
+                    if any(c_[4:]):
+                        assert min(res[o[t] + k], e) > 100 * thr[0], (t, k, res[o[t] + k], e)
+                    else:
+                        assert abs(res[o[t] + k] - e) <= tol * e, (t, k, res[o[t] + k], e)
+                    res[o[t] + k] = e
+        return res
+
+    def clean_only(want, pts, res):
+        """the plain call's bad tracks are second-form tracks (their oracle is not this scene): the clean tracks alone"""
+        badt = set(int(t) for t in gr.bad_tracks())
+        sel = [t for t in range(len(want)) if t not in badt or not (want[t]["status"] & triangulation_ref.ATTEMPTED)]
+        return [want[t] for t in sel], pts[sel], np.concatenate([res[o[t]:o[t + 1]] for t in sel])
+
+    c_, thr, H = CAMS[cam], nf.THR, 8
+    ids, kps, tracks, kd = gr.ids, gr.kps, gr.tracks, gr.kd()
+    first = gr.some(nf.OLD)
+    # plain and robust triangulation
+    want = triangulation_ref.run(tracks, kd, first, c_, *thr)
+    xt.margins_hold(want)
+    got = tw.run(host, tracks, ids, kps, first, c_, thr)
+    sel_want, sel_pts, sel_res = clean_only(want, *got)
+    assert len(sel_want) >= 48
+    w = xt.worst(sel_want, (sel_pts, sel_res))
+    print("plain:", w)
+    xt.within(w)
+    want = robust_triangulation_ref.run(tracks, kd, first, c_, *thr, max_hypotheses=H)
+    xb.guards_hold(want)
+    rob = nf.robtw.run(host, tracks, ids, kps, first, c_, thr + (H,))
+    w = xb.worst(want, (rob[0], bad_slots_apart(rob[1], want, xb.TOL_RES), rob[2]))
+    print("robust:", w)
+    xb.within(w)
+    assert rob[3] == xb.counts_of(want) and rob[3]["retried"] >= 16
+    # point refinement after the robust call
+    pp, pr, pm = rob[:3]
+    want = refine_points_ref.run(tracks, kd, first, c_, robust_triangulation_ref.run(tracks, kd, first, c_, *thr, max_hypotheses=H), True,
+                                 thr[0], thr[1], *xr.PARAMS)
+    xr.guards_hold(want)
+    ref1 = nf.rtw.run(host, tracks, ids, kps, first, c_, pp, pr, pm, thr[:2], xr.PARAMS, trace=True)
+    w = xr.worst(want, (ref1[0], bad_slots_apart(ref1[1], want, xr.TOL_RES)) + ref1[2:], tracks[0])
+    print("refine:", w)
+    xr.within(w)
+    pp, pr = ref1[:2]
+    # registration of REG
+    image_id = int(ids[nf.REG])
+    reg = nf.regtw.run(host, tracks, pp, [image_id], kd, c_, **nf.REG_PARAMS)
+    tids, cu, cv, X = registration_ref.correspondences(tracks, pp, image_id, kd[image_id], c_)
+    f = (c_[0] + c_[1]) / 2
+    want = registration_ref.register(image_id, cu, cv, X, f, lambda it: nf.regtw.sample3(host, image_id, it, len(cu)), **nf.REG_PARAMS)
+    assert want["margin"] > 16 * xg.TOL_RES
+    rec, offs, tid, flags, res = reg
+    assert np.array_equal(tid, tids) and int(rec[0]["status"]) == want["status"] == 15 and np.array_equal(flags.astype(bool), want["flags"])
+    assert int(rec[0]["n_inliers"]) == want["n_inliers"] and int(rec[0]["hypotheses"]) == want["hypotheses"]
+    badc = nf.registration_bad(gr, reg)
+    wr = dict(R=np.abs(rec[0]["R"].reshape(3, 3) - want["R"]).max(), t=np.abs(rec[0]["t"] - want["t"]).max(),
+              res=np.abs(res - want["residuals"])[~badc].max(), res_bad_rel=(np.abs(res - want["residuals"]) / want["residuals"])[badc].max())
+    print("register:", wr)
+    assert wr["R"] <= xg.TOL_R and wr["t"] <= xg.TOL_T and wr["res"] <= xg.TOL_RES
+    assert any(c_[4:]) or wr["res_bad_rel"] <= xg.TOL_RES                          # (see bad_slots_apart)
+    # extension by NEW and REG's pose
+    new = _lib.registered_poses(rec, gr.some(nf.NEW))
+    ext = etw.run(host, tracks, ids, kps, first, new, c_, pp, pr, pm, thr, H, trace=True)
+    want = extend_ref.run(tracks, kd, first, new, c_, pp, pr, pm, thr[0], thr[1], thr[2], H)
+    c = dict(name="gross", cam=c_, thr=thr, mh=H, tracks=tracks, ids=ids, kps=kps, before=(pp, pr, pm), lst=first, new=new, want=want,
+             got=(ext[0], bad_slots_apart(ext[1], want, xe.TOL["new_residual"])) + ext[2:])
+    worst, touched, left, margins = xe.compare(c)
+    print("extend:", worst, touched, left, margins)
+    assert not left and touched == len(gr.lengths) and all(worst[q] <= xe.TOL[q] for q in xe.TOL), worst
+    # pose refinement
+    pp, pr, pm, _, lst = ext[:5]
+    poses = ptw.poses_dict(*lst)
+    # (REG is held as well: the registration has just left it at its own optimum, where the reference's first decision -- does the
+    # cost drop? -- sits 1e-16 from its threshold, inside that module's guard; left out, it would take every 8-view track's re-verdict
+    # out of the comparison with it)
+    fixed = [int(ids[nf.OLD[0]]), int(ids[nf.REG])]
+    params = (10, 1e-4, 15)
+    want = refine_poses_ref.run(tracks, kd, poses, c_, xp.records_of(pp, pr, tracks[0]), pm, thr[0], thr[1], *params, fixed=set(fixed))
+    got = ptw.run(host, tracks, ids, kps, poses, c_, pp, pr, pm, thr[:2], params, fixed, trace=True)   # (both by ascending id)
+    got = (got[0], bad_slots_apart(got[1], want[2], xp.TOL["res"])) + got[2:]
+    w, compared, left_out, n_tracks = xp.compare(dict(want=want, got=got, tracks=tracks), xp.TOL)
+    print("poses:", w, compared, left_out, n_tracks)
+    assert compared == 6 and not left_out and n_tracks == len(gr.lengths) and all(w[k] <= xp.TOL[k] for k in xp.TOL), w
+
+
+# ---- the other fixtures of tests/test_gpu_nonfinite.py, on the twins first ------------------------------------------------------------------
+@pytest.mark.parametrize("T", [257, 256, 255, 65, 64, 63, 1])
+def test_track_count_prefixes_on_the_twins(host, T):
+    for case in nf.drawn(seed=11, k=4):
+        sc, _, gr = nf.lanes(case)
+        sc, gr = sc.prefix(T), gr.prefix(T)
+        assert len(sc.bad_tracks()) == sum(t < T for t in nf.LANES)
+        for mh in (8, 0):
+            compare(sc, case, nf.chain(host, sc, nf.CAM, mh=mh), nf.chain(host, gr, nf.CAM, mh=mh), mh, True)
+
+
+@pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
+def test_replaced_keypoints_on_the_twins(host, case):
+    """The records and inlier bytes come from clean keypoints (every byte 1), then the keypoints are replaced: the bad observations are
+    IN the fitting sets of the point refinement.  It ends; no record takes a NaN; a track whose fitting set holds a non-finite
+    observation is not refined (its cost is not a number: no step is accepted); the registration and the extension that follow treat
+    the value as on any other session."""
+    clean = nf.lanes(None)[0]
+    sc, _, gr = nf.lanes(case)
+    first = sc.some(nf.OLD)
+    pp, pr, pm, _ = nf.robtw.run(host, clean.tracks, clean.ids, clean.kps, first, nf.CAM, nf.THR + (8,))
+    assert pm.sum() == len(nf.OLD) * len(sc.lengths)                       # every observation of a posed image supports its point
+    outs = []
+    for s in (sc, gr):
+        fp, fr, fc, tr = nf.rtw.run(host, s.tracks, s.ids, s.kps, first, nf.CAM, pp, pr, pm, nf.THR[:2], trace=True)
+        reg = nf.regtw.run(host, s.tracks, fp, [int(s.ids[nf.REG])], s.kd(), nf.CAM, **nf.REG_PARAMS)
+        new = _lib.registered_poses(reg[0], s.some(nf.NEW))
+        ext = etw.run(host, s.tracks, s.ids, s.kps, first, new, nf.CAM, fp, fr, pm, nf.THR, 8, trace=True)
+        outs.append((fp, fr, fc, tr, reg, ext))
+    (fp, fr, fc, tr, reg, ext), g = outs
+    badt = sc.bad_tracks()
+    clean_t = np.setdiff1d(np.arange(len(sc.lengths)), badt)
+    per_slot = np.repeat(np.isin(np.arange(len(sc.lengths)), badt), np.diff(sc.tracks[0]))
+    float_fields_finite(fp[clean_t])
+    assert not any(np.isnan(fp[n]).any() for n in ("X", "mean_residual", "tri_angle"))
+    assert fp[clean_t].tobytes() == g[0][clean_t].tobytes() and fr[~per_slot].tobytes() == g[1][~per_slot].tobytes()
+    assert nan_bits(fr) <= {CANONICAL} and not np.isnan(fr[~sc.bad]).any()
+    if nf.non_finite(case):
+        assert not _lib.refined(fp)[badt].any() and fp[badt].tobytes() == pp[badt].tobytes()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(reg[:4], g[4][:4])) and _lib.registered(reg[0]).all()
+    assert nan_bits(reg[4]) <= {CANONICAL} and nan_bits(ext[1]) <= {CANONICAL}
+    assert ext[0][clean_t].tobytes() == g[5][0][clean_t].tobytes() and ext[2].tobytes() == g[5][2].tobytes() and ext[3] == g[5][3]
+    print(case[0], fc, tr[badt]["verdict"], tr[badt]["accepted"])
