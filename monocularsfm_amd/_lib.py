@@ -19,23 +19,6 @@ ORDER_SSE4X4, ORDER_AVX2_FMA, ORDER_AVX512_FMA = 0, 1, 3
 MAX_IMAGES = 10000
 DIM = 128
 
-EXPORTS = [
-    "msfm_create", "msfm_destroy", "msfm_last_error", "msfm_device_info", "msfm_set_accum_order", "msfm_set_prefilter",
-    "msfm_get_profile", "msfm_upload_image", "msfm_image_rows", "msfm_clear_images",
-    "msfm_match_pair", "msfm_match_pairs", "msfm_fetch_matches", "msfm_knn2_pair",
-    "msfm_topscale_select", "msfm_pair_id", "msfm_pair_from_id", "msfm_swap_image_pair",
-    "msfm_version", "msfm_upload_keypoints", "msfm_match_pairs_verified", "msfm_subset_image", "msfm_view_matches", "msfm_set_limits", "msfm_fetch_matches_device",
-    "msfm_fetch_order_certificate", "msfm_set_pipeline", "msfm_device_count", "msfm_finalize_store", "msfm_store_info",
-    "msfm_match_pairs_begin", "msfm_match_pairs_next", "msfm_read_device", "msfm_memory_info", "msfm_match_pairs_end",
-    "msfm_train_vocabulary", "msfm_set_vocabulary", "msfm_image_words", "msfm_retrieve_pairs", "msfm_get_retrieval_profile",
-    "msfm_set_verification_model", "msfm_get_verification_stats", "msfm_set_model_selection", "msfm_fetch_model_selection",
-    "msfm_set_two_view_geometry", "msfm_fetch_two_view_geometry",
-    "msfm_tracks_begin", "msfm_tracks_add", "msfm_tracks_export_forest", "msfm_tracks_import_forest", "msfm_tracks_finish",
-    "msfm_fetch_tracks", "msfm_fetch_track_ids", "msfm_tracks_end",
-    "msfm_triangulate_tracks", "msfm_fetch_points3d", "msfm_register_images", "msfm_fetch_registrations",
-    "msfm_triangulate_tracks_robust", "msfm_fetch_point_inliers", "msfm_refine_points",
-    "msfm_refine_poses", "msfm_fetch_poses", "msfm_fetch_pose_refinements", "msfm_extend_points",
-]
 VERIFY_FUNDAMENTAL, VERIFY_ESSENTIAL, VERIFY_HOMOGRAPHY = 0, 1, 2
 
 
@@ -275,11 +258,90 @@ class MsfmError(RuntimeError):
         self.code = code
 
 
+def _signatures():
+    """The C surface of include/msfm_match.h: name -> (restype, argtypes).  load() applies it; EXPORTS is its list of names."""
+    P, i, i64, vp = C.POINTER, C.c_int, C.c_int64, C.c_void_p
+    ip, fp, i64p, u8p, intp = P(C.c_int32), P(C.c_float), P(i64), P(C.c_uint8), P(i)
+    mp, cam = P(MatchParams), P(Camera)
+    return {
+        "msfm_version": (C.c_char_p, []),
+        "msfm_device_count": (i, []),
+        "msfm_create": (i, [i, P(vp)]),
+        "msfm_destroy": (None, [vp]),
+        "msfm_last_error": (C.c_char_p, [vp]),
+        "msfm_device_info": (i, [vp, C.c_char_p, i, intp, intp]),
+        "msfm_set_accum_order": (i, [vp, i]),
+        "msfm_set_prefilter": (i, [vp, i]),
+        "msfm_get_profile": (i, [vp, P(Profile)]),
+        "msfm_set_limits": (i, [vp, i, i64]),
+        "msfm_set_pipeline": (i, [vp, i]),
+        "msfm_upload_image": (i, [vp, i, vp, i, i, i]),
+        "msfm_image_rows": (i, [vp, i, intp]),
+        "msfm_subset_image": (i, [vp, i, i, ip, i]),
+        "msfm_clear_images": (i, [vp]),
+        "msfm_finalize_store": (i, [vp]),
+        "msfm_store_info": (i, [vp, i64p, i64p, i64p]),
+        "msfm_upload_keypoints": (i, [vp, i, fp, i, i]),
+        "msfm_match_pair": (i, [vp, i, i, C.c_float, i, C.c_double, ip, fp, intp]),
+        "msfm_match_pairs": (i, [vp, ip, i, mp, i64p]),
+        "msfm_match_pairs_verified": (i, [vp, ip, i, mp, P(VerifyParams), i64p]),
+        "msfm_match_pairs_begin": (i, [vp, ip, i, mp, i, P(VerifyParams)]),
+        "msfm_match_pairs_next": (i, [vp, P(Chunk)]),
+        "msfm_match_pairs_end": (i, [vp]),
+        "msfm_fetch_matches": (i, [vp, ip, fp]),
+        "msfm_view_matches": (i, [vp, P(ip), P(fp), i64p]),
+        "msfm_fetch_matches_device": (i, [vp, vp, vp]),
+        "msfm_fetch_order_certificate": (i, [vp, ip]),
+        "msfm_read_device": (i, [vp, vp, vp, i64]),
+        "msfm_memory_info": (i, [vp, P(Memory)]),
+        "msfm_knn2_pair": (i, [vp, i, i, ip, fp, fp, ip, fp, fp]),
+        "msfm_topscale_select": (i, [fp, i, i, ip, intp]),
+        "msfm_pair_id": (i, [i, i, ip]),
+        "msfm_pair_from_id": (i, [C.c_int32, intp, intp]),
+        "msfm_swap_image_pair": (i, [i, i]),
+        # vocabulary retrieval (matching mode 2)
+        "msfm_train_vocabulary": (i, [vp, ip, i, P(RetrievalParams), u8p, intp]),
+        "msfm_set_vocabulary": (i, [vp, u8p, i]),
+        "msfm_image_words": (i, [vp, i, ip]),
+        "msfm_retrieve_pairs": (i, [vp, ip, i, i, ip, fp, intp, fp]),
+        "msfm_get_retrieval_profile": (i, [vp, P(RetrievalProfile)]),
+        # geometric verification
+        "msfm_set_verification_model": (i, [vp, i, cam]),
+        "msfm_get_verification_stats": (i, [vp, i64p, intp]),
+        "msfm_set_model_selection": (i, [vp, i, C.c_double]),
+        "msfm_fetch_model_selection": (i, [vp, ip, ip, ip]),
+        "msfm_set_two_view_geometry": (i, [vp, i, P(TwoViewParams)]),
+        "msfm_fetch_two_view_geometry": (i, [vp, vp]),
+        # feature tracks and the reconstruction stage
+        "msfm_tracks_begin": (i, [vp, ip, i, P(TrackParams)]),
+        "msfm_tracks_add": (i, [vp, ip, i, i64p, ip]),
+        "msfm_tracks_export_forest": (i, [vp, ip]),
+        "msfm_tracks_import_forest": (i, [vp, ip]),
+        "msfm_tracks_finish": (i, [vp, P(TrackFilter), P(TrackStats)]),
+        "msfm_fetch_tracks": (i, [vp, i64p, ip, ip, u8p]),
+        "msfm_fetch_track_ids": (i, [vp, i, ip]),
+        "msfm_tracks_end": (i, [vp]),
+        "msfm_triangulate_tracks": (i, [vp, cam, ip, vp, i, P(TriangulationParams), P(TriangulationStats)]),
+        "msfm_fetch_points3d": (i, [vp, vp, P(C.c_double)]),
+        "msfm_triangulate_tracks_robust": (i, [vp, cam, ip, vp, i, P(RobustTriangulationParams), P(TriangulationStats), P(RobustStats)]),
+        "msfm_fetch_point_inliers": (i, [vp, vp]),
+        "msfm_refine_points": (i, [vp, P(RefineParams), P(RefineStats)]),
+        "msfm_refine_poses": (i, [vp, P(PoseRefineParams), ip, i, P(PoseRefineStats)]),
+        "msfm_fetch_poses": (i, [vp, ip, vp, intp]),
+        "msfm_fetch_pose_refinements": (i, [vp, vp]),
+        "msfm_extend_points": (i, [vp, ip, vp, i, P(ExtendParams), P(ExtendStats)]),
+        "msfm_register_images": (i, [vp, cam, ip, i, P(RegisterParams), P(RegisterStats)]),
+        "msfm_fetch_registrations": (i, [vp, vp, vp, vp, vp, vp]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
 _lib = None
 
 
 def load():
-    """Load libmsfm_match.so; raises (loudly) if the HIP extension has not been built."""
+    """Load libmsfm_match.so; raises (loudly) if the HIP extension has not been built or lacks a declared symbol."""
     global _lib
     if _lib is not None:
         return _lib
@@ -288,93 +350,16 @@ def load():
             "%s is missing: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (or `make -C monocularsfm_amd/csrc`). There is no CPU fallback." % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, ip, fp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)
-    L.msfm_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.msfm_destroy.argtypes = [vp]
-    L.msfm_destroy.restype = None
-    L.msfm_last_error.argtypes = [vp]
-    L.msfm_last_error.restype = C.c_char_p
-    L.msfm_device_info.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.msfm_set_accum_order.argtypes = [vp, C.c_int]
-    L.msfm_set_prefilter.argtypes = [vp, C.c_int]
-    L.msfm_get_profile.argtypes = [vp, C.POINTER(Profile)]
-    L.msfm_set_limits.argtypes = [vp, C.c_int, C.c_int64]
-    L.msfm_set_pipeline.argtypes = [vp, C.c_int]
-    L.msfm_upload_image.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
-    L.msfm_image_rows.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-    L.msfm_subset_image.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int]
-    L.msfm_clear_images.argtypes = [vp]
-    try:   # (the A/B tools also load older builds of the library: tools/ab.py)
-        L.msfm_finalize_store.argtypes = [vp]
-        L.msfm_store_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.msfm_match_pairs_begin.argtypes = [vp, ip, C.c_int, C.POINTER(MatchParams), C.c_int, C.POINTER(VerifyParams)]
-        L.msfm_match_pairs_next.argtypes = [vp, C.POINTER(Chunk)]
-        L.msfm_read_device.argtypes = [vp, vp, vp, C.c_int64]
-        L.msfm_memory_info.argtypes = [vp, C.POINTER(Memory)]
-        L.msfm_match_pairs_end.argtypes = [vp]
-    except AttributeError:
-        pass
-    L.msfm_match_pair.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double, ip, fp, C.POINTER(C.c_int)]
-    L.msfm_match_pairs.argtypes = [vp, ip, C.c_int, C.POINTER(MatchParams), C.POINTER(C.c_int64)]
-    L.msfm_fetch_matches.argtypes = [vp, ip, fp]
-    L.msfm_view_matches.argtypes = [vp, C.POINTER(ip), C.POINTER(fp), C.POINTER(C.c_int64)]
-    L.msfm_fetch_matches_device.argtypes = [vp, vp, vp]
-    L.msfm_fetch_order_certificate.argtypes = [vp, ip]
-    L.msfm_upload_keypoints.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int]
-    L.msfm_match_pairs_verified.argtypes = [vp, ip, C.c_int, C.POINTER(MatchParams), C.POINTER(VerifyParams),
-                                            C.POINTER(C.c_int64)]
-    L.msfm_knn2_pair.argtypes = [vp, C.c_int, C.c_int, ip, fp, fp, ip, fp, fp]
-    L.msfm_topscale_select.argtypes = [fp, C.c_int, C.c_int, ip, C.POINTER(C.c_int)]
-    L.msfm_pair_id.argtypes = [C.c_int, C.c_int, ip]
-    L.msfm_pair_from_id.argtypes = [C.c_int32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.msfm_swap_image_pair.argtypes = [C.c_int, C.c_int]
-    L.msfm_version.restype = C.c_char_p
-    try:   # (the A/B tools also load older builds of the library: tools/ab.py)
-        L.msfm_device_count.argtypes = []
-        L.msfm_device_count.restype = C.c_int
-    except AttributeError:
-        pass
-    try:   # vocabulary retrieval (matching mode 2); older builds loaded by the A/B tools lack it
-        u8p = C.POINTER(C.c_uint8)
-        L.msfm_train_vocabulary.argtypes = [vp, ip, C.c_int, C.POINTER(RetrievalParams), u8p, C.POINTER(C.c_int)]
-        L.msfm_set_vocabulary.argtypes = [vp, u8p, C.c_int]
-        L.msfm_image_words.argtypes = [vp, C.c_int, ip]
-        L.msfm_retrieve_pairs.argtypes = [vp, ip, C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int), fp]
-        L.msfm_get_retrieval_profile.argtypes = [vp, C.POINTER(RetrievalProfile)]
-    except AttributeError:
-        pass
-    L.msfm_set_verification_model.argtypes = [vp, C.c_int, C.POINTER(Camera)]
-    L.msfm_get_verification_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
-    L.msfm_set_model_selection.argtypes = [vp, C.c_int, C.c_double]
-    L.msfm_fetch_model_selection.argtypes = [vp, ip, ip, ip]
-    L.msfm_set_two_view_geometry.argtypes = [vp, C.c_int, C.POINTER(TwoViewParams)]
-    L.msfm_fetch_two_view_geometry.argtypes = [vp, C.c_void_p]
-    i64p = C.POINTER(C.c_int64)
-    L.msfm_tracks_begin.argtypes = [vp, ip, C.c_int, C.POINTER(TrackParams)]
-    L.msfm_tracks_add.argtypes = [vp, ip, C.c_int, i64p, ip]
-    L.msfm_tracks_export_forest.argtypes = [vp, ip]
-    L.msfm_tracks_import_forest.argtypes = [vp, ip]
-    L.msfm_tracks_finish.argtypes = [vp, C.POINTER(TrackFilter), C.POINTER(TrackStats)]
-    L.msfm_fetch_tracks.argtypes = [vp, i64p, ip, ip, C.POINTER(C.c_uint8)]
-    L.msfm_fetch_track_ids.argtypes = [vp, C.c_int, ip]
-    L.msfm_tracks_end.argtypes = [vp]
-    L.msfm_triangulate_tracks.argtypes = [vp, C.POINTER(Camera), ip, C.c_void_p, C.c_int, C.POINTER(TriangulationParams),
-                                          C.POINTER(TriangulationStats)]
-    L.msfm_fetch_points3d.argtypes = [vp, C.c_void_p, C.POINTER(C.c_double)]
-    L.msfm_triangulate_tracks_robust.argtypes = [vp, C.POINTER(Camera), ip, C.c_void_p, C.c_int, C.POINTER(RobustTriangulationParams),
-                                                 C.POINTER(TriangulationStats), C.POINTER(RobustStats)]
-    L.msfm_fetch_point_inliers.argtypes = [vp, C.c_void_p]
-    L.msfm_refine_points.argtypes = [vp, C.POINTER(RefineParams), C.POINTER(RefineStats)]
-    L.msfm_refine_poses.argtypes = [vp, C.POINTER(PoseRefineParams), ip, C.c_int, C.POINTER(PoseRefineStats)]
-    L.msfm_fetch_poses.argtypes = [vp, ip, C.c_void_p, C.POINTER(C.c_int)]
-    L.msfm_fetch_pose_refinements.argtypes = [vp, C.c_void_p]
-    L.msfm_extend_points.argtypes = [vp, ip, C.c_void_p, C.c_int, C.POINTER(ExtendParams), C.POINTER(ExtendStats)]
-    L.msfm_register_images.argtypes = [vp, C.POINTER(Camera), ip, C.c_int, C.POINTER(RegisterParams), C.POINTER(RegisterStats)]
-    L.msfm_fetch_registrations.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name in EXPORTS:
-        getattr(L, name)  # raises AttributeError if the library lacks a declared symbol
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)   # raises AttributeError if the library lacks a declared symbol
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
+
+
+def _dict(st):
+    """A ctypes stats struct as a dict of its fields."""
+    return {k: getattr(st, k) for k, _ in st._fields_}
 
 
 def _ip(a):
@@ -458,7 +443,7 @@ class Context:
     def profile(self):
         p = Profile()
         self._chk(self._L.msfm_get_profile(self._h, C.byref(p)))
-        return {k: getattr(p, k) for k, _ in Profile._fields_}
+        return _dict(p)
 
     def upload_image(self, image_id, desc):
         desc = np.asarray(desc)
@@ -490,8 +475,7 @@ class Context:
 
     def finalize_store(self):
         """Build everything uploaded so far now (otherwise the first matching call does it)."""
-        if hasattr(self._L, "msfm_finalize_store"):
-            self._chk(self._L.msfm_finalize_store(self._h))
+        self._chk(self._L.msfm_finalize_store(self._h))
 
     def store_info(self):
         """-> {device_bytes, rows, pending_images} of the descriptor store."""
@@ -538,7 +522,7 @@ class Context:
     def retrieval_profile(self):
         p = RetrievalProfile()
         self._chk(self._L.msfm_get_retrieval_profile(self._h, C.byref(p)))
-        return {k: getattr(p, k) for k, _ in RetrievalProfile._fields_}
+        return _dict(p)
 
     def match_pair(self, id1, id2, ratio=0.8, cross_check=True, max_distance=0.7):
         n1 = max(self.image_rows(id1), 1)
@@ -560,15 +544,16 @@ class Context:
             return np.zeros((0, 2), np.int32), np.zeros(0, np.float32)
         return np.ctypeslib.as_array(qp, shape=(M, 2)), np.ctypeslib.as_array(dp, shape=(M,))
 
-    def match_pairs(self, pairs, ratio=0.8, cross_check=True, max_distance=0.7, fetch=True):
-        """pairs: P x 2 int array -> (offsets[P+1], qt[M,2], dist[M]); fetch=False skips the copy-out,
-        fetch="view" returns views of the context's buffers (valid until the next matching call)."""
+    def _match(self, pairs, prm, vprm, fetch):
+        """The blocking call: msfm_match_pairs, or msfm_match_pairs_verified under the VerifyParams vprm."""
         pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
         P = pairs.shape[0]
         offs = np.zeros(P + 1, np.int64)
-        prm = MatchParams(ratio, int(bool(cross_check)), max_distance)
-        self._chk(self._L.msfm_match_pairs(self._h, _ip(pairs), P, C.byref(prm),
-                                           offs.ctypes.data_as(C.POINTER(C.c_int64))))
+        o = offs.ctypes.data_as(C.POINTER(C.c_int64))
+        if vprm is None:
+            self._chk(self._L.msfm_match_pairs(self._h, _ip(pairs), P, C.byref(prm), o))
+        else:
+            self._chk(self._L.msfm_match_pairs_verified(self._h, _ip(pairs), P, C.byref(prm), C.byref(vprm), o))
         if not fetch:
             return offs, None, None
         if fetch == "view":
@@ -579,11 +564,17 @@ class Context:
         self._chk(self._L.msfm_fetch_matches(self._h, _ip(qt), _fp(d)))
         return offs, qt[:M], d[:M]
 
+    def match_pairs(self, pairs, ratio=0.8, cross_check=True, max_distance=0.7, fetch=True):
+        """pairs: P x 2 int array -> (offsets[P+1], qt[M,2], dist[M]); fetch=False skips the copy-out,
+        fetch="view" returns views of the context's buffers (valid until the next matching call)."""
+        return self._match(pairs, MatchParams(ratio, int(bool(cross_check)), max_distance), None, fetch)
+
     def match_pairs_stream(self, pairs, ratio=0.8, cross_check=True, max_distance=0.7, verified=False, copy=True, verify=None):
         """Generator over the device sub-batches of the job, in pair order (msfm_match_pairs_begin / _next): nothing accumulates in the
         library.  Yields dicts {first, n_pairs, offsets[n+1] (relative to the chunk), qt[m, 2], dist[m], sensitive[n], d_qt, d_dist
         (device pointers)}; with copy=False qt / dist / offsets are views, valid until the next item is requested.  verify: None (the
-        reference's constants) or a dict of match_pairs_verified's threshold, confidence, max_iters, seed."""
+        reference's constants) or a dict of match_pairs_verified's threshold, confidence, max_iters, seed.  A context has one series
+        at a time: beginning another one (or any other matching call) ends this one, whose next item is then an E_STATE error."""
         pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
         prm = MatchParams(ratio, int(bool(cross_check)), max_distance)
         vprm = None
@@ -592,10 +583,15 @@ class Context:
             vprm = VerifyParams(v["threshold"], v["confidence"], int(v["max_iters"]), int(v["seed"]))
         self._chk(self._L.msfm_match_pairs_begin(self._h, _ip(pairs), pairs.shape[0], C.byref(prm), int(bool(verified)),
                                                  C.byref(vprm) if vprm is not None else None))
+        # the library keeps ONE series per context and cannot tell whose it is: the context counts them, and a generator whose series
+        # a newer one has superseded neither reads the newer one's chunks nor ends it
+        self._series = mine = getattr(self, "_series", 0) + 1
         ch = Chunk()
         done = False
         try:
             while True:
+                if self._series != mine:
+                    raise MsfmError(E_STATE, "this series was superseded by a newer one on the same context")
                 self._chk(self._L.msfm_match_pairs_next(self._h, C.byref(ch)))
                 n = ch.n_pairs
                 if n == 0:
@@ -618,14 +614,14 @@ class Context:
         finally:
             # a consumer that breaks out of the loop (GeneratorExit) or whose body raises must not leave the series open: the store
             # would stay locked for uploads until the next matching call
-            if not done and getattr(self, "_h", None):
+            if not done and getattr(self, "_h", None) and self._series == mine:
                 self._L.msfm_match_pairs_end(self._h)
 
     def memory_info(self):
         """Bytes the context holds (store, inbox, scratch, result lists, page-locked host) + the device's free / total memory."""
         m = Memory()
         self._chk(self._L.msfm_memory_info(self._h, C.byref(m)))
-        return {k: getattr(m, k) for k, _ in Memory._fields_}
+        return _dict(m)
 
     def read_device(self, dev_ptr, shape, dtype):
         """A device buffer (raw pointer) as a new NumPy array, copied through the library's own runtime."""
@@ -655,22 +651,8 @@ class Context:
     def match_pairs_verified(self, pairs, ratio=0.8, cross_check=True, max_distance=0.7, threshold=3.0,
                              confidence=0.99, max_iters=1000, seed=0x5eed5eed, fetch=True):
         """match_pairs + FeatureUtils::FilterMatches (F-matrix RANSAC) on the device."""
-        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
-        P = pairs.shape[0]
-        offs = np.zeros(P + 1, np.int64)
-        prm = MatchParams(ratio, int(bool(cross_check)), max_distance)
-        vprm = VerifyParams(threshold, confidence, int(max_iters), int(seed))
-        self._chk(self._L.msfm_match_pairs_verified(self._h, _ip(pairs), P, C.byref(prm), C.byref(vprm),
-                                                    offs.ctypes.data_as(C.POINTER(C.c_int64))))
-        if not fetch:
-            return offs, None, None
-        if fetch == "view":
-            return (offs,) + self._view()
-        M = int(offs[-1])
-        qt = np.empty((max(M, 1), 2), np.int32)
-        d = np.empty(max(M, 1), np.float32)
-        self._chk(self._L.msfm_fetch_matches(self._h, _ip(qt), _fp(d)))
-        return offs, qt[:M], d[:M]
+        return self._match(pairs, MatchParams(ratio, int(bool(cross_check)), max_distance),
+                           VerifyParams(threshold, confidence, int(max_iters), int(seed)), fetch)
 
     def set_verification_model(self, model, camera=None):
         """Model of the geometric verification of match_pairs_verified and the verified streaming form: VERIFY_FUNDAMENTAL (0,
@@ -678,11 +660,7 @@ class Context:
         or sequence fx, fy, cx, cy[, k1, k2, p1, p2] -- missing distortion coefficients are 0) or VERIFY_HOMOGRAPHY (2: 4-point
         homography RANSAC on pixel coordinates, for planar scenes and rotation-only views; it takes no camera, and a given one is
         passed on and refused with E_INVALID)."""
-        cam = None
-        if camera is not None:
-            keys = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")
-            vals = [camera.get(k, 0.0) for k in keys] if isinstance(camera, dict) else list(camera) + [0.0] * (8 - len(camera))
-            cam = Camera(*[float(v) for v in vals[:8]])
+        cam = camera_struct(camera) if camera is not None else None
         self._chk(self._L.msfm_set_verification_model(self._h, int(model), C.byref(cam) if cam is not None else None))
 
     def verification_stats(self):
@@ -754,14 +732,18 @@ class Context:
         f = TrackFilter(int(min_length), int(max_length), int(bool(keep_inconsistent)), 0)
         st = TrackStats()
         self._chk(self._L.msfm_tracks_finish(self._h, C.byref(f), C.byref(st)))
-        self._track_stats = {k: getattr(st, k) for k, _ in TrackStats._fields_}
+        self._track_stats = _dict(st)
         return dict(self._track_stats)
+
+    def _kept(self):
+        """(kept tracks, kept observations) of the last tracks_finish; (0, 0) without one."""
+        st = getattr(self, "_track_stats", None) or {}
+        return int(st.get("tracks_kept", 0)), int(st.get("observations_kept", 0))
 
     def tracks(self):
         """-> (offsets[T + 1] int64, image_ids[O] int32, point_idx[O] int32, consistent[T] uint8) of the last tracks_finish: kept tracks
         by ascending smallest (image id, keypoint index), the elements of each in that order."""
-        st = getattr(self, "_track_stats", None) or {"tracks_kept": 0, "observations_kept": 0}
-        T, O = int(st["tracks_kept"]), int(st["observations_kept"])
+        T, O = self._kept()
         offs = np.zeros(T + 1, np.int64)
         img, idx = np.zeros(max(O, 1), np.int32), np.zeros(max(O, 1), np.int32)
         cons = np.zeros(max(T, 1), np.uint8)
@@ -816,19 +798,18 @@ class Context:
             rs = RobustStats()
             self._chk(self._L.msfm_triangulate_tracks_robust(self._h, C.byref(cam) if cam is not None else None, _ip(ids), tab.ctypes.data,
                                                              len(ids), C.byref(rprm), C.byref(st), C.byref(rs)))
-            out = {k: getattr(st, k) for k, _ in TriangulationStats._fields_}
-            out.update({k: getattr(rs, k) for k, _ in RobustStats._fields_})
+            out = _dict(st)
+            out.update(_dict(rs))
             return out
         prm = TriangulationParams(float(max_error), float(min_angle), int(min_views), 0)
         self._chk(self._L.msfm_triangulate_tracks(self._h, C.byref(cam) if cam is not None else None, _ip(ids), tab.ctypes.data, len(ids),
                                                   C.byref(prm), C.byref(st)))
-        return {k: getattr(st, k) for k, _ in TriangulationStats._fields_}
+        return _dict(st)
 
     def point_inliers(self):
         """-> uint8, one per kept observation in the tracks' order (aligned with points3d()'s residuals): 1 where the observation
         supports its track's point.  Only after triangulate_tracks(..., robust=True)."""
-        st = getattr(self, "_track_stats", None) or {"tracks_kept": 0, "observations_kept": 0}
-        O = int(st["observations_kept"])
+        O = self._kept()[1]
         out = np.zeros(max(O, 1), np.uint8)
         self._chk(self._L.msfm_fetch_point_inliers(self._h, out.ctypes.data))
         return out[:O]
@@ -841,7 +822,7 @@ class Context:
         prm = RefineParams(float(step_tol), int(max_iters), 0)
         st = RefineStats()
         self._chk(self._L.msfm_refine_points(self._h, C.byref(prm), C.byref(st)))
-        return {k: getattr(st, k) for k, _ in RefineStats._fields_}
+        return _dict(st)
 
     def refine_poses(self, max_iters=10, step_tol=1e-6, min_observations=15, fixed=()):
         """Moves every posed image of the last triangulate_tracks to the minimum of its reprojection error under the current points
@@ -853,7 +834,7 @@ class Context:
         st = PoseRefineStats()
         fx = np.ascontiguousarray(list(fixed), dtype=np.int32).reshape(-1)
         self._chk(self._L.msfm_refine_poses(self._h, C.byref(prm), _ip(fx) if len(fx) else None, len(fx), C.byref(st)))
-        return {k: getattr(st, k) for k, _ in PoseRefineStats._fields_}
+        return _dict(st)
 
     def pose_list(self):
         """-> (ids int32, POSE_RT array) of the session's current pose list, in the order of the triangulation call."""
@@ -904,7 +885,7 @@ class Context:
         st = ExtendStats()
         self._chk(self._L.msfm_extend_points(self._h, _ip(ids) if len(ids) else None, tab.ctypes.data if len(ids) else None, len(ids),
                                              C.byref(prm), C.byref(st)))
-        return {k: getattr(st, k) for k, _ in ExtendStats._fields_}
+        return _dict(st)
 
     def grow(self, camera, image_ids=None, register_params=None, rounds=1, fixed=(), point_params=None, pose_params=None):
         """One increment of the reconstruction: register_images(camera, image_ids, **register_params) -- image_ids None: every declared
@@ -928,8 +909,7 @@ class Context:
     def points3d(self):
         """-> (points: POINT3D array, one per kept track; residuals: float64, one per kept observation in the tracks' order, -1.0 where
         no error was computed) of the last triangulate_tracks.  succeeded(points) is the reference's verdict."""
-        st = getattr(self, "_track_stats", None) or {"tracks_kept": 0, "observations_kept": 0}
-        T, O = int(st["tracks_kept"]), int(st["observations_kept"])
+        T, O = self._kept()
         pts = np.zeros(max(T, 1), POINT3D)
         res = np.zeros(max(O, 1), np.float64)
         self._chk(self._L.msfm_fetch_points3d(self._h, pts.ctypes.data, res.ctypes.data_as(C.POINTER(C.c_double))))
@@ -948,7 +928,7 @@ class Context:
         self._chk(self._L.msfm_register_images(self._h, C.byref(cam) if cam is not None else None, _ip(ids), len(ids), C.byref(prm),
                                                C.byref(st)))
         self._reg_shape = (len(ids), int(st.correspondences))
-        return {k: getattr(st, k) for k, _ in RegisterStats._fields_}
+        return _dict(st)
 
     def registrations(self):
         """-> (records: REGISTRATION array in the order of the list, offsets[n + 1] int64, track_ids int32, inlier uint8, residuals

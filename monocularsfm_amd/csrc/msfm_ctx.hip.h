@@ -801,11 +801,24 @@ inline void note_hip_error(msfm_ctx* ctx, hipError_t e) {
 }
 inline void note_hip_error(const msfm_ctx*, hipError_t) {}
 
+// A streaming series ends HERE and nowhere else (it begins at the successful end of a streaming MatchJob::start): the store is unlocked,
+// msfm_match_pairs_next is MSFM_E_STATE.  Whoever calls it has drained the streams or does so next (the lifecycle table).
+inline void close_series(msfm_ctx* ctx) { ctx->series_open = false; }
+
+// A scratch set forgets the sweeps of the sub-batch it worked on (a new call, a dropped attempt, a sub-batch that is re-run alone):
+// no plan summary is pending, nobody waits for its events.
+inline void forget_sweeps(msfm_ctx* ctx, Scratch& s) {
+    s.pf_pending = PfPending{};
+    s.sweep1_recorded = false;
+    s.sweep2_recorded = false;
+    if (ctx->last_sweep1 == &s) ctx->last_sweep1 = nullptr;
+}
+
 // The exception barrier of the C ABI (msfm_guard.h): every `extern "C"` entry point runs its body between these two.  An exception leaves
 // the context usable: after_api_exception (msfm_match.hip) records the text, drains the streams and closes an open series.
-void after_api_exception(msfm_ctx* ctx, const char* text) noexcept;
+void after_api_exception(msfm_ctx* ctx, int rc, const char* text) noexcept;
 #define MSFM_API_BEGIN(ctxp) \
-    return msfm_guard([&](int, const char* t__) noexcept { after_api_exception(ctxp, t__); }, [&]() -> int {
+    return msfm_guard([&](int rc__, const char* t__) noexcept { after_api_exception(ctxp, rc__, t__); }, [&]() -> int {
 #define MSFM_API_END \
     });
 

@@ -18,6 +18,32 @@
 // Results do not depend on the cut (tests force it every which way).
 #pragma once
 
+// What every matching call (blocking, streaming, msfm_knn2_pair) does before its first launch: its device, scratch set 0, no sweep
+// bookkeeping left over from a call that failed, the frees the call before deferred, the store built.  Nothing is in flight.
+static int call_prologue(msfm_ctx* ctx) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->cur = &ctx->sc[0];
+    for (Scratch& s : ctx->sc) forget_sweeps(ctx, s);
+    if (!ctx->deferred.empty()) {   // (what the call before replaced: nobody waits for a result now)
+        HIPCHK(ctx, hipDeviceSynchronize());
+        ctx->deferred.flush();
+    }
+    // uploads since the last use are built now (msfm_store_host.hip.h)
+    return settle_store(ctx);
+}
+
+// One sub-batch alone until no buffer overflowed (a tie queue, a plan buffer, a candidate list: grown or routed around by then): at most
+// six attempts behind the one that overflowed.  attempt(&retry) builds, issues and completes it once.
+template <class Attempt>
+static int rerun_alone(msfm_ctx* ctx, Attempt attempt) {
+    for (int k = 1;; ++k) {
+        bool retry = false;
+        const int rc = attempt(&retry);
+        if (rc != MSFM_OK || !retry) return rc;
+        if (k >= 6) return fail(ctx, MSFM_E_DEVICE, "batch kept overflowing its queues");
+    }
+}
+
 struct MatchJob {
     msfm_ctx* ctx = nullptr;
     std::vector<int32_t> pairs_own;   // streaming form: the caller's pair list is copied (it need not outlive _begin)
@@ -41,7 +67,6 @@ struct MatchJob {
     SubBatch sb[kInFlight];
     int next_begin = 0;
     long long issued = 0, completed = 0;   // sub-batch k lives in slot k % kSets
-    bool open = false;
     bool memory_wait = false;   // a sub-batch did not fit the device's memory: nothing new is issued until what is in flight has been completed
     int memory_shrinks = 0;
 
@@ -52,11 +77,12 @@ struct MatchJob {
         n_pairs = n;
         streaming = stream_mode;
         verify = nullptr;
+        // what the call before handed out is gone from here on; what this one hands out is set where it completes (match_pairs_impl,
+        // next_impl)
+        c->have_results = c->sel_valid = c->tv_valid = false;
         select = vp && c->model_select && c->verify_model != MSFM_VERIFY_HOMOGRAPHY;
-        c->sel_valid = false;
         c->sel_records.assign(select && !stream_mode ? 3 * (size_t)n : 0, 0);
         pose = vp && c->two_view && c->verify_model == MSFM_VERIFY_ESSENTIAL;
-        c->tv_valid = false;
         c->tv_records.assign(pose && !stream_mode ? (size_t)n : 0, msfm_two_view_record{});
         if (vp) {
             verify_store = *vp;
@@ -70,102 +96,84 @@ struct MatchJob {
         memory_wait = false;
         memory_shrinks = 0;
         ctx->last_hip_error = 0;
-    prm = msfm_match_params{0.8f, 1, 0.7};
-    if (params) prm = *params;
-    // rows / columns that provably fail the ratio test or the distance cut need no exact neighbours
-    prune = PruneParams{1, prm.ratio, (float)prm.max_distance};
-    if ((double)prune.max_distance < prm.max_distance) prune.max_distance = nextafterf(prune.max_distance, __builtin_huge_valf());
-    if (!(prm.ratio > 0.f) || !(prm.ratio <= 1.f)) prune.ratio = 0.f;  // outside (0, 1]: no ratio-based pruning
-    if (!(prm.max_distance >= 0.0)) prune.max_distance = __builtin_huge_valf();  // NaN / negative: no distance-based pruning
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    ctx->cur = &ctx->sc[0];
-    ctx->have_results = false;
-    for (Scratch& s : ctx->sc) {
-        s.pf_pending = PfPending{};
-        s.sweep1_recorded = false;
-        s.sweep2_recorded = false;
-    }
-    ctx->last_sweep1 = nullptr;
-    if (!ctx->deferred.empty()) {   // (what the call before replaced: nothing is in flight now, and nobody waits for a result)
-        HIPCHK(ctx, hipDeviceSynchronize());
-        ctx->deferred.flush();
-    }
-    // uploads since the last use are built now (msfm_store_host.hip.h); twins built before a later upload raised the context's level
-    // (msfm_q8.hip.h) are rebuilt: nothing is in flight
-    {
-        int rc = settle_store(ctx);
+        prm = msfm_match_params{0.8f, 1, 0.7};
+        if (params) prm = *params;
+        // rows / columns that provably fail the ratio test or the distance cut need no exact neighbours
+        prune = PruneParams{1, prm.ratio, (float)prm.max_distance};
+        if ((double)prune.max_distance < prm.max_distance) prune.max_distance = nextafterf(prune.max_distance, __builtin_huge_valf());
+        if (!(prm.ratio > 0.f) || !(prm.ratio <= 1.f)) prune.ratio = 0.f;  // outside (0, 1]: no ratio-based pruning
+        if (!(prm.max_distance >= 0.0)) prune.max_distance = __builtin_huge_valf();  // NaN / negative: no distance-based pruning
+        int rc = call_prologue(ctx);
         if (rc != MSFM_OK) return rc;
+        // twins built before a later upload raised the context's level (msfm_q8.hip.h) are rebuilt: nothing is in flight
         rc = rebuild_stale_twins(ctx, pairs, 2 * n_pairs);
         if (rc != MSFM_OK) return rc;
-    }
-    ctx->res_offsets.assign((size_t)n_pairs + 1, 0);
-    ctx->res_sens.assign((size_t)n_pairs, 0);
-    ctx->res_count = 0;
-    ctx->prof = msfm_profile{};
-    ctx->out_used = 0;
-    for (OutSeg& s : ctx->out_segs) s.count = 0;
-    if (!streaming) {
-        // address space for the host lists: a pair yields at most min(n1, n2) matches (each query row one, each train row once under the
-        // cross-check; without it n1)
-        long long bound = 1;
-        for (int k = 0; k < n_pairs; ++k) {
-            const int i = pairs[2 * k], j = pairs[2 * k + 1];
-            if (i < 0 || i >= kSlots || j < 0 || j >= kSlots) return fail(ctx, MSFM_E_INVALID, "image id out of range");
-            const long long n1 = ctx->images[(size_t)i].n, n2 = ctx->images[(size_t)j].n;
-            if (n1 > 0 && n2 > 0) bound += prm.cross_check ? std::min(n1, n2) : n1;
+        ctx->res_offsets.assign((size_t)n_pairs + 1, 0);
+        ctx->res_sens.assign((size_t)n_pairs, 0);
+        ctx->res_count = 0;
+        ctx->prof = msfm_profile{};
+        ctx->out_used = 0;
+        for (OutSeg& s : ctx->out_segs) s.count = 0;
+        if (!streaming) {
+            // address space for the host lists: a pair yields at most min(n1, n2) matches (each query row one, each train row once under
+            // the cross-check; without it n1)
+            long long bound = 1;
+            for (int k = 0; k < n_pairs; ++k) {
+                const int i = pairs[2 * k], j = pairs[2 * k + 1];
+                if (i < 0 || i >= kSlots || j < 0 || j >= kSlots) return fail(ctx, MSFM_E_INVALID, "image id out of range");
+                const long long n1 = ctx->images[(size_t)i].n, n2 = ctx->images[(size_t)j].n;
+                if (n1 > 0 && n2 > 0) bound += prm.cross_check ? std::min(n1, n2) : n1;
+            }
+            if (ctx->res_qt.reserve((size_t)bound * 8) != hipSuccess || ctx->res_dist.reserve((size_t)bound * 4) != hipSuccess)
+                return fail(ctx, MSFM_E_DEVICE, "cannot reserve address space for the result lists");
         }
-        if (ctx->res_qt.reserve((size_t)bound * 8) != hipSuccess || ctx->res_dist.reserve((size_t)bound * 4) != hipSuccess)
-            return fail(ctx, MSFM_E_DEVICE, "cannot reserve address space for the result lists");
-    }
 
-    ev_begin = get_event(ctx, 0), ev_end = get_event(ctx, 1);
-    if (!ev_begin || !ev_end) return fail(ctx, MSFM_E_DEVICE, "hipEventCreate failed");
-    HIPCHK(ctx, hipEventRecord(ev_begin, ctx->sc[0].stream));
+        ev_begin = get_event(ctx, 0), ev_end = get_event(ctx, 1);
+        if (!ev_begin || !ev_end) return fail(ctx, MSFM_E_DEVICE, "hipEventCreate failed");
+        HIPCHK(ctx, hipEventRecord(ev_begin, ctx->sc[0].stream));
 
-    // ---- the cut: scratch memory per set, pair count, and a cost limit that gives a large call >= `pipeline` sub-batches
-    kSets = ctx->in_flight;
-    // the scratch sets in flight SHARE the budget (three sets at half of it each were 1.5 x the documented limit)
-    // (the automatic budget is derived from the device's free memory ONCE per state of the context -- the store's size and the limit
-    // set by the caller -- not per call: a hipMemGetInfo per call made the cut depend on what else was momentarily allocated on the GPU,
-    // and the pre-emptive filter's many small calls paid the driver query each time)
-    long long budget = ctx->scratch_bytes > 0 ? ctx->scratch_bytes : kDefaultScratchBytes;
-    if (ctx->budget_cached > 0 && ctx->budget_for_store == ctx->store.bytes() && ctx->budget_for_limit == ctx->scratch_bytes) {
-        budget = ctx->budget_cached;
-    } else {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            long long held = 0;   // what the scratch sets hold already is theirs to use
-            for (Scratch& sc : ctx->sc) held += sc.device_bytes();
-            const long long avail = (long long)free_b + held;
-            // (an explicit limit is honoured up to half of what is free: the estimate per pair is the cut, not a cap -- buffers that turn
-            // out too small are re-grown)
-            budget = std::min(budget, ctx->scratch_bytes > 0 ? avail / 2 : avail / 4);
+        // ---- the cut: scratch memory per set, pair count, and a cost limit that gives a large call >= `pipeline` sub-batches
+        kSets = ctx->in_flight;
+        // the scratch sets in flight SHARE the budget (three sets at half of it each were 1.5 x the documented limit)
+        // (the automatic budget is derived from the device's free memory ONCE per state of the context -- the store's size and the
+        // limit set by the caller -- not per call: a hipMemGetInfo per call made the cut depend on what else was momentarily allocated
+        // on the GPU, and the pre-emptive filter's many small calls paid the driver query each time)
+        long long budget = ctx->scratch_bytes > 0 ? ctx->scratch_bytes : kDefaultScratchBytes;
+        if (ctx->budget_cached > 0 && ctx->budget_for_store == ctx->store.bytes() && ctx->budget_for_limit == ctx->scratch_bytes) {
+            budget = ctx->budget_cached;
+        } else {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+                long long held = 0;   // what the scratch sets hold already is theirs to use
+                for (Scratch& sc : ctx->sc) held += sc.device_bytes();
+                const long long avail = (long long)free_b + held;
+                // (an explicit limit is honoured up to half of what is free: the estimate per pair is the cut, not a cap -- buffers
+                // that turn out too small are re-grown)
+                budget = std::min(budget, ctx->scratch_bytes > 0 ? avail / 2 : avail / 4);
+            }
+            ctx->budget_cached = budget;
+            ctx->budget_for_store = ctx->store.bytes();
+            ctx->budget_for_limit = ctx->scratch_bytes;
         }
-        ctx->budget_cached = budget;
-        ctx->budget_for_store = ctx->store.bytes();
-        ctx->budget_for_limit = ctx->scratch_bytes;
-    }
-    kScratchBytes = std::max<long long>(1, budget / kSets);
-    knobs = ctx->route_knobs();
-    kMaxPairsPerBatch = ctx->max_pairs_per_batch;
-    // cumulative-cost marks of the parts (empty: no cost cut): msfm_pipeline_marks (msfm_hostutil.h) -- shrinking parts
-    marks.clear();
-    if (ctx->pipeline > 1 && n_pairs > 1) {
-        long long total = 0;
-        for (int k = 0; k < n_pairs; ++k) {
-            const int i = pairs[2 * k], j = pairs[2 * k + 1];
-            if (i < 0 || i >= kSlots || j < 0 || j >= kSlots) return fail(ctx, MSFM_E_INVALID, "image id out of range");
-            const long long n1 = ctx->images[i].n, n2 = ctx->images[j].n;
-            if (n1 > 0 && n2 > 0) total += n1 * n2;
+        kScratchBytes = std::max<long long>(1, budget / kSets);
+        knobs = ctx->route_knobs();
+        kMaxPairsPerBatch = ctx->max_pairs_per_batch;
+        // cumulative-cost marks of the parts (empty: no cost cut): msfm_pipeline_marks (msfm_hostutil.h) -- shrinking parts
+        marks.clear();
+        if (ctx->pipeline > 1 && n_pairs > 1) {
+            long long total = 0;
+            for (int k = 0; k < n_pairs; ++k) {
+                const int i = pairs[2 * k], j = pairs[2 * k + 1];
+                if (i < 0 || i >= kSlots || j < 0 || j >= kSlots) return fail(ctx, MSFM_E_INVALID, "image id out of range");
+                const long long n1 = ctx->images[i].n, n2 = ctx->images[j].n;
+                if (n1 > 0 && n2 > 0) total += n1 * n2;
+            }
+            marks = msfm_pipeline_marks(total, std::min<long long>(ctx->pipeline, total / kMinPipelineCost), ctx->pipeline_taper);
         }
-        marks = msfm_pipeline_marks(total, std::min<long long>(ctx->pipeline, total / kMinPipelineCost), ctx->pipeline_taper);
-    }
-    cost_done = 0;
-    // a tie in sqrt space can only surface in a match list when a row with d0 == d1 can pass the ratio test
-    need_fix = !(prm.ratio <= 1.f);
-
-        open = true;
-        ctx->series_open = streaming;
+        cost_done = 0;
+        // a tie in sqrt space can only surface in a match list when a row with d0 == d1 can pass the ratio test
+        need_fix = !(prm.ratio <= 1.f);
+        if (streaming) ctx->series_open = true;   // the one place a series opens (close_series is the one where it ends)
         return MSFM_OK;
     }
 
@@ -281,7 +289,6 @@ struct MatchJob {
             hipLaunchKernelGGL(export_tail_kernel, dim3(32), dim3(256), 0, SC.stream, segs);
             HIPCHK(ctx, hipGetLastError());
         }
-        w.active = true;
         return MSFM_OK;
     }
 
@@ -461,7 +468,6 @@ struct MatchJob {
     int complete(SubBatch& w, std::vector<char>& force_exact, bool* retry_out) {
         Batch& b = w.b;
         const size_t P = b.pairs.size();
-        w.active = false;
         *retry_out = false;
         HIPCHK(ctx, hipStreamSynchronize(SC.stream));
         bool retry = false, retry_pf = false;
@@ -581,11 +587,7 @@ struct MatchJob {
         Scratch& sc = ctx->sc[slot];
         if (sc.stream) (void)hipStreamSynchronize(sc.stream);
         (void)hipGetLastError();   // (the runtime keeps the allocation's error for the next hipGetLastError: a launch check would see it)
-        sb[slot].active = false;
-        sc.pf_pending = PfPending{};
-        sc.sweep1_recorded = false;
-        sc.sweep2_recorded = false;
-        if (ctx->last_sweep1 == &sc) ctx->last_sweep1 = nullptr;
+        forget_sweeps(ctx, sc);
         ctx->last_hip_error = 0;
         memory_wait = true;
     }
@@ -646,23 +648,14 @@ struct MatchJob {
             if (rc != MSFM_OK) return rc;
             ctx->deferred.flush();
             for (int k = 0; k < kSets; ++k)
-                if (k != slot) {
-                    sb[k].active = false;
-                    ctx->sc[k].pf_pending = PfPending{};
-                    ctx->sc[k].sweep1_recorded = false;
-                    ctx->sc[k].sweep2_recorded = false;
-                }
-            ctx->last_sweep1 = nullptr;
-            for (int attempt = 1;; ++attempt) {
-                rc = build(sb[slot], sb[slot].begin, force_exact);
-                if (rc != MSFM_OK) return rc;
-                rc = issue(sb[slot], 2 + 12 * (size_t)slot);
-                if (rc != MSFM_OK) return rc;
-                rc = complete(sb[slot], force_exact, &retry);
-                if (rc != MSFM_OK) return rc;
-                if (!retry) break;
-                if (attempt >= 6) return fail(ctx, MSFM_E_DEVICE, "batch kept overflowing its queues");
-            }
+                if (k != slot) forget_sweeps(ctx, ctx->sc[k]);
+            ctx->last_sweep1 = nullptr;   // (this set's own sweep 1 has long run: nothing waits for it)
+            rc = rerun_alone(ctx, [&](bool* again) {
+                int r = build(sb[slot], sb[slot].begin, force_exact);
+                if (r == MSFM_OK) r = issue(sb[slot], 2 + 12 * (size_t)slot);
+                return r != MSFM_OK ? r : complete(sb[slot], force_exact, again);
+            });
+            if (rc != MSFM_OK) return rc;
             next_begin = sb[slot].end;
             issued = completed + 1;
         }
@@ -682,8 +675,7 @@ struct MatchJob {
         float ms = 0.f;
         HIPCHK(ctx, hipEventElapsedTime(&ms, ev_begin, ev_end));
         ctx->prof.total_device_ms = ms;
-        open = false;
-        ctx->series_open = false;
+        close_series(ctx);
         if (std::getenv("MSFM_DEBUG_TIMING")) {
             AllocClock& c = alloc_clock();
             std::fprintf(stderr, "[msfm alloc] since the last report: %d hipMalloc %.1f ms (%.2f GiB), %d hipFree %.1f ms, %d hipHostMalloc %.1f ms (%.2f GiB)\n",

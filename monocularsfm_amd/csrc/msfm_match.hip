@@ -275,11 +275,12 @@ int msfm_get_profile(const msfm_ctx* ctx, msfm_profile* out) {
     MSFM_API_END
 }
 
-// An error return may leave launches of the failed batch in flight: drain the stream before handing control back, so
-// that the caller can free or reuse its buffers and a following call starts from an idle stream.
-static int drained(msfm_ctx* ctx, int rc) {
+// A matching entry point is returning rc: THE way out on failure.  An error return may leave launches of the failed batch in flight:
+// the streams are drained before control goes back, so that the caller can free or reuse its buffers and a following call starts from
+// idle streams; a series, open before the call or opened by it, is closed.
+static int leave(msfm_ctx* ctx, int rc) {
     if (rc != MSFM_OK && ctx) {
-        ctx->series_open = false;
+        close_series(ctx);
         for (Scratch& sc : ctx->sc)
             if (sc.stream) (void)hipStreamSynchronize(sc.stream);
         ctx->cur = &ctx->sc[0];
@@ -291,7 +292,6 @@ namespace {
 
 // host state of one sub-batch in flight (parallel to ctx->sc[slot])
 struct SubBatch {
-    bool active = false;
     Batch b;
     int begin = 0, end = 0;
     size_t ev_base = 0;
@@ -350,33 +350,32 @@ extern "C++" {   // (MatchJob has member templates)
 
 namespace {
 // behind an exception caught at the C ABI (msfm_guard.h): the text for msfm_last_error, nothing left in flight, no series left open
-void after_api_exception(msfm_ctx* ctx, const char* text) noexcept {
+void after_api_exception(msfm_ctx* ctx, int rc, const char* text) noexcept {
     if (!ctx) return;
     try {
         ctx->err = text ? text : "C++ exception";
     } catch (...) {
     }
-    ctx->series_open = false;
     ctx->have_results = false;
-    if (ctx->job) ctx->job->open = false;
-    for (Scratch& sc : ctx->sc)
-        if (sc.stream) (void)hipStreamSynchronize(sc.stream);
-    ctx->cur = &ctx->sc[0];
+    (void)leave(ctx, rc);
 }
 }  // namespace
 
 // Any matching call ends a streaming series that was left open (msfm_match_pairs_begin without the msfm_match_pairs_next that returns
 // n_pairs == 0): its sub-batches in flight are drained, the store is unlocked, a later msfm_match_pairs_next returns MSFM_E_STATE.
 static int abandon_series(msfm_ctx* ctx) {
-    MatchJob& job = *ctx->job;
-    if (ctx->series_open || (job.open && job.streaming)) {
-        const int rc = drain_streams(ctx);
-        ctx->series_open = false;
-        job.open = false;
-        if (rc != MSFM_OK) return rc;
-        for (SubBatch& w : job.sb) w.active = false;
-    }
-    job.open = false;
+    if (!ctx->series_open) return MSFM_OK;
+    close_series(ctx);
+    return drain_streams(ctx);
+}
+
+// the verification parameters of a verified call: the reference's (FeatureUtils.cpp:196: FM_RANSAC, 3.0, 0.99; OpenCV's maxIters) unless
+// the caller gives its own
+static int verify_params(msfm_ctx* ctx, const msfm_verify_params* given, msfm_verify_params* v) {
+    *v = msfm_verify_params{3.0, 0.99, 1000, 0x5eed5eedULL};
+    if (given) *v = *given;
+    if (!(v->threshold >= 0.0) || !(v->confidence > 0.0) || !(v->confidence < 1.0) || v->max_iters < 1 || v->max_iters > (1 << 16))
+        return fail(ctx, MSFM_E_INVALID, "bad verification parameters");
     return MSFM_OK;
 }
 
@@ -385,9 +384,8 @@ static int match_pairs_impl(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, co
     if (!ctx) return MSFM_E_INVALID;
     if (n_pairs < 0 || (n_pairs > 0 && !pairs) || !out_offsets) return fail(ctx, MSFM_E_INVALID, "bad pair list");
     MatchJob& job = *ctx->job;
-    const int rc0 = abandon_series(ctx);   // a streaming series left open is abandoned: what it has in flight is drained first
-    if (rc0 != MSFM_OK) return rc0;
-    int rc = job.start(ctx, pairs, n_pairs, params, verify, false);
+    int rc = abandon_series(ctx);   // a streaming series left open is abandoned: what it has in flight is drained first
+    if (rc == MSFM_OK) rc = job.start(ctx, pairs, n_pairs, params, verify, false);
     if (rc != MSFM_OK) return rc;
     while (job.more()) {
         int slot = 0;
@@ -397,7 +395,7 @@ static int match_pairs_impl(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, co
     rc = job.finish();
     if (rc != MSFM_OK) return rc;
     std::memcpy(out_offsets, ctx->res_offsets.data(), ((size_t)n_pairs + 1) * sizeof(int64_t));
-    ctx->have_results = true;
+    ctx->have_results = true;   // what the blocking form hands out: set here and nowhere else
     ctx->sel_valid = job.select;
     ctx->tv_valid = job.pose;
     return MSFM_OK;
@@ -406,18 +404,17 @@ static int match_pairs_impl(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, co
 int msfm_match_pairs(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, const msfm_match_params* params,
                      int64_t* out_offsets) {
     MSFM_API_BEGIN(ctx)
-    return drained(ctx, match_pairs_impl(ctx, pairs, n_pairs, params, nullptr, out_offsets));
+    return leave(ctx, match_pairs_impl(ctx, pairs, n_pairs, params, nullptr, out_offsets));
     MSFM_API_END
 }
 
 int msfm_match_pairs_verified(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, const msfm_match_params* params,
                               const msfm_verify_params* verify, int64_t* out_offsets) {
     MSFM_API_BEGIN(ctx)
-    msfm_verify_params v = {3.0, 0.99, 1000, 0x5eed5eedULL};  // FeatureUtils.cpp:196: FM_RANSAC, 3.0, 0.99; OpenCV's maxIters
-    if (verify) v = *verify;
-    if (!(v.threshold >= 0.0) || !(v.confidence > 0.0) || !(v.confidence < 1.0) || v.max_iters < 1 || v.max_iters > (1 << 16))
-        return fail(ctx, MSFM_E_INVALID, "bad verification parameters");
-    return drained(ctx, match_pairs_impl(ctx, pairs, n_pairs, params, &v, out_offsets));
+    msfm_verify_params v;
+    const int rc = verify_params(ctx, verify, &v);
+    if (rc != MSFM_OK) return rc;
+    return leave(ctx, match_pairs_impl(ctx, pairs, n_pairs, params, &v, out_offsets));
     MSFM_API_END
 }
 
@@ -519,14 +516,11 @@ static void delete_match_job(MatchJob* j) { delete j; }
 static int begin_impl(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, const msfm_match_params* params, int geometric_verification,
                       const msfm_verify_params* verify) {
     if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return fail(ctx, MSFM_E_INVALID, "bad pair list");
-    msfm_verify_params v = {3.0, 0.99, 1000, 0x5eed5eedULL};
-    if (verify) v = *verify;
-    if (geometric_verification &&
-        (!(v.threshold >= 0.0) || !(v.confidence > 0.0) || !(v.confidence < 1.0) || v.max_iters < 1 || v.max_iters > (1 << 16)))
-        return fail(ctx, MSFM_E_INVALID, "bad verification parameters");
+    msfm_verify_params v;
+    int rc = geometric_verification ? verify_params(ctx, verify, &v) : MSFM_OK;
+    if (rc == MSFM_OK) rc = abandon_series(ctx);
+    if (rc != MSFM_OK) return rc;
     MatchJob& job = *ctx->job;
-    const int rc0 = abandon_series(ctx);
-    if (rc0 != MSFM_OK) return rc0;
     job.pairs_own.assign(pairs, pairs + 2 * (size_t)n_pairs);
     return job.start(ctx, job.pairs_own.data(), n_pairs, params, geometric_verification ? &v : nullptr, true);
 }
@@ -535,52 +529,47 @@ int msfm_match_pairs_begin(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, con
                            const msfm_verify_params* verify) {
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
-    const int rc = drained(ctx, begin_impl(ctx, pairs, n_pairs, params, geometric_verification, verify));
-    if (rc != MSFM_OK) ctx->job->open = false;
-    return rc;
+    return leave(ctx, begin_impl(ctx, pairs, n_pairs, params, geometric_verification, verify));
     MSFM_API_END
 }
 
 static int next_impl(msfm_ctx* ctx, msfm_chunk* out) {
+    // (one thread may drive contexts on several devices in turn: step() allocates scratch and asks for the free memory)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->series_open) return fail(ctx, MSFM_E_STATE, "msfm_match_pairs_next without msfm_match_pairs_begin");
     MatchJob& job = *ctx->job;
-    if (!job.open || !job.streaming) return fail(ctx, MSFM_E_STATE, "msfm_match_pairs_next without msfm_match_pairs_begin");
     *out = msfm_chunk{};
-    ctx->sel_valid = false;
-    ctx->sel_records.clear();
-    ctx->tv_valid = false;
-    ctx->tv_records.clear();
-    if (!job.more()) {   // n_pairs == 0: the series is complete
-        ctx->sel_valid = job.select;
-        ctx->tv_valid = job.pose;
-        return job.finish();
-    }
+    ctx->sel_valid = ctx->tv_valid = false;   // (the chunk before is gone; a step that fails hands out nothing)
+    const SubBatch* w = nullptr;   // the chunk; none: the series is complete, n_pairs == 0
     int slot = 0;
-    const int rc = job.step(&slot);
-    if (rc != MSFM_OK) return rc;
-    const SubBatch& w = job.sb[slot];
-    ctx->sel_records = w.sel;
+    if (job.more()) {
+        const int rc = job.step(&slot);
+        if (rc != MSFM_OK) return rc;
+        w = &job.sb[slot];
+    }
+    // what the streaming form hands out, set here and nowhere else: the chunk's records, none behind the last chunk
+    ctx->sel_records = w ? w->sel : std::vector<int32_t>();
     ctx->sel_valid = job.select;
-    ctx->tv_records = w.tv;
+    ctx->tv_records = w ? w->tv : std::vector<msfm_two_view_record>();
     ctx->tv_valid = job.pose;
+    if (!w) return job.finish();
     const Scratch& sc = ctx->sc[slot];
-    out->first_pair = w.begin;
-    out->n_pairs = w.end - w.begin;
-    out->offsets = w.offsets.data();
-    out->count = w.offsets.empty() ? 0 : w.offsets.back();
+    out->first_pair = w->begin;
+    out->n_pairs = w->end - w->begin;
+    out->offsets = w->offsets.data();
+    out->count = w->offsets.empty() ? 0 : w->offsets.back();
     out->qt = sc.h_sub_qt.as<int32_t>();
     out->dist = sc.h_sub_d.as<float>();
     out->d_qt = sc.d_sub_qt.as<int32_t>();
     out->d_dist = sc.d_sub_d.as<float>();
-    out->sensitive_rows = w.sens.data();
+    out->sensitive_rows = w->sens.data();
     return MSFM_OK;
 }
 
 int msfm_match_pairs_next(msfm_ctx* ctx, msfm_chunk* out) {
     MSFM_API_BEGIN(ctx)
     if (!ctx || !out) return MSFM_E_INVALID;
-    const int rc = drained(ctx, next_impl(ctx, out));
-    if (rc != MSFM_OK) ctx->job->open = false;
-    return rc;
+    return leave(ctx, next_impl(ctx, out));
     MSFM_API_END
 }
 
@@ -698,32 +687,22 @@ int msfm_knn2_pair(msfm_ctx* ctx, int id1, int id2, int32_t* fwd_idx0, float* fw
                    int32_t* rev_idx0, float* rev_d0, float* rev_d1) {
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
-    // a streaming series left open is abandoned (include/msfm_match.h): what it has in flight is drained first -- this call runs on
-    // scratch set 0 and would otherwise overwrite the tail words of a sub-batch the series still has to complete (ADVICE r05)
-    const int rc0 = abandon_series(ctx);
-    if (rc0 != MSFM_OK) return rc0;
-    const int rc = drained(ctx, knn2_pair_impl(ctx, id1, id2, fwd_idx0, fwd_d0, fwd_d1, rev_idx0, rev_d0, rev_d1));
-    if (rc != MSFM_OK) ctx->job->open = false;
-    return rc;
+    return leave(ctx, knn2_pair_impl(ctx, id1, id2, fwd_idx0, fwd_d0, fwd_d1, rev_idx0, rev_d0, rev_d1));
     MSFM_API_END
 }
 
 static int knn2_pair_impl(msfm_ctx* ctx, int id1, int id2, int32_t* fwd_idx0, float* fwd_d0, float* fwd_d1,
                           int32_t* rev_idx0, float* rev_d0, float* rev_d1) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    ctx->cur = &ctx->sc[0];
+    // a streaming series left open is abandoned (include/msfm_match.h): what it has in flight is drained first -- this call runs on
+    // scratch set 0 and would otherwise overwrite the tail words of a sub-batch the series still has to complete (ADVICE r05)
+    int rc = abandon_series(ctx);
+    if (rc != MSFM_OK) return rc;
     ctx->prof = msfm_profile{};
-    for (Scratch& sc : ctx->sc) {   // (a failed earlier batch may have left its end-of-batch state behind)
-        sc.pf_pending = PfPending{};
-        sc.sweep1_recorded = false;
-        sc.sweep2_recorded = false;
-    }
-    ctx->last_sweep1 = nullptr;
+    rc = call_prologue(ctx);
+    if (rc != MSFM_OK) return rc;
     Batch b;
     PairDesc pd;
     PfPair pp;
-    int rc = settle_store(ctx);
-    if (rc != MSFM_OK) return rc;
     rc = fill_pair(ctx, id1, id2, pd, pp);
     if (rc != MSFM_OK) return rc;
     b.pairs.push_back(pd);
@@ -733,31 +712,35 @@ static int knn2_pair_impl(msfm_ctx* ctx, int id1, int id2, int32_t* fwd_idx0, fl
     bool exact_launched = false;
     int regrows = 0, fallbacks = 0;
     std::vector<char> force_exact(1, 0);
-    for (int attempt = 0;; ++attempt) {
+    // the knnMatch twin: nothing is pruned (the float forms), every row keeps its neighbours, no CSR
+    auto attempt = [&](bool* again) {
         b.n_items = 0;
         b.rp_elems = b.cp_elems = b.kf_elems = b.kr_elems = b.out_elems = b.cand_elems = 0;
         b.desc_pairs = b.algo_bytes = 0;
         b.pairs[0].path = b.pf[0].use = force_exact[0] ? 0 : pp.use;
-        rc = prepare_batch_images(ctx, b, PruneParams{0, 0.f, 0.f});   // (the kNN-level API reads the float forms: nothing is pruned)
-        if (rc != MSFM_OK) return rc;
+        int r = prepare_batch_images(ctx, b, PruneParams{0, 0.f, 0.f});
+        if (r != MSFM_OK) return r;
         SC.prof = msfm_profile{};   // only the attempt that is kept counts
-        rc = run_knn(ctx, b, 2, &exact_launched, PruneParams{0, 0.f, 0.f}, true, false);  // knnMatch twin: every row keeps its neighbours
-        if (rc != MSFM_OK) return rc;
-        SC.d_offsets.release();   // (no CSR on this path: the export kernel skips absent segments)
+        r = run_knn(ctx, b, 2, &exact_launched, PruneParams{0, 0.f, 0.f}, true, false);
+        if (r != MSFM_OK) return r;
+        SC.d_offsets.release();   // (the export kernel skips absent segments)
         SC.d_sens.release();
-        rc = queue_tail_copies(ctx, 1);
-        if (rc != MSFM_OK) return rc;
+        r = queue_tail_copies(ctx, 1);
+        if (r != MSFM_OK) return r;
         HIPCHK(ctx, hipStreamSynchronize(SC.stream));
         bool retry = false, retry_pf = false;
-        rc = check_fix_overflow(ctx, &retry);
-        if (rc != MSFM_OK) return rc;
-        rc = finish_prefilter(ctx, b, force_exact, &retry_pf);
-        if (rc != MSFM_OK) return rc;
-        if (!retry && !retry_pf) break;
+        r = check_fix_overflow(ctx, &retry);
+        if (r == MSFM_OK) r = finish_prefilter(ctx, b, force_exact, &retry_pf);
+        if (r != MSFM_OK) return r;
         if (retry) ++regrows;
         if (retry_pf) fallbacks += SC.prof.fallback_pairs;
-        if (attempt >= 6) return fail(ctx, MSFM_E_DEVICE, "batch kept overflowing its queues");
-    }
+        *again = retry || retry_pf;
+        return (int)MSFM_OK;
+    };
+    bool again = false;
+    rc = attempt(&again);
+    if (rc == MSFM_OK && again) rc = rerun_alone(ctx, attempt);
+    if (rc != MSFM_OK) return rc;
     rc = accumulate_kernel_time(ctx, 2, exact_launched);
     if (rc != MSFM_OK) return rc;
     ctx->prof = SC.prof;

@@ -148,3 +148,135 @@ def test_knn2_pair_and_an_early_exit_both_end_an_open_series():
         offs, qt, d, _, chunks = collect(ctx, pairs, **kw)
         assert chunks == -(-len(pairs) // 3)
         assert np.array_equal(offs, ref[0]) and np.array_equal(qt, ref[1]) and np.array_equal(bits(d), bits(ref[2]))
+
+
+@pytest.fixture(scope="module")
+def eight_u8():
+    """The images of test_knn2_pair_and_an_early_exit_both_end_an_open_series and their one-call lists."""
+    imgs = synth.u8_images(8, [900, 1400, 700, 1100, 1300, 600, 1000, 1200], seed=81, dup_frac=0.2, as_float=False)
+    pairs = synth.all_pairs(8)
+    with _lib.Context(0) as ctx:
+        for i, im in enumerate(imgs):
+            ctx.upload_image(i, im)
+        ref = ctx.match_pairs(pairs, max_distance=1e9)
+    return imgs, pairs, ref
+
+
+def rest_of(it, first, n_pairs):
+    """The chunks of the generator `it` behind `first`, joined to it like collect() joins them."""
+    offs, qt, d, nxt = [np.zeros(1, np.int64)], [], [], 0
+    for ch in [first] + list(it):
+        assert ch["first"] == nxt and ch["n_pairs"] > 0
+        offs.append(offs[-1][-1] + ch["offsets"][1:])
+        qt.append(ch["qt"])
+        d.append(ch["dist"])
+        nxt += ch["n_pairs"]
+    assert nxt == n_pairs
+    return np.concatenate(offs), np.concatenate(qt), np.concatenate(d)
+
+
+@pytest.mark.parametrize("how", ["close", "collect"])
+def test_a_stale_generator_does_not_end_a_newer_series(eight_u8, how):
+    """A generator whose series a newer one on the same context has superseded is closed, or dropped and collected, while the newer
+    series is under way: its `finally` must not call msfm_match_pairs_end, which knows no owner -- the newer series'
+    next chunk used to fail with E_STATE in mid-job.  Its own next() is a state error, not a chunk of the newer series."""
+    import gc
+    imgs, pairs, ref = eight_u8
+    kw = {"max_distance": 1e9}
+    with _lib.Context(0) as ctx:
+        for i, im in enumerate(imgs):
+            ctx.upload_image(i, im)
+        ctx.set_limits(max_pairs_per_batch=3)          # ten chunks, two sub-batches in flight behind each
+        a0 = ctx.match_pairs_stream(pairs, **kw)
+        assert next(a0)["n_pairs"] == 3
+        a = ctx.match_pairs_stream(pairs, **kw)
+        assert next(a)["n_pairs"] == 3
+        b = ctx.match_pairs_stream(pairs, **kw)
+        first = next(b)
+        with pytest.raises(_lib.MsfmError) as err:      # a0 is suspended at its first chunk; a and b came after it
+            next(a0)
+        assert err.value.code == _lib.E_STATE
+        if how == "close":
+            a.close()
+        else:
+            del a
+            gc.collect()
+        offs, qt, d = rest_of(b, first, len(pairs))     # at the parent of this change: E_STATE at b's second chunk
+        assert np.array_equal(offs, ref[0]) and np.array_equal(qt, ref[1]) and np.array_equal(bits(d), bits(ref[2]))
+        ctx.upload_image(0, imgs[0])                    # b ran to its end: the store is unlocked
+
+
+def test_a_series_that_fails_is_closed_and_nothing_of_it_is_left(eight_u8):
+    """The lifecycle rows of DESIGN.md 4.3 for a streaming call that fails without a device error.  An image that was never uploaded
+    is reported by the msfm_match_pairs_next that first builds its pair (msfm_match_pairs_begin looks at no image), an image id out of
+    range by msfm_match_pairs_begin itself.  After either: _next is E_STATE, _end is a no-op, the store is unlocked, and the blocking
+    call's lists from before are gone -- msfm_match_pairs_begin had started, and a matching call that starts gives up what the call
+    before it handed out."""
+    imgs, pairs, ref = eight_u8
+    L = _lib.load()
+    prm = _lib.MatchParams(0.8, 1, 1e9)
+    ch = _lib.Chunk()
+
+    def begin(ctx, plist):
+        plist = np.ascontiguousarray(plist, np.int32)
+        return L.msfm_match_pairs_begin(ctx._h, _lib._ip(plist), len(plist), _lib.C.byref(prm), 0, None)
+
+    def closed_and_empty(ctx):
+        assert L.msfm_match_pairs_next(ctx._h, _lib.C.byref(ch)) == _lib.E_STATE
+        assert L.msfm_match_pairs_end(ctx._h) == _lib.OK
+        ctx.upload_image(7, imgs[7])
+        assert L.msfm_fetch_matches(ctx._h, None, None) == _lib.E_STATE
+
+    with _lib.Context(0) as ctx:
+        for i, im in enumerate(imgs):
+            ctx.upload_image(i, im)
+        ctx.set_limits(max_pairs_per_batch=3)
+        for bad in ([[0, 1], [2, 3], [4, 9], [5, 6]], [[0, 1], [2, 3 * _lib.MAX_IMAGES]]):
+            again = ctx.match_pairs(pairs, max_distance=1e9)
+            assert np.array_equal(again[0], ref[0]) and np.array_equal(again[1], ref[1])
+            assert L.msfm_fetch_matches(ctx._h, None, None) == _lib.OK
+            rc = begin(ctx, bad)
+            if bad[-1][1] > 2 * _lib.MAX_IMAGES:       # (the slots go on to 2 * MAX_IMAGES + 1)
+                assert rc == _lib.E_INVALID             # image id out of range: found before the first launch
+            else:
+                assert rc == _lib.OK                    # image 9 was never uploaded: the first sub-batch finds out
+                assert L.msfm_match_pairs_next(ctx._h, _lib.C.byref(ch)) == _lib.E_NOIMAGE
+            closed_and_empty(ctx)
+        # an argument error before the call starts leaves everything as it was: the lists of the call before stay fetchable
+        again = ctx.match_pairs(pairs, max_distance=1e9)
+        assert L.msfm_match_pairs_begin(ctx._h, None, 3, _lib.C.byref(prm), 0, None) == _lib.E_INVALID
+        qt = np.empty((len(ref[1]) + 1, 2), np.int32)
+        d = np.empty(len(ref[1]) + 1, np.float32)
+        assert L.msfm_fetch_matches(ctx._h, _lib._ip(qt), _lib._fp(d)) == _lib.OK
+        assert np.array_equal(qt[:-1], ref[1]) and np.array_equal(bits(d[:-1]), bits(ref[2]))
+
+
+def test_one_thread_alternates_the_series_of_two_devices():
+    """msfm_match_pairs_next selects its context's device: one thread takes the chunks of a series on device 0 and of one
+    on device 1 in turn -- every step allocates its scratch and asks for the free memory on its own device -- and both equal the
+    one-call lists."""
+    if _lib.device_count() < 2:
+        pytest.skip("needs two gfx950 devices")
+    imgs = synth.u8_images(4, [2000, 1500, 1800, 900], seed=80, dup_frac=0.3, as_float=False)
+    pairs = synth.all_pairs(4)
+    kw = {"max_distance": 1e9}
+    with _lib.Context(0) as c0, _lib.Context(1) as c1:
+        for ctx in (c0, c1):
+            for i, im in enumerate(imgs):
+                ctx.upload_image(i, im)
+        ref = c0.match_pairs(pairs, **kw)
+        for ctx in (c0, c1):
+            ctx.set_limits(max_pairs_per_batch=2)
+        its = [c0.match_pairs_stream(pairs, **kw), c1.match_pairs_stream(pairs, **kw)]
+        chunks = [[], []]
+        while its[0] or its[1]:                         # three chunks of two pairs each, taken in turn
+            for k in (0, 1):
+                ch = next(its[k], None) if its[k] else None
+                if ch is None:
+                    its[k] = None
+                else:
+                    chunks[k].append(ch)
+        for k in (0, 1):
+            assert len(chunks[k]) == 3
+            offs, qt, d = rest_of(chunks[k][1:], chunks[k][0], len(pairs))
+            assert np.array_equal(offs, ref[0]) and np.array_equal(qt, ref[1]) and np.array_equal(bits(d), bits(ref[2]))

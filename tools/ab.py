@@ -11,9 +11,10 @@ box's thermal state hit every variant alike).  A variant is a BUILD of the libra
 
 Per variant: sub-batches, sweep-1 / sweep-2 event times, the call's device span and wall clock (median / min), sweep-1 rate; the variants'
 results must be identical (--nocheck: timing experiments with wrong results).  --p1: pipeline off (one sub-batch, every kernel alone).
+The POSITION of a variant is not neutral: with three variants the middle context's two sub-batches overlapped less and its call took 3 ms
+longer whatever build it was (profiles/match_lifecycle_ab.json).  Run a control with one build in every position, or swap the roles.
 (Replaces ab_env.py, ab_envs.py, ab_libs.py and ab_multi.py of rounds 2-5 -- the same loop four times.)"""
 import argparse
-import ctypes
 import os
 import sys
 import time
@@ -43,16 +44,14 @@ def main():
     args = ap.parse_args()
     imgs, pairs, name = synth.job("synthetic-u8", args.images or 48, 8192, seed=1329) if args.u8 else synth.job("south-building", args.images or 128)
     kw = {"max_distance": 1e9} if args.u8 else {}
-    tree, all_exports = _lib.LIB_PATH, list(_lib.EXPORTS)
+    tree = _lib.LIB_PATH
     ctxs = {}
     for spec in args.variants:
         label, lib, env = parse(spec)
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         _lib._lib = None
-        _lib.LIB_PATH = lib or tree
-        probe = ctypes.CDLL(_lib.LIB_PATH)
-        _lib.EXPORTS = [e for e in all_exports if hasattr(probe, e)]   # (an older build may lack the newest entry points)
+        _lib.LIB_PATH = lib or tree   # (another build of the same C ABI: _lib.load() refuses one that lacks a declared symbol)
         ctx = _lib.Context(0)
         for k, v in old.items():
             if v is None:
