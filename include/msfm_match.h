@@ -835,6 +835,70 @@ typedef struct msfm_extend_stats {   /* 96 bytes, no implicit padding */
 int msfm_extend_points(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses,
                        const msfm_extend_params* params, msfm_extend_stats* stats);
 
+/* ---- map filtering: drop outlier observations and weak points (opt-in) ---------------
+ * The step the reference runs after every local or global adjustment (MapBuilder::FilterTracks / FilterAllTracks ->
+ * Map::FilterPoints3DWithLargeReprojectionError, then ...WithSmallTriangulationAngle).  msfm_filter_points takes observations that no
+ * longer fit their point out of its fitting set and removes the points that are left with fewer than two observations or without a
+ * wide pair: the only call of this library that takes anything out of the map.  No X and no pose ever changes.  The arithmetic is
+ * csrc/msfm_filter.h, bit-identical to the host twin FilterPoints.
+ *   inputs       none besides the context, the thresholds and the scope: like msfm_refine_points the call works on what the last
+ *                successful msfm_triangulate_tracks / _robust left in the session (camera, thresholds, pose list, records, residuals,
+ *                inlier bytes), with the poses as msfm_refine_poses and msfm_extend_points left them.
+ *   thresholds   max_error in pixels, min_angle in degrees.  params NULL = the SESSION's own max_error and min_angle: a point is
+ *                judged by the test it was admitted by (the reference's filtered_max_reproj_error is a looser 4 px).  Explicit
+ *                values may be tighter or looser than the session's.
+ *   inlier bytes the call needs one byte per kept observation.  A session without them gets them first, exactly as
+ *                msfm_extend_points creates them: 1 on every used observation of an attempted track, else 0.  After a successful
+ *                call the bytes are valid whatever the triangulation was.
+ *   scope        n_images == 0: every track.  Otherwise only the tracks with a fitting observation in a listed image (the
+ *                reference's FilterPoints3DInImage / GetModifiedPoint3DIds).  A listed image without a valid pose selects nothing.
+ *   eligible     a consistent track whose record has ATTEMPTED | POINT and which is in scope.  Its fitting set F: its used
+ *                observations whose inlier byte is 1, in element order.  Every other track stays bit for bit.
+ *   drop         per observation of F: err = the reprojection error at the record's X under the current pose (pixels, f = (fx + fy)
+ *                / 2).  Dropped by depth iff its depth is not > DBL_EPSILON; otherwise dropped by error iff !(err <= max_error) (a
+ *                NaN is dropped).  K: the survivors.
+ *   removed      by views iff |K| < 2; otherwise by angle iff the parallax scan over K in element order with the CALL's min_angle
+ *                finds no pair, whether or not anything was dropped.  The record becomes status = MSFM_TRI_ATTEMPTED |
+ *                MSFM_TRI_FILTERED with every other field 0, every residual slot of the track -1.0 and every inlier byte of the
+ *                track 0 (the robust call's "no consensus" record).  It is no longer POINT: registration and the refinements skip
+ *                it, msfm_extend_points creates it afresh when a new image sees it.
+ *   untouched    nothing dropped and not removed: not one byte is written, the residual slots included.
+ *   trimmed      something dropped and not removed.  The dropped observations' bytes become 0.  The record is evaluated again over K
+ *                at the unchanged X with the SESSION's thresholds and the triangulation's code: an error for every used observation
+ *                (the dropped ones keep theirs), n_views = |K|, mean_residual = the errors of K summed in element order / |K|,
+ *                tri_angle, ERROR_OK, ANGLE_OK, DEPTH_OK over K;  status = ATTEMPTED | POINT | those bits | the record's ROBUST,
+ *                REFINED, REPOSED, EXTENDED | MSFM_TRI_FILTERED.  regained: a trimmed track that did not have POINT & ERROR_OK &
+ *                ANGLE_OK and now has it.
+ * The call is idempotent: repeated with the same thresholds and scope it changes not one byte.  Under NULL params every trimmed
+ * record has ERROR_OK | ANGLE_OK | DEPTH_OK.  Information is lost on purpose: a point without ANGLE_OK that the triangulation kept as
+ * a diagnostic record is removed by the angle rule.  A later msfm_refine_points / msfm_refine_poses / msfm_extend_points treats
+ * MSFM_TRI_FILTERED as it treats MSFM_TRI_EXTENDED when it rewrites a record.
+ * The call invalidates registrations and pose-refinement records like msfm_refine_points; points, inlier bytes and the pose list stay
+ * valid.  Errors, after each of which the session is exactly what it was: MSFM_E_STATE -- as msfm_refine_points.  MSFM_E_INVALID -- a
+ * non-finite or negative max_error or min_angle, n_images < 0 or a NULL list with n_images > 0, an id that is not declared in the
+ * session or given twice.  MSFM_E_NOIMAGE -- as msfm_refine_points.
+ * The counters only count: no order reaches an output. */
+enum { MSFM_TRI_FILTERED = 512 };
+typedef struct msfm_filter_params {   /* 16 bytes, no implicit padding */
+    double max_error;                /* pixels */
+    double min_angle;                /* degrees */
+} msfm_filter_params;
+typedef struct msfm_filter_stats {   /* 88 bytes, no implicit padding */
+    int64_t eligible;                /* consistent tracks with ATTEMPTED | POINT in scope */
+    int64_t dropped_by_depth;        /* fitting observations of eligible tracks behind their camera */
+    int64_t dropped_by_error;        /* ... in front of it with an error that is not <= max_error */
+    int64_t trimmed;                 /* eligible tracks that lost an observation and stand */
+    int64_t regained;                /* ... of which gain POINT & ERROR_OK & ANGLE_OK */
+    int64_t removed_by_views;        /* eligible tracks left with fewer than two observations */
+    int64_t removed_by_angle;        /* ... with two or more and no pair that reaches min_angle */
+    int64_t succeeded;               /* POINT & ERROR_OK & ANGLE_OK over all tracks after the call */
+    int64_t observations_used;       /* n_views summed over all tracks after the call */
+    double filter_ms;                /* HIP events around all launches of the call */
+    double prepare_ms;               /* ... of which the pose table, the inlier bytes and the per-observation array */
+} msfm_filter_stats;
+int msfm_filter_points(msfm_ctx* ctx, const msfm_filter_params* params, const int32_t* image_ids, int n_images,
+                       msfm_filter_stats* stats);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

@@ -139,6 +139,26 @@ def extended(points):
     return (np.asarray(points)["status"] & TRI_EXTENDED) != 0
 
 
+# map filtering (include/msfm_match.h): the record's extra status bit, the 16-byte parameters, the 88-byte stats
+TRI_FILTERED = 512
+
+
+class FilterParams(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("min_angle", C.c_double)]
+
+
+class FilterStats(C.Structure):
+    """msfm_filter_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("eligible", "dropped_by_depth", "dropped_by_error", "trimmed", "regained", "removed_by_views",
+                                         "removed_by_angle", "succeeded", "observations_used")] + \
+               [(k, C.c_double) for k in ("filter_ms", "prepare_ms")]
+
+
+def filtered(points):
+    """The records of a POINT3D array that a map filtering trimmed or removed (MSFM_TRI_FILTERED)."""
+    return (np.asarray(points)["status"] & TRI_FILTERED) != 0
+
+
 def succeeded(points):
     """The reference's is_succeed per record of a POINT3D array: POINT & ERROR_OK & ANGLE_OK."""
     want = TRI_POINT | TRI_ERROR_OK | TRI_ANGLE_OK
@@ -330,6 +350,7 @@ def _signatures():
         "msfm_fetch_poses": (i, [vp, ip, vp, intp]),
         "msfm_fetch_pose_refinements": (i, [vp, vp]),
         "msfm_extend_points": (i, [vp, ip, vp, i, P(ExtendParams), P(ExtendStats)]),
+        "msfm_filter_points": (i, [vp, P(FilterParams), ip, i, P(FilterStats)]),
         "msfm_register_images": (i, [vp, cam, ip, i, P(RegisterParams), P(RegisterStats)]),
         "msfm_fetch_registrations": (i, [vp, vp, vp, vp, vp, vp]),
     }
@@ -793,6 +814,7 @@ class Context:
         ids, tab = pose_table(poses)
         st = TriangulationStats()
         self._tri_route = int(max_hypotheses) if robust else 0   # (what extend_points(max_hypotheses=None) follows)
+        self._tri_thresholds = (float(max_error), float(min_angle))   # (what filter_points() without thresholds follows)
         if robust:
             rprm = RobustTriangulationParams(float(max_error), float(min_angle), int(min_views), int(max_hypotheses))
             rs = RobustStats()
@@ -905,6 +927,37 @@ class Context:
         ext = self.extend_points(new)
         alt = self.alternate(rounds, fixed=fixed, point_params=point_params, pose_params=pose_params)
         return reg, ext, alt, sorted(new)
+
+    def filter_points(self, max_error=None, min_angle=None, image_ids=None):
+        """Takes observations that no longer fit their point out of its fitting set and removes the points left with fewer than two
+        observations or without a pair of views min_angle apart (msfm_filter_points); no point and no pose moves.  max_error in pixels,
+        min_angle in degrees; if either is None both are those of this context's last triangulate_tracks.  image_ids: only the tracks
+        with a fitting observation in a listed image (None or empty: every track).  -> stats dict.  filtered(points) is the mask of the
+        records it trimmed or removed; point_inliers() works after it whatever the triangulation was.  Registrations and pose
+        refinements are invalidated."""
+        prm = None
+        if max_error is not None and min_angle is not None:
+            prm = FilterParams(float(max_error), float(min_angle))
+        elif getattr(self, "_tri_thresholds", None) is not None:
+            prm = FilterParams(*self._tri_thresholds)
+        ids = np.ascontiguousarray(list(image_ids) if image_ids is not None else [], dtype=np.int32).reshape(-1)
+        st = FilterStats()
+        self._chk(self._L.msfm_filter_points(self._h, C.byref(prm) if prm is not None else None, _ip(ids) if len(ids) else None, len(ids),
+                                             C.byref(st)))
+        return _dict(st)
+
+    def reconstruct(self, camera, rounds=1, filter_params=None, max_increments=None, **grow_kwargs):
+        """The reference's DoBuild loop with its filter: grow(camera, rounds=rounds, **grow_kwargs) followed by
+        filter_points(**filter_params), repeated until no image registers or max_increments increments have run.
+        -> one dict per increment: register, extend, alternate (grow's results), filter (filter_points' stats), registered (the ids)."""
+        out = []
+        while max_increments is None or len(out) < int(max_increments):
+            reg, ext, alt, new = self.grow(camera, rounds=rounds, **grow_kwargs)
+            if not new:
+                break
+            flt = self.filter_points(**(filter_params or {}))
+            out.append({"register": reg, "extend": ext, "alternate": alt, "filter": flt, "registered": new})
+        return out
 
     def points3d(self):
         """-> (points: POINT3D array, one per kept track; residuals: float64, one per kept observation in the tracks' order, -1.0 where

@@ -47,6 +47,7 @@ using namespace msfm;
 #include "msfm_refine.hip.h"
 #include "msfm_refine_poses.hip.h"
 #include "msfm_extend.hip.h"
+#include "msfm_filter.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -909,6 +910,15 @@ int msfm_extend_points(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return extend_impl(ctx, image_ids, poses, n_poses, params, stats);
+    MSFM_API_END
+}
+
+// ---- map filtering (msfm_filter.hip.h) -------------------------------------------------------------------------------------------------
+
+int msfm_filter_points(msfm_ctx* ctx, const msfm_filter_params* params, const int32_t* image_ids, int n_images, msfm_filter_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return filter_impl(ctx, params, image_ids, n_images, stats);
     MSFM_API_END
 }
 

@@ -19,6 +19,7 @@
 #include "../csrc/msfm_refine.h"
 #include "../csrc/msfm_refine_poses.h"
 #include "../csrc/msfm_extend.h"
+#include "../csrc/msfm_filter.h"
 #include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
@@ -837,6 +838,58 @@ int host_extend_points(const long long* offsets, const int* image_ids, const int
     if (counts7) {
         const long long v[7] = {ec.tracks_touched, ec.continued, ec.observations_added, ec.observations_rejected, ec.created_attempted,
                                 ec.created, ec.retried};
+        for (int k = 0; k < 7; ++k) counts7[k] += v[k];
+    }
+    return 0;
+}
+
+// ---- map filtering: the host twin of the device kernel (csrc/msfm_filter.h, FilterPoints) ----------------------------------------------
+// The inputs of host_extend_points without the new images: the session's CURRENT pose list, the thresholds of the triangulation that
+// made the points (max_error, min_angle), the call's own (flt_max_error, flt_min_angle) and scope_ids: the images the call is limited to
+// (n_scope == 0: every track).  points, residuals and mask are read and rewritten in place; have_mask 0: the bytes of the computed
+// tracks are created first.  Tracks [first, first + count) are computed.  counts7 (may be NULL): eligible, dropped_by_depth,
+// dropped_by_error, trimmed, regained, removed_by_views, removed_by_angle of those tracks are ADDED to it.  out_trace (may be NULL)
+// receives msfm_flt::Trace (four int32) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3: a non-finite or
+// negative threshold or n_scope < 0; 4: a scope id that is not declared or given twice.
+int host_filter_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent, const int* ids,
+                       int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses,
+                       const int* scope_ids, int n_scope, const double* cam, double max_error, double min_angle, double flt_max_error,
+                       double flt_min_angle, long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask,
+                       int have_mask, long long* counts7, int* out_trace) {
+    static_assert(sizeof(msfm_flt::Trace) == 4 * sizeof(int), "the trace is four int32");
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        rank_of[(size_t)ids[k]] = k;
+    }
+    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
+    }
+    if (!msfm_pose::finite(flt_max_error) || !msfm_pose::finite(flt_min_angle) || !(flt_max_error >= 0.0) || !(flt_min_angle >= 0.0) ||
+        n_scope < 0)
+        return 3;
+    std::vector<uint8_t> scope((size_t)std::max(n_images, 1), 0);
+    for (int k = 0; k < n_scope; ++k) {
+        const int r = (scope_ids[k] >= 0 && scope_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)scope_ids[k]] : -1;
+        if (r < 0 || scope[(size_t)r]) return 4;
+        scope[(size_t)r] = 1;
+    }
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    msfm_flt::Counts fc = {0, 0, 0, 0, 0, 0, 0};
+    msfm_flt::FilterPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(), kxy,
+                           table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, c, msfm_tri::Params{max_error, min_angle, 2, 0},
+                           msfm_ref::Verdict{flt_max_error, flt_min_angle}, have_mask != 0, points, residuals, mask, &fc,
+                           reinterpret_cast<msfm_flt::Trace*>(out_trace));
+    if (counts7) {
+        const long long v[7] = {fc.eligible, fc.dropped_by_depth, fc.dropped_by_error, fc.trimmed, fc.regained, fc.removed_by_views,
+                                fc.removed_by_angle};
         for (int k = 0; k < 7; ++k) counts7[k] += v[k];
     }
     return 0;

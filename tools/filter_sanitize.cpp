@@ -1,0 +1,132 @@
+// A stand-alone driver of the map filtering's host twin (csrc/msfm_filter.h, FilterPoints) for sanitizer builds: a generated ring job of
+// 12 images -- 150 tracks of 2 .. 12 views, every fifth with one observation moved by 40 px, some tracks inconsistent, image ids 3 i + 1
+// with the ranks in ANOTHER order than the ids -- triangulated under a loose (60 px, 1 degree) session by the plain and by the robust
+// twin, then filtered at (3 px, 2 degrees): without a scope list, with one (two images), with an EMPTY one (every track, as the C entry
+// point reads n_images == 0), and each time a second, idempotent call.  The pose table and the scope have exactly one entry per rank,
+// records, residuals and bytes exactly one per track / observation: an index by image id or list position where the rank is meant, or
+// past a track's own slots, runs off the end.  Prints the counters; exits 1 if nothing was trimmed or removed, if an untouched or
+// ineligible track changed, if a removed record has another shape than the header states, or if the second call changed a byte.
+//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
+//       tools/filter_sanitize.cpp -o filter_sanitize && ./filter_sanitize
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <random>
+#include <vector>
+
+#include "../monocularsfm_amd/csrc/msfm_filter.h"
+
+int main() {
+    const int n_img = 12, n_tr = 150;
+    const msfm_emat::Camera cam{2500.0, 2400.0, 1536.0, 1152.0, -0.1, 0.02, 1e-3, -5e-4};
+    const msfm_tri::Params prm = {60.0, 1.0, 2, 0};
+    const msfm_ref::Verdict flt = {3.0, 2.0};
+    std::mt19937_64 rng(7);
+    std::uniform_real_distribution<double> box(-1.0, 1.0);
+    std::normal_distribution<double> noise(0.0, 1.0);
+    std::vector<msfm_pose_rt> truth((size_t)n_img);
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1), rank((size_t)n_img);
+    for (int i = 0; i < n_img; ++i) {
+        const double th = 2.0 * 3.14159265358979323846 * i / 300.0;
+        msfm_pose_rt p = {};
+        p.valid = 1;
+        const double z[3] = {-std::sin(th), 0.0, std::cos(th)}, x[3] = {z[2], 0.0, -z[0]};
+        const double R[9] = {x[0], x[1], x[2], 0.0, 1.0, 0.0, z[0], z[1], z[2]};
+        for (int k = 0; k < 9; ++k) p.R[k] = R[k];
+        p.t[2] = 6.5;
+        truth[(size_t)i] = p;
+        rank[(size_t)i] = (5 * i + 3) % n_img;   // (5 and 12 are coprime: a permutation)
+        rank_of[(size_t)(3 * i + 1)] = rank[(size_t)i];
+    }
+    std::vector<std::vector<float>> kxy((size_t)n_img, std::vector<float>((size_t)(2 * n_tr), 0.f));   // by rank
+    std::vector<int64_t> offsets{0};
+    std::vector<int32_t> img, idx;
+    std::vector<uint8_t> cons;
+    for (int j = 0; j < n_tr; ++j) {
+        const int len = 2 + j % (n_img - 1), first = j % (n_img - len + 1);   // track j runs through the images first .. first + len - 1
+        const double X[3] = {box(rng), box(rng), box(rng)};
+        for (int i = first; i < first + len; ++i) {
+            const msfm_pose_rt& p = truth[(size_t)i];
+            const double Y0 = p.R[0] * X[0] + p.R[1] * X[1] + p.R[2] * X[2] + p.t[0], Y1 = p.R[3] * X[0] + p.R[4] * X[1] + p.R[5] * X[2] + p.t[1],
+                         Y2 = p.R[6] * X[0] + p.R[7] * X[1] + p.R[8] * X[2] + p.t[2];
+            std::vector<float>& k = kxy[(size_t)rank[(size_t)i]];
+            k[(size_t)(2 * j)] = (float)(cam.fx * Y0 / Y2 + cam.cx + noise(rng));
+            k[(size_t)(2 * j + 1)] = (float)(cam.fy * Y1 / Y2 + cam.cy + noise(rng) + ((j % 5 == 0 && i == first + (j / 5) % len) ? 40.0 : 0.0));
+            img.push_back(3 * i + 1);
+            idx.push_back(j);
+        }
+        offsets.push_back((int64_t)img.size());
+        cons.push_back(j % 11 != 5);
+    }
+    std::vector<const float*> ptr;
+    for (auto& k : kxy) ptr.push_back(k.data());
+    std::vector<msfm_tri::Pose> table((size_t)n_img);
+    for (int i = 0; i < n_img - 1; ++i) msfm_tri::prepare_pose(truth[(size_t)i], &table[(size_t)rank[(size_t)i]]);
+    const msfm_pose_rt none = {};
+    msfm_tri::prepare_pose(none, &table[(size_t)rank[(size_t)(n_img - 1)]]);   // the last image has no pose: its elements are not USED
+    const std::vector<std::vector<int>> scopes = {{-1}, {4, 7}, {}};   // {-1}: no list at all
+    long long trimmed = 0, removed = 0;
+    bool bad = false;
+    for (int robust = 0; robust < 2; ++robust)
+        for (const auto& listed : scopes) {
+            std::vector<msfm_point3d> pts((size_t)n_tr);
+            std::vector<double> res(img.size());
+            std::vector<uint8_t> mask(img.size());
+            if (robust) {
+                msfm_tri::RobustCounts c = {0, 0, 0, 0};
+                msfm_tri::TriangulateTracksRobust(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr.data(), table.data(),
+                                                  cam, msfm_tri::RobustParams{prm.max_error, prm.min_angle, prm.min_views, 64}, pts.data(), res.data(),
+                                                  mask.data(), &c);
+            } else {
+                msfm_tri::TriangulateTracks(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr.data(), table.data(), cam,
+                                            prm, pts.data(), res.data());
+            }
+            std::vector<uint8_t> scope((size_t)n_img, 0);   // one byte per rank
+            bool any = false;
+            for (int i : listed)
+                if (i >= 0) {
+                    scope[(size_t)rank[(size_t)i]] = 1;
+                    any = true;
+                }
+            bool have_mask = robust != 0;
+            for (int pass = 0; pass < 2; ++pass) {
+                const std::vector<msfm_point3d> p0 = pts;
+                const std::vector<double> r0 = res;
+                const std::vector<uint8_t> m0 = mask;
+                std::vector<msfm_flt::Trace> trace((size_t)n_tr);
+                msfm_flt::Counts c = {0, 0, 0, 0, 0, 0, 0};
+                msfm_flt::FilterPoints(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr.data(), table.data(), n_img,
+                                       any ? scope.data() : nullptr, cam, prm, flt, have_mask, pts.data(), res.data(), mask.data(), &c, trace.data());
+                for (int t = 0; t < n_tr; ++t) {
+                    const size_t b = (size_t)offsets[(size_t)t], n = (size_t)offsets[(size_t)t + 1] - b;
+                    const int kind = trace[(size_t)t].kind;
+                    if (kind == msfm_flt::KIND_NOT_ELIGIBLE || kind == msfm_flt::KIND_UNTOUCHED) {
+                        bad = bad || std::memcmp(&pts[(size_t)t], &p0[(size_t)t], sizeof(msfm_point3d)) || std::memcmp(&res[b], &r0[b], n * sizeof(double)) ||
+                              (have_mask && std::memcmp(&mask[b], &m0[b], n));
+                    } else if (kind == msfm_flt::KIND_TRIMMED) {
+                        bad = bad || std::memcmp(pts[(size_t)t].X, p0[(size_t)t].X, sizeof(double) * 3) || pts[(size_t)t].n_views != trace[(size_t)t].kept ||
+                              !(pts[(size_t)t].status & MSFM_TRI_FILTERED);
+                    } else {
+                        msfm_point3d blank;
+                        std::memset(&blank, 0, sizeof(blank));
+                        blank.status = MSFM_TRI_ATTEMPTED | MSFM_TRI_FILTERED;
+                        bad = bad || std::memcmp(&pts[(size_t)t], &blank, sizeof(blank));
+                        for (size_t k = 0; k < n; ++k) bad = bad || res[b + k] != -1.0 || mask[b + k] != 0;
+                    }
+                }
+                std::printf("robust %d scope %zu pass %d: eligible %lld dropped %lld + %lld trimmed %lld regained %lld removed %lld + %lld\n", robust,
+                            any ? listed.size() : 0, pass, c.eligible, c.dropped_by_depth, c.dropped_by_error, c.trimmed, c.regained,
+                            c.removed_by_views, c.removed_by_angle);
+                if (pass == 1)   // the second call: not one byte, nothing counted but the eligible tracks
+                    bad = bad || std::memcmp(pts.data(), p0.data(), pts.size() * sizeof(msfm_point3d)) ||
+                          std::memcmp(res.data(), r0.data(), res.size() * sizeof(double)) || std::memcmp(mask.data(), m0.data(), mask.size()) ||
+                          c.dropped_by_depth + c.dropped_by_error + c.trimmed + c.regained + c.removed_by_views + c.removed_by_angle != 0;
+                else {
+                    trimmed += c.trimmed;
+                    removed += c.removed_by_views + c.removed_by_angle;
+                }
+                have_mask = true;
+            }
+        }
+    return trimmed > 0 && removed > 0 && !bad ? 0 : 1;
+}
