@@ -8,7 +8,8 @@ struct Batch {
     std::vector<PfPair> pf;
     std::vector<int> id1, id2;       // store slots of the pairs' images
     std::vector<int> item_base;      // per pair: index of its first work item in the linear list (-1: none on this path)
-    size_t n_items = 0, items_per_xcd = 0;   // length of the XCD-interleaved list (a multiple of 8), items per XCD chunk
+    size_t n_items = 0, items_per_xcd = 0;   // length of the XCD-interleaved list (a multiple of 8), items of the longest XCD chunk
+    MsfmItemChunks chunks = {};              // where the linear list is cut into the XCDs' chunks
     long long rp_elems = 0, cp_elems = 0, kf_elems = 0, kr_elems = 0, out_elems = 0, cand_elems = 0;
     int max_npad = 0;
     int64_t desc_pairs = 0;
@@ -21,10 +22,13 @@ struct Batch {
 
 // Work items of the pairs whose `path` matches: only their NUMBERING is made on the host -- per pair the index of its
 // first item in the linear list -- the list itself (85 000 items of 32 B for the bench job) is written by
-// build_items_kernel from the pair descriptors.  Items of one pair are contiguous; the linear list is cut into 8 chunks,
-// one per XCD (workgroup b runs on XCD b % 8): linear item k sits at position (k % per) * 8 + k / per.
-// (`only`: a subset of the pairs -- the list of one route of a mixed sub-batch -- into the given outputs instead of the batch's own)
-void build_items(Batch& b, int path, const std::vector<char>* only = nullptr, std::vector<int>* base_out = nullptr, size_t* per_out = nullptr) {
+// build_items_kernel from the pair descriptors.  Items of one pair are contiguous; the linear list is cut into 8 contiguous chunks
+// of nearly equal COST, one per XCD (workgroup b runs on XCD b % 8; msfm_item_chunks, msfm_hostutil.h): item k of chunk x sits at
+// position (k - start[x]) * 8 + x, and the list is 8 x the longest chunk long (the shorter ones end in padding items).
+// (`only`: a subset of the pairs -- the list of one route of a mixed sub-batch -- into the given outputs instead of the batch's own;
+// `idle`: pairs of the list that this list's sweep skips -- the pairs without twins in the twins' sweep -- cost next to nothing)
+void build_items(Batch& b, int path, const std::vector<char>* only = nullptr, std::vector<int>* base_out = nullptr,
+                 MsfmItemChunks* chunks_out = nullptr, const std::vector<char>* idle = nullptr) {
     // Pairs in the order of their STREAMED image (id2): the 32 workgroups of an XCD walk 32 consecutive items of their
     // chunk at a time, and those then stream the same B image -- one image (1.4 MB at 5000 rows) stays in the XCD's 4 MB
     // L2 while ~30 workgroups read it, instead of three or four images evicting one another (pair order = id1-major:
@@ -36,24 +40,42 @@ void build_items(Batch& b, int path, const std::vector<char>* only = nullptr, st
     std::vector<int>& base = base_out ? *base_out : b.item_base;
     base.assign(b.pairs.size(), -1);
     long long n = 0;
+    std::vector<MsfmItemRun> runs;
+    runs.reserve(2 * order.size());
+    // the sweeps' blocks: 512 A rows in 16 waves of 32 (integer kernel) or 8 of 64 (fp16 kernel) -- per SIMD the same share of a block;
+    // the brute-force kernel's items (path 0) count alike whatever their size: equal chunk lengths, as before
+    const int wave_rows = kPfWgRows / 16, waves = 16;
     for (size_t q = 0; q < order.size(); ++q) {
         const size_t p = (size_t)order[q];
         const PairDesc& pd = b.pairs[p];
         if (!pd.valid || pd.path != path) continue;
         if (only && !(*only)[p]) continue;
         base[p] = (int)n;
-        n += (long long)pd.ranges * (path == 1 ? pd.a_blocks256 : pd.a_blocks);
+        const int nab = path == 1 ? pd.a_blocks256 : pd.a_blocks;
+        n += (long long)pd.ranges * nab;
+        if (path != 1 || (idle && (*idle)[p])) {
+            runs.push_back(MsfmItemRun{(long long)pd.ranges * nab, path != 1 ? 1 : msfm_item_cost(0, 0, wave_rows, waves)});
+            continue;
+        }
+        const int last_rows = pd.n1 - (nab - 1) * kPfWgRows;   // (<= 0: the padded allocation holds a block without a real row)
+        for (int r = 0; r < pd.ranges; ++r) {
+            const int tiles = 2 * (int)((long long)pd.b_tiles * (r + 1) / pd.ranges - (long long)pd.b_tiles * r / pd.ranges);
+            if (nab > 1) runs.push_back(MsfmItemRun{nab - 1, msfm_item_cost(tiles, kPfWgRows, wave_rows, waves)});
+            runs.push_back(MsfmItemRun{1, msfm_item_cost(tiles, last_rows, wave_rows, waves)});
+        }
     }
-    if (per_out) {
-        *per_out = (size_t)((n + 7) / 8);
+    const MsfmItemChunks chunks = msfm_item_chunks(runs);
+    if (chunks_out) {
+        *chunks_out = chunks;
         return;
     }
-    b.items_per_xcd = (size_t)((n + 7) / 8);
+    b.chunks = chunks;
+    b.items_per_xcd = (size_t)chunks.longest();
     b.n_items = b.items_per_xcd * 8;
 }
 
 // one workgroup per pair: its items, in the order (range, A block), at their XCD-interleaved positions
-__global__ void build_items_kernel(const PairDesc* __restrict__ pairs, const int* __restrict__ item_base, int path, int per,
+__global__ void build_items_kernel(const PairDesc* __restrict__ pairs, const int* __restrict__ item_base, int path, MsfmItemChunks chunks,
                                    WorkItem* __restrict__ items) {
     MSFM_TAIL_PRIO();
     const int p = blockIdx.x;
@@ -69,8 +91,7 @@ __global__ void build_items_kernel(const PairDesc* __restrict__ pairs, const int
         w.bt_begin = (int)((long long)pd.b_tiles * r / pd.ranges);
         w.bt_end = (int)((long long)pd.b_tiles * (r + 1) / pd.ranges);
         w.range = r;
-        const int k = base + i;
-        items[(size_t)(k % per) * 8 + (size_t)(k / per)] = w;
+        items[msfm_item_position(chunks, base + i)] = w;
     }
 }
 
@@ -264,7 +285,8 @@ struct FillBatch {
 // The pair tables of one route of the sub-batch (slot 0: matrix-core route, 2: brute-force route) in ONE copy, the work-item list
 // cleared (pair = -1: padding item) together with `more` in ONE fill launch, the items written by build_items_kernel.
 int upload_pair_tables(msfm_ctx* ctx, Batch& b, int path, const std::vector<PfPair>* pfq, FillBatch& fills, const std::vector<PfPair>* pf16 = nullptr,
-                       const std::vector<int>* item_base16 = nullptr, size_t per16 = 0) {
+                       const std::vector<int>* item_base16 = nullptr, const MsfmItemChunks* chunks16 = nullptr) {
+    const size_t per16 = chunks16 ? (size_t)chunks16->longest() : 0;
     const size_t P = b.pairs.size();
     const int slot = path == 1 ? 0 : 2;
     UploadPlan up;
@@ -284,11 +306,11 @@ int upload_pair_tables(msfm_ctx* ctx, Batch& b, int path, const std::vector<PfPa
     HIPCHK(ctx, fills.launch(SC.stream));
     if (b.n_items == 0) return MSFM_OK;
     hipLaunchKernelGGL(build_items_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, (const PairDesc*)SC.d_pairs.as<PairDesc>(),
-                       (const int*)SC.d_item_base.as<int>(), path, (int)b.items_per_xcd, SC.d_items.as<WorkItem>());
+                       (const int*)SC.d_item_base.as<int>(), path, b.chunks, SC.d_items.as<WorkItem>());
     HIPCHK(ctx, hipGetLastError());
     if (item_base16 && per16) {   // the second route's own list: a kernel that walks the common list and skips pays ~17 us per skipped item
         hipLaunchKernelGGL(build_items_kernel, dim3((unsigned)P), dim3(64), 0, SC.stream, (const PairDesc*)SC.d_pairs.as<PairDesc>(),
-                           (const int*)SC.d_item_base16.as<int>(), path, (int)per16, SC.d_items16.as<WorkItem>());
+                           (const int*)SC.d_item_base16.as<int>(), path, *chunks16, SC.d_items16.as<WorkItem>());
         HIPCHK(ctx, hipGetLastError());
     }
     return MSFM_OK;
@@ -426,6 +448,8 @@ constexpr size_t kHsTotals = 2 * sizeof(PlanSummary), kHsOverflow = kHsTotals + 
 //   exact pinned-order S of the candidates, 64-bit atomicMin reduce, finalize
 // The launch sequence of one sub-batch on the prefilter path, stage by stage (VERDICT r05 hygiene: it was one 490-line function).
 // Everything the stages share lives in the struct; each stage only LAUNCHES -- nothing waits for the device.
+constexpr size_t kTotalsBytes = 160;   // Scratch::d_totals: totals and cursors (build_and_upload says which int is whose)
+constexpr int kTotalsSweep2 = 8, kTotalsSpans = 16, kTotalsSweep1 = 24, kTotalsSweep1b = 32;
 struct PrefilterLaunch {
     msfm_ctx* ctx;
     Batch& b;
@@ -438,7 +462,8 @@ struct PrefilterLaunch {
     long long dense_cand = 0;
     // work items and buffers (build_and_upload)
     std::vector<int> item_base16;
-    size_t per16 = 0;
+    MsfmItemChunks chunks16 = {};    // the cut of a mixed sub-batch's second list (the pairs of the fp16 first sweep)
+    size_t per16 = 0;                // ... and its longest chunk
     long long kn = 1;
     // launch state (launch_sweep1 onwards)
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
@@ -524,14 +549,19 @@ struct PrefilterLaunch {
     // ---- stage 2: work items, the buffers of sweep 1 and of the reduce, every clear in one launch, the tables in one copy
     int build_and_upload() {
         item_base16.clear();
+        chunks16 = MsfmItemChunks{};
         per16 = 0;
-        build_items(b, 1);
-        if (b.n_items == 0) return MSFM_OK;   // (nothing on this path: run() stops here)
-        if (route.kind == kRouteQ8Mixed) {   // the fp16 first sweep's own item list: the pairs without twins
+        if (route.kind == kRouteQ8Mixed) {   // the fp16 first sweep's own item list: the pairs without twins, which the twins' sweep skips
             std::vector<char> only(P, 0);
             for (size_t p = 0; p < P; ++p) only[p] = (b.pairs[p].valid && b.pf[p].use && !route.twin[p]) ? 1 : 0;
-            build_items(b, 1, &only, &item_base16, &per16);
-    }
+            build_items(b, 1, nullptr, nullptr, nullptr, &only);
+            if (b.n_items == 0) return MSFM_OK;
+            build_items(b, 1, &only, &item_base16, &chunks16);
+            per16 = (size_t)chunks16.longest();
+        } else {
+            build_items(b, 1);
+            if (b.n_items == 0) return MSFM_OK;   // (nothing on this path: run() stops here)
+        }
     kn = std::max<long long>(1, b.kf_elems + b.kr_elems);
     HIPCHK(ctx, SC.d_rp_s0.ensure(std::max<long long>(1, b.rp_elems) * 4));
     HIPCHK(ctx, SC.d_rp_s1.ensure(std::max<long long>(1, b.rp_elems) * 4));
@@ -544,17 +574,17 @@ struct PrefilterLaunch {
     HIPCHK(ctx, SC.d_second.ensure(kn * 8));
     HIPCHK(ctx, SC.d_overflow.ensure(P));
     // [0..1] candidate / overflow totals (64-bit), ints [8..15]: per-XCD item cursors of sweep 2, ints [16..23]: per-XCD span cursors
-    // of the exact re-check
-    HIPCHK(ctx, SC.d_totals.ensure(128));
+    // of the exact re-check, ints [24..31]: per-XCD item cursors of sweep 1, ints [32..39]: those of a mixed sub-batch's second sweep 1
+    HIPCHK(ctx, SC.d_totals.ensure(kTotalsBytes));
     FillBatch fills;
     if (!route.compact()) {   // (compacted sweep 2: pf_assign_kernel initialises the live slots only)
         fills.add(SC.d_best.p, (size_t)kn * 8, 0xff);
         fills.add(SC.d_second.p, (size_t)kn * 8, 0xff);
     }
-    fills.add(SC.d_totals.p, 128, 0);
+    fills.add(SC.d_totals.p, kTotalsBytes, 0);
     fills.add(SC.d_overflow.p, P, 0);   // (which pairs own an overflowed list: pf_overflow_kernel at the end of the chain)
     const int rc = upload_pair_tables(ctx, b, 1, route.q8() ? &pfq : nullptr, fills, route.kind == kRouteQ8Mixed ? &pf16 : nullptr,
-                                        route.kind == kRouteQ8Mixed ? &item_base16 : nullptr, per16);
+                                        route.kind == kRouteQ8Mixed ? &item_base16 : nullptr, route.kind == kRouteQ8Mixed ? &chunks16 : nullptr);
     if (rc != MSFM_OK) return rc;
     return MSFM_OK;
     }
@@ -581,24 +611,33 @@ struct PrefilterLaunch {
         for (Scratch& other : ctx->sc)
             if (&other != ctx->cur && other.sweep2_recorded && other.seq + 2 <= SC.seq)
                 HIPCHK(ctx, hipStreamWaitEvent(SC.stream, other.sweep2_done, 0));
+        // MSFM_WG_TRACE: the integer sweep's workgroups stamp their start and end (finish_prefilter prints the launch's drain)
+        unsigned long long* wg_end = nullptr;
+        if (ctx->wg_trace && (route.kind == kRouteI8 || route.q8())) {
+            HIPCHK(ctx, SC.d_wg_end.ensure((size_t)sweep_grid * 16));
+            wg_end = SC.d_wg_end.as<unsigned long long>();
+            SC.pf_pending.wg_trace_grid = (int)std::min<unsigned>(sweep_grid, (unsigned)b.n_items);
+        }
+        // (the list's length is a multiple of 8, so a grid cut to it still is: workgroup index mod 8 names a chunk)
+        int* cursors = SC.d_totals.as<int>() + kTotalsSweep1;
         HIPCHK(ctx, hipEventRecord(e0, SC.stream));
         if (route.kind == kRouteI8 || route.q8())
-            hipLaunchKernelGGL(sweep_i8_kernel<1>, dim3(std::min<unsigned>(sweep_grid, (unsigned)b.n_items)), dim3(kI8Threads), kI8LdsBytes, SC.stream, dp,
+            hipLaunchKernelGGL(sweep_i8_kernel<1>, dim3(std::min<unsigned>(sweep_grid, (unsigned)b.n_items)), dim3(kI8Threads), kI8LdsBytes1, SC.stream, dp,
                                route.q8() ? (const PfPair*)SC.d_pfq.as<PfPair>() : dpf,
                                SC.d_items.as<WorkItem>(), SC.d_rp_s0.as<float>(), SC.d_rp_s1.as<float>(), SC.d_cp_s0.as<float>(),
-                               (const float*)nullptr, (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)b.n_items, (int*)nullptr,
-                               (int*)nullptr);
+                               (const float*)nullptr, (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)b.n_items, cursors, b.chunks,
+                               (int*)nullptr, wg_end);
         else
             hipLaunchKernelGGL(sweep_kernel<1>, dim3(std::min<unsigned>(sweep_grid, (unsigned)b.n_items)), block, kPfLdsBytes, SC.stream, dp, dpf,
                                SC.d_items.as<WorkItem>(), SC.d_rp_s0.as<float>(), SC.d_rp_s1.as<float>(),
                                SC.d_cp_s0.as<float>(), (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                               (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)b.n_items, (int*)nullptr);
+                               (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)b.n_items, cursors, b.chunks);
         HIPCHK(ctx, hipGetLastError());
         if (route.kind == kRouteQ8Mixed && per16) {   // the pairs without twins: their own item list (the twins' sweep skipped them: not in use in ITS table)
             hipLaunchKernelGGL(sweep_kernel<1>, dim3(std::min<unsigned>(sweep_grid, (unsigned)(per16 * 8))), block, kPfLdsBytes, SC.stream, dp,
                                (const PfPair*)SC.d_pf16.as<PfPair>(), SC.d_items16.as<WorkItem>(), SC.d_rp_s0.as<float>(), SC.d_rp_s1.as<float>(),
                                SC.d_cp_s0.as<float>(), (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                               (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)(per16 * 8), (int*)nullptr);
+                               (int2*)nullptr, (unsigned long long*)nullptr, (const int*)nullptr, (int)(per16 * 8), SC.d_totals.as<int>() + kTotalsSweep1b, chunks16);
             HIPCHK(ctx, hipGetLastError());
             SC.prof.mixed_route_sub_batches += 1;
     }
@@ -763,7 +802,7 @@ struct PrefilterLaunch {
                                (const WorkItem*)SC.d_vitems.as<WorkItem>(), SC.d_cmp_s0.as<float>(), SC.d_cmp_s1.as<float>(), (float*)nullptr,
                                (float*)nullptr, (const float*)SC.d_cmp_tu.as<float>(), (const float*)nullptr, (int2*)nullptr,
                                (unsigned long long*)nullptr, (const int*)&SC.d_summary_a.as<PlanSummary>()->n_items, 0,
-                               SC.d_totals.as<int>() + 8);
+                               SC.d_totals.as<int>() + kTotalsSweep2, MsfmItemChunks{});
             HIPCHK(ctx, hipGetLastError());
             DBGSYNC(ctx, "sweep_kernel<4>");
             HIPCHK(ctx, hipEventRecord(e5, SC.stream));
@@ -810,14 +849,14 @@ struct PrefilterLaunch {
                                (const WorkItem*)SC.d_vitems.as<WorkItem>(), (float*)nullptr, (float*)nullptr, (float*)nullptr,
                                (const float*)SC.d_cmp_tu.as<float>(), SC.d_cand.as<int2>(),
                                SC.d_cand_count.as<unsigned long long>(), (const int*)&SC.d_summary.as<PlanSummary>()->n_items, 0,
-                               SC.d_totals.as<int>() + 8, SC.d_cand_val.as<int>());
+                               SC.d_totals.as<int>() + kTotalsSweep2, MsfmItemChunks{}, SC.d_cand_val.as<int>(), (unsigned long long*)nullptr);
         else
             hipLaunchKernelGGL(sweep_kernel<3>, dim3(sweep_grid), block, kPfLdsBytes, SC.stream,
                                (const PairDesc*)SC.d_vpairs.as<PairDesc>(), (const PfPair*)SC.d_vpf.as<PfPair>(),
                                (const WorkItem*)SC.d_vitems.as<WorkItem>(), (float*)nullptr, (float*)nullptr, (float*)nullptr,
                                (float*)nullptr, (const float*)SC.d_cmp_tu.as<float>(), (const float*)nullptr, SC.d_cand.as<int2>(),
                                SC.d_cand_count.as<unsigned long long>(), (const int*)&SC.d_summary.as<PlanSummary>()->n_items, 0,
-                               SC.d_totals.as<int>() + 8);
+                               SC.d_totals.as<int>() + kTotalsSweep2, MsfmItemChunks{});
         HIPCHK(ctx, hipGetLastError());
         DBGSYNC(ctx, "sweep_kernel<3>");
         SC.prof.sweep2_launches += 1;
@@ -850,7 +889,7 @@ struct PrefilterLaunch {
         hipLaunchKernelGGL(sweep_kernel<2>, dim3(std::min<unsigned>(sweep_grid, (unsigned)b.n_items)), block, kPfLdsBytes, SC.stream, dp, dpf,
                            SC.d_items.as<WorkItem>(), (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
                            (const float*)tuv, (const float*)tuv, SC.d_cand.as<int2>(), SC.d_cand_count.as<unsigned long long>(),
-                           (const int*)nullptr, (int)b.n_items, (int*)nullptr);
+                           (const int*)nullptr, (int)b.n_items, (int*)nullptr, MsfmItemChunks{});
         HIPCHK(ctx, hipGetLastError());
         DBGSYNC(ctx, "sweep_kernel<2>");
         SC.prof.sweep2_launches += 1;
@@ -872,7 +911,7 @@ struct PrefilterLaunch {
 #define MSFM_LAUNCH_EXACT(O)                                                                                             \
         hipLaunchKernelGGL(pf_exact_candidates_kernel<O>, cgrid, dim3(kExSpan), 0, SC.stream, dp, dl, dcount,                  \
                            (const int2*)SC.d_cand.as<int2>(), SC.d_best.as<unsigned long long>(), SC.d_second.as<unsigned long long>(), \
-                           (int)n_lists, SC.d_totals.as<int>() + 16, (const int*)SC.d_cand_val.as<int>(), 0)
+                           (int)n_lists, SC.d_totals.as<int>() + kTotalsSpans, (const int*)SC.d_cand_val.as<int>(), 0)
             // byte pairs on the integer route: the sweep handed over exact integers -- no rows are read, the named order does not matter
             if (route.kind == kRouteI8) MSFM_LAUNCH_EXACT(4);
             else if (ctx->order == MSFM_ORDER_SSE4X4) MSFM_LAUNCH_EXACT(0);
@@ -946,6 +985,26 @@ int finish_prefilter(msfm_ctx* ctx, Batch& b, std::vector<char>& force_exact, bo
     SC.prof.approx_kernel_ms += ms;
     HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev_pool[pe.ev_base + 2], ctx->ev_pool[pe.ev_base + 3]));
     SC.prof.sweep2_ms += ms;
+    if (pe.wg_trace_grid > 0) {
+        // MSFM_WG_TRACE: when sweep 1's workgroups ended, relative to the launch's span on the 100 MHz wall clock (first start .. last
+        // end): 1 - mean is the share of the launch its workgroups stood idle at the end; per XCD = per workgroup index mod 8
+        std::vector<unsigned long long> st((size_t)pe.wg_trace_grid * 2);
+        HIPCHK(ctx, hipMemcpy(st.data(), SC.d_wg_end.p, st.size() * 8, hipMemcpyDeviceToHost));
+        unsigned long long t0 = ~0ull, t1 = 0;
+        for (int w = 0; w < pe.wg_trace_grid; ++w) t0 = std::min(t0, st[2 * w]), t1 = std::max(t1, st[2 * w + 1]);
+        const double span = (double)std::max<unsigned long long>(1, t1 - t0);
+        double mean = 0, xsum[8] = {}, first = 1.0;
+        int xn[8] = {};
+        for (int w = 0; w < pe.wg_trace_grid; ++w) {
+            const double e = (double)(st[2 * w + 1] - t0) / span;
+            mean += e / pe.wg_trace_grid, first = std::min(first, e), xsum[w & 7] += e, xn[w & 7] += 1;
+        }
+        float ms1 = 0.f;
+        (void)hipEventElapsedTime(&ms1, ctx->ev_pool[pe.ev_base], ctx->ev_pool[pe.ev_base + 1]);
+        std::fprintf(stderr, "[msfm wg] sweep 1: %d workgroups, events %.3f ms, span %.3f ms | end / span: mean %.4f first %.4f max 1 | per XCD mean", pe.wg_trace_grid, ms1, span * 1e-5, mean, first);
+        for (int x = 0; x < 8; ++x) std::fprintf(stderr, " %.4f", xn[x] ? xsum[x] / xn[x] : 0.0);
+        std::fprintf(stderr, "\n");
+    }
     if (std::getenv("MSFM_DEBUG_TIMING") && pe.compact) {
         PlanSummary d;
         std::memcpy(&d, hs, sizeof(PlanSummary));

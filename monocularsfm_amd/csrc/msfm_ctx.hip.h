@@ -548,6 +548,7 @@ struct PfPending {                // what the end-of-batch synchronisation has t
     int compact_pairs = 0;
     long long dense_swept = 0;
     size_t ev_base = 0;
+    int wg_trace_grid = 0;            // workgroups of the sweep-1 launch that stamped Scratch::d_wg_end (0: none did)
 };
 
 struct Scratch {
@@ -571,6 +572,7 @@ struct Scratch {
     DevBuf d_tu, d_tv, d_cand, d_cand_count, d_best, d_second;
     DevBuf d_cmp_tu, d_live_idx, d_row_pair, d_row_src, d_vpairs, d_vpf, d_vitems, d_lists, d_items16;
     DevBuf d_cmp_s0, d_cmp_s1, d_summary_a;   // route Q: sweep 1' row results, summary of plan A
+    DevBuf d_wg_end;                          // MSFM_WG_TRACE: (start, end) clock of every sweep-1 workgroup
     DevBuf d_cand_val, d_cmp_n2;              // integer route: the candidates' accumulators (parallel to d_cand), n' per compacted row
     // device-side plan of the compacted sweep 2 (msfm_plan.hip.h)
     DevBuf d_colmask, d_gtot, d_grow0, d_cnt, d_mrow, d_summary, d_overflow, d_totals;
@@ -603,7 +605,7 @@ struct Scratch {
                           &d_vpairs, &d_vpf, &d_vitems, &d_lists, &d_colmask, &d_gtot, &d_grow0, &d_cnt, &d_mrow, &d_summary, &d_overflow,
                           &d_totals, &d_vf_pairs,
                           &d_vf_x1, &d_vf_y1, &d_vf_x2, &d_vf_y2, &d_vf_hyp, &d_vf_best_it, &d_vf_best_count, &d_vf_flags, &d_st2_qt,
-                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_tv_records, &d_tv_idx, &d_tv_angles, &d_tv_best_it, &d_tk_pairs, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2};
+                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_tv_records, &d_tv_idx, &d_tv_angles, &d_tv_best_it, &d_tk_pairs, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2, &d_wg_end};
         for (DevBuf* b : bufs) fn(*b, arg);
     }
     long long device_bytes() {
@@ -737,6 +739,7 @@ struct msfm_ctx {
     long long issue_seq = 0;          // sub-batches issued so far
     double pipeline_taper = kDefaultTaper;   // size of a call's last part relative to the average part (MSFM_PIPELINE_TAPER; 1: equal parts)
     int in_flight = kInFlight;        // scratch sets used (MSFM_IN_FLIGHT=1 at msfm_create: no sub-batch overlap, for A/B measurements)
+    bool wg_trace = false;            // -DMSFM_WG_TRACE build with MSFM_WG_TRACE=1 at msfm_create: sweep 1 stamps every workgroup's start and end (tools/item_balance.py)
     int pipeline = kDefaultPipeline;  // sub-batches a large call is cut into at least, so that tails overlap sweeps (1: off)
     int prefilter = 1;                // 0: brute force only; 1: MFMA prefilter, integer matrix cores for byte stores; 2: fp16 MFMA only
     int byte_detect = 1;              // a float upload holding only integers in [0, 255] is a byte store (MSFM_BYTE_DETECT=0: off)

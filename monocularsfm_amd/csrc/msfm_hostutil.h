@@ -53,6 +53,117 @@ inline std::vector<long long> msfm_pipeline_marks(long long total, long long n_s
     return marks;
 }
 
+// ---- The hand-out of the sweeps' work items to the 8 XCDs.  The linear item list -- pairs in the order of their
+// streamed image, a pair's items in the order (range, A block) -- is cut into 8 CONTIGUOUS chunks of nearly equal COST, one per XCD;
+// chunk x's items sit at positions (k - start[x]) * 8 + x of the device list, whose length is 8 x the longest chunk.  The workgroups
+// of an XCD take the items of its chunk in order from a cursor (sweep kernels), so a chunk's cost is what its XCD has to do.
+constexpr int kItemChunks = 8;
+struct MsfmItemChunks {                      // (a kernel argument as it is)
+    int start[kItemChunks + 1];              // chunk x = linear items start[x] .. start[x + 1] - 1; start[8] = all items
+    int items() const { return start[kItemChunks]; }
+    int longest() const {
+        int m = 0;
+        for (int x = 0; x < kItemChunks; ++x) m = start[x + 1] - start[x] > m ? start[x + 1] - start[x] : m;
+        return m;
+    }
+};
+MSFM_HD int msfm_item_chunk_of(const MsfmItemChunks& c, int k) {   // the chunk of linear item k
+    int x = 0;
+#pragma unroll
+    for (int j = 1; j < kItemChunks; ++j) x += k >= c.start[j] ? 1 : 0;
+    return x;
+}
+MSFM_HD long long msfm_item_position(const MsfmItemChunks& c, int k) {
+    const int x = msfm_item_chunk_of(c, k);
+    return (long long)(k - c.start[x]) * kItemChunks + x;
+}
+
+// Cost of one sweep-1 item, in arbitrary units (a full tile = 64): `b_tiles` 64-row tiles of the streamed image against one block of
+// `wave_rows * waves` A rows of which `rows` are real.  This is a MODEL, not a measurement: a tile's time is taken as a fixed part
+// (barrier, DMA issue, the slowest wave's wake-up: 16) plus the matrix and epilogue work of the busiest SIMD, proportional to the
+// waves of the block that hold a real row there (waves w, w + 4, ... share a SIMD; a wave without a real row skips both halves);
+// an item's own prologue and row transposition count as 2.5 full tiles.  Only the RATIO between an image's last block and a full
+// one, and between items of different tile counts, matters -- and only across XCDs: within one the cursor evens out what is left.
+constexpr int kItemCostTileFixed = 16, kItemCostTileWaves = 48, kItemCostFixed = 160;
+inline long long msfm_item_cost(int b_tiles, int rows, int wave_rows, int waves) {
+    const int active = rows <= 0 ? 0 : (rows >= wave_rows * waves ? waves : (rows + wave_rows - 1) / wave_rows);
+    const int per_simd = (active + 3) / 4, full = (waves + 3) / 4;
+    return kItemCostFixed + (long long)b_tiles * (kItemCostTileFixed + kItemCostTileWaves * per_simd / full);
+}
+
+// `count` consecutive items of the linear list, each of cost `cost` (a pair and range: its full A blocks, then its last block)
+struct MsfmItemRun { long long count, cost; };
+// The cut: boundary x is the item boundary whose cumulative cost is NEAREST to x / 8 of the total (ties: the earlier one).  Every
+// boundary is then at most half an item's cost (the most expensive one's) from its mark, so every chunk's cost is within one item's
+// cost of total / 8 and any two chunks within two; equal costs give chunk lengths that differ by at most one item.  A second step
+// (below) narrows the spread between the chunks to one item's cost where moving boundaries by single items can.  Fewer than 8
+// items leave chunks empty.
+inline MsfmItemChunks msfm_item_chunks(const std::vector<MsfmItemRun>& runs) {
+    MsfmItemChunks c = {};
+    long long total = 0, n = 0;
+    for (const MsfmItemRun& r : runs) total += (r.count > 0 ? r.count : 0) * (r.cost > 1 ? r.cost : 1), n += r.count > 0 ? r.count : 0;
+    c.start[kItemChunks] = (int)n;
+    std::size_t ri = 0;
+    long long acc = 0, idx = 0;      // cost and items before run ri
+    for (int x = 1; x < kItemChunks; ++x) {
+        const long long mark = total * x;   // in units of 1 / 8 cost: compare with 8 x a cumulative cost
+        // the run the mark falls into: the first whose end reaches it
+        while (ri < runs.size()) {
+            const long long cnt = runs[ri].count > 0 ? runs[ri].count : 0, cost = runs[ri].cost > 1 ? runs[ri].cost : 1;
+            if (kItemChunks * (acc + cnt * cost) >= mark) break;
+            acc += cnt * cost, idx += cnt, ++ri;
+        }
+        if (ri == runs.size()) { c.start[x] = (int)n; continue; }
+        const long long cnt = runs[ri].count > 0 ? runs[ri].count : 0, cost = runs[ri].cost > 1 ? runs[ri].cost : 1;
+        const long long num = mark - kItemChunks * acc, den = kItemChunks * cost;   // j items of the run: |j * den - num| smallest
+        long long j = (2 * num + den - 1) / (2 * den);
+        j = j < 0 ? 0 : (j > cnt ? cnt : j);
+        c.start[x] = (int)(idx + j);
+    }
+    // Two boundaries may err in opposite directions, which leaves two chunks up to two items' cost apart: while the most and the
+    // least expensive chunk differ by more than the most expensive item, the boundaries between them move one item towards the
+    // expensive one -- it hands an item down the row, the cheap one receives one -- as long as that narrows the spread.
+    std::vector<long long> items_end(runs.size()), cost_end(runs.size());
+    long long cmax = 0;
+    acc = 0, idx = 0;
+    for (std::size_t r = 0; r < runs.size(); ++r) {
+        const long long cnt = runs[r].count > 0 ? runs[r].count : 0, cost = runs[r].cost > 1 ? runs[r].cost : 1;
+        acc += cnt * cost, idx += cnt, items_end[r] = idx, cost_end[r] = acc;
+        if (cnt > 0 && cost > cmax) cmax = cost;
+    }
+    auto cum = [&](long long k) -> long long {   // cost of the first k items
+        std::size_t lo = 0, hi = runs.size();
+        while (lo < hi) {                        // the first run that ends at or behind item k
+            const std::size_t mid = (lo + hi) / 2;
+            if (items_end[mid] < k) lo = mid + 1; else hi = mid;
+        }
+        if (lo == runs.size()) return total;
+        const long long cost = runs[lo].cost > 1 ? runs[lo].cost : 1;
+        return cost_end[lo] - (items_end[lo] - k) * cost;
+    };
+    auto spread = [&](const MsfmItemChunks& t, int* most, int* least) -> long long {
+        long long hi = -1, lo = -1;
+        for (int x = 0; x < kItemChunks; ++x) {
+            const long long v = cum(t.start[x + 1]) - cum(t.start[x]);
+            if (hi < 0 || v > hi) hi = v, *most = x;
+            if (lo < 0 || v < lo) lo = v, *least = x;
+        }
+        return hi - lo;
+    };
+    for (int pass = 0; pass < 8 * kItemChunks; ++pass) {
+        int most = 0, least = 0;
+        const long long s = spread(c, &most, &least);
+        if (s <= cmax) break;
+        MsfmItemChunks t = c;
+        if (most < least) for (int x = most + 1; x <= least; ++x) t.start[x] -= 1;
+        else for (int x = least + 1; x <= most; ++x) t.start[x] += 1;
+        int m2 = 0, l2 = 0;
+        if (spread(t, &m2, &l2) >= s) break;
+        c = t;
+    }
+    return c;
+}
+
 // What the two-view geometry (msfm_set_two_view_geometry) adds to msfm_pair_scratch_bytes for one pair: per staged match (at most
 // n1) the kept-index slot (4 B) and the angle slot (8 B) of tv_pose_kernel, per pair its record (144 B) and the saved winner (4 B).
 inline long long msfm_pair_two_view_bytes(int n1, int n2) {

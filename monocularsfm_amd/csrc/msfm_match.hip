@@ -103,7 +103,7 @@ static int create_rest(msfm_ctx* ctx) {
         {reinterpret_cast<const void*>(dist_top2_kernel<3>), kLdsBytesIdxStash},
         {reinterpret_cast<const void*>(sweep_kernel<1>), kPfLdsBytes},       {reinterpret_cast<const void*>(sweep_kernel<2>), kPfLdsBytes},
         {reinterpret_cast<const void*>(sweep_kernel<3>), kPfLdsBytes},       {reinterpret_cast<const void*>(sweep_kernel<4>), kPfLdsBytes},
-        {reinterpret_cast<const void*>(sweep_i8_kernel<1>), kI8LdsBytes},    {reinterpret_cast<const void*>(sweep_i8_kernel<3>), kI8LdsBytes3},
+        {reinterpret_cast<const void*>(sweep_i8_kernel<1>), kI8LdsBytes1},    {reinterpret_cast<const void*>(sweep_i8_kernel<3>), kI8LdsBytes3},
     };
     for (const auto& a : attrs)
         if ((e = hipFuncSetAttribute(a.f, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes)) != hipSuccess)
@@ -173,6 +173,9 @@ int msfm_create(int device_ordinal, msfm_ctx** out_ctx) {
         if (std::atoi(e) >= 1 && std::atoi(e) <= kInFlight) ctx->in_flight = std::atoi(e);
     if (const char* e = std::getenv("MSFM_PIPELINE"))
         if (std::atoi(e) > 0) ctx->pipeline = std::min(std::atoi(e), 64);
+#ifdef MSFM_WG_TRACE   // (the diagnostic build of `make trace`)
+    if (const char* e = std::getenv("MSFM_WG_TRACE")) ctx->wg_trace = e[0] != '0';
+#endif
     if (const char* e = std::getenv("MSFM_SCRATCH_MIB"))
         if (std::atoll(e) > 0) ctx->scratch_bytes = std::atoll(e) * (1LL << 20);
     *out_ctx = ctx;

@@ -71,6 +71,78 @@ __device__ __forceinline__ void lds_barrier() {
 
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }  // folds to v_max3_f32
 
+// Which item a persistent workgroup runs next (both sweep kernels).  The list is XCD-interleaved -- position
+// c * 8 + x is item c of chunk x, and workgroup b runs on XCD b % 8 --, the grid a multiple of 8.
+//   * no cursors (dense sweep 2): a fixed stride over the list, padding items skipped;
+//   * cursors (8 ints, cleared before the launch): workgroup b starts on item b / 8 of chunk b % 8, and every further item of the
+//     chunk is handed out IN ORDER by the chunk's cursor, so the workgroups of an XCD stay on consecutive items -- one streamed
+//     image in the XCD's L2 -- however unequal the items are.  The cursor is read ONE ITEM AHEAD: one lane issues the atomic behind
+//     the item's prologue loads and parks the value in LDS (fetch_next); the wait that follows there for the A fragments and the
+//     first tiles covers the atomic's round trip, and the barrier that stands at every item boundary anyway publishes the value: no
+//     barrier and no exposed round trip per item.  The two LDS slots alternate, so the value for item n + 1 never lands on the one
+//     item n was read from.  (The value goes to LDS inside the lane's branch: carried in a register through the item it made
+//     hipcc keep the item's fragments alive around the item loop -- 29 to 67 spilled registers in every sweep kernel.)
+//   * a chunk table (sweep 1: msfm_item_chunks; all-zero = none, the list's length ends the walk): the walk stops at the chunk's real
+//     length instead of running through its padding, and a workgroup whose chunk is handed out goes on with the next chunks'
+//     cursors -- the cost model of the cut need not be exact, and no XCD waits idle for another.  Such a change of chunk costs a
+//     round trip and a barrier, at most seven times per workgroup.
+// Which workgroup runs an item is invisible in the results: every item writes its own partials.
+struct ItemWalk {
+    int* dyn_next;
+    int* s_next;      // LDS: the two alternating slots
+    int n_items, chunk, cur, par;
+    int first, tabled, fetched;   // flags: before the first item | a chunk table came with the launch | this item called fetch_next()
+    __device__ __forceinline__ int chunk_len(const MsfmItemChunks& ch) const {
+        return tabled ? ch.start[chunk + 1] - ch.start[chunk] : 0x7fffffff;   // (read from the kernel's arguments where it is needed)
+    }
+    __device__ __forceinline__ void init(int* cursors, int* lds_slots, const MsfmItemChunks& ch, int n) {
+        dyn_next = cursors, s_next = lds_slots, n_items = n;
+        chunk = (int)(blockIdx.x & 7), cur = (int)(blockIdx.x >> 3), par = 0;
+        first = 1, fetched = 0, tabled = ch.start[kItemChunks] != 0 ? 1 : 0;
+    }
+    __device__ __forceinline__ void fetch_now() const {   // one lane: the next position of the chunk, into the slot in use
+        if (threadIdx.x == 0) s_next[par] = atomicAdd(&dyn_next[chunk], 1) + (int)(gridDim.x >> 3);
+    }
+    // At an item boundary (behind the previous item's last LDS access): the next item's position in `it`, or false: nothing left.
+    // fetch_next() follows once per item that runs (a skipped item leaves without: a lane-divergent branch in front of a `continue`
+    // makes hipcc carry the item's fragments around the item loop; the next call then fetches on the spot).
+    // (The sweeps' register allocation is touchy about this state: packed into one word it cost every sweep kernel 15 to 21 vector
+    // registers, the eight chunk lengths in registers instead of read from the arguments six scalar ones -- and the integer sweep 1
+    // has none to spare: run tools/kernel_resources.py after any change here.)
+    __device__ __forceinline__ bool next(int& it, const MsfmItemChunks& ch) {
+        if (!first) lds_barrier();   // the previous item's last LDS accesses (class arrays, the parked cursor value) are done
+        if (!dyn_next) {
+            it = first ? (int)blockIdx.x : it + (int)gridDim.x;
+            first = 0;
+            return it < n_items;
+        }
+        if (!first) {
+            if (!fetched) {   // (uniform) the previous item was a skipped one: it left before its fetch_next()
+                fetch_now();
+                lds_barrier();
+            }
+            cur = __builtin_amdgcn_readfirstlane(s_next[par]);
+        }
+        first = 0, fetched = 0;
+        while (cur >= chunk_len(ch)) {   // (uniform) this chunk is handed out: on to the next one's cursor
+            chunk = (chunk + 1) & 7;
+            if (chunk == (int)(blockIdx.x & 7)) return false;   // once around: every chunk is handed out
+            par ^= 1;
+            fetch_now();
+            lds_barrier();
+            cur = __builtin_amdgcn_readfirstlane(s_next[par]);
+        }
+        it = cur * kItemChunks + chunk;
+        if (it >= n_items) return false;
+        par ^= 1;
+        return true;
+    }
+    __device__ __forceinline__ void fetch_next() {
+        if (dyn_next) fetch_now();
+        fetched = 1;
+    }
+};
+
 template <int PASS>
 __global__ __launch_bounds__(kPfThreads, 2) void sweep_kernel(
     const PairDesc* __restrict__ pairs, const PfPair* __restrict__ pf, const WorkItem* __restrict__ items,
@@ -78,7 +150,7 @@ __global__ __launch_bounds__(kPfThreads, 2) void sweep_kernel(
     const float* __restrict__ tu, const float* __restrict__ tv, int2* __restrict__ cand,
     unsigned long long* __restrict__ cand_count /* 64-bit: n1 * n2 hits of a flooded list do not fit 32 bits */,
     const int* __restrict__ n_items_dev /* item count in device memory (a plan built on the device), or null */, int n_items_host,
-    int* __restrict__ dyn_next /* 8 per-XCD cursors: items are fetched dynamically (sweep 2: unequal items), or null */) {
+    int* __restrict__ dyn_next /* 8 per-XCD item cursors, or null (ItemWalk) */, MsfmItemChunks chunks /* sweep 1: the list's cut; else all-zero */) {
     typedef const __attribute__((address_space(1))) float* gfloat_p;  // keep these loads off the FLAT path
     typedef const __attribute__((address_space(1))) h8* gh8_p;
     extern __shared__ __attribute__((aligned(16))) char pf_smem[];
@@ -90,21 +162,14 @@ __global__ __launch_bounds__(kPfThreads, 2) void sweep_kernel(
     // Persistent workgroups: one per CU (the LDS ring allows no more), striding over the item list.  The list is
     // XCD-interleaved (item i belongs to XCD i % 8) and the grid is a multiple of 8, so a workgroup keeps streaming the B
     // panels its XCD's L2 already holds.
-    // Uniform items (sweep 1) are taken in a fixed stride; the unequal items of the compacted sweep 2 (79-tile forward
-    // sweeps next to 8-tile reverse ones) are fetched from a per-XCD cursor, longest first.
+    // The items are handed out by per-XCD cursors (ItemWalk above): sweep 1's in the order of the streamed image, the unequal
+    // items of the compacted sweep 2 (79-tile forward sweeps next to 8-tile reverse ones) longest first.
     const int n_items = n_items_dev ? *n_items_dev : n_items_host;
-    __shared__ int s_next_item;
-    bool first_item = true;
+    __shared__ int s_next_item[2];
+    ItemWalk walk;
+    walk.init(dyn_next, s_next_item, chunks, n_items);
 #pragma unroll 1
-    for (int it = blockIdx.x;; it += gridDim.x) {
-    if (!first_item || dyn_next) lds_barrier();   // the previous item's last LDS accesses (class arrays, the cursor) are done
-    first_item = false;
-    if (dyn_next) {
-        if (threadIdx.x == 0) s_next_item = atomicAdd(&dyn_next[blockIdx.x & 7], 1);
-        lds_barrier();
-        it = s_next_item * 8 + (int)(blockIdx.x & 7);
-    }
-    if (it >= n_items) break;
+    for (int it = 0; walk.next(it, chunks);) {
     const WorkItem item = items[it];
     if (item.pair < 0) continue;
     const PfPair pp = pf[item.pair];
@@ -219,6 +284,7 @@ __global__ __launch_bounds__(kPfThreads, 2) void sweep_kernel(
         for (int ks = 0; ks < 8; ++ks) asm volatile("" ::"v"(af[rb][ks]));
         asm volatile("" ::"v"(ae[rb]));
     }
+    walk.fetch_next();   // (its round trip hides in the wait for the loads above)
     wait_vmcnt<0>();  // prologue loads and the first three DMA groups are done: counted waits start clean
 
     // sweep 2: wave-private candidate buffer in LDS

@@ -51,9 +51,11 @@ constexpr int kI8WaveRows = kPfWgRows / kI8Waves;       // 32: one MFMA row bloc
 // Ring of EIGHT 11-KiB tiles, DMA seven tiles ahead: a tile takes ~1 us here, so the three-tile lead of the fp16
 // kernel (1.6 us per tile there) would leave little more than an L2 miss.
 constexpr int kI8Ring = 8;
-// ring | per-wave candidate buffers (q, t) (PASS 3) | column class maxima (PASS 1) | per-wave accumulator values of the candidates (PASS 3)
-constexpr int kI8LdsBytes = kI8Ring * kI8TileBytes + kI8Waves * kPfCandBuf * 8 + 4 * kPfBT * kPfColClasses * 4;
-constexpr int kI8LdsBytes3 = kI8LdsBytes + kI8Waves * kPfCandBuf * 4;
+// PASS 1: ring | column class maxima (the row transposition at an item's end uses the ring): 92 KiB, the rest of the CU's LDS stays free
+// for what runs beside the sweep.  PASS 3: ring | per-wave candidate buffers (q, t) | (unused) | per-wave accumulator values of the candidates
+constexpr int kI8ColBytes = 4 * kPfBT * kPfColClasses * 4;
+constexpr int kI8LdsBytes1 = kI8Ring * kI8TileBytes + kI8ColBytes;
+constexpr int kI8LdsBytes3 = kI8Ring * kI8TileBytes + kI8Waves * kPfCandBuf * 8 + kI8ColBytes + kI8Waves * kPfCandBuf * 4;
 static_assert(kI8WaveRows == 32, "one 32-row block per wave");
 constexpr int kI8Pad = -(1 << 29);                      // "-inf" of a padding row / column (two of them still fit an int32)
 constexpr int kI8PadTest = -(1 << 27);                  // anything below is padding
@@ -77,29 +79,27 @@ __global__ __launch_bounds__(kI8Threads) void sweep_i8_kernel(
     const PairDesc* __restrict__ pairs, const PfPair* __restrict__ pf, const WorkItem* __restrict__ items,
     float* __restrict__ rp_s0, float* __restrict__ rp_s1, float* __restrict__ cp_s0, const float* __restrict__ tu,
     int2* __restrict__ cand, unsigned long long* __restrict__ cand_count, const int* __restrict__ n_items_dev, int n_items_host,
-    int* __restrict__ dyn_next, int* __restrict__ cand_val /* PASS 3: the accumulator of every candidate, parallel to `cand` */) {
+    int* __restrict__ dyn_next /* 8 per-XCD item cursors, or null (ItemWalk) */, MsfmItemChunks chunks /* sweep 1: the list's cut; else all-zero */,
+    int* __restrict__ cand_val /* PASS 3: the accumulator of every candidate, parallel to `cand` */,
+    unsigned long long* __restrict__ wg_end /* -DMSFM_WG_TRACE builds: (start, end) clock per workgroup, or null */) {
     static_assert(PASS == 1 || PASS == 3, "sweep 1 and the compacted sweep 2");
     typedef const __attribute__((address_space(1))) float* gfloat_p;
     typedef const __attribute__((address_space(1))) i4v* gi4_p;
     extern __shared__ __attribute__((aligned(16))) char pf_smem[];
     char* sB = pf_smem;                                                   // [ring slot][64 rows x 176 B]
     char* sCand = pf_smem + kI8Ring * kI8TileBytes;                       // [wave][kPfCandBuf] int2 (PASS 3)
-    int* sCol = reinterpret_cast<int*>(sCand + kI8Waves * kPfCandBuf * 8);  // [4 tiles][4 classes][64 columns] (PASS 1)
-    int* sVal = sCol + 4 * kPfBT * kPfColClasses;                           // [wave][kPfCandBuf] (PASS 3; only kI8LdsBytes3 launches have it)
+    int* sCol = reinterpret_cast<int*>(pf_smem + kI8Ring * kI8TileBytes);   // [4 tiles][4 classes][64 columns] (PASS 1: in the candidates' place)
+    int* sVal = reinterpret_cast<int*>(sCand + kI8Waves * kPfCandBuf * 8 + kI8ColBytes);   // [wave][kPfCandBuf] (PASS 3)
 
     const int n_items = n_items_dev ? *n_items_dev : n_items_host;
-    __shared__ int s_next_item;
-    bool first_item = true;
+#ifdef MSFM_WG_TRACE   // (diagnostic build only, `make trace`: the library that ships reads no clock)
+    if (wg_end && threadIdx.x == 0) wg_end[2 * blockIdx.x] = wall_clock64();
+#endif
+    __shared__ int s_next_item[2];
+    ItemWalk walk;   // (msfm_sweep.hip.h)
+    walk.init(dyn_next, s_next_item, chunks, n_items);
 #pragma unroll 1
-    for (int it = blockIdx.x;; it += gridDim.x) {
-    if (!first_item || dyn_next) lds_barrier();
-    first_item = false;
-    if (dyn_next) {
-        if (threadIdx.x == 0) s_next_item = atomicAdd(&dyn_next[blockIdx.x & 7], 1);
-        lds_barrier();
-        it = s_next_item * 8 + (int)(blockIdx.x & 7);
-    }
-    if (it >= n_items) break;
+    for (int it = 0; walk.next(it, chunks);) {
     const WorkItem item = items[it];
     if (item.pair < 0) continue;
     const PfPair pp = pf[item.pair];
@@ -199,6 +199,7 @@ __global__ __launch_bounds__(kI8Threads) void sweep_i8_kernel(
     for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(af[ks]));
     asm volatile("" ::"v"(a_digit));
     if (PASS == 3) asm volatile("" ::"v"(rowc));
+    walk.fetch_next();   // (its round trip hides in the wait for the loads above)
     wait_vmcnt<0>();
 
     int2* cbuf = reinterpret_cast<int2*>(sCand) + wave * kPfCandBuf;
@@ -444,4 +445,7 @@ __global__ __launch_bounds__(kI8Threads) void sweep_i8_kernel(
         }
     }
     }   // item loop
+#ifdef MSFM_WG_TRACE
+    if (wg_end && threadIdx.x == 0) wg_end[2 * blockIdx.x + 1] = wall_clock64();
+#endif
 }
