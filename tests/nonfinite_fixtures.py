@@ -13,6 +13,7 @@ triangulation (one posed view), created by the extension from the views 0, 1, 2,
 import numpy as np
 
 import extend_twin as etw
+import filter_twin as ftw
 import refine_points_twin as rtw
 import refine_poses_twin as ptw
 import registration_twin as regtw
@@ -26,6 +27,18 @@ CAM = (2500.0, 2500.0, 1536.0, 1152.0)
 CAM_D = CAM + (-0.1, 0.02, 1e-3, -5e-4)
 THR = (2.0, 1.5, 2)                  # the reference's Triangulator::Parameters
 GROSS = np.float32(1e6)              # the twin scene's coordinate
+# msfm_filter_points at the end of the chain: under the session's own thresholds it drops nothing there (every track untouched: the
+# no-op path alone), so the filter steps pass explicit (max_error px, min_angle degrees) -- the three pairs that reach its routes on
+# the 0.3 px ring jobs (tests/test_nonfinite_reference.py asserts that they do)
+FILTER_MIX = (0.45, 1.5)             # a mix of untouched and trimmed tracks
+FILTER_ANGLE = (2.0, 12.0)           # every track removed by angle, nothing dropped
+FILTER_VIEWS = (0.3, 20.0)           # removed by views and by angle
+# ... and a fourth.  Under FILTER_MIX the five bad tracks of the lane placement under CAM end untouched (3) or removed by views (2):
+# none is TRIMMED, the one route that rewrites a bad observation's slot.  0.6 px is two sigma of the ring jobs' 0.3 px of noise per
+# axis: an error passes it with probability 1 - exp(-2) = 0.86, a track with five fitting observations loses at least one with
+# probability 0.5 and four of them with 1e-3 -- about half the tracks are trimmed, hardly any is removed.
+FILTER_TRIM = (0.6, 1.5)
+FILTER_PAIRS = (("mix", FILTER_MIX), ("angle", FILTER_ANGLE), ("views", FILTER_VIEWS), ("trim", FILTER_TRIM))
 
 # float32 bit patterns
 VALUES = (("nan", 0x7fc00000), ("nan_signed", 0xffc00000), ("nan_payload", 0x7fc00001), ("inf", 0x7f800000), ("minus_inf", 0xff800000),
@@ -165,8 +178,12 @@ POSE_PARAMS = (10, 1e-6, 15)
 def chain(host, sc, cam=CAM, thr=THR, H=8, mh=8, robust=True, trace=True):
     """The reconstruction stage's twins over one scene, each fed the previous one's outputs: triangulation (plain, or robust with H
     hypotheses), point refinement, registration of REG, extension by NEW + REG's registered pose with max_hypotheses mh, pose refinement
-    (image OLD[0] fixed), point refinement again.  -> dict step -> that twin's outputs (tuples as the twins return them; None for a step
-    that did not run: REG is absent from scenes with fewer than 8 images)"""
+    (image OLD[0] fixed), point refinement again; then the filter once per pair of FILTER_PAIRS, each from that same state, and a
+    point refinement behind the first of them.  On the plain session (robust=False) the filter also runs behind the first point
+    refinement, under the session's thresholds and without inlier bytes (it creates them) -- a side step: the steps after it start from
+    the refinement's outputs, as they always did.  -> dict step -> that twin's outputs (tuples as the twins return them; "filter" is a
+    dict by pair name; None for a step that did not run: REG is absent from scenes with fewer than 8 images, "filter0" from the
+    robust session)"""
     ids, kps, tracks = sc.ids, sc.kps, sc.tracks
     first = sc.some([p for p in OLD if p < len(ids)])
     out = {}
@@ -179,6 +196,7 @@ def chain(host, sc, cam=CAM, thr=THR, H=8, mh=8, robust=True, trace=True):
         (pts, res), mask = out["plain"], None
     out["refine1"] = rtw.run(host, tracks, ids, kps, first, cam, pts, res, mask, thr[:2], trace=trace)
     pts, res = out["refine1"][:2]
+    out["filter0"] = None if robust else ftw.run(host, tracks, ids, kps, first, cam, pts, res, None, thr[:2], trace=True)
     new = sc.some([p for p in NEW if p < len(ids)])
     out["register"] = None
     if REG < len(ids):
@@ -190,11 +208,15 @@ def chain(host, sc, cam=CAM, thr=THR, H=8, mh=8, robust=True, trace=True):
     out["poses"] = ptw.run(host, tracks, ids, kps, lst, cam, pts, res, mask, thr[:2], POSE_PARAMS, fixed, trace=trace)
     pts, res, lst = out["poses"][:3]
     out["refine2"] = rtw.run(host, tracks, ids, kps, lst, cam, pts, res, mask, thr[:2], trace=trace)
+    pts, res = out["refine2"][:2]
+    out["filter"] = {name: ftw.run(host, tracks, ids, kps, lst, cam, pts, res, mask, thr[:2], pair, trace=True) for name, pair in FILTER_PAIRS}
+    pts, res, mask = out["filter"]["mix"][:3]
+    out["refine3"] = rtw.run(host, tracks, ids, kps, lst, cam, pts, res, mask, thr[:2], trace=trace)
     return out
 
 
 def load_host():
-    L = etw.load_host()
+    L = ftw.load_host()                  # (etw.load_host()'s exports and host_filter_points)
     R = regtw.load_host()
     for name in ("host_register_counts", "host_register_images", "host_register_sample3", "host_p3p", "host_register_refine"):
         f = getattr(R, name)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import extend_twin as etw
+import filter_twin as ftw
 import nonfinite_fixtures as nf
 import refine_points_twin as rtw
 import refine_poses_twin as ptw
@@ -19,7 +20,7 @@ import registration_twin as regtw
 import robust_triangulation_twin as robtw
 import triangulation_twin as tw
 from monocularsfm_amd import _lib
-from test_gpu_extend_points import state
+from test_gpu_extend_points import same_state, state
 from test_gpu_robust_triangulation import open_ring
 
 pytestmark = pytest.mark.gpu
@@ -149,10 +150,38 @@ def poses_refined(ctx, host, sc, tracks, cam, what):
     return st, pts, res, rec
 
 
+def filtered(ctx, host, sc, tracks, cam, what, params=None, creates_bytes=False):
+    """one msfm_filter_points (params: the call's (max_error, min_angle), None: the session's) against FilterPoints run from the
+    device's state before the call -- records, residuals, inlier bytes and the pose list by bytes, all nine counters -- THE NaN alone,
+    and a second call that changes no byte and counts nothing.  creates_bytes: the session has no inlier bytes before the call.
+    -> (stats, points, residuals, bytes, the twin's trace)"""
+    p0, r0, m0, l0 = state(ctx)
+    assert (m0 is None) == creates_bytes, what
+    kw = {} if params is None else dict(max_error=params[0], min_angle=params[1])
+    st = ctx.filter_points(**kw)
+    pts, res, mask, lst = after = state(ctx)
+    wp, wr, wm, wc, tr = ftw.run(host, tracks, sc.ids, sc.kps, l0, cam, p0, r0, m0, nf.THR[:2], params, trace=True)
+    same_bytes(pts, wp, what)
+    same_bytes(res, wr, what)
+    assert mask is not None, what
+    same_bytes(mask, wm, what)
+    same_bytes(lst[0], l0[0], what)
+    same_bytes(lst[1], l0[1], what)
+    assert {k: st[k] for k in ftw.ALL_KEYS} == {k: wc[k] for k in ftw.ALL_KEYS}, (what, st, wc)
+    only_the_nan(res, sc.bad, what)
+    st2 = ctx.filter_points(**kw)
+    assert same_state(after, state(ctx)), what
+    assert all(st2[k] == (st[k] if k in ("succeeded", "observations_used") else 0) for k in ftw.ALL_KEYS if k != "eligible"), (what, st2)
+    return st, pts, res, mask, tr
+
+
 def chain(ctx, host, sc, cam, mh, case):
     """The calls of the stage in order on one session, each against its twin fed the device's state before it: plain triangulation and
-    a point refinement on it, robust triangulation, point refinement, registration of REG, extension by NEW and REG's registered pose
-    with max_hypotheses mh, pose refinement, point refinement.  -> dict step -> the device's outputs"""
+    a point refinement on it, the filter on that plain session (it creates the inlier bytes) and the refinement that follows it;
+    robust triangulation, point refinement, registration of REG, extension by NEW and REG's registered pose with max_hypotheses mh,
+    pose refinement, point refinement; the filter under FILTER_TRIM, then under the tighter FILTER_MIX, and a point refinement; then,
+    each behind a robust triangulation under the session's final poses (the state no filter has touched), the filter under
+    FILTER_ANGLE and under FILTER_VIEWS.  -> dict step -> the device's outputs"""
     what = (case and case[0], mh)
     tracks = open_scene(ctx, sc)
     first = sc.some([p for p in nf.OLD if p < len(sc.ids)])
@@ -162,6 +191,9 @@ def chain(ctx, host, sc, cam, mh, case):
     # both sides; under a NaN or an infinity the track has no point and the sums are finite -- tests/test_nonfinite_reference.py)
     finite = case is None or nf.non_finite(case) or case[0].startswith(("denormal", "minus_zero"))
     out["refine0"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine0",), finite_costs=finite)
+    # (the filter removes or trims every eligible bad track, the others have no point: every sum is finite behind it, whatever the value)
+    out["filter0"] = filtered(ctx, host, sc, tracks, cam, what + ("filter0",), creates_bytes=True)
+    out["refine0f"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine0f",))
     out["robust"] = triangulated(ctx, host, sc, tracks, first, cam, True, what + ("robust",))
     out["refine1"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine1",))
     new = sc.some([p for p in nf.NEW if p < len(sc.ids)])
@@ -172,6 +204,13 @@ def chain(ctx, host, sc, cam, mh, case):
     out["poses"] = poses_refined(ctx, host, sc, tracks, cam, what + ("poses",))
     # (with max_hypotheses 0 a bad 3-view track is created on the plain route: after it the sums may be +inf as after the plain call)
     out["refine2"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine2",), finite_costs=mh > 0 or finite)
+    out["filter_trim"] = filtered(ctx, host, sc, tracks, cam, what + ("trim",), nf.FILTER_TRIM)
+    out["filter_mix"] = filtered(ctx, host, sc, tracks, cam, what + ("mix",), nf.FILTER_MIX)
+    out["refine3"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine3",))
+    last = ctx.poses()
+    for name, pair in (("angle", nf.FILTER_ANGLE), ("views", nf.FILTER_VIEWS)):
+        triangulated(ctx, host, sc, tracks, last, cam, True, what + ("robust before " + name,))
+        out["filter_" + name] = filtered(ctx, host, sc, tracks, cam, what + (name,), pair)
     ctx.tracks_end()
     return out
 
@@ -180,7 +219,8 @@ def chain(ctx, host, sc, cam, mh, case):
 @pytest.mark.parametrize("place", sorted(PLACEMENTS))
 def test_the_chain_on_one_session(tctx, host, place, cam):
     """every call of the chain against its twin, with max_hypotheses 8 (the retry list runs) and 0 (ext_mask_kernel and the plain
-    route); the routes the fixture is for, on the device's own outputs"""
+    route); the routes the fixture is for, on the device's own outputs.  The filter runs five times per chain: on the plain session
+    (ext_mask_kernel as the filter launches it) and under the four pairs of nonfinite_fixtures.FILTER_PAIRS."""
     for n, case in enumerate(nf.drawn(seed=sorted(PLACEMENTS).index(place) * 2 + sorted(CAMS).index(cam), k=3)):
         sc = PLACEMENTS[place](case)[0]
         for mh in (8, 0):
@@ -196,6 +236,13 @@ def test_the_chain_on_one_session(tctx, host, place, cam):
                 short_bad = [t for t in sc.bad_tracks() if sc.lengths[t] == 3]
                 assert np.all(tr["kind"][short_bad] == etw.KIND_CREATE) and ext_st["retried"] == (len(short_bad) if mh else 0)
                 assert _lib.registered(out["register"][1][0]).all()
+            # the filter's routes, on the twin's traces of the device's own states
+            badt = np.zeros(len(sc.lengths), bool)
+            badt[sc.bad_tracks()] = True
+            trims = [out[k][4]["kind"] == ftw.KIND_TRIMMED for k in ("filter_trim", "filter_mix")]
+            assert (trims[0] & badt).any() or (trims[1] & badt).any(), (case[0], mh)      # a bad track's slots were rewritten
+            assert (out["filter_trim"][4]["kind"][~badt] == ftw.KIND_UNTOUCHED).any() and out["filter_mix"][0]["trimmed"] > 0
+            assert out["filter_angle"][0]["removed_by_angle"] > 0 and out["filter_views"][0]["removed_by_views"] > 0, (case[0], mh)
 
 
 @pytest.mark.parametrize("T", [257, 256, 255, 65, 64, 63, 1])
@@ -210,8 +257,9 @@ def test_track_count_prefixes_of_the_lane_placement(tctx, host, T):
 def test_the_clean_neighbours(tctx, host):
     """In the lane placement every clean track's record, residuals and inlier bytes equal, byte for byte, those of the same job
     without any bad value: a poisoned lane leaks through no shuffle, ballot or shared list.  Through the triangulations, the point
-    refinements and the extension by the NEW images under their true poses (the registration and the pose refinement fit over all
-    tracks of an image: there a bad observation changes its clean neighbours by definition)."""
+    refinements, the extension by the NEW images under their true poses and the filter under FILTER_MIX, whose nine counters' wave
+    reduction is the only exchange between lanes (the registration and the pose refinement fit over all tracks of an image: there a
+    bad observation changes its clean neighbours by definition)."""
     def run(sc, case):
         tracks = open_scene(tctx, sc)
         first, new = sc.some(nf.OLD), sc.some(nf.NEW)
@@ -220,6 +268,7 @@ def test_the_clean_neighbours(tctx, host):
         out.append(triangulated(tctx, host, sc, tracks, first, nf.CAM, True, "robust")[1:] + (tctx.point_inliers(),))
         out.append(points_refined(tctx, host, sc, tracks, nf.CAM, "refine1")[1:])
         out.append(extended(tctx, host, sc, tracks, new, 8, nf.CAM, "extend")[1:4])
+        out.append(filtered(tctx, host, sc, tracks, nf.CAM, "filter", nf.FILTER_MIX)[1:4])
         tctx.tracks_end()
         return out
     clean_sc = nf.lanes(None)[0]
@@ -238,11 +287,15 @@ def test_the_clean_neighbours(tctx, host):
 
 def test_tile_elements(tctx, host):
     """tracks of 2, 3, 64, 65 and 130 views with the bad observation at element 0, 63, 64 and last: the 64-observation LDS tiles of
-    trr_retry_kernel, enumerated (H 64 covers the 3-view tracks' pairs) and sampled hypotheses; then the point refinement"""
+    trr_retry_kernel, enumerated (H 64 covers the 3-view tracks' pairs) and sampled hypotheses; then the point refinement.  Before the
+    robust calls the filter runs on the plain session: flt_track_kernel's element loops over the same tracks."""
     for case in nf.drawn(seed=7, k=3):
         sc = nf.elements(case)[0]
         tracks = open_scene(tctx, sc)
         triangulated(tctx, host, sc, tracks, sc.poses, nf.CAM, False, (case[0], "plain"))
+        # the filter on the plain session, under its thresholds: the bad element at 0, 63, 64 and last of a fitting set of 2 .. 130
+        st, _, _, mask, tr = filtered(tctx, host, sc, tracks, nf.CAM, (case[0], "filter"), creates_bytes=True)
+        assert st["eligible"] >= 5 and (nf.non_finite(case) or not mask[sc.bad].all()), (case[0], st)
         for hyp in (8, 64):
             st = tctx.triangulate_tracks(nf.CAM, sc.poses, *nf.THR, robust=True, max_hypotheses=hyp)
             pts, res = tctx.points3d()
@@ -259,8 +312,8 @@ def test_tile_elements(tctx, host):
 
 def test_replacing_keypoints_after_the_triangulation(tctx, host):
     """upload_keypoints with a bad value after the robust triangulation: the records were made from clean data, the next calls read
-    poisoned data -- point refinement, registration, extension, pose refinement against their twins fed the device's state and the
-    NEW keypoints"""
+    poisoned data -- point refinement, registration, extension, the filter and a point refinement behind it against their twins fed
+    the device's state and the NEW keypoints"""
     for case in nf.drawn(seed=9, k=3):
         clean, _, _ = nf.lanes(None)
         sc = nf.lanes(case)[0]
@@ -274,6 +327,11 @@ def test_replacing_keypoints_after_the_triangulation(tctx, host):
         _, got = registered(tctx, host, sc, tracks, nf.CAM, (case[0], "register"))
         new = _lib.registered_poses(got[0], sc.some(nf.NEW))
         extended(tctx, host, sc, tracks, new, 8, nf.CAM, (case[0], "extend"))
+        # the filter drops the replaced observations that still sit in a fitting set (those of the OLD image: the extension admitted
+        # none of the others); behind it every cost sum is finite
+        st, _, _, mask, tr = filtered(tctx, host, sc, tracks, nf.CAM, (case[0], "filter"))
+        assert not mask[sc.bad].any() and st["dropped_by_depth"] + st["dropped_by_error"] >= len(nf.LANES), (case[0], st)
+        points_refined(tctx, host, sc, tracks, nf.CAM, (case[0], "refine after the filter"))
         tctx.tracks_end()
 
 

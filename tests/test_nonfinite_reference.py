@@ -18,11 +18,18 @@ WHICH PLACEMENT IS COMPARED WHICH WAY
                 other field 0, every slot -1, n_views = the posed elements (msfm_triangulate.h, "DLT").  The counters and cost sums of
                 a step that has such tracks follow them (eligible, iterations, points_reposed, the costs) and are not compared there.
 The 1e6 scene itself is anchored: test_the_gross_scene_against_the_references holds its twins to the independent numpy references
-with those modules' own comparisons, margins and tolerances."""
+with those modules' own comparisons, margins and tolerances.
+
+THE FILTER (msfm_filter_points' twin, FilterPoints) runs at the end of the chain under the three pairs of nf.FILTER_PAIRS, each from the
+state after the last point refinement -- under the session's own thresholds it drops nothing there and would only walk its no-op path
+-- and, on the plain session, behind the first point refinement under the session's thresholds, where it creates the inlier bytes
+(compare_filter, test_the_plain_session_filter).  A trimmed track goes through point_verdict in its `residuals != nullptr` mode, which
+rewrites the slot of every USED observation, the bad ones included: one more store of a NaN."""
 import numpy as np
 import pytest
 
 import extend_twin as etw
+import filter_twin as ftw
 import nonfinite_fixtures as nf
 import refine_poses_twin as ptw
 import triangulation_twin as tw
@@ -155,16 +162,82 @@ def compare(sc, case, a, b, mh, robust, canonical=True):
             assert nan_bits(sa) <= {CANONICAL}, (case[0], step, [hex(v) for v in nan_bits(sa)])
 
 
+def compare_filter(host, sc, case, cam, a, b, mh, robust, routes=True, mix_trims_bad=True):
+    """The filter steps at the end of the chain outputs `a` (the scene) against those of `b` (the twin scene), under every pair of
+    nf.FILTER_PAIRS.  FIRST FORM on every track but the second-form tracks of the last point refinement: records, inlier bytes, the
+    twin's trace and every residual slot but the bad observations' own byte for byte, the counters where no track is of the second
+    form; no inlier byte on a bad observation.  THE EXCEPTION in its own form: a second-form track (created on the plain route with
+    max_hypotheses 0) under a non-finite value is ATTEMPTED alone, so not eligible: record, slots and bytes stay bit for bit, the
+    bytes 1 on every element, the bad one included (the extension made them so); under a finite value it either has no point as well
+    and stays the same way, or has a point without ERROR_OK, is eligible and is trimmed or removed.  Everywhere: every float field of every record finite after the call, NaNs only in the bad
+    slots and only THE NaN, a second call that changes no byte and counts nothing.  With `routes`, on the robust session, the twin's
+    trace shows that the pair did what it is for (a pair that quietly reaches nothing proves nothing)."""
+    o = sc.tracks[0]
+    per_slot = np.repeat(np.arange(len(sc.lengths)), np.diff(o))
+    loose = loose_tracks("refine2", sc, a, mh, robust)
+    tight, tight_slot = ~loose, ~loose[per_slot]
+    badt = np.zeros(len(sc.lengths), bool)
+    badt[sc.bad_tracks()] = True
+    p0, r0, m0, lst = a["refine2"][0], a["refine2"][1], a["extend"][2], a["poses"][2]
+    quiet = [k for k in ftw.ALL_KEYS if k not in ("eligible", "succeeded", "observations_used")]
+    for name, pair in nf.FILTER_PAIRS:
+        what = (case[0], name, mh, robust)
+        pa, sa, ma, ca, ta = a["filter"][name]
+        pb, sb, mb, cb, tb = b["filter"][name]
+        assert pa[tight].tobytes() == pb[tight].tobytes(), (what, np.nonzero(pa != pb)[0][:8])
+        assert sa[tight_slot & ~sc.bad].tobytes() == sb[tight_slot & ~sc.bad].tobytes(), what
+        assert ma[tight_slot].tobytes() == mb[tight_slot].tobytes() and ta[tight].tobytes() == tb[tight].tobytes(), what
+        assert not ma[sc.bad & tight_slot].any(), what
+        if not loose.any():
+            assert ca == cb, (what, ca, cb)
+        for t in np.nonzero(loose)[0]:
+            sl = slice(int(o[t]), int(o[t + 1]))
+            has_point = bool(int(p0[t]["status"]) & _lib.TRI_POINT)
+            if nf.non_finite(case):
+                assert not has_point and (int(p0[t]["status"]) & ~_lib.TRI_EXTENDED) == _lib.TRI_ATTEMPTED, (what, t, p0[t])
+                assert ma[sl].all() and sc.bad[sl].any(), (what, t, ma[sl])
+            if has_point:       # (it lacks ERROR_OK under the session's 2 px: one fitting observation at least fails every pair's max_error)
+                assert ta[t]["kind"] >= ftw.KIND_TRIMMED, (what, t, ta[t])
+            else:               # (a DLT over 3e38 may end without a point as well)
+                assert ta[t]["kind"] == ftw.KIND_NOT_ELIGIBLE, (what, t, ta[t])
+                assert pa[t].tobytes() == p0[t].tobytes() and sa[sl].tobytes() == r0[sl].tobytes() and ma[sl].tobytes() == m0[sl].tobytes(), (what, t)
+        float_fields_finite(pa)
+        assert not np.isnan(sa[~sc.bad]).any() and nan_bits(sa) <= {CANONICAL}, (what, [hex(v) for v in nan_bits(sa)])
+        again = ftw.run(host, sc.tracks, sc.ids, sc.kps, lst, cam, pa, sa, ma, nf.THR[:2], pair)
+        assert again[0].tobytes() == pa.tobytes() and again[1].tobytes() == sa.tobytes() and again[2].tobytes() == ma.tobytes(), what
+        assert all(again[3][k] == 0 for k in quiet) and all(again[3][k] == ca[k] for k in ("succeeded", "observations_used")), (what, again[3])
+        if not (routes and robust):
+            continue
+        kind = ta["kind"]
+        drops = int((ta["dropped_by_depth"] + ta["dropped_by_error"])[tight].sum())
+        if name in ("mix", "trim"):
+            # a bad track is trimmed (its bad slots are rewritten: under a NaN, THE NaN stands in every one of them afterwards) and
+            # a clean one is untouched.  `mix_trims_bad` False: the lane placement under CAM, whose five bad tracks FILTER_MIX leaves
+            # untouched or removes by views (nonfinite_fixtures.FILTER_TRIM) -- there FILTER_TRIM alone reaches the route
+            trimmed_bad = badt & tight & (kind == ftw.KIND_TRIMMED)
+            assert (kind[~badt] == ftw.KIND_UNTOUCHED).any() and (kind == ftw.KIND_TRIMMED).any(), (what, np.bincount(kind, minlength=5))
+            assert trimmed_bad.any() or (name == "mix" and not mix_trims_bad), (what, ta[badt])
+            if case[0].startswith("nan"):
+                assert np.isnan(sa[sc.bad & trimmed_bad[per_slot]]).all(), what
+        elif name == "angle":
+            assert ca["removed_by_angle"] > 0 and drops == 0, (what, ca)
+        else:
+            assert ca["removed_by_views"] > 0 and drops > 0, (what, ca)
+
+
 @pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
 @pytest.mark.parametrize("cam", sorted(CAMS))
 @pytest.mark.parametrize("place", sorted(PLACEMENTS))
 def test_the_chain_equals_the_gross_outlier_scene(host, place, cam, case):
-    """robust and plain session, the extension with max_hypotheses 8 and 0: the module docstring says what is compared which way"""
+    """robust and plain session, the extension with max_hypotheses 8 and 0: the module docstring says what is compared which way; then
+    the filter steps at the end of every one of these chains (compare_filter)"""
     sc = PLACEMENTS[place](case)[0]
     for robust in (True, False):
         for mh in (8, 0):
             a = nf.chain(host, sc, CAMS[cam], mh=mh, robust=robust)
             compare(sc, case, a, gross_chain(host, place, case, cam, mh, robust), mh, robust)
+            compare_filter(host, sc, case, CAMS[cam], a, gross_chain(host, place, case, cam, mh, robust), mh, robust,
+                           mix_trims_bad=(place, cam) != ("lanes", "cam"))
 
 
 @pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
@@ -222,6 +295,92 @@ def test_tile_elements_equal_the_gross_outlier_scene(host, cam, case):
                 assert s == _lib.TRI_ATTEMPTED and a[step][0][t]["n_views"] == sc.lengths[t] and np.all(a[step][1][o[t]:o[t + 1]] == -1.0)
     for t in np.nonzero(two)[0]:                                  # never retried: the plain record stands in the robust call
         assert a["robust"][0][t].tobytes() == a["plain"][0][t].tobytes()
+
+
+# ---- the filter on the plain session --------------------------------------------------------------------------------------------------------
+PLAIN_PLACEMENTS = {"lanes": nf.lanes, "images": nf.images, "elements": nf.elements}
+
+
+def plain_session(host, sc, cam, place):
+    """plain triangulation, point refinement, the filter under the session's thresholds WITHOUT inlier bytes (the call creates them),
+    point refinement -> (poses, the posed mask per slot, the first refinement's outputs, the filter's with its trace, the second
+    refinement's).  lanes and images: the chain's own steps under the OLD images' poses; elements: every image posed."""
+    if place == "elements":
+        poses = sc.poses
+        pp, pr = tw.run(host, sc.tracks, sc.ids, sc.kps, poses, cam, nf.THR)
+        before = nf.rtw.run(host, sc.tracks, sc.ids, sc.kps, poses, cam, pp, pr, None, nf.THR[:2])
+        flt = ftw.run(host, sc.tracks, sc.ids, sc.kps, poses, cam, before[0], before[1], None, nf.THR[:2], trace=True)
+    else:
+        poses = sc.some(nf.OLD)
+        a = nf.chain(host, sc, cam, mh=0, robust=False)
+        before, flt = a["refine1"][:3], a["filter0"]
+    after = nf.rtw.run(host, sc.tracks, sc.ids, sc.kps, poses, cam, flt[0], flt[1], flt[2], nf.THR[:2])
+    return poses, np.isin(sc.tracks[1], [int(i) for i in poses]), before, flt, after
+
+
+@pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
+@pytest.mark.parametrize("cam", sorted(CAMS))
+@pytest.mark.parametrize("place", sorted(PLAIN_PLACEMENTS))
+def test_the_plain_session_filter(host, place, cam, case):
+    """The filter behind the plain triangulation and its point refinement, where a bad track's record is a DLT over the bad observation
+    (second form: nothing here is held to the 1e6 scene).  The call creates the inlier bytes: 1 on the posed elements of an ATTEMPTED
+    track (msfm_extend.h, plain_byte), whatever the observation holds.
+      a non-finite value   the bad tracks are ATTEMPTED alone: not eligible, record, slots and (created) bytes as they were -- 1 on
+                           the bad observation too.
+      a finite value       (+-3e38, 1e30, the pixel 0) a bad track that has a point lacks ERROR_OK: eligible, trimmed or removed; one
+                           without a point stays as under a non-finite value.  Before the call the records of +-3e38 in x hold
+                           +inf (mean_residual) and the refinement's cost sums are +inf on the lane and image placements;
+                           after it every float field of every record is finite and the next refinement's sums are finite: the
+                           filter is the call that cures the only non-finite record fields the library hands out.
+    Always: NaNs only in bad slots and only THE NaN, a second call that changes no byte."""
+    sc = PLAIN_PLACEMENTS[place](case)[0]
+    poses, posed, (qp, qr, qc), (fp, fr, fm, fc, ft), (ap, ar, ac) = plain_session(host, sc, CAMS[cam], place)
+    o = sc.tracks[0]
+    per_slot = np.repeat(np.arange(len(sc.lengths)), np.diff(o))
+    attempted = (qp["status"] & _lib.TRI_ATTEMPTED) != 0
+    bad_posed = np.add.reduceat((sc.bad & posed).astype(np.int64), o[:-1]) > 0
+    assert bad_posed.sum() >= 5
+    created = (posed & attempted[per_slot]).astype(np.uint8)
+    same = ft["kind"] <= ftw.KIND_UNTOUCHED
+    assert fm[same[per_slot]].tobytes() == created[same[per_slot]].tobytes() and np.all(fm <= created), case[0]
+    assert fp[same].tobytes() == qp[same].tobytes() and fr[same[per_slot]].tobytes() == qr[same[per_slot]].tobytes(), case[0]
+    has_point = (qp["status"] & _lib.TRI_POINT) != 0
+    assert not (qp["status"][bad_posed] & _lib.TRI_ERROR_OK).any()
+    assert np.all(ft["kind"][bad_posed & has_point] >= ftw.KIND_TRIMMED) and np.all(ft["kind"][bad_posed & ~has_point] == ftw.KIND_NOT_ELIGIBLE)
+    if nf.non_finite(case):
+        assert np.all(qp["status"][bad_posed] == _lib.TRI_ATTEMPTED) and np.all(ft["kind"][bad_posed] == ftw.KIND_NOT_ELIGIBLE)
+        assert fm[sc.bad & posed].all()                                   # plain_byte's definition: the bad observation included
+    else:
+        # (+-3e38 in y on the 5-view tracks: the DLT ends without a point, as under a non-finite value; on the elements placement
+        # its long tracks give a point whose errors stay below 1e308)
+        no_point = case[0] in ("3e38_y", "minus_3e38_y") and place != "elements"
+        assert has_point[bad_posed].any() != no_point, case[0]
+        if case[0] in ("3e38_x", "minus_3e38_x") and place != "elements":
+            assert np.isposinf(qp["mean_residual"][bad_posed & has_point]).any() and qc["cost_before"] == qc["cost_after"] == np.inf, (case[0], qc)
+        float_fields_finite(fp)
+        assert all(np.isfinite(ac[k]) for k in nf.rtw.COST_KEYS), (case[0], ac)
+        float_fields_finite(ap)
+    assert not np.isnan(fr[~sc.bad]).any() and nan_bits(fr) <= {CANONICAL} and nan_bits(ar) <= {CANONICAL}, case[0]
+    assert not any(np.isnan(fp[n]).any() for n in ("X", "mean_residual", "tri_angle"))
+    again = ftw.run(host, sc.tracks, sc.ids, sc.kps, poses, CAMS[cam], fp, fr, fm, nf.THR[:2])
+    assert again[0].tobytes() == fp.tobytes() and again[1].tobytes() == fr.tobytes() and again[2].tobytes() == fm.tobytes(), case[0]
+    print(place, cam, case[0], "bad tracks by kind", np.bincount(ft["kind"][bad_posed], minlength=5).tolist(), fc)
+
+
+def test_the_plain_session_filter_reaches_every_kind_on_the_tile_elements(host):
+    """over the finite values, on the elements placement (bad tracks of 2 .. 130 views): a bad track is trimmed under one value at
+    least, removed by views under one, removed by angle under one"""
+    kinds = {}
+    for case in nf.CASES:
+        if nf.non_finite(case):
+            continue
+        sc = nf.elements(case)[0]
+        _, posed, _, flt, _ = plain_session(host, sc, nf.CAM, "elements")
+        bad_posed = np.add.reduceat((sc.bad & posed).astype(np.int64), sc.tracks[0][:-1]) > 0
+        kinds[case[0]] = set(int(k) for k in flt[4]["kind"][bad_posed])
+    print(kinds)
+    for k in (ftw.KIND_TRIMMED, ftw.KIND_REMOVED_BY_VIEWS, ftw.KIND_REMOVED_BY_ANGLE):
+        assert any(k in v for v in kinds.values()), (k, kinds)
 
 
 @pytest.mark.parametrize("case", [c for c in nf.CASES if c[2] == "x" or c[0] == "nan_xy"], ids=lambda c: c[0])
@@ -361,7 +520,8 @@ def test_verification_twins(vhosts, kind, cam, case):
 def test_the_gross_scene_against_the_references(host, cam, axes):
     """The twin scene (1e6 in the bad coordinates) of the images placement is finite, so the independent numpy references process it:
     every twin of the chain against its reference, fed the same state, with the comparison functions, guards and tolerances of that
-    twin's own reference test (tests/test_*_reference.py); the point and pose refinements with those modules' step_tol 1e-4."""
+    twin's own reference test (tests/test_*_reference.py); the point and pose refinements with those modules' step_tol 1e-4.  Then
+    the filter steps of nf.chain on this scene against tests/filter_ref.py."""
     import extend_ref
     import refine_points_ref
     import refine_poses_ref
@@ -394,6 +554,7 @@ def test_the_gross_scene_against_the_references(host, cam, axes):
                         assert min(res[o[t] + k], e) > 100 * thr[0], (t, k, res[o[t] + k], e)
                     else:
                         assert abs(res[o[t] + k] - e) <= tol * e, (t, k, res[o[t] + k], e)
+                        rel.append(abs(res[o[t] + k] - e) / e)
                     res[o[t] + k] = e
         return res
 
@@ -404,6 +565,7 @@ def test_the_gross_scene_against_the_references(host, cam, axes):
         return [want[t] for t in sel], pts[sel], np.concatenate([res[o[t]:o[t + 1]] for t in sel])
 
     c_, thr, H = CAMS[cam], nf.THR, 8
+    rel = []                                   # what bad_slots_apart measured
     ids, kps, tracks, kd = gr.ids, gr.kps, gr.tracks, gr.kd()
     first = gr.some(nf.OLD)
     # plain and robust triangulation
@@ -471,6 +633,24 @@ def test_the_gross_scene_against_the_references(host, cam, axes):
     w, compared, left_out, n_tracks = xp.compare(dict(want=want, got=got, tracks=tracks), xp.TOL)
     print("poses:", w, compared, left_out, n_tracks)
     assert compared == 6 and not left_out and n_tracks == len(gr.lengths) and all(w[k] <= xp.TOL[k] for k in xp.TOL), w
+    # the filter at the end of the twin scene's chain, under every pair, after the extension with max_hypotheses 8 and 0 (with 0 the bad
+    # 3-view tracks are plain records over the 1e6 observation: eligible, the observation FITTING, dropped by error on both sides);
+    # the comparison and the tolerances of tests/test_filter_points_reference.py
+    import filter_ref
+    import test_filter_points_reference as xf
+    rel.clear()
+    for mh in (8, 0):
+        g = nf.chain(host, gr, c_, mh=mh)
+        pp, pr, pm, lst = g["refine2"][0], g["refine2"][1], g["extend"][2], g["poses"][2]
+        for name, pair in nf.FILTER_PAIRS:
+            want = filter_ref.run(tracks, kd, ptw.poses_dict(*lst), c_, pp, pr, pm, thr[:2], pair)
+            got = g["filter"][name]
+            got = (got[0], bad_slots_apart(got[1], want, xf.TOL["residual"])) + got[2:]
+            w, eligible, left, margins = xf.compare(dict(name=(name, mh), tracks=tracks, before=(pp, pr, pm), got=got, want=want))
+            print("filter %s, max_hypotheses %d:" % (name, mh), w, eligible, left, margins, got[3])
+            assert eligible == len(gr.lengths) and not left and all(w[q] <= xf.TOL[q] for q in xf.TOL), (name, mh, w, left)
+    print("filter: the bad observations' errors, worst difference relative to their size: %.3g over %d slots" % (max(rel, default=0.0), len(rel)))
+    assert any(c_[4:]) or len(rel) > 0
 
 
 # ---- the other fixtures of tests/test_gpu_nonfinite.py, on the twins first ------------------------------------------------------------------
@@ -481,7 +661,9 @@ def test_track_count_prefixes_on_the_twins(host, T):
         sc, gr = sc.prefix(T), gr.prefix(T)
         assert len(sc.bad_tracks()) == sum(t < T for t in nf.LANES)
         for mh in (8, 0):
-            compare(sc, case, nf.chain(host, sc, nf.CAM, mh=mh), nf.chain(host, gr, nf.CAM, mh=mh), mh, True)
+            a, b = nf.chain(host, sc, nf.CAM, mh=mh), nf.chain(host, gr, nf.CAM, mh=mh)
+            compare(sc, case, a, b, mh, True)
+            compare_filter(host, sc, case, nf.CAM, a, b, mh, True, routes=False)     # (one track has no clean neighbour to leave untouched)
 
 
 @pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
@@ -489,7 +671,7 @@ def test_replaced_keypoints_on_the_twins(host, case):
     """The records and inlier bytes come from clean keypoints (every byte 1), then the keypoints are replaced: the bad observations are
     IN the fitting sets of the point refinement.  It ends; no record takes a NaN; a track whose fitting set holds a non-finite
     observation is not refined (its cost is not a number: no step is accepted); the registration and the extension that follow treat
-    the value as on any other session."""
+    the value as on any other session; the filter drops exactly the replaced observations."""
     clean = nf.lanes(None)[0]
     sc, _, gr = nf.lanes(case)
     first = sc.some(nf.OLD)
@@ -516,3 +698,16 @@ def test_replaced_keypoints_on_the_twins(host, case):
     assert nan_bits(reg[4]) <= {CANONICAL} and nan_bits(ext[1]) <= {CANONICAL}
     assert ext[0][clean_t].tobytes() == g[5][0][clean_t].tobytes() and ext[2].tobytes() == g[5][2].tobytes() and ext[3] == g[5][3]
     print(case[0], fc, tr[badt]["verdict"], tr[badt]["accepted"])
+    # the filter right behind the upload, under the session's thresholds: the observations dropped are exactly the bad observations in
+    # posed images (each by error: their tracks are trimmed, every other track is untouched), the trimmed tracks' slots are rewritten
+    # (a NaN's with THE NaN), and everything equals the twin scene's
+    posed = np.isin(sc.tracks[1], [int(i) for i in first])
+    (qp, qr, qm, qc, qt), w = [ftw.run(host, s.tracks, s.ids, s.kps, first, nf.CAM, pp, pr, pm, nf.THR[:2], trace=True) for s in (sc, gr)]
+    assert qm.tobytes() == np.where(sc.bad & posed, 0, pm).astype(np.uint8).tobytes() and (sc.bad & posed).sum() == len(badt)
+    assert (qc["dropped_by_error"], qc["dropped_by_depth"], qc["trimmed"]) == (len(badt), 0, len(badt)), qc
+    assert np.all(qt["kind"][badt] == ftw.KIND_TRIMMED) and np.all(qt["kind"][clean_t] == ftw.KIND_UNTOUCHED)
+    assert qp.tobytes() == w[0].tobytes() and qm.tobytes() == w[2].tobytes() and qc == w[3] and qt.tobytes() == w[4].tobytes()
+    assert qr[~sc.bad].tobytes() == w[1][~sc.bad].tobytes() and qr[~per_slot].tobytes() == pr[~per_slot].tobytes()
+    assert nan_bits(qr) <= {CANONICAL} and not np.isnan(qr[~sc.bad]).any()
+    assert np.isnan(qr[sc.bad & posed]).all() == case[0].startswith("nan") and not (qr[sc.bad & posed] <= nf.THR[0]).any()
+    float_fields_finite(qp)

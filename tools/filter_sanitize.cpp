@@ -6,6 +6,7 @@
 // records, residuals and bytes exactly one per track / observation: an index by image id or list position where the rank is meant, or
 // past a track's own slots, runs off the end.  Prints the counters; exits 1 if nothing was trimmed or removed, if an untouched or
 // ineligible track changed, if a removed record has another shape than the header states, or if the second call changed a byte.
+// A second pass replaces keypoints of fitting observations by the non-finite and huge values of DESIGN.md section 21 (see there).
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
 //       tools/filter_sanitize.cpp -o filter_sanitize && ./filter_sanitize
 #include <cmath>
@@ -128,5 +129,89 @@ int main() {
                 have_mask = true;
             }
         }
-    return trimmed > 0 && removed > 0 && !bad ? 0 : 1;
+    // Non-finite and huge keypoints: after the triangulation twins the keypoint of one FITTING observation of
+    // every third eligible track is replaced by each of the ten values -- x, y or both by turns -- and the filter runs under the
+    // session's thresholds and at (0.45 px, 1.5 degrees), each followed by a second call.  Checked: the replaced observation is dropped
+    // (every value lies more than 60 px off its point, the pixel 0 included), no record field is a NaN or an infinity, a NaN in a
+    // residual slot is THE NaN and sits in a replaced observation's slot, the second call changes no byte.
+    const uint32_t values[10] = {0x7fc00000u, 0xffc00000u, 0x7fc00001u, 0x7f800000u, 0xff800000u, 0x7f61b1e6u /* 3e38 */, 0xff61b1e6u,
+                                 0x7149f2cau /* 1e30 */, 0x00000001u, 0x80000000u};
+    const msfm_ref::Verdict pairs[2] = {{prm.max_error, prm.min_angle}, {0.45, 1.5}};
+    long long replaced_dropped = 0, nan_slots = 0;
+    for (int robust = 0; robust < 2; ++robust) {
+        std::vector<msfm_point3d> pts0((size_t)n_tr);
+        std::vector<double> res0(img.size());
+        std::vector<uint8_t> mask0(img.size(), 0);
+        if (robust) {
+            msfm_tri::RobustCounts c = {0, 0, 0, 0};
+            msfm_tri::TriangulateTracksRobust(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr.data(), table.data(), cam,
+                                              msfm_tri::RobustParams{prm.max_error, prm.min_angle, prm.min_views, 64}, pts0.data(), res0.data(),
+                                              mask0.data(), &c);
+        } else {
+            msfm_tri::TriangulateTracks(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr.data(), table.data(), cam, prm,
+                                        pts0.data(), res0.data());
+        }
+        const int unposed = rank[(size_t)(n_img - 1)];
+        for (int v = 0; v < 10; ++v)
+            for (const msfm_ref::Verdict& call : pairs) {
+                std::vector<std::vector<float>> kbad = kxy;
+                std::vector<uint8_t> replaced(img.size(), 0);
+                float value;
+                std::memcpy(&value, &values[v], sizeof(value));
+                for (int j = 0; j < n_tr; j += 3) {
+                    const size_t b = (size_t)offsets[(size_t)j], n = (size_t)offsets[(size_t)j + 1] - b;
+                    if (!cons[(size_t)j] || !msfm_ref::eligible(pts0[(size_t)j])) continue;
+                    for (size_t q = 0; q < n; ++q) {   // the first fitting element from a start that moves with the track
+                        const size_t k = (q + (size_t)j / 3) % n;
+                        const int r = rank_of[(size_t)img[b + k]];
+                        if (r == unposed || (robust && !mask0[b + k])) continue;
+                        const int axes = 1 + (j / 3 + v) % 3;   // 1: x, 2: y, 3: both
+                        if (axes & 1) kbad[(size_t)r][(size_t)(2 * j)] = value;
+                        if (axes & 2) kbad[(size_t)r][(size_t)(2 * j + 1)] = value;
+                        replaced[b + k] = 1;
+                        break;
+                    }
+                }
+                std::vector<const float*> pbad;
+                for (auto& k : kbad) pbad.push_back(k.data());
+                std::vector<msfm_point3d> pts = pts0;
+                std::vector<double> res = res0;
+                std::vector<uint8_t> mask = mask0;
+                bool have_mask = robust != 0;
+                for (int pass = 0; pass < 2; ++pass) {
+                    const std::vector<msfm_point3d> p0 = pts;
+                    const std::vector<double> r0 = res;
+                    const std::vector<uint8_t> m0 = mask;
+                    msfm_flt::Counts c = {0, 0, 0, 0, 0, 0, 0};
+                    msfm_flt::FilterPoints(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), pbad.data(), table.data(), n_img,
+                                           nullptr, cam, prm, call, have_mask, pts.data(), res.data(), mask.data(), &c);
+                    have_mask = true;
+                    if (pass == 1) {
+                        bad = bad || std::memcmp(pts.data(), p0.data(), pts.size() * sizeof(msfm_point3d)) ||
+                              std::memcmp(res.data(), r0.data(), res.size() * sizeof(double)) || std::memcmp(mask.data(), m0.data(), mask.size());
+                        continue;
+                    }
+                    for (size_t o = 0; o < img.size(); ++o) {
+                        if (replaced[o]) {
+                            bad = bad || mask[o] != 0;
+                            replaced_dropped += 1;
+                        }
+                        if (res[o] != res[o]) {
+                            uint64_t bits;
+                            std::memcpy(&bits, &res[o], sizeof(bits));
+                            bad = bad || bits != 0x7ff8000000000000ull || !replaced[o];
+                            nan_slots += 1;
+                        }
+                    }
+                    for (const msfm_point3d& r : pts)
+                        bad = bad || !std::isfinite(r.X[0]) || !std::isfinite(r.X[1]) || !std::isfinite(r.X[2]) || !std::isfinite(r.mean_residual) ||
+                              !std::isfinite(r.tri_angle);
+                    std::printf("robust %d value %08x at (%.2f, %.1f): eligible %lld dropped %lld + %lld trimmed %lld removed %lld + %lld\n", robust,
+                                (unsigned)values[v], call.max_error, call.min_angle, c.eligible, c.dropped_by_depth, c.dropped_by_error, c.trimmed,
+                                c.removed_by_views, c.removed_by_angle);
+                }
+            }
+    }
+    std::printf("replaced observations dropped %lld, NaN slots %lld, %s\n", replaced_dropped, nan_slots, bad ? "BAD" : "ok");
+    return trimmed > 0 && removed > 0 && replaced_dropped > 0 && nan_slots > 0 && !bad ? 0 : 1;
 }
