@@ -899,6 +899,63 @@ typedef struct msfm_filter_stats {   /* 88 bytes, no implicit padding */
 int msfm_filter_points(msfm_ctx* ctx, const msfm_filter_params* params, const int32_t* image_ids, int n_images,
                        msfm_filter_stats* stats);
 
+/* ---- map completion: re-admit observations that fit again (opt-in) ---------------
+ * The step the reference runs behind its filter after every local adjustment (MapBuilder::CompleteTracks -> Map::CompletePoints3D /
+ * CompletePoint3D).  An observation that msfm_extend_points, msfm_triangulate_tracks_robust or msfm_filter_points rejected keeps
+ * inlier byte 0 whatever the refinements do to its pose and its point afterwards; msfm_complete_points tests such observations of the
+ * standing points again and re-admits those that fit: the only call that sets an inlier byte of an existing point back to 1.  No X
+ * and no pose ever changes.  The arithmetic is csrc/msfm_complete.h, bit-identical to the host twin CompletePoints (DESIGN.md section
+ * 23).  The tracks are whole connected components of the match graph, so the reference's walk over further correspondences has
+ * nothing to discover and its MergeTracks has no counterpart: two tracks never share a correspondence.
+ *   inputs       none besides the context, the threshold and the scope: as msfm_filter_points.
+ *   threshold    max_error in pixels.  params NULL = the SESSION's own max_error.  An explicit value may be tighter than the
+ *                session's, not looser: an observation admitted above it would clear ERROR_OK of the point it joins when the record
+ *                is evaluated again (the reference's 4 px completion threshold sits beside a 4 px filter and no such bit).
+ *   inlier bytes as msfm_filter_points: a session without them gets them first, 1 on every used observation of an attempted track,
+ *                else 0.  On such a session there is no candidate and the call's only effect is that the bytes exist.
+ *   candidate    a used observation (its image has a valid pose) whose inlier byte is 0.  n_images == 0: every image.  Otherwise
+ *                only the candidates IN a listed image -- unlike msfm_filter_points, whose list selects tracks by where their
+ *                fitting observations lie: "image 7's pose has just been refined: test what image 7 had rejected".  A listed image
+ *                without a valid pose selects nothing.
+ *   eligible     a consistent track whose record has POINT & ERROR_OK & ANGLE_OK.  Every other track stays bit for bit: a point
+ *                that does not stand is filtered or extended, not completed.
+ *   admission    per candidate, in element order: err = the reprojection error at the record's X under the current pose (pixels, f =
+ *                (fx + fy) / 2).  Rejected by depth iff its depth is not > DBL_EPSILON; otherwise rejected by error iff !(err <=
+ *                max_error) (a NaN is rejected); otherwise admitted: its inlier byte becomes 1.  X does not move, so candidates do
+ *                not depend on each other and one pass is a fixed point.
+ *   untouched    nothing admitted: not one byte is written, the residual slots of the rejected candidates included.
+ *   completed    something admitted.  The record is evaluated again over the enlarged fitting set K at the unchanged X with the
+ *                SESSION's thresholds and the triangulation's code: an error for every used observation, n_views = |K|,
+ *                mean_residual = the errors of K summed in element order / |K|, tri_angle, ERROR_OK, ANGLE_OK, DEPTH_OK over K;
+ *                status = ATTEMPTED | POINT | those bits | the record's ROBUST, REFINED, REPOSED, EXTENDED, FILTERED |
+ *                MSFM_TRI_COMPLETED.
+ * The call is idempotent: repeated with the same threshold and scope it changes not one byte and admits nothing.  Inlier bytes only
+ * rise.  A later msfm_refine_points / msfm_refine_poses / msfm_extend_points / msfm_filter_points treats MSFM_TRI_COMPLETED as it
+ * treats MSFM_TRI_FILTERED when it rewrites a record.
+ * The call invalidates registrations and pose-refinement records like msfm_filter_points; points, inlier bytes and the pose list stay
+ * valid.  Errors, after each of which the session is exactly what it was: MSFM_E_STATE -- as msfm_refine_points.  MSFM_E_INVALID -- a
+ * non-finite or negative max_error or one above the session's, n_images < 0 or a NULL list with n_images > 0, an id that is not
+ * declared in the session or given twice.  MSFM_E_NOIMAGE -- as msfm_refine_points.
+ * The counters only count: no order reaches an output. */
+enum { MSFM_TRI_COMPLETED = 1024 };
+typedef struct msfm_complete_params {   /* 8 bytes, no implicit padding */
+    double max_error;                /* pixels; not above the session's */
+} msfm_complete_params;
+typedef struct msfm_complete_stats {   /* 80 bytes, no implicit padding */
+    int64_t eligible;                /* consistent tracks with POINT & ERROR_OK & ANGLE_OK */
+    int64_t candidates;              /* their used observations with inlier byte 0 in scope: tested */
+    int64_t admitted;                /* ... in front of their camera with an error <= max_error */
+    int64_t rejected_by_depth;       /* ... behind their camera */
+    int64_t rejected_by_error;       /* ... in front of it with an error that is not <= max_error */
+    int64_t completed;               /* eligible tracks that admitted an observation */
+    int64_t succeeded;               /* POINT & ERROR_OK & ANGLE_OK over all tracks after the call */
+    int64_t observations_used;       /* n_views summed over all tracks after the call */
+    double complete_ms;              /* HIP events around all launches of the call */
+    double prepare_ms;               /* ... of which the pose table, the inlier bytes and the per-observation array */
+} msfm_complete_stats;
+int msfm_complete_points(msfm_ctx* ctx, const msfm_complete_params* params, const int32_t* image_ids, int n_images,
+                         msfm_complete_stats* stats);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

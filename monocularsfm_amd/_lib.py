@@ -159,6 +159,26 @@ def filtered(points):
     return (np.asarray(points)["status"] & TRI_FILTERED) != 0
 
 
+# map completion (include/msfm_match.h): the record's extra status bit, the 8-byte parameters, the 80-byte stats
+TRI_COMPLETED = 1024
+
+
+class CompleteParams(C.Structure):
+    _fields_ = [("max_error", C.c_double)]
+
+
+class CompleteStats(C.Structure):
+    """msfm_complete_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("eligible", "candidates", "admitted", "rejected_by_depth", "rejected_by_error", "completed",
+                                         "succeeded", "observations_used")] + \
+               [(k, C.c_double) for k in ("complete_ms", "prepare_ms")]
+
+
+def completed(points):
+    """The records of a POINT3D array that a map completion admitted an observation into (MSFM_TRI_COMPLETED)."""
+    return (np.asarray(points)["status"] & TRI_COMPLETED) != 0
+
+
 def succeeded(points):
     """The reference's is_succeed per record of a POINT3D array: POINT & ERROR_OK & ANGLE_OK."""
     want = TRI_POINT | TRI_ERROR_OK | TRI_ANGLE_OK
@@ -351,6 +371,7 @@ def _signatures():
         "msfm_fetch_pose_refinements": (i, [vp, vp]),
         "msfm_extend_points": (i, [vp, ip, vp, i, P(ExtendParams), P(ExtendStats)]),
         "msfm_filter_points": (i, [vp, P(FilterParams), ip, i, P(FilterStats)]),
+        "msfm_complete_points": (i, [vp, P(CompleteParams), ip, i, P(CompleteStats)]),
         "msfm_register_images": (i, [vp, cam, ip, i, P(RegisterParams), P(RegisterStats)]),
         "msfm_fetch_registrations": (i, [vp, vp, vp, vp, vp, vp]),
     }
@@ -946,10 +967,25 @@ class Context:
                                              C.byref(st)))
         return _dict(st)
 
-    def reconstruct(self, camera, rounds=1, filter_params=None, max_increments=None, **grow_kwargs):
+    def complete_points(self, max_error=None, image_ids=None):
+        """Tests the observations of the standing points whose inlier byte is 0 again and re-admits those that fit under the current
+        poses (msfm_complete_points); no point and no pose moves.  max_error in pixels, at most that of this context's last
+        triangulate_tracks; None = that value (NULL parameters).  image_ids: only the candidates in a listed image (None or empty:
+        every image).  -> stats dict.  completed(points) is the mask of the records it admitted an observation into; point_inliers()
+        works after it whatever the triangulation was.  Registrations and pose refinements are invalidated."""
+        prm = CompleteParams(float(max_error)) if max_error is not None else None
+        ids = np.ascontiguousarray(list(image_ids) if image_ids is not None else [], dtype=np.int32).reshape(-1)
+        st = CompleteStats()
+        self._chk(self._L.msfm_complete_points(self._h, C.byref(prm) if prm is not None else None, _ip(ids) if len(ids) else None, len(ids),
+                                               C.byref(st)))
+        return _dict(st)
+
+    def reconstruct(self, camera, rounds=1, filter_params=None, max_increments=None, complete_params=None, **grow_kwargs):
         """The reference's DoBuild loop with its filter: grow(camera, rounds=rounds, **grow_kwargs) followed by
-        filter_points(**filter_params), repeated until no image registers or max_increments increments have run.
-        -> one dict per increment: register, extend, alternate (grow's results), filter (filter_points' stats), registered (the ids)."""
+        filter_points(**filter_params), repeated until no image registers or max_increments increments have run.  complete_params: a
+        dict (may be empty) runs complete_points(**complete_params) behind the filter of every increment; None: no completion.
+        -> one dict per increment: register, extend, alternate (grow's results), filter (filter_points' stats), registered (the ids),
+        and with complete_params "complete" (complete_points' stats)."""
         out = []
         while max_increments is None or len(out) < int(max_increments):
             reg, ext, alt, new = self.grow(camera, rounds=rounds, **grow_kwargs)
@@ -957,6 +993,8 @@ class Context:
                 break
             flt = self.filter_points(**(filter_params or {}))
             out.append({"register": reg, "extend": ext, "alternate": alt, "filter": flt, "registered": new})
+            if complete_params is not None:
+                out[-1]["complete"] = self.complete_points(**complete_params)
         return out
 
     def points3d(self):

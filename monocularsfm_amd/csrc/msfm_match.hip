@@ -48,6 +48,7 @@ using namespace msfm;
 #include "msfm_refine_poses.hip.h"
 #include "msfm_extend.hip.h"
 #include "msfm_filter.hip.h"
+#include "msfm_complete.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -922,6 +923,16 @@ int msfm_filter_points(msfm_ctx* ctx, const msfm_filter_params* params, const in
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return filter_impl(ctx, params, image_ids, n_images, stats);
+    MSFM_API_END
+}
+
+// ---- map completion (msfm_complete.hip.h) -----------------------------------------------------------------------------------------------
+
+int msfm_complete_points(msfm_ctx* ctx, const msfm_complete_params* params, const int32_t* image_ids, int n_images,
+                         msfm_complete_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return complete_impl(ctx, params, image_ids, n_images, stats);
     MSFM_API_END
 }
 

@@ -20,6 +20,7 @@
 #include "../csrc/msfm_refine_poses.h"
 #include "../csrc/msfm_extend.h"
 #include "../csrc/msfm_filter.h"
+#include "../csrc/msfm_complete.h"
 #include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
@@ -891,6 +892,53 @@ int host_filter_points(const long long* offsets, const int* image_ids, const int
         const long long v[7] = {fc.eligible, fc.dropped_by_depth, fc.dropped_by_error, fc.trimmed, fc.regained, fc.removed_by_views,
                                 fc.removed_by_angle};
         for (int k = 0; k < 7; ++k) counts7[k] += v[k];
+    }
+    return 0;
+}
+
+// ---- map completion: the host twin of the device kernel (csrc/msfm_complete.h, CompletePoints) ----------------------------------------
+// The inputs of host_filter_points with one threshold of the call's own (cmp_max_error) and scope_ids: the images whose candidates the
+// call is limited to (n_scope == 0: every image).  points, residuals and mask are read and rewritten in place; have_mask 0: the bytes
+// of the computed tracks are created first.  Tracks [first, first + count) are computed.  counts6 (may be NULL): eligible, candidates,
+// admitted, rejected_by_depth, rejected_by_error, completed of those tracks are ADDED to it.  out_trace (may be NULL) receives
+// msfm_cmp::Trace (four int32) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3: a non-finite or negative
+// threshold, one above max_error, or n_scope < 0; 4: a scope id that is not declared or given twice.
+int host_complete_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                         const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses,
+                         const int* scope_ids, int n_scope, const double* cam, double max_error, double min_angle, double cmp_max_error,
+                         long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask,
+                         long long* counts6, int* out_trace) {
+    static_assert(sizeof(msfm_cmp::Trace) == 4 * sizeof(int), "the trace is four int32");
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        rank_of[(size_t)ids[k]] = k;
+    }
+    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
+    }
+    if (!msfm_pose::finite(cmp_max_error) || !(cmp_max_error >= 0.0) || cmp_max_error > max_error || n_scope < 0) return 3;
+    std::vector<uint8_t> scope((size_t)std::max(n_images, 1), 0);
+    for (int k = 0; k < n_scope; ++k) {
+        const int r = (scope_ids[k] >= 0 && scope_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)scope_ids[k]] : -1;
+        if (r < 0 || scope[(size_t)r]) return 4;
+        scope[(size_t)r] = 1;
+    }
+    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    msfm_cmp::Counts cc = {0, 0, 0, 0, 0, 0};
+    msfm_cmp::CompletePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(), kxy,
+                             table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, c, msfm_tri::Params{max_error, min_angle, 2, 0},
+                             cmp_max_error, have_mask != 0, points, residuals, mask, &cc, reinterpret_cast<msfm_cmp::Trace*>(out_trace));
+    if (counts6) {
+        const long long v[6] = {cc.eligible, cc.candidates, cc.admitted, cc.rejected_by_depth, cc.rejected_by_error, cc.completed};
+        for (int k = 0; k < 6; ++k) counts6[k] += v[k];
     }
     return 0;
 }

@@ -1,0 +1,231 @@
+// A stand-alone driver of the map completion's host twin (csrc/msfm_complete.h, CompletePoints) for sanitizer builds: the generated ring
+// job of tools/filter_sanitize.cpp -- 12 images, 150 tracks of 2 .. 12 views, every fifth with one observation moved by 40 px, some tracks
+// inconsistent, image ids 3 i + 1 with the ranks in ANOTHER order than the ids -- triangulated under a loose (60 px, 1 degree) session by
+// the plain and by the robust twin and filtered at (3 px, 2 degrees) by the filter twin, which drops the moved observations.  Then the
+// moved keypoints are put back and the completion runs at 10 px (the points still carry the pull of the moved observation): without a
+// scope list, with one (two images), with an EMPTY one (every image, as the C entry point reads n_images == 0), and each time a second
+// call that changes no byte.  The pose table and the scope have exactly one entry per rank, records, residuals and bytes exactly one
+// per track / observation: an index by image id or list position where the rank is meant, or past a track's own slots, runs off the
+// end.  Prints the counters; exits 1 if nothing was admitted, if an untouched or ineligible track changed, if a completed record moved
+// its X or miscounts its views, if a byte fell, or if the second call changed a byte or admitted anything.
+// A second pass puts the non-finite and huge values of DESIGN.md section 21 into every second candidate's keypoint: every such
+// candidate is rejected, no record field is non-finite, a NaN in a residual slot is THE NaN in such a candidate's slot.
+//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
+//       tools/complete_sanitize.cpp -o complete_sanitize && ./complete_sanitize
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <random>
+#include <vector>
+
+#include "../monocularsfm_amd/csrc/msfm_complete.h"
+#include "../monocularsfm_amd/csrc/msfm_filter.h"
+
+int main() {
+    const int n_img = 12, n_tr = 150;
+    const msfm_emat::Camera cam{2500.0, 2400.0, 1536.0, 1152.0, -0.1, 0.02, 1e-3, -5e-4};
+    const msfm_tri::Params prm = {60.0, 1.0, 2, 0};
+    const msfm_ref::Verdict flt = {3.0, 2.0};
+    const double cmp_max_error = 10.0;
+    std::mt19937_64 rng(7);
+    std::uniform_real_distribution<double> box(-1.0, 1.0);
+    std::normal_distribution<double> noise(0.0, 1.0);
+    std::vector<msfm_pose_rt> truth((size_t)n_img);
+    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1), rank((size_t)n_img);
+    for (int i = 0; i < n_img; ++i) {
+        const double th = 2.0 * 3.14159265358979323846 * i / 300.0;
+        msfm_pose_rt p = {};
+        p.valid = 1;
+        const double z[3] = {-std::sin(th), 0.0, std::cos(th)}, x[3] = {z[2], 0.0, -z[0]};
+        const double R[9] = {x[0], x[1], x[2], 0.0, 1.0, 0.0, z[0], z[1], z[2]};
+        for (int k = 0; k < 9; ++k) p.R[k] = R[k];
+        p.t[2] = 6.5;
+        truth[(size_t)i] = p;
+        rank[(size_t)i] = (5 * i + 3) % n_img;   // (5 and 12 are coprime: a permutation)
+        rank_of[(size_t)(3 * i + 1)] = rank[(size_t)i];
+    }
+    // by rank: `moved` is what the triangulation and the filter see, `clean` what the completion finds
+    std::vector<std::vector<float>> moved((size_t)n_img, std::vector<float>((size_t)(2 * n_tr), 0.f)), clean = moved;
+    std::vector<int64_t> offsets{0};
+    std::vector<int32_t> img, idx;
+    std::vector<uint8_t> cons;
+    for (int j = 0; j < n_tr; ++j) {
+        const int len = 2 + j % (n_img - 1), first = j % (n_img - len + 1);   // track j runs through the images first .. first + len - 1
+        const double X[3] = {box(rng), box(rng), box(rng)};
+        for (int i = first; i < first + len; ++i) {
+            const msfm_pose_rt& p = truth[(size_t)i];
+            const double Y0 = p.R[0] * X[0] + p.R[1] * X[1] + p.R[2] * X[2] + p.t[0], Y1 = p.R[3] * X[0] + p.R[4] * X[1] + p.R[5] * X[2] + p.t[1],
+                         Y2 = p.R[6] * X[0] + p.R[7] * X[1] + p.R[8] * X[2] + p.t[2];
+            const size_t r = (size_t)rank[(size_t)i];
+            const double kx = cam.fx * Y0 / Y2 + cam.cx + noise(rng), ky = cam.fy * Y1 / Y2 + cam.cy + noise(rng);
+            clean[r][(size_t)(2 * j)] = moved[r][(size_t)(2 * j)] = (float)kx;
+            clean[r][(size_t)(2 * j + 1)] = (float)ky;
+            moved[r][(size_t)(2 * j + 1)] = (float)(ky + ((j % 5 == 0 && i == first + (j / 5) % len) ? 40.0 : 0.0));
+            img.push_back(3 * i + 1);
+            idx.push_back(j);
+        }
+        offsets.push_back((int64_t)img.size());
+        cons.push_back(j % 11 != 5);
+    }
+    std::vector<const float*> ptr_moved, ptr_clean;
+    for (auto& k : moved) ptr_moved.push_back(k.data());
+    for (auto& k : clean) ptr_clean.push_back(k.data());
+    std::vector<msfm_tri::Pose> table((size_t)n_img);
+    for (int i = 0; i < n_img - 1; ++i) msfm_tri::prepare_pose(truth[(size_t)i], &table[(size_t)rank[(size_t)i]]);
+    const msfm_pose_rt none = {};
+    msfm_tri::prepare_pose(none, &table[(size_t)rank[(size_t)(n_img - 1)]]);   // the last image has no pose: its elements are not USED
+
+    // the state the completion starts from: triangulation twin, then the filter twin, over the moved keypoints
+    auto filtered_state = [&](int robust, std::vector<msfm_point3d>* pts, std::vector<double>* res, std::vector<uint8_t>* mask) {
+        pts->assign((size_t)n_tr, msfm_point3d{});
+        res->assign(img.size(), 0.0);
+        mask->assign(img.size(), 0);
+        if (robust) {
+            msfm_tri::RobustCounts c = {0, 0, 0, 0};
+            msfm_tri::TriangulateTracksRobust(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr_moved.data(),
+                                              table.data(), cam, msfm_tri::RobustParams{prm.max_error, prm.min_angle, prm.min_views, 64},
+                                              pts->data(), res->data(), mask->data(), &c);
+        } else {
+            msfm_tri::TriangulateTracks(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr_moved.data(), table.data(),
+                                        cam, prm, pts->data(), res->data());
+        }
+        msfm_flt::Counts c = {0, 0, 0, 0, 0, 0, 0};
+        msfm_flt::FilterPoints(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr_moved.data(), table.data(), n_img,
+                               nullptr, cam, prm, flt, robust != 0, pts->data(), res->data(), mask->data(), &c);
+        return c.dropped_by_depth + c.dropped_by_error;
+    };
+
+    const std::vector<std::vector<int>> scopes = {{-1}, {4, 7}, {}};   // {-1}: no list at all
+    long long admitted = 0, completed = 0;
+    bool bad = false;
+    for (int robust = 0; robust < 2; ++robust)
+        for (const auto& listed : scopes) {
+            std::vector<msfm_point3d> pts;
+            std::vector<double> res;
+            std::vector<uint8_t> mask;
+            bad = bad || filtered_state(robust, &pts, &res, &mask) == 0;
+            std::vector<uint8_t> scope((size_t)n_img, 0);   // one byte per rank
+            bool any = false;
+            for (int i : listed)
+                if (i >= 0) {
+                    scope[(size_t)rank[(size_t)i]] = 1;
+                    any = true;
+                }
+            for (int pass = 0; pass < 2; ++pass) {
+                const std::vector<msfm_point3d> p0 = pts;
+                const std::vector<double> r0 = res;
+                const std::vector<uint8_t> m0 = mask;
+                std::vector<msfm_cmp::Trace> trace((size_t)n_tr);
+                msfm_cmp::Counts c = {0, 0, 0, 0, 0, 0};
+                msfm_cmp::CompletePoints(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr_clean.data(), table.data(),
+                                         n_img, any ? scope.data() : nullptr, cam, prm, cmp_max_error, true, pts.data(), res.data(), mask.data(), &c,
+                                         trace.data());
+                long long rose = 0;
+                for (int t = 0; t < n_tr; ++t) {
+                    const size_t b = (size_t)offsets[(size_t)t], n = (size_t)offsets[(size_t)t + 1] - b;
+                    const msfm_cmp::Trace& tr = trace[(size_t)t];
+                    if (tr.kind != msfm_cmp::KIND_COMPLETED) {
+                        bad = bad || std::memcmp(&pts[(size_t)t], &p0[(size_t)t], sizeof(msfm_point3d)) || std::memcmp(&res[b], &r0[b], n * sizeof(double)) ||
+                              std::memcmp(&mask[b], &m0[b], n) || tr.admitted != 0;
+                        continue;
+                    }
+                    const int ok = MSFM_TRI_POINT | MSFM_TRI_ERROR_OK | MSFM_TRI_ANGLE_OK | MSFM_TRI_COMPLETED;
+                    bad = bad || std::memcmp(pts[(size_t)t].X, p0[(size_t)t].X, sizeof(double) * 3) ||
+                          pts[(size_t)t].n_views != p0[(size_t)t].n_views + tr.admitted || (pts[(size_t)t].status & ok) != ok || tr.admitted <= 0;
+                    for (size_t k = 0; k < n; ++k) {
+                        bad = bad || mask[b + k] < m0[b + k];
+                        rose += mask[b + k] - m0[b + k];
+                        if (any && mask[b + k] != m0[b + k]) bad = bad || !scope[(size_t)rank_of[(size_t)img[b + k]]];
+                    }
+                }
+                bad = bad || rose != c.admitted || c.candidates != c.admitted + c.rejected_by_depth + c.rejected_by_error;
+                std::printf("robust %d scope %zu pass %d: eligible %lld candidates %lld admitted %lld rejected %lld + %lld completed %lld\n", robust,
+                            any ? listed.size() : 0, pass, c.eligible, c.candidates, c.admitted, c.rejected_by_depth, c.rejected_by_error, c.completed);
+                if (pass == 1)   // the second call: not one byte, nothing admitted
+                    bad = bad || std::memcmp(pts.data(), p0.data(), pts.size() * sizeof(msfm_point3d)) ||
+                          std::memcmp(res.data(), r0.data(), res.size() * sizeof(double)) || std::memcmp(mask.data(), m0.data(), mask.size()) ||
+                          c.admitted + c.completed != 0;
+                else {
+                    admitted += c.admitted;
+                    completed += c.completed;
+                }
+            }
+        }
+    // Non-finite and huge keypoints in CANDIDATE positions: behind the same two states, every second candidate of
+    // an eligible track (counted over the job) gets each of the ten values -- x, y or both by turns -- the others their clean keypoint;
+    // the completion runs at the session's 60 px and at 10 px, each followed by a second call.  Checked: no replaced candidate is
+    // admitted (a non-finite value gives a NaN error, a huge one an error or a depth that fails), no record field is a NaN or an
+    // infinity, a NaN in a residual slot is THE NaN and sits in a replaced candidate's slot, the second call changes no byte.
+    const uint32_t values[10] = {0x7fc00000u, 0xffc00000u, 0x7fc00001u, 0x7f800000u, 0xff800000u, 0x7f61b1e6u /* 3e38 */, 0xff61b1e6u,
+                                 0x7149f2cau /* 1e30 */, 0x00000001u, 0x80000000u};
+    const double calls[2] = {prm.max_error, cmp_max_error};
+    long long replaced_rejected = 0, nan_slots = 0, beside = 0;
+    for (int robust = 0; robust < 2; ++robust) {
+        std::vector<msfm_point3d> pts0;
+        std::vector<double> res0;
+        std::vector<uint8_t> mask0;
+        filtered_state(robust, &pts0, &res0, &mask0);
+        const int unposed = rank[(size_t)(n_img - 1)];
+        for (int v = 0; v < 10; ++v)
+            for (const double call : calls) {
+                std::vector<std::vector<float>> kbad = clean;
+                std::vector<uint8_t> replaced(img.size(), 0);
+                float value;
+                std::memcpy(&value, &values[v], sizeof(value));
+                int seen = 0;
+                for (int j = 0; j < n_tr; ++j) {
+                    const size_t b = (size_t)offsets[(size_t)j], n = (size_t)offsets[(size_t)j + 1] - b;
+                    if (!cons[(size_t)j] || !msfm_ext::continues(pts0[(size_t)j])) continue;
+                    for (size_t k = 0; k < n; ++k) {
+                        const int r = rank_of[(size_t)img[b + k]];
+                        if (r == unposed || mask0[b + k]) continue;
+                        if (seen++ % 2) continue;
+                        const int axes = 1 + (j + v) % 3;   // 1: x, 2: y, 3: both
+                        if (axes & 1) kbad[(size_t)r][(size_t)(2 * j)] = value;
+                        if (axes & 2) kbad[(size_t)r][(size_t)(2 * j + 1)] = value;
+                        replaced[b + k] = 1;
+                    }
+                }
+                std::vector<const float*> pbad;
+                for (auto& k : kbad) pbad.push_back(k.data());
+                std::vector<msfm_point3d> pts = pts0;
+                std::vector<double> res = res0;
+                std::vector<uint8_t> mask = mask0;
+                for (int pass = 0; pass < 2; ++pass) {
+                    const std::vector<msfm_point3d> p0 = pts;
+                    const std::vector<double> r0 = res;
+                    const std::vector<uint8_t> m0 = mask;
+                    msfm_cmp::Counts c = {0, 0, 0, 0, 0, 0};
+                    msfm_cmp::CompletePoints(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), pbad.data(), table.data(), n_img,
+                                             nullptr, cam, prm, call, true, pts.data(), res.data(), mask.data(), &c);
+                    if (pass == 1) {
+                        bad = bad || std::memcmp(pts.data(), p0.data(), pts.size() * sizeof(msfm_point3d)) ||
+                              std::memcmp(res.data(), r0.data(), res.size() * sizeof(double)) || std::memcmp(mask.data(), m0.data(), mask.size()) ||
+                              c.admitted != 0;
+                        continue;
+                    }
+                    for (size_t o = 0; o < img.size(); ++o) {
+                        if (replaced[o]) {
+                            bad = bad || mask[o] != 0;
+                            replaced_rejected += 1;
+                        }
+                        if (res[o] != res[o]) {
+                            uint64_t bits;
+                            std::memcpy(&bits, &res[o], sizeof(bits));
+                            bad = bad || bits != 0x7ff8000000000000ull || !replaced[o];
+                            nan_slots += 1;
+                        }
+                    }
+                    beside += c.admitted;
+                    for (const msfm_point3d& r : pts)
+                        bad = bad || !std::isfinite(r.X[0]) || !std::isfinite(r.X[1]) || !std::isfinite(r.X[2]) || !std::isfinite(r.mean_residual) ||
+                              !std::isfinite(r.tri_angle);
+                    std::printf("robust %d value %08x at %.1f: eligible %lld candidates %lld admitted %lld rejected %lld + %lld completed %lld\n", robust,
+                                (unsigned)values[v], call, c.eligible, c.candidates, c.admitted, c.rejected_by_depth, c.rejected_by_error, c.completed);
+                }
+            }
+    }
+    std::printf("admitted %lld in %lld records; replaced candidates rejected %lld (admitted beside them %lld), NaN slots %lld, %s\n", admitted,
+                completed, replaced_rejected, beside, nan_slots, bad ? "BAD" : "ok");
+    return admitted > 0 && completed > 0 && replaced_rejected > 0 && beside > 0 && !bad ? 0 : 1;
+}
