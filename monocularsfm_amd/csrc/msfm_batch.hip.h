@@ -483,7 +483,9 @@ struct PrefilterLaunch {
     PlanCounts pc = {};
     PlanOut po = {};
 
-    PrefilterLaunch(msfm_ctx* c, Batch& batch, size_t ev, PruneParams pr) : ctx(c), b(batch), ev_base(ev), prune(pr), route(batch.route) {}
+    PrefilterLaunch(msfm_ctx* c, Batch& batch, size_t ev, PruneParams pr) : ctx(c), b(batch), ev_base(ev), prune(pr), route(batch.route) {
+        prune.cap = msfm_ratio_cap_on(pr.prune, pr.ratio) ? 1 : 0;   // (a subset of route.compact(): the dense sweep 2 and ratios above 0.9 keep the uncapped thresholds)
+    }
 
     // ---- stage 1: the pairs' tables of each sweep for the sub-batch's route (byte stores, route Q, mixed sub-batches)
     int apply_route() {
@@ -924,7 +926,7 @@ struct PrefilterLaunch {
     if (!SC.keys_epilogue) {
         hipLaunchKernelGGL(pf_finalize_kernel, mgrid, dim3(256), 0, SC.stream, dp, dpf, (const float*)tuv, SC.d_best.as<unsigned long long>(),
                            SC.d_second.as<unsigned long long>(), SC.d_k_i0.as<int>(), SC.d_k_d0.as<float>(),
-                           SC.d_k_d1.as<float>(), SC.d_fix_count.as<int>(), SC.d_fix_list.as<int4>(), SC.fix_cap_eff);
+                           SC.d_k_d1.as<float>(), SC.d_fix_count.as<int>(), SC.d_fix_list.as<int4>(), SC.fix_cap_eff, prune.cap);
         HIPCHK(ctx, hipGetLastError());
         DBGSYNC(ctx, "pf_finalize_kernel");
     }

@@ -1,8 +1,9 @@
 // msfm_hostutil.h -- small pure functions shared by device and host code, compilable on their own (tests/test_hostutil.py builds a
 // g++ driver around them): the 4-byte packing of the integer sweeps' column partials, the cost marks of a call's sub-batches, the
 // scratch memory one image pair of a sub-batch needs, the matching route of a sub-batch, the fold of a candidate's key into a slot's
-// (best, second), the two-view model selection's rule.
+// (best, second), the ratio cap of the reverse thresholds and the order-invariance certificate, the two-view model selection's rule.
 #pragma once
+#include <cmath>
 #include <vector>
 
 #if defined(__HIPCC__)
@@ -347,6 +348,74 @@ MSFM_HD void msfm_fold_key(unsigned long long* best, unsigned long long* second,
         if (loser == ~0ull) return;
     }
     if (loser < seen_second) (void)amin(second, loser);
+}
+
+// ---- The order-invariance certificate (msfm_kernels.hip.h states the bound): two conforming fp32 builds of the distance differ by at
+// most a relative kOrderEps in any distance they report.
+constexpr double kOrderEps = 1.0e-5;
+constexpr float kNoNeighbour = 3.402823466e+38f;   // FLT_MAX: batchDistance's initial value -- "fewer than two neighbours"
+
+// ---- The ratio cap of the REVERSE thresholds (match lists with 0 < ratio <= 0.9: msfm_ratio_cap_on).  A column's second neighbour is
+// used for one thing only, the Lowe test d0 < ratio * d1; its value is never handed out.  The test -- and its certificate -- is decided
+// as soon as every element that can VIOLATE it is known: an element t != best with
+//        d0 (1 + e)  >=  ratio d_t (1 - e),      e = kOrderEps, d = the pinned fp32 distances.
+// So the threshold that collects a column's candidates need not reach the second neighbour (today's bound), only d0 / ratio -- on real
+// correspondences far less.  INVARIANT of the helpers below: every violator t has S~_t <= T (resp. a real distance <= the capped
+// bound), and so has the best element itself.  What follows from it (msfm_order_sensitive): if a column ends WITHOUT a second candidate
+// no violator exists -- the test passes under every conforming order; a second candidate that was found is >= the true second.
+// Where it applies: match lists with 0 < ratio <= kRatioCapMax = 0.9 -- a SUBSET of the compacted sweep 2 (ratio <= 0.95), not all of it.
+// The bound itself holds for every ratio < 1; the limit is one of scope.  With capped masks a live column is counted once per block
+// that holds a row within d0 / ratio of it, i.e. about once, and the first plan of a fresh context (msfm_plan_room: every row once for
+// a small sub-batch) then holds any data whose neighbours are unique.  tests/test_gpu_jobs.py reaches the re-run path of an outgrown
+// plan with exactly such data at ratio 0.95, through the uncapped masks; as long as that test stands as it is, ratios in (0.9, 0.95]
+// keep the uncapped thresholds (follow-ups).
+constexpr float kRatioCapMax = 0.9f;
+inline bool msfm_ratio_cap_on(int prune, float ratio) { return prune != 0 && ratio > 0.f && ratio <= kRatioCapMax; }
+
+// Distance space (route Q, direct thresholds).  u0 / u1: upper bounds of the REAL distance of the twins' nearest / second-nearest
+// element.  The pinned order is within g = 4e-6 relative of real arithmetic (msfm_kernels.hip.h), so the pinned d0 <= u0 (1 + g) and a
+// violator's real distance is <= d_t / (1 - g) <= u0 / ratio * (1 + e)(1 + g) / ((1 - e)(1 - g)) < u0 / ratio * (1 + 2.9e-5): the factor
+// 1 + 4 e leaves 1.1e-5 for the three roundings here (2e-7).  The best element: real distance <= u0 (1 + 2 g) < the cap (ratio < 1).
+MSFM_HD float msfm_ratio_cap_distance(float u0, float u1, float ratio) {
+    const float c = u0 / ratio * (1.f + 4.f * (float)kOrderEps);
+    return c < u1 ? c : u1;   // (a NaN keeps u1)
+}
+
+// S~ space, fp16 sweep (pf_thresholds_kernel).  s0: the column's smallest S~; eps >= |S~ - S| for every element (S: the pinned order's);
+// norms = the column's norm + the other image's largest (the scale of the roundings, as in today's slack).  The best element's
+// S <= s0 + eps; a violator's S_t = d_t^2 (1 +- 2^-23: d is a rounded sqrtf) <= S0 / ratio^2 * ((1 + e) / (1 - e))^2 (1 + 3e-7)
+// < S0 / ratio^2 * (1 + 4.1e-5) -- the factor 1 + 1e-4 covers it and the four roundings of c; its S~_t <= S_t + eps.
+MSFM_HD float msfm_ratio_cap_sweep(float s0, float eps, float norms, float ratio) {
+    const float tiny = 1e-5f * (fabsf(s0) + norms);
+    const float s0ub = fmaxf(s0 + eps + tiny, 0.f);
+    const float c = s0ub / (ratio * ratio) * (1.f + 1e-4f);
+    return c + eps + 1e-5f * (fabsf(c) + norms);
+}
+// Integer sweeps (byte images): S~ <= S <= S~ + eps, all of them integers; the cap is one too.
+MSFM_HD float msfm_ratio_cap_sweep_i8(float s0, float eps, float ratio) {
+    return ceilf(fmaxf(s0 + eps, 0.f) / (ratio * ratio) * (1.f + 1e-4f)) + eps;
+}
+
+// Which rows could come out differently under another conforming evaluation order?  (i0, d0, d1): the row's neighbour and its two
+// distances in the pinned order; the derivation is the comment block above order_sensitive (msfm_kernels.hip.h), which calls this.
+// d1 == +inf: a capped column without a second candidate -- no element can violate the ratio test under any order (the invariant
+// above), and the first neighbour is the same element under every order (a violator-free column has d0 (1 + e) < ratio d_t (1 - e)
+// < d_t (1 - e) for all t); what is left is the forward distance cut on d0.
+MSFM_HD bool msfm_order_sensitive(int i0, float d0, float d1, float ratio, double max_distance, bool forward) {
+    const bool no_violator = d1 == __builtin_huge_valf();
+    if (i0 < 0 || !(d1 < kNoNeighbour || no_violator)) return false;   // no match under any order (pruned with margin / < 2 neighbours)
+    const double lo0 = (double)d0 * (1.0 - kOrderEps), hi0 = (double)d0 * (1.0 + kOrderEps);
+    if (forward && lo0 > max_distance) return false;        // cut by FilterMatchesByDistance whatever the ratio test says
+    const bool cut_certified = !forward || hi0 <= max_distance || lo0 > max_distance;
+    if (no_violator) return !cut_certified;
+    const double lo1 = (double)d1 * (1.0 - kOrderEps), hi1 = (double)d1 * (1.0 + kOrderEps);
+    const bool pass = d0 < ratio * d1;
+    bool certified;
+    if (pass)
+        certified = hi0 < (double)ratio * lo1 && hi0 < lo1 && cut_certified;
+    else
+        certified = lo0 >= (double)ratio * hi1;
+    return !certified;
 }
 
 // The two-view model selection (msfm_set_model_selection): a pair keeps the homography's list iff the epipolar model (F or E) keeps

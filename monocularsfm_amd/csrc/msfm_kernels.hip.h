@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "msfm_hostutil.h"
 
 #pragma clang fp contract(off)
 
@@ -607,20 +608,25 @@ struct EpiParams {
 // Rows pruned by the prefilter are dead with a margin of eps >= 1.5e-3 (na + nb) >> gamma S (msfm_prefilter.hip.h).
 // Pairs of byte images are exact integers under every order.  Rows that are not certified are "order-sensitive";
 // zero of them in a call <=> the stored rows are identical under any conforming normL2Sqr_ build.
-constexpr double kOrderEps = 1.0e-5;
-
+//
+// Capped reverse thresholds (match lists with ratio <= 0.9; msfm_hostutil.h: msfm_ratio_cap_on, msfm_ratio_cap_*).  A column's candidates then
+// hold its best element and every element that can VIOLATE the ratio test, d0 (1+e) >= ratio d_t (1-e), not necessarily its true
+// second neighbour.  Two cases:
+//   no second candidate:  reported as d1 = +inf (FLT_MAX keeps meaning "fewer than two neighbours").  No element violates, so under
+//                         every order B  d0_B <= d0 (1+e) < ratio d_t (1-e) <= ratio d_t_B  for all t: the row passes, with the same
+//                         first neighbour -- certified, but for the forward distance cut on d0;
+//   a second candidate:   it is >= the true second neighbour.  Either the true second is itself a candidate -- then it is the one found,
+//                         and (d0, d1) are what the uncapped threshold gives -- or it is not: then it does not violate, and neither does
+//                         the found one (its distance is no smaller), so the row passes with d0 (1+e) < ratio d1 (1-e) for both values
+//                         of d1: the same decision and the same certificate (d0 (1+e) < d1 (1-e) follows, ratio < 1).
+// The kept match carries d0 only, so the lists, and order_sensitive_rows, are those of the uncapped thresholds on every route.
+// (kOrderEps and the function itself: msfm_hostutil.h, where a g++-built test drives it against the brute-force (d0, true d1).)
 __device__ __forceinline__ bool order_sensitive(int i0, float d0, float d1, float ratio, double max_distance, bool forward) {
-    if (i0 < 0 || !(d1 < 3.402823466e+38f)) return false;   // no match under any order (pruned with margin / < 2 neighbours)
-    const double lo0 = (double)d0 * (1.0 - kOrderEps), hi0 = (double)d0 * (1.0 + kOrderEps);
-    const double lo1 = (double)d1 * (1.0 - kOrderEps), hi1 = (double)d1 * (1.0 + kOrderEps);
-    if (forward && lo0 > max_distance) return false;        // cut by FilterMatchesByDistance whatever the ratio test says
-    const bool pass = d0 < ratio * d1;
-    bool certified;
-    if (pass)
-        certified = hi0 < (double)ratio * lo1 && hi0 < lo1 && (!forward || hi0 <= max_distance || lo0 > max_distance);
-    else
-        certified = lo0 >= (double)ratio * hi1;
-    return !certified;
+    return msfm_order_sensitive(i0, d0, d1, ratio, max_distance, forward);
+}
+// the Lowe test of the epilogue: m[0].distance < distance_ratio * m[1].distance, fp32 product, strict; d1 = +inf: proven pass (above)
+__device__ __forceinline__ bool lowe_keep(int i0, float d0, float d1, float ratio) {
+    return (i0 >= 0) && (d1 < kNoNeighbour || d1 == f_inf()) && (d0 < ratio * d1);
 }
 
 // Where the epilogue takes a row's (idx0, d0, d1) from: the final kNN arrays (brute-force route, knnMatch-level API, tie fix-up), or --
@@ -631,7 +637,7 @@ struct KnnFromArrays {
     const int* i0;
     const float* d0;
     const float* d1;
-    __device__ __forceinline__ void get(long long slot, int& i, float& a, float& b) const {
+    __device__ __forceinline__ void get(long long slot, bool /*reverse*/, int& i, float& a, float& b) const {
         i = i0[slot];
         a = d0[slot];
         b = d1[slot];
@@ -641,13 +647,15 @@ struct KnnFromKeys {
     const float* tuv;
     const unsigned long long* best;
     const unsigned long long* second;
-    __device__ __forceinline__ void get(long long slot, int& i, float& a, float& b) const {
+    int cap;   // the reverse thresholds are capped (msfm_ratio_cap_on): a live column without a second candidate has no violator
+    __device__ __forceinline__ void get(long long slot, bool reverse, int& i, float& a, float& b) const {
         i = -1;
-        a = b = 3.402823466e+38f;
+        a = b = kNoNeighbour;
         if (tuv[slot] == -f_inf()) return;
         const unsigned long long kb = best[slot], ks = second[slot];
         if (kb != ~0ull) { i = (int)(unsigned)(kb & 0xffffffffu); a = sqrtf(__uint_as_float((unsigned)(kb >> 32))); }
         if (ks != ~0ull) b = sqrtf(__uint_as_float((unsigned)(ks >> 32)));
+        else if (cap && reverse && kb != ~0ull) b = f_inf();
     }
 };
 
@@ -677,15 +685,14 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const PairDesc* __restric
         float d0 = 0.f;
         if (q < pd.n1) {
             float d1;
-            knn.get(pd.kf_off + q, t, d0, d1);
-            // m[0].distance < distance_ratio * m[1].distance, fp32 product, strict
-            keep = (t >= 0) && (d1 < 3.402823466e+38f) && (d0 < prm.ratio * d1);
+            knn.get(pd.kf_off + q, false, t, d0, d1);
+            keep = lowe_keep(t, d0, d1, prm.ratio);
             sens = certify && order_sensitive(t, d0, d1, prm.ratio, prm.max_distance, true);
             if (keep && prm.cross_check) {
                 int rq;
                 float rd0, rd1;
-                knn.get(pd.kr_off + t, rq, rd0, rd1);
-                const bool rkeep = (rq >= 0) && (rd1 < 3.402823466e+38f) && (rd0 < prm.ratio * rd1);
+                knn.get(pd.kr_off + t, true, rq, rd0, rd1);
+                const bool rkeep = lowe_keep(rq, rd0, rd1, prm.ratio);
                 const int vis = rkeep ? rq : 0;  // unordered_map::operator[] default-inserts 0
                 keep = (vis == q);
             }
@@ -713,7 +720,7 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const PairDesc* __restric
             const int t = t0 + threadIdx.x;
             int ri = -1;
             float rd0 = 0.f, rd1 = 0.f;
-            if (t < pd.n2) knn.get(pd.kr_off + t, ri, rd0, rd1);
+            if (t < pd.n2) knn.get(pd.kr_off + t, true, ri, rd0, rd1);
             const bool s = t < pd.n2 && order_sensitive(ri, rd0, rd1, prm.ratio, prm.max_distance, false);
             const unsigned long long sb = __ballot(s);
             if (lane == 0 && sb) atomicAdd(&n_sens, __popcll(sb));

@@ -2,7 +2,8 @@
 //
 // After sweep 1 and pf_thresholds_kernel every row / column of every pair is either dead (it provably cannot yield a
 // match: threshold -inf) or alive, and for every live column a bit mask names the 512-row blocks of image 1 that can
-// hold a candidate of it.  Sweep 2 only multiplies live rows:
+// hold a candidate of it -- with the ratio cap of the column thresholds (msfm_prefilter.hip.h) the blocks with a row within
+// d0 / ratio of the column: on real correspondences the block of its best neighbour and no other.  Sweep 2 only multiplies live rows:
 //
 //   forward group  (streamed image j):             the live ROWS of image i of every pair (i, j) of the batch, one after
 //                                                  the other, against ALL tiles of image j;

@@ -9,7 +9,8 @@
 //                              v_mfma_f32_32x32x16_f16 -- the norms ride in a ninth k-step (below), so the
 //                              accumulator IS -S~/2; per row / column the two smallest S~ values.
 //   thresholds_kernel          T = S~(2) + 2*eps, eps = rigorous bound on |S~ - S_exact| (below); rows /
-//                              columns that provably cannot match get T = -inf (match lists only).
+//                              columns that provably cannot match get T = -inf (match lists only).  Match lists with
+//                              ratio <= 0.9: a live COLUMN's T is capped at the S~ of d0 / ratio (below).
 //   sweep 2  sweep_kernel<3>   live rows of one image (compacted) against the other image, per direction:
 //                              the row threshold rides in the ninth k-step too, a hit is accumulator >= 0;
 //            sweep_kernel<2>   dense variant (nothing pruned): S~ <= T_row[q] or S~ <= T_col[t];
@@ -22,6 +23,18 @@
 // elements with the smallest S~ have S_exact <= S~(2) + eps, so the true second-smallest S_exact is
 // <= S~(2) + eps.  A non-candidate has S~ > S~(2) + 2 eps, hence S_exact > S~(2) + eps: strictly
 // worse than the true second neighbour, so it can neither enter the top-2 nor tie with it.
+//
+// The ratio cap (reverse direction, match lists with 0 < ratio <= 0.9: msfm_ratio_cap_on, which says why not up to 0.95).  A column's second neighbour only decides
+// the Lowe test d0 < ratio * d1 -- its value is never handed out -- and only an element within d0 / ratio of the column can make that
+// test fail.  So a live column's threshold is T = min(S~(2) + 2 eps, cap), cap = the S~ bound of an exact S <= (S~min + eps) / ratio^2
+// (msfm_hostutil.h: msfm_ratio_cap_sweep / _sweep_i8 / _distance state it once, with the roundings, for the three thresholds kernels'
+// branches; tests/test_ratio_cap_host.py drives them against an fp64 statement of "every element that can violate the test is a
+// candidate").  On real correspondences d0 / ratio is far below the second neighbour: a live column keeps ~1 candidate instead of ~4
+// and its block mask names the one 512-row block of its best neighbour instead of every second block (tools/ratio_cap_study.py).  A
+// live column that ends WITHOUT a second candidate has no violator: pf_finalize_kernel / KnnFromKeys report d1 = +inf, the epilogue
+// passes it, the order certificate certifies it (msfm_kernels.hip.h, above order_sensitive).  The forward thresholds stay uncapped:
+// tests/test_gpu_q8.py requires the refined route to collect FEWER candidates than the direct one, and with both directions capped
+// both routes would keep exactly one per live row on clean data (the known follow-up: DESIGN.md 5.1.1).
 //
 // eps.  a~ = fl16(a) (round to nearest): |a~_c - a_c| <= max(2^-11 |a_c|, 2^-25).  MFMA products of
 // two fp16 values are exact in fp32; the fp32 accumulation of 128 terms errs by at most
@@ -130,6 +143,7 @@ struct PruneParams {
     int prune;
     float ratio;
     float max_distance;  // rounded up to float
+    int cap;             // cap the reverse thresholds at d0 / ratio (set by PrefilterLaunch: msfm_ratio_cap_on)
 };
 
 __device__ __forceinline__ bool pf_dead(float s0, float s1, float nrm, float eps, float other_max, PruneParams pr) {
@@ -235,7 +249,11 @@ __global__ void pf_thresholds_kernel(const PairDesc* __restrict__ pairs, const P
         const float eps = pp.i8 ? kI8Eps : kEpsRel * (nb_ + pp.a_nrm_max) + kEpsAbs * (sqrtf(nb_) + sqrtf(pp.a_nrm_max)) + eps_norm;
         const float slack = pp.i8 ? 2.f * eps : 2.f * eps + 1e-5f * (fabsf(s1) + nb_ + pp.a_nrm_max);
         const bool live = (e < pd.n2) && !pf_dead(s0, s1, nb_, eps, pp.a_nrm_max, pr);
-        const float T = live ? s1 + slack : -f_inf();
+        // match lists: the column's second neighbour only decides the Lowe test, and only an element within d0 / ratio of the column can
+        // fail it -- the threshold (and with it the block mask below) need not reach further (msfm_hostutil.h: msfm_ratio_cap_*)
+        float T = live ? s1 + slack : -f_inf();
+        if (live && pr.cap)
+            T = fminf(T, pp.i8 ? msfm_ratio_cap_sweep_i8(s0, eps, pr.ratio) : msfm_ratio_cap_sweep(s0, eps, nb_ + pp.a_nrm_max, pr.ratio));
         tv[pp.tv_off + e] = T;
         if (colmask) {
             // which 512-row blocks of image 1 can hold a candidate of this column at all: the block's smallest S~ must
@@ -550,7 +568,8 @@ __global__ void pf_finalize_kernel(const PairDesc* __restrict__ pairs, const PfP
                                    const float* __restrict__ tuv,
                                    const unsigned long long* __restrict__ best, const unsigned long long* __restrict__ second,
                                    int* __restrict__ k_i0, float* __restrict__ k_d0, float* __restrict__ k_d1,
-                                   int* __restrict__ fix_count, int4* __restrict__ fix_list, int fix_cap) {
+                                   int* __restrict__ fix_count, int4* __restrict__ fix_list, int fix_cap,
+                                   int cap /* capped reverse thresholds: a live column without a second candidate -> d1 = +inf */) {
     MSFM_TAIL_PRIO();
     const PairDesc pd = pairs[blockIdx.y];
     const PfPair pp = pf[blockIdx.y];
@@ -568,6 +587,7 @@ __global__ void pf_finalize_kernel(const PairDesc* __restrict__ pairs, const PfP
         float d0 = 3.402823466e+38f, d1 = 3.402823466e+38f;
         if (b != ~0ull) { i0 = (int)(unsigned)(b & 0xffffffffu); d0 = sqrtf(__uint_as_float((unsigned)(b >> 32))); }
         if (s != ~0ull) d1 = sqrtf(__uint_as_float((unsigned)(s >> 32)));
+        else if (cap && dir == 1 && i0 >= 0) d1 = f_inf();   // no element can violate the ratio test (KnnFromKeys::get)
         k_i0[ko] = i0;
         k_d0[ko] = d0;
         k_d1[ko] = d1;

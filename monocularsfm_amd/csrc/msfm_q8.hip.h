@@ -23,8 +23,13 @@
 //   sweep 1     sweep_i8_kernel<1> on the twins, every descriptor pair of the batch               (the dominant kernel)
 //   prune       pf_prune_q8_kernel(direct): live / dead, T = U1^2 + eps_fp16 per live row / column, the block masks of the
 //               reverse direction from the twins' per-block column minima, the live counts of the plan
-//   plan, sweep 2 (fp16), exact re-check, ...   as on the fp16 route.  4.9 candidates per live row instead of 2.5, mask density
-//               0.50 instead of 0.24 -- and no sweep 1' (12 candidates per live row at s = 255: hence the adaptive scale).
+//               Live COLUMNS (match lists, ratio <= 0.9): the bound is min(U1, U0 / ratio) -- U0 the same upper bound for the nearest twin -- for
+//               the threshold and the block mask alike: nothing beyond d0 / ratio can fail the column's Lowe test
+//               (msfm_ratio_cap_distance, msfm_hostutil.h; msfm_prefilter.hip.h "The ratio cap")
+//   plan, sweep 2 (fp16), exact re-check, ...   as on the fp16 route.  Forward: 4.9 candidates per live row instead of 2.5 -- and no
+//               sweep 1' (12 candidates per live row at s = 255: hence the adaptive scale).  Reverse: with the cap ~1 candidate per
+//               live column and one 512-row block per mask (mask density 0.50 uncapped -- 0.24 on the fp16 route; the float64 model
+//               of tools/ratio_cap_study.py gives 0.46 -> 0.10 -- and sweep 2's work 0.102 -> 0.072 of sweep 1's on the bench job).
 // COARSE twins (values beyond 0.625; MSFM_Q8_DIRECT=0 forces it) -- the live rows get an fp16 sweep 1 of their own first:
 //   sweep 1, prune (live / dead only)
 //   plan A      the compacted-sweep plan (msfm_plan.hip.h) with every live column in EVERY 512-row block group
@@ -137,8 +142,10 @@ __global__ void pf_prune_q8_kernel(const PairDesc* __restrict__ pairs, const PfP
             col_bits = live ? (bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u)) : 0u;
         } else {
             // the blocks of image 1 that can hold a candidate of this column: the block's nearest row may be as close as
-            // lower(block minimum), a candidate is at most U1 away
-            const float u1 = live ? upper(s1, err) : 0.f;
+            // lower(block minimum), a candidate is at most U1 away -- match lists, ratio <= 0.9: at most min(U1, U0 / ratio), U0 the bound of the
+            // nearest twin's real distance: nothing further away can fail the column's Lowe test (msfm_ratio_cap_distance)
+            float u1 = live ? upper(s1, err) : 0.f;
+            if (live && pr.cap) u1 = msfm_ratio_cap_distance(upper(s0, err), u1, pr.ratio);
             tuv[pp.tv_off + e] = live ? threshold(u1, ld_bnrm, pp.a_nrm_max) : -f_inf();
             if (live) {
                 if (nb <= 16) {
