@@ -117,11 +117,7 @@ inline void CompletePoints(const int64_t* offsets, const int32_t* image_ids, con
         const int64_t b = offsets[t], e = offsets[t + 1];
         const int n = (int)(e - b);
         const msfm_tri::HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
-        if (!have_mask)
-            for (int k = 0; k < n; ++k) {
-                const msfm_tri::Pose* p = a.pose(k);
-                mask[b + k] = msfm_ext::plain_byte(points[t], p, p ? (int)(p - poses) : 0, gained.data());
-            }
+        if (!have_mask) msfm_ext::plain_bytes(a, n, points[t], gained.data(), mask + b);
         Trace tr = {KIND_NOT_ELIGIBLE, 0, 0, 0};
         if (consistent[t] && msfm_ext::continues(points[t])) {
             obs.resize((size_t)n);

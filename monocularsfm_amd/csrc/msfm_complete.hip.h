@@ -3,10 +3,9 @@
 // CompletePoints: the same bits.  Included by msfm_match.hip behind msfm_filter.hip.h; like it, it launches msfm_extend.hip.h's
 // ext_mask_kernel and msfm_refine.hip.h's ref_obs_kernel unchanged.
 //
-// Everything runs on the library's stream between HIP events; the host waits once, at the end.
-//   ext_mask_kernel    (msfm_extend.hip.h) with an all-zero `gained`; launched only on a session without inlier bytes.
-//   ref_obs_kernel     (msfm_refine.hip.h) under the session's pose table and the current bytes.
-//   cmp_track_kernel   one lane per kept track, a wave-uniform grid-stride loop, 256 threads, no LDS, the shape of flt_track_kernel.
+// The call runs inside msfm_extend.hip.h's MapEditFrame ("the map-edit call frame"), with an all-zero `gained`:
+// the frame prepares the inlier bytes and the per-observation array and holds the failure rule; the host waits once, at the end.
+//   cmp_track_kernel  one lane per kept track, a wave-uniform grid-stride loop, 256 threads, no LDS, the shape of flt_track_kernel.
 //                      A lane of a track that is not eligible only counts its record; the others run msfm_cmp::complete_track, which
 //                      sets OBS_FIT of the observations it admits in the call's own Obs array.  Lanes diverge by their tracks'
 //                      lengths and kinds: nothing is exchanged between them before the counters, which go through wave_add_counters.
@@ -67,87 +66,26 @@ int complete_impl(msfm_ctx* ctx, const msfm_complete_params* params, const int32
     if (max_error > ts.tri_prm.max_error)
         return fail(ctx, MSFM_E_INVALID, who + ": max_error must not exceed the session's: an admitted observation would clear ERROR_OK");
     if (n_images < 0 || (n_images > 0 && !image_ids)) return fail(ctx, MSFM_E_INVALID, who + ": bad list of images");
-    const int n_img = (int)ts.nd.ids.size();
-    std::vector<unsigned char> scope((size_t)std::max(n_img, 1), 0), gained((size_t)std::max(n_img, 1), 0);
-    for (int k = 0; k < n_images; ++k) {
-        const int id = image_ids[k];
-        if (!ts.declares(id)) return fail(ctx, MSFM_E_INVALID, who + ": image not declared in the session: " + std::to_string(id));
-        const int r = ts.rank_of[(size_t)id];
-        if (scope[(size_t)r]) return fail(ctx, MSFM_E_INVALID, who + ": an image is given twice: " + std::to_string(id));
-        scope[(size_t)r] = 1;
+    std::vector<unsigned char> scope;
+    if (const int rc = rank_bytes(ctx, image_ids, n_images, who + ": image not declared in the session: ", who + ": an image is given twice: ", &scope))
+        return rc;
+    const std::vector<unsigned char> gained(scope.size(), 0);   // no image gains a pose in this call
+    MapEditFrame fr(ctx, who);
+    if (const int rc = fr.begin(ts.tri_ids, ts.tri_poses, {&scope, &gained}, sizeof(CmpCounters))) return rc;
+    if (const int rc = fr.observe(fr.d_bytes(1))) return rc;
+    if (fr.live()) {
+        hipLaunchKernelGGL(cmp_track_kernel, dim3(fr.grid), dim3(256), 0, fr.st, (const long long*)ts.r_offsets.as<long long>(),
+                           (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)fr.T, fr.obs.as<msfm_ref::Obs>(), fr.pt.d_poses(),
+                           n_images > 0 ? fr.d_bytes(0) : (const unsigned char*)nullptr, (fr.pt.cam.fx + fr.pt.cam.fy) / 2.0, max_error,
+                           msfm_ref::Verdict{fr.prm.max_error, fr.prm.min_angle}, ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(),
+                           ts.t_mask.as<unsigned char>(), fr.counters.as<CmpCounters>());
+        fr.wrote(hipGetLastError());
     }
-    const msfm_tri::Params prm = {ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0};
-    std::vector<msfm_pose_rt> by_rank;
-    std::vector<TriImage> table;
-    if (const int rc = tri_tables(ctx, who, &ts.tri_camera, ts.tri_ids.data(), ts.tri_poses.data(), (int)ts.tri_ids.size(), prm, &by_rank, &table))
-        return rc;   // (a posed image lost its keypoints: still nothing of the session is touched)
-    // every check has passed: the registrations and the pose refinement's records are gone, they describe the map as it was
-    ts.reg_valid = ts.rp_valid = false;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const bool had_mask = ts.mask_valid;
-    const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
-    PoseTables pt;   // (the temporaries are freed when the call returns, whatever it returns)
-    struct {
-        TmpBuf bytes, counters, obs;
-    } t;
-    TmpEvents<3> ev;
-    hipStream_t st = store_stream(ctx);
-    HIPCHK(ctx, ev.create());
-    HIPCHK(ctx, t.bytes.ensure(2 * scope.size()));   // the scope | the all-zero `gained`
-    HIPCHK(ctx, t.counters.ensure(sizeof(CmpCounters)));
-    HIPCHK(ctx, t.obs.ensure((size_t)std::max<long long>(1, O) * sizeof(msfm_ref::Obs)));
-    HIPCHK(ctx, ts.t_mask.ensure((size_t)std::max<long long>(1, O)));
-    HIPCHK(ctx, pt.upload(ts.tri_camera, by_rank, table, n_img));
-    // (synchronous copies of the small tables: nothing queued reads host memory that an early return below would free)
-    unsigned char* d_scope = t.bytes.as<unsigned char>();
-    unsigned char* d_gained = d_scope + scope.size();
-    HIPCHK(ctx, hipMemcpy(d_scope, scope.data(), scope.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(d_gained, gained.data(), gained.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(CmpCounters), st));
-    HIPCHK(ctx, hipEventRecord(ev[0], st));
-    HIPCHK(ctx, pt.prepare(st));
-    const msfm_emat::Camera cam = pt.cam;
-    const unsigned grid = tk_grid(ctx, T);
-    hipError_t queued = hipSuccess;   // from the first kernel that writes session memory on, an error drops the session's points
-    auto wrote = [&](hipError_t e) {
-        if (e != hipSuccess && queued == hipSuccess) queued = e;
-        return e == hipSuccess;
-    };
-    if (T > 0 && O > 0) {
-        if (!had_mask) {
-            hipLaunchKernelGGL(ext_mask_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
-                               (const int*)ts.r_img.as<int>(), (int)T, pt.d_table(), pt.d_poses(), (const unsigned char*)d_gained,
-                               (const msfm_point3d*)ts.t_points.as<msfm_point3d>(), ts.t_mask.as<unsigned char>());
-            wrote(hipGetLastError());
-        }
-        if (queued == hipSuccess) {
-            hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
-                               pt.d_table(), pt.d_poses(), (const unsigned char*)ts.t_mask.as<unsigned char>(), cam,
-                               t.obs.as<msfm_ref::Obs>());
-            wrote(hipGetLastError());
-        }
-    }
-    if (queued == hipSuccess) wrote(hipEventRecord(ev[1], st));
-    if (T > 0 && O > 0 && queued == hipSuccess) {
-        hipLaunchKernelGGL(cmp_track_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
-                           (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)T, t.obs.as<msfm_ref::Obs>(), pt.d_poses(),
-                           n_images > 0 ? (const unsigned char*)d_scope : (const unsigned char*)nullptr, (cam.fx + cam.fy) / 2.0, max_error,
-                           msfm_ref::Verdict{prm.max_error, prm.min_angle}, ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(),
-                           ts.t_mask.as<unsigned char>(), t.counters.as<CmpCounters>());
-        wrote(hipGetLastError());
-    }
-    if (queued == hipSuccess) wrote(hipEventRecord(ev[2], st));
-    const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
-    wrote(done);
-    if (queued != hipSuccess) ts.tri_valid = ts.mask_valid = false;   // (the records and the bytes may be half rewritten)
-    HIPCHK(ctx, queued);
-    ts.mask_valid = true;
+    if (const int rc = fr.finish()) return rc;
     CmpCounters hc = {};
-    HIPCHK(ctx, hipMemcpy(&hc, t.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
-    float prep_ms = 0.f, all_ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, ev[0], ev[1]));
-    HIPCHK(ctx, hipEventElapsedTime(&all_ms, ev[0], ev[2]));
+    HIPCHK(ctx, hipMemcpy(&hc, fr.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
     msfm_complete_stats s = {};
+    HIPCHK(ctx, fr.elapsed(&s.prepare_ms, &s.complete_ms));
     s.eligible = (int64_t)hc.eligible;
     s.candidates = (int64_t)hc.candidates;
     s.admitted = (int64_t)hc.admitted;
@@ -156,10 +94,9 @@ int complete_impl(msfm_ctx* ctx, const msfm_complete_params* params, const int32
     s.completed = (int64_t)hc.completed;
     s.succeeded = (int64_t)hc.succeeded;
     s.observations_used = (int64_t)hc.observations_used;
-    s.complete_ms = all_ms;
-    s.prepare_ms = prep_ms;
     if (stats) *stats = s;
     return MSFM_OK;
 }
 
 }  // namespace
+

@@ -117,6 +117,14 @@ struct Counts {
     long long tracks_touched, continued, observations_added, observations_rejected, created_attempted, created, retried;
 };
 
+// the bytes of one track (a: its n elements) on a session without them: plain_byte of every element under a's pose table
+inline void plain_bytes(const msfm_tri::HostTrack& a, int n, const msfm_point3d& r, const uint8_t* gained, uint8_t* mask) {
+    for (int k = 0; k < n; ++k) {
+        const msfm_tri::Pose* p = a.pose(k);
+        mask[k] = plain_byte(r, p, p ? (int)(p - a.poses) : 0, gained);   // (without a pose the rank is not read)
+    }
+}
+
 // tracks, rank_of_id, kxy as TriangulateTracks takes them; poses: the ENLARGED table by rank; gained: one byte per rank; prm: the
 // thresholds of the triangulation that made the points; max_hypotheses: 0 = the plain route for created tracks, 1 .. 1024 = the robust
 // one.  points / residuals / mask: read and rewritten in place; have_mask false: the bytes of the tracks of this call are created
@@ -134,11 +142,7 @@ inline void ExtendPoints(const int64_t* offsets, const int32_t* image_ids, const
         const int64_t b = offsets[t], e = offsets[t + 1];
         const int n = (int)(e - b);
         const msfm_tri::HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
-        if (!have_mask)
-            for (int k = 0; k < n; ++k) {
-                const msfm_tri::Pose* p = a.pose(k);
-                mask[b + k] = plain_byte(points[t], p, p ? (int)(p - poses) : -1, gained);
-            }
+        if (!have_mask) plain_bytes(a, n, points[t], gained, mask + b);
         obs.resize((size_t)n);
         msfm_ref::host_obs(a, n, mask + b, cam, obs.data());
         const int fresh = consistent[t] ? new_observations(obs.data(), n, gained) : 0;

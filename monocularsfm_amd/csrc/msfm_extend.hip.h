@@ -105,6 +105,107 @@ __global__ __launch_bounds__(256) void ext_mark_kernel(const int* __restrict__ l
 
 namespace {
 
+// The frame of one map-edit call (msfm_extend_points, msfm_filter_points, msfm_complete_points): what the
+// three own for the length of the call, the order of their work on the library's stream, and their failure rule.  A call checks its
+// own parameters, then runs begin, observe, its track kernel(s) through `wrote`, and finish, and maps its counters to its stats.
+// Until the first kernel that writes session memory is queued an error returns at once; from then on `queued` latches the first
+// error, nothing more is launched, and finish still waits before it fails (the temporaries die with the frame).
+struct MapEditFrame {
+    msfm_ctx* const ctx;
+    TrackSession& ts;
+    const std::string who;
+    const hipStream_t st;
+    const long long T, O;          // the session's kept tracks and observations
+    const unsigned grid;           // of a kernel with one lane per kept track
+    const msfm_tri::Params prm;    // the thresholds of the triangulation that made the points
+    bool had_mask = false;
+    PoseTables pt;
+    TmpBuf bytes, counters, obs;   // the caller's byte tables one behind the other | its counters | ref_obs_kernel's array
+    TmpEvents<3> ev;
+    hipError_t queued = hipSuccess;
+
+    MapEditFrame(msfm_ctx* c, const std::string& name)
+        : ctx(c), ts(c->tracks), who(name), st(store_stream(c)), T(ts.stats.tracks_kept), O(ts.stats.observations_kept), grid(tk_grid(c, T)),
+          prm{ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0} {}
+
+    bool wrote(hipError_t e) {
+        if (e != hipSuccess && queued == hipSuccess) queued = e;
+        return e == hipSuccess;
+    }
+    // whether a kernel over the tracks is still to be launched
+    bool live() const { return T > 0 && O > 0 && queued == hipSuccess; }
+    // table k of begin's `tables` on the device
+    const unsigned char* d_bytes(size_t k) const { return bytes.as<unsigned char>() + k * std::max<size_t>(ts.nd.ids.size(), 1); }
+
+    // The pose list the call runs under (the session's, or extend's enlarged one) passes tri_tables' checks, which still leave the
+    // session untouched.  Then the registrations and the pose refinement's records are gone, the temporaries exist, the small tables
+    // (`tables`: one byte per rank each) are on the device and the counters are zeroed on the stream.  `more`: a buffer of the caller's
+    // own that is allocated among the frame's.
+    int begin(const std::vector<int32_t>& ids, const std::vector<msfm_pose_rt>& list, std::initializer_list<const std::vector<unsigned char>*> tables,
+              size_t counter_bytes, TmpBuf* more = nullptr, size_t more_bytes = 0) {
+        std::vector<msfm_pose_rt> by_rank;
+        std::vector<TriImage> table;
+        if (const int rc = tri_tables(ctx, who, &ts.tri_camera, ids.data(), list.data(), (int)ids.size(), prm, &by_rank, &table))
+            return rc;   // (a posed image of the session lost its keypoints)
+        // every check has passed: the registrations and the pose refinement's records describe the map as it was
+        ts.reg_valid = ts.rp_valid = false;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        had_mask = ts.mask_valid;
+        HIPCHK(ctx, ev.create());
+        HIPCHK(ctx, bytes.ensure(tables.size() * by_rank.size()));
+        HIPCHK(ctx, counters.ensure(counter_bytes));
+        HIPCHK(ctx, obs.ensure((size_t)std::max<long long>(1, O) * sizeof(msfm_ref::Obs)));
+        if (more) HIPCHK(ctx, more->ensure(more_bytes));
+        HIPCHK(ctx, ts.t_mask.ensure((size_t)std::max<long long>(1, O)));
+        HIPCHK(ctx, pt.upload(ts.tri_camera, by_rank, table, (int)ts.nd.ids.size()));
+        // (synchronous copies, like upload's: nothing queued reads host memory that an early return would free)
+        size_t k = 0;
+        for (const std::vector<unsigned char>* b : tables)
+            HIPCHK(ctx, hipMemcpy(bytes.as<unsigned char>() + k++ * b->size(), b->data(), b->size(), hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemsetAsync(counters.p, 0, counter_bytes, st));
+        return MSFM_OK;
+    }
+
+    // ev[0], the prepared poses, the inlier bytes where the session had none (ext_mask_kernel under `d_gained`, one byte per rank),
+    // the per-observation array under them, ev[1]
+    int observe(const unsigned char* d_gained) {
+        HIPCHK(ctx, hipEventRecord(ev[0], st));
+        HIPCHK(ctx, pt.prepare(st));
+        if (T > 0 && O > 0) {
+            if (!had_mask) {
+                hipLaunchKernelGGL(ext_mask_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
+                                   (const int*)ts.r_img.as<int>(), (int)T, pt.d_table(), pt.d_poses(), d_gained,
+                                   (const msfm_point3d*)ts.t_points.as<msfm_point3d>(), ts.t_mask.as<unsigned char>());
+                wrote(hipGetLastError());
+            }
+            if (queued == hipSuccess) wrote(launch_ref_obs(ctx, pt, ts.t_mask.as<unsigned char>(), obs.as<msfm_ref::Obs>(), st));
+        }
+        if (queued == hipSuccess) wrote(hipEventRecord(ev[1], st));
+        return MSFM_OK;
+    }
+
+    // ev[2] and the call's last wait.  An error latched since the first write drops the points and the bytes: they may be half
+    // rewritten.  Otherwise the session has inlier bytes from here on.
+    int finish() {
+        if (queued == hipSuccess) wrote(hipEventRecord(ev[2], st));
+        wrote(hipStreamSynchronize(st));
+        if (queued != hipSuccess) ts.tri_valid = ts.mask_valid = false;
+        HIPCHK(ctx, queued);
+        ts.mask_valid = true;
+        return MSFM_OK;
+    }
+
+    // after finish: ev[0] .. ev[1] and ev[0] .. ev[2]
+    hipError_t elapsed(double* prepare_ms, double* all_ms) const {
+        float prep = 0.f, all = 0.f;
+        hipError_t e = hipEventElapsedTime(&prep, ev[0], ev[1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&all, ev[0], ev[2]);
+        *prepare_ms = prep;
+        *all_ms = all;
+        return e;
+    }
+};
+
 int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* poses, int n_poses, const msfm_extend_params* params,
                 msfm_extend_stats* stats) {
     TrackSession& ts = ctx->tracks;
@@ -121,7 +222,7 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
     std::vector<msfm_pose_rt> list = ts.tri_poses;
     std::vector<unsigned char> gained((size_t)std::max(n_img, 1), 0), given((size_t)std::max(n_img, 1), 0);
     long long added = 0;
-    for (int k = 0; k < n_poses; ++k) {
+    for (int k = 0; k < n_poses; ++k) {   // (not rank_bytes: each id's own checks come before the next id's)
         const int id = image_ids[k];
         if (!ts.declares(id)) return fail(ctx, MSFM_E_INVALID, who + ": image not declared in the session: " + std::to_string(id));
         const int r = ts.rank_of[(size_t)id];
@@ -149,107 +250,57 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
         gained[(size_t)r] = 1;
         added += 1;
     }
-    const bool had_mask = ts.mask_valid;
-    const msfm_tri::Params prm = {ts.tri_prm.max_error, ts.tri_prm.min_angle, ts.tri_prm.min_views, 0};
-    std::vector<msfm_pose_rt> by_rank;
-    std::vector<TriImage> table;
-    if (const int rc = tri_tables(ctx, who, &ts.tri_camera, ids.data(), list.data(), (int)ids.size(), prm, &by_rank, &table))
-        return rc;   // (an OLD posed image lost its keypoints: still nothing of the session is touched)
-    // every check has passed: the registrations and the pose refinement's records are gone, they describe the map as it was
-    ts.reg_valid = ts.rp_valid = false;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const long long T = ts.stats.tracks_kept, O = ts.stats.observations_kept;
-    PoseTables pt;   // (the temporaries are freed when the call returns, whatever it returns)
-    struct {
-        TmpBuf gained, counters, obs, list, positions;
-    } t;
-    TmpEvents<3> ev;
-    hipStream_t st = store_stream(ctx);
-    HIPCHK(ctx, ev.create());
-    HIPCHK(ctx, t.gained.ensure(gained.size()));
-    HIPCHK(ctx, t.counters.ensure(sizeof(ExtCounters) + sizeof(TrrCounters)));   // this file's | the retry kernel's
-    HIPCHK(ctx, t.obs.ensure((size_t)std::max<long long>(1, O) * sizeof(msfm_ref::Obs)));
-    HIPCHK(ctx, t.list.ensure((size_t)(std::max<long long>(1, T) + 1) * sizeof(int)));   // the list | its length
-    HIPCHK(ctx, ts.t_mask.ensure((size_t)std::max<long long>(1, O)));
-    HIPCHK(ctx, pt.upload(ts.tri_camera, by_rank, table, n_img));
-    // (synchronous copies of the small tables: nothing queued reads host memory that an early return below would free)
-    HIPCHK(ctx, hipMemcpy(t.gained.p, gained.data(), gained.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemsetAsync(t.counters.p, 0, sizeof(ExtCounters) + sizeof(TrrCounters), st));
-    ExtCounters* d_ext = t.counters.as<ExtCounters>();
+    TmpBuf t_list, t_positions;   // the retry list | its length, and trr_retry_kernel's scratch (released behind the frame's events)
+    MapEditFrame fr(ctx, who);
+    const long long T = fr.T, O = fr.O;
+    hipStream_t st = fr.st;
+    if (const int rc = fr.begin(ids, list, {&gained}, sizeof(ExtCounters) + sizeof(TrrCounters),   // this file's counters | the retry kernel's
+                                &t_list, (size_t)(std::max<long long>(1, T) + 1) * sizeof(int)))   // the list | its length
+        return rc;
+    ExtCounters* d_ext = fr.counters.as<ExtCounters>();
     TrrCounters* d_trr = reinterpret_cast<TrrCounters*>(d_ext + 1);
-    int* d_list = t.list.as<int>();
+    int* d_list = t_list.as<int>();
     int* d_listed = d_list + std::max<long long>(1, T);
     HIPCHK(ctx, hipMemsetAsync(d_listed, 0, sizeof(int), st));
-    HIPCHK(ctx, hipEventRecord(ev[0], st));
-    HIPCHK(ctx, pt.prepare(st));
-    const msfm_emat::Camera cam = pt.cam;
-    const unsigned grid = tk_grid(ctx, T);
-    hipError_t queued = hipSuccess;   // from the first kernel that writes session memory on, an error drops the session's points
-    auto wrote = [&](hipError_t e) {
-        if (e != hipSuccess && queued == hipSuccess) queued = e;
-        return e == hipSuccess;
-    };
+    if (const int rc = fr.observe(fr.d_bytes(0))) return rc;
+    const PoseTables& pt = fr.pt;
     int listed = 0;
-    if (T > 0 && O > 0) {
-        if (!had_mask) {
-            hipLaunchKernelGGL(ext_mask_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
-                               (const int*)ts.r_img.as<int>(), (int)T, pt.d_table(),
-                               pt.d_poses(), (const unsigned char*)t.gained.as<unsigned char>(),
-                               (const msfm_point3d*)ts.t_points.as<msfm_point3d>(), ts.t_mask.as<unsigned char>());
-            wrote(hipGetLastError());
-        }
-        if (queued == hipSuccess) {
-            hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
-                               pt.d_table(), pt.d_poses(),
-                               (const unsigned char*)ts.t_mask.as<unsigned char>(), cam, t.obs.as<msfm_ref::Obs>());
-            wrote(hipGetLastError());
-        }
-    }
-    if (queued == hipSuccess) wrote(hipEventRecord(ev[1], st));
-    if (T > 0 && O > 0 && queued == hipSuccess) {
-        hipLaunchKernelGGL(ext_track_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
+    if (fr.live()) {
+        hipLaunchKernelGGL(ext_track_kernel, dim3(fr.grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(),
                            (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), (const unsigned char*)ts.r_cons.as<unsigned char>(), (int)T,
-                           (const msfm_ref::Obs*)t.obs.as<msfm_ref::Obs>(), pt.d_table(),
-                           pt.d_poses(), (const unsigned char*)t.gained.as<unsigned char>(), cam, prm,
+                           (const msfm_ref::Obs*)fr.obs.as<msfm_ref::Obs>(), pt.d_table(), pt.d_poses(), fr.d_bytes(0), pt.cam, fr.prm,
                            max_hyp > 0 ? 1 : 0, ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), d_list,
                            d_listed, d_ext);
-        wrote(hipGetLastError());
-        if (max_hyp > 0 && queued == hipSuccess) {
-            if (wrote(hipMemcpyAsync(&listed, d_listed, sizeof(int), hipMemcpyDeviceToHost, st)))
-                wrote(hipStreamSynchronize(st));   // the first wait: the length of the retry list
-            if (queued != hipSuccess) listed = 0;
+        fr.wrote(hipGetLastError());
+        if (max_hyp > 0 && fr.queued == hipSuccess) {
+            if (fr.wrote(hipMemcpyAsync(&listed, d_listed, sizeof(int), hipMemcpyDeviceToHost, st)))
+                fr.wrote(hipStreamSynchronize(st));   // the first wait: the length of the retry list
+            if (fr.queued != hipSuccess) listed = 0;
         }
     }
-    if (listed > 0 && wrote(t.positions.ensure((size_t)O * sizeof(int)))) {
-        const msfm_tri::RobustParams rp = {prm.max_error, prm.min_angle, prm.min_views, max_hyp};
+    if (listed > 0 && fr.wrote(t_positions.ensure((size_t)O * sizeof(int)))) {
+        const msfm_tri::RobustParams rp = {fr.prm.max_error, fr.prm.min_angle, fr.prm.min_views, max_hyp};
         const unsigned groups = (unsigned)((listed + kTrrWaves - 1) / kTrrWaves);
         const unsigned rgrid = std::min<unsigned>(groups, (unsigned)(kTrrGroupsPerCU * std::max(1, ctx->cu_count)));
         hipLaunchKernelGGL(trr_retry_kernel, dim3(rgrid), dim3(64 * kTrrWaves), 0, st, (const long long*)ts.r_offsets.as<long long>(),
                            (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), pt.d_table(),
-                           pt.d_poses(), cam, rp, (const int*)d_list, listed, t.positions.as<int>(),
+                           pt.d_poses(), pt.cam, rp, (const int*)d_list, listed, t_positions.as<int>(),
                            ts.t_points.as<msfm_point3d>(), ts.t_resid.as<double>(), ts.t_mask.as<unsigned char>(), d_trr);
-        if (wrote(hipGetLastError())) {
+        if (fr.wrote(hipGetLastError())) {
             hipLaunchKernelGGL(ext_mark_kernel, dim3((unsigned)((listed + 255) / 256)), dim3(256), 0, st, (const int*)d_list, listed,
                                ts.t_points.as<msfm_point3d>());
-            wrote(hipGetLastError());
+            fr.wrote(hipGetLastError());
         }
     }
-    if (queued == hipSuccess) wrote(hipEventRecord(ev[2], st));
-    const hipError_t done = hipStreamSynchronize(st);   // (before anything returns: the temporaries die with this function)
-    wrote(done);
-    if (queued != hipSuccess) ts.tri_valid = ts.mask_valid = false;   // (the records and the bytes may be half rewritten)
-    HIPCHK(ctx, queued);
+    if (const int rc = fr.finish()) return rc;
     ts.tri_ids.swap(ids);   // (the records describe the enlarged list from here on, whatever the copies below return)
     ts.tri_poses.swap(list);
-    ts.mask_valid = true;
     ExtCounters hc = {};
     TrrCounters hr = {};
     HIPCHK(ctx, hipMemcpy(&hc, d_ext, sizeof(hc), hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(&hr, d_trr, sizeof(hr), hipMemcpyDeviceToHost));
-    float prep_ms = 0.f, all_ms = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&prep_ms, ev[0], ev[1]));
-    HIPCHK(ctx, hipEventElapsedTime(&all_ms, ev[0], ev[2]));
     msfm_extend_stats s = {};
+    HIPCHK(ctx, fr.elapsed(&s.prepare_ms, &s.extend_ms));
     s.images_added = added;
     s.tracks_touched = (int64_t)hc.tracks_touched;
     s.continued = (int64_t)hc.continued;
@@ -260,10 +311,9 @@ int extend_impl(msfm_ctx* ctx, const int32_t* image_ids, const msfm_pose_rt* pos
     s.retried = (int64_t)hr.retried;
     s.succeeded = (int64_t)(hc.succeeded + hr.tri[5]);
     s.observations_used = (int64_t)(hc.observations_used + hr.tri[6]);
-    s.extend_ms = all_ms;
-    s.prepare_ms = prep_ms;
     if (stats) *stats = s;
     return MSFM_OK;
 }
 
 }  // namespace
+

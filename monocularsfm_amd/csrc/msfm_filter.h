@@ -162,11 +162,7 @@ inline void FilterPoints(const int64_t* offsets, const int32_t* image_ids, const
         const int64_t b = offsets[t], e = offsets[t + 1];
         const int n = (int)(e - b);
         const msfm_tri::HostTrack a{image_ids + b, point_idx + b, rank_of_id, kxy, poses};
-        if (!have_mask)
-            for (int k = 0; k < n; ++k) {
-                const msfm_tri::Pose* p = a.pose(k);
-                mask[b + k] = msfm_ext::plain_byte(points[t], p, p ? (int)(p - poses) : 0, gained.data());
-            }
+        if (!have_mask) msfm_ext::plain_bytes(a, n, points[t], gained.data(), mask + b);
         obs.resize((size_t)n);
         msfm_ref::host_obs(a, n, mask + b, cam, obs.data());
         Tally tl = {Trace{KIND_NOT_ELIGIBLE, 0, 0, 0}, 0};

@@ -84,6 +84,16 @@ __global__ __launch_bounds__(256) void ref_track_kernel(const long long* __restr
 
 namespace {
 
+// ref_obs_kernel over the session's kept observations (there are some) under the pose tables of a call; mask: the inlier bytes, or
+// nullptr on a plain session
+hipError_t launch_ref_obs(msfm_ctx* ctx, const PoseTables& pt, const unsigned char* mask, msfm_ref::Obs* obs, hipStream_t st) {
+    const TrackSession& ts = ctx->tracks;
+    const long long O = ts.stats.observations_kept;
+    hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
+                       pt.d_table(), pt.d_poses(), mask, pt.cam, obs);
+    return hipGetLastError();
+}
+
 int refine_impl(msfm_ctx* ctx, const msfm_refine_params* params, msfm_refine_stats* stats) {
     TrackSession& ts = ctx->tracks;
     const std::string who = "msfm_refine_points";
@@ -118,13 +128,8 @@ int refine_impl(msfm_ctx* ctx, const msfm_refine_params* params, msfm_refine_sta
     HIPCHK(ctx, hipEventRecord(ev[0], st));
     HIPCHK(ctx, pt.prepare(st));
     const msfm_emat::Camera cam = pt.cam;
-    if (T > 0 && O > 0) {
-        hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
-                           pt.d_table(), pt.d_poses(),
-                           had_mask ? (const unsigned char*)ts.t_mask.as<unsigned char>() : (const unsigned char*)nullptr, cam,
-                           obs.as<msfm_ref::Obs>());
-        HIPCHK(ctx, hipGetLastError());
-    }
+    if (T > 0 && O > 0)
+        HIPCHK(ctx, launch_ref_obs(ctx, pt, had_mask ? ts.t_mask.as<unsigned char>() : nullptr, obs.as<msfm_ref::Obs>(), st));
     HIPCHK(ctx, hipEventRecord(ev[1], st));
     if (T > 0) {
         hipLaunchKernelGGL(ref_track_kernel, dim3(grid), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(), (int)T,

@@ -213,14 +213,10 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
     if (prm.min_observations < 3) return fail(ctx, MSFM_E_INVALID, who + ": min_observations must be at least 3");
     if (n_fixed < 0 || (n_fixed > 0 && !fixed_ids)) return fail(ctx, MSFM_E_INVALID, who + ": bad list of fixed images");
     const int n_img = (int)ts.nd.ids.size();
-    std::vector<unsigned char> fixed((size_t)std::max(n_img, 1), 0);
-    for (int k = 0; k < n_fixed; ++k) {
-        const int id = fixed_ids[k];
-        if (!ts.declares(id)) return fail(ctx, MSFM_E_INVALID, who + ": fixed image not declared in the session: " + std::to_string(id));
-        const int r = ts.rank_of[(size_t)id];
-        if (fixed[(size_t)r]) return fail(ctx, MSFM_E_INVALID, who + ": a fixed image is given twice: " + std::to_string(id));
-        fixed[(size_t)r] = 1;
-    }
+    std::vector<unsigned char> fixed;
+    if (const int rc = rank_bytes(ctx, fixed_ids, n_fixed, who + ": fixed image not declared in the session: ",
+                                  who + ": a fixed image is given twice: ", &fixed))
+        return rc;
     // from here on the registrations and the previous records are gone, as after msfm_refine_points
     ts.reg_valid = ts.rp_valid = false;
     const bool had_mask = ts.mask_valid;
@@ -276,11 +272,7 @@ int refine_poses_impl(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
     const unsigned long long* keys2 = t.keys2.as<unsigned long long>();
     long long M = 0;
     if (T > 0 && O > 0) {
-        hipLaunchKernelGGL(ref_obs_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const int*)ts.r_img.as<int>(), (const int*)ts.r_idx.as<int>(), O,
-                           pt.d_table(), pt.d_poses(),
-                           had_mask ? (const unsigned char*)ts.t_mask.as<unsigned char>() : (const unsigned char*)nullptr, cam,
-                           t.obs.as<msfm_ref::Obs>());
-        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, launch_ref_obs(ctx, pt, had_mask ? ts.t_mask.as<unsigned char>() : nullptr, t.obs.as<msfm_ref::Obs>(), st));
         hipLaunchKernelGGL(rp_key_kernel, dim3(tk_grid(ctx, O)), dim3(256), 0, st, (const long long*)ts.r_offsets.as<long long>(), (int)T, O, d_obs,
                            d_points, (const unsigned char*)t.candidate.as<unsigned char>(), n_img, t.keys.as<unsigned long long>(), t.vals.as<int>());
         HIPCHK(ctx, hipGetLastError());

@@ -148,6 +148,21 @@ int tri_session_check(msfm_ctx* ctx, const std::string& who, bool needs_points) 
     return MSFM_OK;
 }
 
+// A caller's list of image ids as one byte per declared-image rank.  Per id, in this order: it is declared in the session (else
+// `undeclared`), it is not in the list already (else `twice`); both texts are the caller's own and the id is appended to them.
+int rank_bytes(msfm_ctx* ctx, const int32_t* ids, int n, const std::string& undeclared, const std::string& twice,
+               std::vector<unsigned char>* bytes) {
+    const TrackSession& ts = ctx->tracks;
+    bytes->assign(std::max<size_t>(ts.nd.ids.size(), 1), 0);
+    for (int k = 0; k < n; ++k) {
+        if (!ts.declares(ids[k])) return fail(ctx, MSFM_E_INVALID, undeclared + std::to_string(ids[k]));
+        unsigned char& b = (*bytes)[(size_t)ts.rank_of[(size_t)ids[k]]];
+        if (b) return fail(ctx, MSFM_E_INVALID, twice + std::to_string(ids[k]));
+        b = 1;
+    }
+    return MSFM_OK;
+}
+
 // What a call (`who`) checks of a camera, thresholds and a pose list before any device work, and the two tables it uploads: the
 // caller's poses by declared-image rank, the per-image-id entry of the kernels.  It reads the session and changes nothing of it.
 int tri_tables(msfm_ctx* ctx, const std::string& who, const msfm_camera* camera, const int32_t* image_ids, const msfm_pose_rt* poses,

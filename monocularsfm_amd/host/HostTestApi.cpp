@@ -607,31 +607,61 @@ int host_tracks_build(const int* ids, const int* rows, int n, int min_pair_match
 // msfm_triangulate_tracks takes it, cam = fx, fy, cx, cy, k1, k2, p1, p2.  Tracks [first, first + count) are computed and written at
 // their own positions of out_points / out_residuals (so that several threads can share one result).  Returns 0; 1: a pose's image is
 // not declared or given twice; 2: an image id outside [0, MSFM_MAX_IMAGES).
+// What every twin of the reconstruction stage makes of its raw arguments first: the rank of each declared image, the prepared pose of
+// each rank (invalid where the list has none), the rank of each entry of the pose list, and the camera.
+struct TwinScene {
+    std::vector<int> rank_of;
+    std::vector<msfm_tri::Pose> table;
+    std::vector<int> list_rank;
+    msfm_emat::Camera cam;
+    // the rank of a declared id, -1 for any other
+    int rank(int id) const { return (id >= 0 && id < MSFM_MAX_IMAGES) ? rank_of[(size_t)id] : -1; }
+};
+// Returns 0, or the twins' codes 2 and 1.
+static int twin_scene(const int* ids, int n_images, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const double* cam, TwinScene* s) {
+    s->rank_of.assign((size_t)MSFM_MAX_IMAGES, -1);
+    for (int k = 0; k < n_images; ++k) {
+        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
+        s->rank_of[(size_t)ids[k]] = k;   // (any one-to-one numbering serves the twin: the device's ranks never reach the output)
+    }
+    s->table.resize((size_t)std::max(n_images, 1));
+    s->list_rank.assign((size_t)std::max(n_poses, 1), 0);
+    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    const msfm_pose_rt none = {};
+    for (auto& p : s->table) msfm_tri::prepare_pose(none, &p);
+    for (int k = 0; k < n_poses; ++k) {
+        const int r = s->rank(pose_ids[k]);
+        if (r < 0 || given[(size_t)r]) return 1;
+        given[(size_t)r] = 1;
+        s->list_rank[(size_t)k] = r;
+        msfm_tri::prepare_pose(poses[k], &s->table[(size_t)r]);
+    }
+    s->cam = msfm_emat::Camera{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    return 0;
+}
+// A list of ids as one byte per rank; false (the twins' code 4) for an id that is not declared, is given twice or, with `posed`, has
+// no valid pose in the scene's table.
+static bool twin_rank_bytes(const TwinScene& s, const int* ids, int n, bool posed, std::vector<uint8_t>* bytes) {
+    bytes->assign(s.table.size(), 0);
+    for (int k = 0; k < n; ++k) {
+        const int r = s.rank(ids[k]);
+        if (r < 0 || (*bytes)[(size_t)r] || (posed && !s.table[(size_t)r].valid)) return false;
+        (*bytes)[(size_t)r] = 1;
+    }
+    return true;
+}
+
 int host_triangulate_tracks(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
                             const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
                             int n_poses, const double* cam, double max_error, double min_angle, int min_views, long long first,
                             long long count, msfm_point3d* out_points, double* out_residuals) {
-    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        rank_of[(size_t)ids[k]] = k;   // (any one-to-one numbering serves the twin: the device's ranks never reach the output)
-    }
-    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
-    const msfm_pose_rt none = {};
-    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
-        if (r < 0 || given[(size_t)r]) return 1;
-        given[(size_t)r] = 1;
-        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
-    }
-    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    TwinScene sc;
+    if (const int rc = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return rc;
     const msfm_tri::Params prm = {max_error, min_angle, min_views, 0};
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are int64");
     static_assert(sizeof(msfm_tri::RobustTrace) == 12 * sizeof(int), "the trace is twelve int32");
-    msfm_tri::TriangulateTracks(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(),
-                                kxy, table.data(), c, prm, out_points, out_residuals);
+    msfm_tri::TriangulateTracks(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(),
+                                kxy, sc.table.data(), sc.cam, prm, out_points, out_residuals);
     return 0;
 }
 
@@ -644,27 +674,13 @@ int host_triangulate_tracks_robust_trace(const long long* offsets, const int* im
                                          int n_poses, const double* cam, double max_error, double min_angle, int min_views,
                                          int max_hypotheses, long long first, long long count, msfm_point3d* out_points,
                                          double* out_residuals, unsigned char* out_mask, long long* counts4, int* out_trace) {
-    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        rank_of[(size_t)ids[k]] = k;
-    }
-    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
-    const msfm_pose_rt none = {};
-    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
-        if (r < 0 || given[(size_t)r]) return 1;
-        given[(size_t)r] = 1;
-        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
-    }
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
     if (max_hypotheses < 1 || max_hypotheses > 1024) return 3;
-    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
     const msfm_tri::RobustParams prm = {max_error, min_angle, min_views, max_hypotheses};
     msfm_tri::RobustCounts rc = {0, 0, 0, 0};
     msfm_tri::TriangulateTracksRobust(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count,
-                                      rank_of.data(), kxy, table.data(), c, prm, out_points, out_residuals, out_mask, &rc,
+                                      sc.rank_of.data(), kxy, sc.table.data(), sc.cam, prm, out_points, out_residuals, out_mask, &rc,
                                       reinterpret_cast<msfm_tri::RobustTrace*>(out_trace));
     if (counts4) {
         counts4[0] += rc.retried;
@@ -698,27 +714,13 @@ int host_refine_points(const long long* offsets, const int* image_ids, const int
                        msfm_point3d* points, double* residuals, const unsigned char* mask, long long* counts5, double* costs2,
                        void* out_trace) {
     static_assert(sizeof(msfm_ref::Trace) == 40 && sizeof(msfm_ref::Obs) == 24, "the trace is six int32 and two doubles");
-    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        rank_of[(size_t)ids[k]] = k;
-    }
-    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
-    const msfm_pose_rt none = {};
-    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
-        if (r < 0 || given[(size_t)r]) return 1;
-        given[(size_t)r] = 1;
-        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
-    }
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
     if (max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol)) return 3;
-    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
     msfm_ref::Counts rc = {0, 0, 0, 0, 0, 0.0, 0.0};
-    msfm_ref::RefinePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, first, count, rank_of.data(), kxy, table.data(),
-                           mask, c, msfm_ref::Verdict{max_error, min_angle}, msfm_ref::Params{step_tol, max_iters, 0}, points, residuals,
-                           &rc, static_cast<msfm_ref::Trace*>(out_trace));
+    msfm_ref::RefinePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, first, count, sc.rank_of.data(), kxy,
+                           sc.table.data(), mask, sc.cam, msfm_ref::Verdict{max_error, min_angle}, msfm_ref::Params{step_tol, max_iters, 0},
+                           points, residuals, &rc, static_cast<msfm_ref::Trace*>(out_trace));
     if (counts5) {
         counts5[0] += rc.eligible;
         counts5[1] += rc.refined;
@@ -746,41 +748,21 @@ int host_refine_poses(const long long* offsets, const int* image_ids, const int*
                       msfm_point3d* points, double* residuals, const unsigned char* mask, msfm_pose_refinement* out_records,
                       long long* counts9, double* costs2, void* out_trace) {
     static_assert(sizeof(msfm_ref::Trace) == 40 && sizeof(msfm_pose_refinement) == 48, "the trace is six int32 and two doubles");
-    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        rank_of[(size_t)ids[k]] = k;
-    }
-    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
-    std::vector<int> list_rank((size_t)std::max(n_poses, 1), 0);
-    const msfm_pose_rt none = {};
-    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
-        if (r < 0 || given[(size_t)r]) return 1;
-        given[(size_t)r] = 1;
-        list_rank[(size_t)k] = r;
-        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
-    }
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
     if (max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol) || min_observations < 3 || n_fixed < 0) return 3;
-    std::vector<uint8_t> fixed((size_t)std::max(n_images, 1), 0), changed((size_t)std::max(n_images, 1), 0);
-    for (int k = 0; k < n_fixed; ++k) {
-        const int r = (fixed_ids[k] >= 0 && fixed_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)fixed_ids[k]] : -1;
-        if (r < 0 || fixed[(size_t)r]) return 4;
-        fixed[(size_t)r] = 1;
-    }
-    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    std::vector<uint8_t> fixed, changed(sc.table.size(), 0);
+    if (!twin_rank_bytes(sc, fixed_ids, n_fixed, false, &fixed)) return 4;
     msfm_rp::Counts rc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
-    msfm_rp::RefinePoses(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, rank_of.data(), kxy, table.data(),
-                         n_images, mask, c, msfm_ref::Verdict{max_error, min_angle}, msfm_rp::Params{step_tol, max_iters, min_observations},
-                         list_rank.data(), pose_ids, n_poses, fixed.data(), points, residuals, out_records, changed.data(), &rc,
+    msfm_rp::RefinePoses(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, sc.rank_of.data(), kxy, sc.table.data(),
+                         n_images, mask, sc.cam, msfm_ref::Verdict{max_error, min_angle}, msfm_rp::Params{step_tol, max_iters, min_observations},
+                         sc.list_rank.data(), pose_ids, n_poses, fixed.data(), points, residuals, out_records, changed.data(), &rc,
                          static_cast<msfm_ref::Trace*>(out_trace));
     for (int k = 0; k < n_poses; ++k) {
-        const size_t r = (size_t)list_rank[(size_t)k];
+        const size_t r = (size_t)sc.list_rank[(size_t)k];
         if (!changed[r]) continue;
-        for (int q = 0; q < 9; ++q) poses[k].R[q] = table[r].R[q];
-        for (int q = 0; q < 3; ++q) poses[k].t[q] = table[r].t[q];
+        for (int q = 0; q < 9; ++q) poses[k].R[q] = sc.table[r].R[q];
+        for (int q = 0; q < 3; ++q) poses[k].t[q] = sc.table[r].t[q];
     }
     if (counts9) {
         const long long v[9] = {rc.images, rc.eligible, rc.refined, rc.rejected_by_inliers, rc.iterations, rc.observations, rc.points_reposed,
@@ -809,32 +791,14 @@ int host_extend_points(const long long* offsets, const int* image_ids, const int
                        long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask, long long* counts7,
                        int* out_trace) {
     static_assert(sizeof(msfm_ext::Trace) == 4 * sizeof(int), "the trace is four int32");
-    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        rank_of[(size_t)ids[k]] = k;
-    }
-    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
-    const msfm_pose_rt none = {};
-    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
-        if (r < 0 || given[(size_t)r]) return 1;
-        given[(size_t)r] = 1;
-        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
-    }
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
     if (max_hypotheses < 0 || max_hypotheses > 1024) return 3;
-    std::vector<uint8_t> gained((size_t)std::max(n_images, 1), 0);
-    for (int k = 0; k < n_new; ++k) {
-        const int r = (new_ids[k] >= 0 && new_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)new_ids[k]] : -1;
-        if (r < 0 || gained[(size_t)r] || !table[(size_t)r].valid) return 4;
-        gained[(size_t)r] = 1;
-    }
-    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    std::vector<uint8_t> gained;
+    if (!twin_rank_bytes(sc, new_ids, n_new, true, &gained)) return 4;
     msfm_ext::Counts ec = {0, 0, 0, 0, 0, 0, 0};
-    msfm_ext::ExtendPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(), kxy,
-                           table.data(), gained.data(), c, msfm_tri::Params{max_error, min_angle, min_views, 0}, max_hypotheses,
+    msfm_ext::ExtendPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(), kxy,
+                           sc.table.data(), gained.data(), sc.cam, msfm_tri::Params{max_error, min_angle, min_views, 0}, max_hypotheses,
                            have_mask != 0, points, residuals, mask, &ec, reinterpret_cast<msfm_ext::Trace*>(out_trace));
     if (counts7) {
         const long long v[7] = {ec.tracks_touched, ec.continued, ec.observations_added, ec.observations_rejected, ec.created_attempted,
@@ -858,34 +822,16 @@ int host_filter_points(const long long* offsets, const int* image_ids, const int
                        double flt_min_angle, long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask,
                        int have_mask, long long* counts7, int* out_trace) {
     static_assert(sizeof(msfm_flt::Trace) == 4 * sizeof(int), "the trace is four int32");
-    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        rank_of[(size_t)ids[k]] = k;
-    }
-    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
-    const msfm_pose_rt none = {};
-    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
-        if (r < 0 || given[(size_t)r]) return 1;
-        given[(size_t)r] = 1;
-        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
-    }
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
     if (!msfm_pose::finite(flt_max_error) || !msfm_pose::finite(flt_min_angle) || !(flt_max_error >= 0.0) || !(flt_min_angle >= 0.0) ||
         n_scope < 0)
         return 3;
-    std::vector<uint8_t> scope((size_t)std::max(n_images, 1), 0);
-    for (int k = 0; k < n_scope; ++k) {
-        const int r = (scope_ids[k] >= 0 && scope_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)scope_ids[k]] : -1;
-        if (r < 0 || scope[(size_t)r]) return 4;
-        scope[(size_t)r] = 1;
-    }
-    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    std::vector<uint8_t> scope;
+    if (!twin_rank_bytes(sc, scope_ids, n_scope, false, &scope)) return 4;
     msfm_flt::Counts fc = {0, 0, 0, 0, 0, 0, 0};
-    msfm_flt::FilterPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(), kxy,
-                           table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, c, msfm_tri::Params{max_error, min_angle, 2, 0},
+    msfm_flt::FilterPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(), kxy,
+                           sc.table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, sc.cam, msfm_tri::Params{max_error, min_angle, 2, 0},
                            msfm_ref::Verdict{flt_max_error, flt_min_angle}, have_mask != 0, points, residuals, mask, &fc,
                            reinterpret_cast<msfm_flt::Trace*>(out_trace));
     if (counts7) {
@@ -909,32 +855,14 @@ int host_complete_points(const long long* offsets, const int* image_ids, const i
                          long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask,
                          long long* counts6, int* out_trace) {
     static_assert(sizeof(msfm_cmp::Trace) == 4 * sizeof(int), "the trace is four int32");
-    std::vector<int> rank_of((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        rank_of[(size_t)ids[k]] = k;
-    }
-    std::vector<msfm_tri::Pose> table((size_t)std::max(n_images, 1));
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
-    const msfm_pose_rt none = {};
-    for (auto& p : table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = (pose_ids[k] >= 0 && pose_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)pose_ids[k]] : -1;
-        if (r < 0 || given[(size_t)r]) return 1;
-        given[(size_t)r] = 1;
-        msfm_tri::prepare_pose(poses[k], &table[(size_t)r]);
-    }
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
     if (!msfm_pose::finite(cmp_max_error) || !(cmp_max_error >= 0.0) || cmp_max_error > max_error || n_scope < 0) return 3;
-    std::vector<uint8_t> scope((size_t)std::max(n_images, 1), 0);
-    for (int k = 0; k < n_scope; ++k) {
-        const int r = (scope_ids[k] >= 0 && scope_ids[k] < MSFM_MAX_IMAGES) ? rank_of[(size_t)scope_ids[k]] : -1;
-        if (r < 0 || scope[(size_t)r]) return 4;
-        scope[(size_t)r] = 1;
-    }
-    const msfm_emat::Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    std::vector<uint8_t> scope;
+    if (!twin_rank_bytes(sc, scope_ids, n_scope, false, &scope)) return 4;
     msfm_cmp::Counts cc = {0, 0, 0, 0, 0, 0};
-    msfm_cmp::CompletePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, rank_of.data(), kxy,
-                             table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, c, msfm_tri::Params{max_error, min_angle, 2, 0},
+    msfm_cmp::CompletePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(), kxy,
+                             sc.table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, sc.cam, msfm_tri::Params{max_error, min_angle, 2, 0},
                              cmp_max_error, have_mask != 0, points, residuals, mask, &cc, reinterpret_cast<msfm_cmp::Trace*>(out_trace));
     if (counts6) {
         const long long v[6] = {cc.eligible, cc.candidates, cc.admitted, cc.rejected_by_depth, cc.rejected_by_error, cc.completed};

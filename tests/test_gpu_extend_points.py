@@ -313,6 +313,33 @@ def test_no_op_calls_and_the_bytes_of_a_plain_session(tctx, host):
     tctx.tracks_end()
 
 
+@pytest.mark.parametrize("robust_session", (False, True))
+def test_every_call_on_a_map_without_tracks(tctx, robust_session):
+    """min_length above every track's length: the session finishes with no kept track.  After the triangulation every call of the
+    reconstruction stage succeeds without a launch over tracks or observations: one new pose is taken into the list, every other count
+    is zero (refine_poses counts the listed images), the points and the bytes are empty."""
+    ids, kps, poses, lst = ring_job([3] * 5)
+    assert open_ring(tctx, ids, kps, lst, 5)["tracks_kept"] == 5
+    st = tctx.tracks_finish(min_length=4)
+    assert st["tracks_kept"] == st["observations_kept"] == 0
+
+    def counts(st, **nonzero):
+        got = {k: v for k, v in st.items() if isinstance(v, int)}
+        assert len(got) >= 5 and got == dict({k: 0 for k in got}, **nonzero), st
+
+    tctx.triangulate_tracks(CAM, some(poses, ids, (0, 1)), *THR, robust=robust_session, max_hypotheses=8)
+    counts(tctx.extend_points(some(poses, ids, (2,))), images_added=1)
+    counts(tctx.filter_points())
+    counts(tctx.complete_points())
+    counts(tctx.refine_points())
+    counts(tctx.refine_poses(), images=3)
+    pts, res = tctx.points3d()
+    assert len(pts) == 0 and len(res) == 0 and len(tctx.point_inliers()) == 0
+    pid, tab = tctx.pose_list()
+    assert pid.tolist() == [int(i) for i in ids] and np.all(tab["valid"] == 1)
+    tctx.tracks_end()
+
+
 def test_two_increments_order_and_replacement(tctx, host):
     """two increments against the twin's two; the second list permuted (nothing but the pose list's order depends on it); a
     valid == 0 entry of the triangulation's list replaced in place"""
