@@ -956,6 +956,68 @@ typedef struct msfm_complete_stats {   /* 80 bytes, no implicit padding */
 int msfm_complete_points(msfm_ctx* ctx, const msfm_complete_params* params, const int32_t* image_ids, int n_images,
                          msfm_complete_stats* stats);
 
+/* ---- map visibility: covisibility counts for the builder's decisions (opt-in, read-only) ---------------
+ * The one quantity the reference's MapBuilder derives its decisions from: how many tracks or points two images share.  Where to start
+ * (TryInitialize: FindFirstInitialImage orders images by their correspondences, FindSecondInitialImage by those shared with the
+ * first), which image next (Map::GetNextImageIds: unregistered images by how much of the map they see), what to adjust
+ * (Map::GetLocalBAData: the new image and its most covisible neighbours).  msfm_map_visibility counts all of it on the device from
+ * the track CSR, the records' status words and the inlier bytes; nothing is fetched to the host but the counts.  Integer counting:
+ * every output is a sum of ones, identical to the host twin MapVisibility (csrc/msfm_visibility.h).
+ * Let n be the number of images declared in the session, in rank order (ascending id).
+ *   standing track   basis MSFM_VIS_TRACKS: every kept consistent track of the last msfm_tracks_finish -- no points are needed, the
+ *                    call works right after msfm_tracks_finish.  Basis MSFM_VIS_MAP: a kept consistent track whose record has POINT &
+ *                    ERROR_OK & ANGLE_OK, the test msfm_complete_points and msfm_register_images use.  Inconsistent tracks kept by
+ *                    keep_inconsistent never count.
+ *   counting element of a standing track.  TRACKS: every element.  MAP, image without a valid pose in the session's pose list (listed
+ *                    without one or not listed at all): every element -- a correspondence a registration would use.  MAP, image with
+ *                    a valid pose: iff its observation is fitting -- inlier byte 1 where the session has bytes, otherwise every
+ *                    used observation.
+ *   per image I      n_elements: elements of kept consistent tracks in I, the same under both bases.  n_visible: elements of
+ *                    standing tracks in I, counting or not.  n_points: counting elements in I if I is posed, else 0 (TRACKS: 0).
+ *                    flags: MSFM_VIS_POSED iff I has a valid pose (MAP only), MSFM_VIS_QUERIED iff I is in the list.
+ *   matrix           out_covisible[r * n + j]: the standing tracks in which the r-th query image and the image of rank j both have a
+ *                    counting element; at the query image's own rank, its number of counting elements.
+ *   stats            tracks_counted: standing tracks.  elements_counted: all counting elements.  pair_increments: the sum of the
+ *                    matrix.  route: the one that ran.  device_bytes: the peak of the call's temporaries, all freed on return.
+ *   route            MSFM_VIS_ROUTE_GLOBAL: agent-scope adds in global memory.  MSFM_VIS_ROUTE_LDS: the per-image counters, and the
+ *                    matrix rows where they fit, are privatised per workgroup in LDS and flushed once.  MSFM_VIS_ROUTE_AUTO picks
+ *                    (msfm_vis::vis_route).  All give the same counts.
+ * params NULL = {MSFM_VIS_MAP, MSFM_VIS_ROUTE_AUTO}.  out_images (n records) and out_covisible (n_query x n, row-major) may be NULL.
+ * The call is READ-ONLY: not one byte of the session changes -- points, residuals, inlier bytes and the pose list stay as they are, the
+ * registrations and the pose-refinement records stay valid, and a session without inlier bytes still has none.  It may run between
+ * msfm_register_images and msfm_fetch_registrations.
+ * Errors, after each of which the session is what it was: MSFM_E_STATE -- no finished track session, basis MAP without valid points,
+ * a streaming series open.  MSFM_E_INVALID -- an unknown basis or route, n_query < 0 or a NULL list with n_query > 0, an id that is not
+ * declared in the session or given twice, MSFM_VIS_ROUTE_LDS at a shape whose per-image counters do not fit one workgroup's LDS. */
+enum { MSFM_VIS_TRACKS = 0, MSFM_VIS_MAP = 1 };                                            /* basis */
+enum { MSFM_VIS_ROUTE_AUTO = 0, MSFM_VIS_ROUTE_GLOBAL = 1, MSFM_VIS_ROUTE_LDS = 2 };
+enum { MSFM_VIS_POSED = 1, MSFM_VIS_QUERIED = 2 };                                         /* record flags */
+typedef struct msfm_visibility_params {   /* 8 bytes, no implicit padding */
+    int32_t basis;
+    int32_t route;
+} msfm_visibility_params;
+typedef struct msfm_image_visibility {   /* 24 bytes, no implicit padding */
+    int32_t image_id;
+    int32_t flags;
+    int32_t n_elements;
+    int32_t n_visible;
+    int32_t n_points;
+    int32_t reserved;
+} msfm_image_visibility;
+typedef struct msfm_visibility_stats {   /* 56 bytes, no implicit padding */
+    int64_t tracks_counted;
+    int64_t elements_counted;
+    int64_t pair_increments;
+    int64_t device_bytes;
+    int32_t images;                  /* n */
+    int32_t posed;                   /* images with a valid pose (MAP) */
+    int32_t query;                   /* n_query */
+    int32_t route;                   /* the one that ran */
+    double visibility_ms;            /* HIP events around the launches */
+} msfm_visibility_stats;
+int msfm_map_visibility(msfm_ctx* ctx, const msfm_visibility_params* params, const int32_t* query_ids, int n_query,
+                        msfm_image_visibility* out_images, uint32_t* out_covisible, msfm_visibility_stats* stats);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

@@ -179,6 +179,62 @@ def completed(points):
     return (np.asarray(points)["status"] & TRI_COMPLETED) != 0
 
 
+# map visibility (include/msfm_match.h): bases, routes, record flags, the 8-byte parameters, the 24-byte record, the 56-byte stats
+VIS_TRACKS, VIS_MAP = 0, 1
+VIS_ROUTE_AUTO, VIS_ROUTE_GLOBAL, VIS_ROUTE_LDS = 0, 1, 2
+VIS_POSED, VIS_QUERIED = 1, 2
+VISIBILITY = np.dtype([(k, "<i4") for k in ("image_id", "flags", "n_elements", "n_visible", "n_points", "reserved")])
+_VIS_BASES = {"tracks": VIS_TRACKS, "map": VIS_MAP}
+_VIS_ROUTES = {"auto": VIS_ROUTE_AUTO, "global": VIS_ROUTE_GLOBAL, "lds": VIS_ROUTE_LDS}
+
+
+class VisibilityParams(C.Structure):
+    _fields_ = [("basis", C.c_int32), ("route", C.c_int32)]
+
+
+class VisibilityStats(C.Structure):
+    """msfm_visibility_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("tracks_counted", "elements_counted", "pair_increments", "device_bytes")] + \
+               [(k, C.c_int32) for k in ("images", "posed", "query", "route")] + [("visibility_ms", C.c_double)]
+
+
+def _by_count(ids, counts):
+    """ids by count descending, id ascending -> list of int"""
+    ids, counts = np.asarray(ids, np.int64), np.asarray(counts, np.int64)
+    return [int(i) for i in ids[np.lexsort((ids, -counts))]]
+
+
+def next_images(records, min_visible=15):
+    """Map::GetNextImageIds over Context.visibility()'s records: the images without a pose that see at least min_visible standing
+    points (15: register_images' min_inliers), by n_visible descending, id ascending."""
+    r = np.asarray(records)
+    r = r[((r["flags"] & VIS_POSED) == 0) & (r["n_visible"] >= int(min_visible))]
+    return _by_count(r["image_id"], r["n_visible"])
+
+
+def local_window(row, records, image_id, size=5):
+    """Map::GetLocalBAData over one row of Context.visibility()'s matrix (the row of image_id): the posed images other than image_id
+    that share a point with it, by shared count descending, id ascending, at most `size` (the reference's kMaxRelatedImageNum = 5)."""
+    r, row = np.asarray(records), np.asarray(row)
+    keep = ((r["flags"] & VIS_POSED) != 0) & (r["image_id"] != int(image_id)) & (row > 0)
+    return _by_count(r["image_id"][keep], row[keep])[:max(int(size), 0)]
+
+
+def initial_first_images(records):
+    """FindFirstInitialImage's order over Context.visibility(basis="tracks")'s records: every image by n_elements descending, id
+    ascending."""
+    r = np.asarray(records)
+    return _by_count(r["image_id"], r["n_elements"])
+
+
+def initial_second_images(row, records, image_id):
+    """FindSecondInitialImage's order over the row of image_id: the other images by shared count descending, id ascending, images that
+    share nothing left out."""
+    r, row = np.asarray(records), np.asarray(row)
+    keep = (r["image_id"] != int(image_id)) & (row > 0)
+    return _by_count(r["image_id"][keep], row[keep])
+
+
 def succeeded(points):
     """The reference's is_succeed per record of a POINT3D array: POINT & ERROR_OK & ANGLE_OK."""
     want = TRI_POINT | TRI_ERROR_OK | TRI_ANGLE_OK
@@ -372,6 +428,7 @@ def _signatures():
         "msfm_extend_points": (i, [vp, ip, vp, i, P(ExtendParams), P(ExtendStats)]),
         "msfm_filter_points": (i, [vp, P(FilterParams), ip, i, P(FilterStats)]),
         "msfm_complete_points": (i, [vp, P(CompleteParams), ip, i, P(CompleteStats)]),
+        "msfm_map_visibility": (i, [vp, P(VisibilityParams), ip, i, vp, vp, P(VisibilityStats)]),
         "msfm_register_images": (i, [vp, cam, ip, i, P(RegisterParams), P(RegisterStats)]),
         "msfm_fetch_registrations": (i, [vp, vp, vp, vp, vp, vp]),
     }
@@ -930,22 +987,91 @@ class Context:
                                              C.byref(prm), C.byref(st)))
         return _dict(st)
 
-    def grow(self, camera, image_ids=None, register_params=None, rounds=1, fixed=(), point_params=None, pose_params=None):
+    # ---- map visibility (include/msfm_match.h) ----
+    def visibility(self, query=(), basis="map", route="auto"):
+        """Covisibility counts of the session on the device (msfm_map_visibility), read-only: basis "tracks" counts the kept consistent
+        tracks of the last tracks_finish (no points needed), "map" the standing points and, in a posed image, only their fitting
+        observations.  query: the image ids whose rows of the matrix are wanted.  route: "auto", "global" or "lds" (the same counts).
+        -> (records: VISIBILITY array, one per declared image by ascending id; matrix: uint32 [len(query), n], matrix[r, j] = the
+        standing tracks query[r] shares with the image of records[j], its own count at its own column; stats dict).  next_images,
+        local_window, initial_first_images and initial_second_images order them as the reference's MapBuilder does."""
+        q = np.ascontiguousarray([int(i) for i in query], dtype=np.int32).reshape(-1)
+        n = len(getattr(self, "_track_ids", None) or ())
+        prm = VisibilityParams(_VIS_BASES[basis], _VIS_ROUTES[route])
+        rec = np.zeros(max(n, 1), VISIBILITY)
+        mat = np.zeros((len(q), n), np.uint32)
+        st = VisibilityStats()
+        self._chk(self._L.msfm_map_visibility(self._h, C.byref(prm), _ip(q) if len(q) else None, len(q), rec.ctypes.data,
+                                              mat.ctypes.data if mat.size else None, C.byref(st)))
+        return rec[:n], mat, _dict(st)
+
+    def initialize(self, camera, two_view, max_trials=100, min_points=100, **triangulate_kwargs):
+        """The reference's TryInitialize order over the finished tracks: first images by their number of track elements
+        (initial_first_images), per first image one visibility([id], basis="tracks") and its second images by the tracks they share
+        with it (initial_second_images).  two_view: {(id1, id2): TWO_VIEW_RECORD}; a pair is a trial iff its record exists (under
+        either key order), is valid and has is_initial_candidate.  A trial calls triangulate_tracks(camera, ...) with the record's
+        first image at (I, 0) and its second at the record's (R, t) and succeeds when the call's `succeeded` reaches min_points (100:
+        the two-view parameters' min_num_inliers default); at most max_trials trials (100: the reference's max_num_init_trials).
+        -> (the record's (id1, id2) or None, trials run, the last trial's stats or None)."""
+        records = self.visibility(basis="tracks")[0]
+        trials, stats, tried = 0, None, set()
+        for a in initial_first_images(records):
+            if trials >= int(max_trials):
+                break
+            rec_a, mat, _ = self.visibility([a], basis="tracks")
+            for b in initial_second_images(mat[0], rec_a, a):
+                if trials >= int(max_trials):
+                    break
+                key = (a, b) if (a, b) in two_view else (b, a)
+                if key not in two_view or key in tried:
+                    continue
+                tv = two_view[key]
+                if not (int(tv["valid"]) and int(tv["is_initial_candidate"])):
+                    continue
+                tried.add(key)
+                trials += 1
+                poses = {key[0]: (np.eye(3), np.zeros(3)), key[1]: (np.asarray(tv["R"], np.float64).reshape(3, 3), np.asarray(tv["t"], np.float64))}
+                stats = self.triangulate_tracks(camera, poses, **triangulate_kwargs)
+                if stats["succeeded"] >= int(min_points):
+                    return key, trials, stats
+        return None, trials, stats
+
+    def grow(self, camera, image_ids=None, register_params=None, rounds=1, fixed=(), point_params=None, pose_params=None, max_images=None,
+             window=None):
         """One increment of the reconstruction: register_images(camera, image_ids, **register_params) -- image_ids None: every declared
         image without a valid pose in the session -- then extend_points(the registered poses), then alternate(rounds, fixed=...).
         -> (register stats, extend stats or None, alternate's list, the ids that registered).  When no image registers nothing but the
-        registrations has changed and the call returns early."""
-        if image_ids is None:
-            posed = set(self.poses())
-            image_ids = [int(i) for i in sorted(getattr(self, "_track_ids", ())) if int(i) not in posed]
-        image_ids = [int(i) for i in image_ids]
-        if not image_ids:
-            return None, None, [], []
-        reg = self.register_images(camera, image_ids, **(register_params or {}))
-        new = registered_poses(self.registrations()[0])
+        registrations has changed and the call returns early.
+        max_images=k (image_ids None): the candidates are next_images(visibility()[0]) -- the unposed images that see enough of the
+        map, best-seen first -- tried in batches of k until a batch registers something or the list ends.  window=w: behind
+        extend_points one visibility(query=the new ids); alternate holds every posed image fixed that is neither new nor in a new
+        image's local_window(..., size=w).  max_images=1, window=5 is the reference's loop; both None: every call as before."""
+        if image_ids is None and max_images is not None:
+            cand = next_images(self.visibility()[0])
+            batches = [cand[k:k + int(max_images)] for k in range(0, len(cand), max(int(max_images), 1))]
+        else:
+            if image_ids is None:
+                posed = set(self.poses())
+                image_ids = [int(i) for i in sorted(getattr(self, "_track_ids", ())) if int(i) not in posed]
+            batches = [[int(i) for i in image_ids]]
+        reg, new = None, {}
+        for batch in batches:
+            if not batch:
+                continue
+            reg = self.register_images(camera, batch, **(register_params or {}))
+            new = registered_poses(self.registrations()[0])
+            if new:
+                break
         if not new:
             return reg, None, [], []
         ext = self.extend_points(new)
+        if window is not None:
+            records, mat, _ = self.visibility(query=sorted(new))
+            inside = set(new)
+            for row, i in zip(mat, sorted(new)):
+                inside.update(local_window(row, records, i, size=window))
+            outside = [int(r["image_id"]) for r in records if (r["flags"] & VIS_POSED) and int(r["image_id"]) not in inside]
+            fixed = sorted(set(int(i) for i in fixed) | set(outside))
         alt = self.alternate(rounds, fixed=fixed, point_params=point_params, pose_params=pose_params)
         return reg, ext, alt, sorted(new)
 
@@ -984,6 +1110,8 @@ class Context:
         """The reference's DoBuild loop with its filter: grow(camera, rounds=rounds, **grow_kwargs) followed by
         filter_points(**filter_params), repeated until no image registers or max_increments increments have run.  complete_params: a
         dict (may be empty) runs complete_points(**complete_params) behind the filter of every increment; None: no completion.
+        grow's max_images=1, window=5 make it the reference's loop in order as well: one image an increment, best-seen first, the new
+        image and its five most covisible neighbours adjusted.
         -> one dict per increment: register, extend, alternate (grow's results), filter (filter_points' stats), registered (the ids),
         and with complete_params "complete" (complete_points' stats)."""
         out = []

@@ -49,6 +49,7 @@ using namespace msfm;
 #include "msfm_extend.hip.h"
 #include "msfm_filter.hip.h"
 #include "msfm_complete.hip.h"
+#include "msfm_visibility.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -933,6 +934,16 @@ int msfm_complete_points(msfm_ctx* ctx, const msfm_complete_params* params, cons
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return complete_impl(ctx, params, image_ids, n_images, stats);
+    MSFM_API_END
+}
+
+// ---- map visibility (msfm_visibility.hip.h) ------------------------------------------------------------------------------------------------
+
+int msfm_map_visibility(msfm_ctx* ctx, const msfm_visibility_params* params, const int32_t* query_ids, int n_query,
+                        msfm_image_visibility* out_images, uint32_t* out_covisible, msfm_visibility_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return visibility_impl(ctx, params, query_ids, n_query, out_images, out_covisible, stats);
     MSFM_API_END
 }
 

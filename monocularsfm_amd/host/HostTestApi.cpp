@@ -21,6 +21,7 @@
 #include "../csrc/msfm_extend.h"
 #include "../csrc/msfm_filter.h"
 #include "../csrc/msfm_complete.h"
+#include "../csrc/msfm_visibility.h"
 #include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
@@ -869,6 +870,59 @@ int host_complete_points(const long long* offsets, const int* image_ids, const i
         for (int k = 0; k < 6; ++k) counts6[k] += v[k];
     }
     return 0;
+}
+
+// ---- map visibility: the host twin of the device kernels (csrc/msfm_visibility.h, MapVisibility) -----------------------------------------
+// A finished track result, the declared images `ids` IN RANK ORDER (the records and the matrix columns follow it), the session's current
+// pose list (n_poses == 0 under basis 0), the query list, the basis (0 tracks, 1 map), points (the records; NULL under basis 0) and mask
+// (the session's inlier bytes or NULL).  out_records: n_images msfm_image_visibility; out_matrix: n_query x n_images uint32 (may be NULL
+// without a query); counts3 (may be NULL): tracks_counted, elements_counted, pair_increments.  Nothing is read and rewritten: the call
+// counts.  Returns 0; 1, 2 as above; 3: an unknown basis or n_query < 0; 4: a query id that is not declared or given twice.
+int host_map_visibility(const long long* offsets, const int* image_ids, const unsigned char* consistent, long long n_tracks, const int* ids,
+                        int n_images, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const int* query_ids, int n_query, int basis,
+                        const msfm_point3d* points, const unsigned char* mask, msfm_image_visibility* out_records, unsigned* out_matrix,
+                        long long* counts3) {
+    static_assert(sizeof(msfm_image_visibility) == 24 && sizeof(msfm_visibility_params) == 8 && sizeof(msfm_visibility_stats) == 56,
+                  "the visibility structs of include/msfm_match.h");
+    const double cam[8] = {1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // (no pixel is read: only the poses' validity)
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, basis == msfm_vis::BASIS_MAP ? n_poses : 0, cam, &sc)) return e;
+    if ((basis != msfm_vis::BASIS_TRACKS && basis != msfm_vis::BASIS_MAP) || n_query < 0) return 3;
+    std::vector<uint8_t> queried;
+    if (!twin_rank_bytes(sc, query_ids, n_query, false, &queried)) return 4;
+    const size_t n = (size_t)std::max(n_images, 1);
+    std::vector<uint8_t> posed(n, 0);
+    std::vector<int> row_of(n, -1);
+    for (size_t r = 0; r < n; ++r) posed[r] = sc.table[r].valid ? 1 : 0;
+    for (int k = 0; k < n_query; ++k) row_of[(size_t)sc.rank(query_ids[k])] = k;
+    std::vector<uint32_t> image_counters((size_t)msfm_vis::kImageCounters * n, 0);
+    msfm_vis::Tally tl = {0, 0, 0};
+    msfm_vis::MapVisibility(reinterpret_cast<const int64_t*>(offsets), image_ids, consistent, n_tracks, sc.rank_of.data(), (int)n, posed.data(),
+                            row_of.data(), n_query, basis, basis == msfm_vis::BASIS_MAP ? points : nullptr,
+                            basis == msfm_vis::BASIS_MAP ? mask : nullptr, image_counters.data(), out_matrix, &tl);
+    for (int r = 0; r < n_images; ++r) {
+        msfm_image_visibility v = {};
+        v.image_id = ids[r];
+        v.flags = (posed[(size_t)r] ? MSFM_VIS_POSED : 0) | (queried[(size_t)r] ? MSFM_VIS_QUERIED : 0);
+        v.n_elements = (int32_t)image_counters[(size_t)msfm_vis::IMG_ELEMENTS * n + (size_t)r];
+        v.n_visible = (int32_t)image_counters[(size_t)msfm_vis::IMG_VISIBLE * n + (size_t)r];
+        v.n_points = (int32_t)image_counters[(size_t)msfm_vis::IMG_POINTS * n + (size_t)r];
+        out_records[r] = v;
+    }
+    if (counts3) {
+        counts3[0] = tl.tracks;
+        counts3[1] = tl.elements;
+        counts3[2] = tl.increments;
+    }
+    return 0;
+}
+// msfm_vis::vis_route: out4 = route (0: ROUTE_LDS asked for and no fit), lds_bytes, matrix_in_lds, wgs_per_cu
+void host_vis_route(int want, long long n, long long n_query, long long T, long long O, int* out4) {
+    const msfm_vis::Route r = msfm_vis::vis_route(want, n, n_query, T, O);
+    out4[0] = r.route;
+    out4[1] = r.lds_bytes;
+    out4[2] = r.matrix_in_lds;
+    out4[3] = r.wgs_per_cu;
 }
 
 // pieces, for tests/test_triangulation_reference.py
