@@ -10,8 +10,11 @@ The layout of every chain scene: tracks of 8 views through the images 0 .. 7 and
 A bad 8-view track carries the bad value in an OLD image (4), a NEW one (1) and REG (7): the consensus rejects the first, the
 continuation the second, the registration meets the third.  A bad 3-view track carries it in image 1: not attempted at the
 triangulation (one posed view), created by the extension from the views 0, 1, 2, of which 0 and 2 (2.4 degrees apart) agree."""
+import ctypes as C
+
 import numpy as np
 
+import complete_twin as ctw
 import extend_twin as etw
 import filter_twin as ftw
 import refine_points_twin as rtw
@@ -76,9 +79,10 @@ BAD_AT_SHORT = (1,)                  # of a bad 3-view track
 
 class Scene:
     """ids, kps (list by image position), poses (the true ones, dict by id), lst (for tracks_add), tracks (the finished result),
-    lengths, bad (bool per observation slot)"""
-    def __init__(self, ids, kps, poses, lst, lengths, bad):
+    lengths, bad (bool per observation slot), clean (the keypoints without any bad value: what the cure uploads; None: kps)"""
+    def __init__(self, ids, kps, poses, lst, lengths, bad, clean=None):
         self.ids, self.kps, self.poses, self.lst, self.lengths, self.bad = ids, kps, poses, lst, list(lengths), bad
+        self.clean = kps if clean is None else clean
         self.tracks = tracks_of(self.lengths, ids)
         self.rows = len(kps[0])
 
@@ -97,7 +101,7 @@ class Scene:
         n_img = max(lengths)
         full = ring_list(lengths, self.ids)
         return Scene(self.ids[:n_img], self.kps[:n_img], {int(i): self.poses[int(i)] for i in self.ids[:n_img]}, full, lengths,
-                     self.bad[:int(np.sum(lengths))])
+                     self.bad[:int(np.sum(lengths))], self.clean[:n_img])
 
 
 def ring_list(lengths, ids):
@@ -113,6 +117,7 @@ def placed(lengths, where, case=None, seed=3, noise_px=0.3):
     offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
     bad = np.zeros(int(offs[-1]), bool)
     gross = [k.copy() for k in kps]
+    clean = [k.copy() for k in kps]
     for t, positions in where.items():
         for pos in positions:
             assert pos < lengths[t]
@@ -122,7 +127,7 @@ def placed(lengths, where, case=None, seed=3, noise_px=0.3):
             for ax in case[2]:
                 kps[pos][t, "xy".index(ax)] = value(case[1])
                 gross[pos][t, "xy".index(ax)] = GROSS
-    return Scene(ids, kps, poses, lst, lengths, bad), bad, Scene(ids, gross, poses, lst, lengths, bad)
+    return Scene(ids, kps, poses, lst, lengths, bad, clean), bad, Scene(ids, gross, poses, lst, lengths, bad, clean)
 
 
 # ---- the placements -----------------------------------------------------------------------------------------------------------------------
@@ -175,6 +180,136 @@ REG_PARAMS = dict(min_inliers=15)
 POSE_PARAMS = (10, 1e-6, 15)
 
 
+# msfm_complete_points behind the filter: the pairs whose trimmed tracks hold candidates again (behind FILTER_ANGLE and FILTER_VIEWS
+# nearly every track is removed and no longer stands)
+COMPLETE_BEHIND = ("mix", "trim")
+PLANT_AT = 3                         # the element of an 8-view track that the planted step moves: an OLD image, not in BAD_AT
+PLANT_PX = np.float32(40.0)
+
+
+def completed_twice(host, sc, kps, lst, cam, state, thr=THR, max_error=None, scope=()):
+    """complete_twin.run from `state` = (records, residuals, inlier bytes) at max_error (None: the session's), then once more from its
+    own outputs: the fixed point on the twin.  -> (first, again), each (records, residuals, bytes, counters, trace)"""
+    first = ctw.run(host, sc.tracks, sc.ids, kps, lst, cam, state[0], state[1], state[2], thr[:2], max_error, scope, trace=True)
+    again = ctw.run(host, sc.tracks, sc.ids, kps, lst, cam, first[0], first[1], first[2], thr[:2], max_error, scope, trace=True)
+    return first, again
+
+
+def planted_tracks(sc):
+    """the tracks of the planted step: every third 8-view track and every bad 8-view track.  The bad 3-view tracks of the images
+    placement are left out: they have no element PLANT_AT, and with two fitting views (0 and 2) they cannot lose one -- the filter
+    would remove them by views and nothing would stand to be completed."""
+    bad = set(int(t) for t in sc.bad_tracks())
+    return np.asarray([t for t, n in enumerate(sc.lengths) if n == 8 and (t % 3 == 0 or t in bad)], np.int64)
+
+
+def moved_keypoints(sc):
+    """the scene's keypoints with the clean observation at element PLANT_AT of every planted track moved by 40 px in y"""
+    kps = list(sc.kps)
+    k = np.array(kps[PLANT_AT], copy=True)
+    k[planted_tracks(sc), 1] += PLANT_PX
+    kps[PLANT_AT] = k
+    return kps
+
+
+def complete_planted(host, sc, lst, cam, state, thr=THR):
+    """The deterministic route into a completed bad track (tests/test_gpu_complete_points.plant on the twins): under
+    moved_keypoints(sc) the filter twin runs from `state` (the chain's state behind refine2) with the session's thresholds and drops
+    the moved observations; then the completion runs twice under the scene's ORIGINAL keypoints.  X did not move and the observation
+    fitted before, so it is admitted again: every planted track that stands is COMPLETED, and in a bad one the bad observations --
+    byte 0 and USED -- are the candidates rejected beside it.  -> dict(where = planted_tracks, filter, first, again)"""
+    flt = ftw.run(host, sc.tracks, sc.ids, moved_keypoints(sc), lst, cam, state[0], state[1], state[2], thr[:2], None, trace=True)
+    first, again = completed_twice(host, sc, sc.kps, lst, cam, flt[:3], thr)
+    return dict(where=planted_tracks(sc), filter=flt, first=first, again=again)
+
+
+# ---- what a completion call owes a bad observation (tests/test_nonfinite_reference.py and tests/test_gpu_nonfinite.py) ------------------
+CANONICAL = 0x7ff8000000000000
+
+
+def bad_slot_class(case, cam):
+    """What a REWRITTEN bad slot of a completed track holds (point_verdict writes canonical(err) into the slot of every USED
+    observation; err = f * |projection - undistorted observation|):
+      a NaN coordinate        the difference is a NaN under either camera: THE NaN.
+      an infinite coordinate  CAM: (inf - cx) / fx = inf, its square inf, the root inf, times f: +inf for either sign.  CAM_D: the
+                              undistortion's first step multiplies inf by a factor built from inf (inf - inf, or inf * 0 in the
+                              tangential term): a NaN, so THE NaN.
+      3e38, -3e38, 1e30       CAM: the distance in px from the projection to the value, about |value|: finite (3e38 / fx squared is
+                              1.4e70) and beyond 1e29.  CAM_D: the fixed-point undistortion leaves a finite number that depends on
+                              the step count; what is owed is "finite or +inf, never a NaN -- or THE NaN --
+                              and never within max_error": asserted as `not (slot <= max_error)` and THE NaN alone.  (Measured on
+                              the chain scenes: finite, about |value|, as under CAM.)
+      the denormal, -0.0      the pixel 0: a finite error of hundreds of px or more under both cameras.
+    -> "nan", "inf", "huge", "gross" (finite, beyond max_error) or "any" (CAM_D under a huge finite value)"""
+    name = case[0].rsplit("_", 1)[0]
+    distorted = any(cam[4:])
+    if name.startswith("nan"):
+        return "nan"
+    if name in ("inf", "minus_inf"):
+        return "nan" if distorted else "inf"
+    if name in ("3e38", "minus_3e38", "1e30"):
+        return "any" if distorted else "huge"
+    return "gross"
+
+
+def holds_class(slots, kind, max_error):
+    slots = np.ascontiguousarray(slots, np.float64)
+    if kind == "nan":
+        return bool(np.all(slots.view(np.uint64) == CANONICAL))
+    if kind == "inf":
+        return bool(np.all(np.isposinf(slots)))
+    if kind == "huge":
+        return bool(np.all(np.isfinite(slots) & (slots > 1e29)))
+    if kind == "gross":
+        return bool(np.all(np.isfinite(slots) & (slots > 100 * max_error)))
+    return not bool(np.any(slots <= max_error)) and bool(np.all(slots.view(np.uint64)[np.isnan(slots)] == CANONICAL))
+
+
+def completion_routes(sc, case, cam, posed, before, out, tight=None, what=None, scope=None):
+    """One completion call: `before` = (records, residuals, bytes) it started from, `out` = (records, residuals, bytes, counters, the
+    twin's trace) behind it; posed: bool per slot, the elements in an image with a pose; tight: bool per track, None = every track
+    (the second-form tracks are left out: tests/test_nonfinite_reference.py); scope: the call's image list, None = every image.
+    Asserted:
+      rejection   no bad observation gets byte 1; every bad observation of an eligible track in a posed (and listed) image is a
+                  candidate and is rejected by its error: the track's rejections by depth are 0, those by error at least its bad observations.
+      untouched   a track that is not COMPLETED is bit for bit what it was, its bad slots included; the bytes only rise.
+      completed   a completed bad track: every bad slot holds what bad_slot_class says and nothing else, the clean ones an error;
+                  n_views = the bytes = those before + admitted, none on a bad observation; mean_residual finite, within max_error.
+    -> (the completed bad tracks, the UNTOUCHED bad tracks with a rejected bad candidate): bool per track"""
+    o = sc.tracks[0]
+    T = len(sc.lengths)
+    per_slot = np.repeat(np.arange(T), np.diff(o))
+    tight = np.ones(T, bool) if tight is None else tight
+    badt = np.zeros(T, bool)
+    badt[sc.bad_tracks()] = True
+    listed = np.ones(len(posed), bool) if scope is None else np.isin(sc.tracks[1], [int(i) for i in scope])
+    # the bad candidates per track (a one-track scene registers no image: REG stays without a pose and its element is not USED)
+    n_bad = np.add.reduceat((sc.bad & posed & listed).astype(np.int64), o[:-1])
+    p0, r0, m0 = before
+    pa, sa, ma, ca, ta = out
+    max_error = THR[0]
+    assert not ma[sc.bad & tight[per_slot]].any(), (what, np.nonzero((ma != 0) & sc.bad & tight[per_slot])[0][:8])
+    kind = ta["kind"]
+    by_error = ta["candidates"] - ta["admitted"] - ta["rejected_by_depth"]
+    sel = (kind != ctw.KIND_NOT_ELIGIBLE) & tight & badt
+    assert np.all(ta["rejected_by_depth"][sel] == 0) and np.all(by_error[sel] >= n_bad[sel]), (what, ta[sel], n_bad[sel])
+    same = kind != ctw.KIND_COMPLETED
+    assert pa[same].tobytes() == p0[same].tobytes() and sa[same[per_slot]].tobytes() == r0[same[per_slot]].tobytes(), what
+    assert ma[same[per_slot]].tobytes() == m0[same[per_slot]].tobytes() and np.all(ma >= m0), what
+    untouched = (kind == ctw.KIND_UNTOUCHED) & tight & badt & (by_error >= np.maximum(n_bad, 1))
+    done = (kind == ctw.KIND_COMPLETED) & tight & badt
+    slot_class = bad_slot_class(case, cam)
+    for t in np.nonzero(done)[0]:
+        sl = slice(int(o[t]), int(o[t + 1]))
+        bad_used = (sc.bad & posed)[sl]                                    # (the slot of an element in an image without a pose: -1)
+        assert holds_class(sa[sl][bad_used], slot_class, max_error), (what, t, slot_class, sa[sl][bad_used])
+        assert not (sa[sl][bad_used] <= max_error).any() and np.all(sa[sl][posed[sl] & ~bad_used] >= 0.0), (what, t, sa[sl])
+        assert pa[t]["n_views"] == ma[sl].sum() == m0[sl].sum() + ta[t]["admitted"] and not ma[sl][sc.bad[sl]].any(), (what, t, pa[t])
+        assert np.isfinite(pa[t]["mean_residual"]) and pa[t]["mean_residual"] <= max_error, (what, t, pa[t])
+        assert ta[t]["admitted"] >= 1 and by_error[t] >= n_bad[t] >= (scope is None), (what, t, ta[t])
+    return done, untouched
+
+
 def chain(host, sc, cam=CAM, thr=THR, H=8, mh=8, robust=True, trace=True):
     """The reconstruction stage's twins over one scene, each fed the previous one's outputs: triangulation (plain, or robust with H
     hypotheses), point refinement, registration of REG, extension by NEW + REG's registered pose with max_hypotheses mh, pose refinement
@@ -210,6 +345,8 @@ def chain(host, sc, cam=CAM, thr=THR, H=8, mh=8, robust=True, trace=True):
     out["refine2"] = rtw.run(host, tracks, ids, kps, lst, cam, pts, res, mask, thr[:2], trace=trace)
     pts, res = out["refine2"][:2]
     out["filter"] = {name: ftw.run(host, tracks, ids, kps, lst, cam, pts, res, mask, thr[:2], pair, trace=True) for name, pair in FILTER_PAIRS}
+    out["complete"] = {name: completed_twice(host, sc, kps, lst, cam, out["filter"][name][:3], thr) for name in COMPLETE_BEHIND}
+    out["complete_planted"] = complete_planted(host, sc, lst, cam, (pts, res, mask), thr)
     pts, res, mask = out["filter"]["mix"][:3]
     out["refine3"] = rtw.run(host, tracks, ids, kps, lst, cam, pts, res, mask, thr[:2], trace=trace)
     return out
@@ -217,6 +354,10 @@ def chain(host, sc, cam=CAM, thr=THR, H=8, mh=8, robust=True, trace=True):
 
 def load_host():
     L = ftw.load_host()                  # (etw.load_host()'s exports and host_filter_points)
+    vp = C.c_void_p                      # host_complete_points as complete_twin.load_host declares it
+    L.host_complete_points.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, ctw.DP, C.c_double, C.c_double, C.c_double,
+                                       C.c_longlong, C.c_longlong, vp, vp, vp, C.c_int, vp, vp]
+    L.host_complete_points.restype = C.c_int
     R = regtw.load_host()
     for name in ("host_register_counts", "host_register_images", "host_register_sample3", "host_p3p", "host_register_refine"):
         f = getattr(R, name)

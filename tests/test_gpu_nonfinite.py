@@ -7,10 +7,19 @@ draws a few values from a fixed seed (always a signed NaN and an infinity: the v
 generate with different bits -- msfm_pose.h, "THE NaN RULE").
 
 The thin comparison helpers below are the existing *_same helpers with one change: a cost sum is compared to 1e-9 relative where
-both sides are finite, and must otherwise be the same infinity or NaN on both sides."""
+both sides are finite, and must otherwise be the same infinity or NaN on both sides.  (msfm_complete_points reports no cost sum: its
+eight counters are integers and compared exactly, by test_gpu_complete_points.complete_same itself.)
+
+THE COMPLETION runs on a SECOND PASS of the chain: the calls up to the last point refinement are made again (rebuilt(): the same calls
+on the same inputs, so the same state -- asserted byte for byte against the first pass), then the filter under FILTER_TRIM and the
+completion behind it; again, then FILTER_TRIM, FILTER_MIX and the completion; again, then the planted route and the cure
+(planted_and_cured()).  So the inputs of every comparison of the first pass are what they were before the completion was added."""
+import time
+
 import numpy as np
 import pytest
 
+import complete_twin as ctw
 import extend_twin as etw
 import filter_twin as ftw
 import nonfinite_fixtures as nf
@@ -20,6 +29,7 @@ import registration_twin as regtw
 import robust_triangulation_twin as robtw
 import triangulation_twin as tw
 from monocularsfm_amd import _lib
+from test_gpu_complete_points import complete_same
 from test_gpu_extend_points import same_state, state
 from test_gpu_robust_triangulation import open_ring
 
@@ -155,6 +165,7 @@ def filtered(ctx, host, sc, tracks, cam, what, params=None, creates_bytes=False)
     device's state before the call -- records, residuals, inlier bytes and the pose list by bytes, all nine counters -- THE NaN alone,
     and a second call that changes no byte and counts nothing.  creates_bytes: the session has no inlier bytes before the call.
     -> (stats, points, residuals, bytes, the twin's trace)"""
+    t0 = time.perf_counter()
     p0, r0, m0, l0 = state(ctx)
     assert (m0 is None) == creates_bytes, what
     kw = {} if params is None else dict(max_error=params[0], min_angle=params[1])
@@ -172,7 +183,120 @@ def filtered(ctx, host, sc, tracks, cam, what, params=None, creates_bytes=False)
     st2 = ctx.filter_points(**kw)
     assert same_state(after, state(ctx)), what
     assert all(st2[k] == (st[k] if k in ("succeeded", "observations_used") else 0) for k in ftw.ALL_KEYS if k != "eligible"), (what, st2)
+    SECONDS["filter"].append(time.perf_counter() - t0)
     return st, pts, res, mask, tr
+
+
+SECONDS = {"filter": [], "complete": []}     # wall time of every filtered() and completed() of a run, twins and second calls included
+
+
+def completed(ctx, host, sc, tracks, cam, what, kps=None, max_error=None, scope=None, case=None):
+    """one msfm_complete_points (max_error None: the session's; kps: the keypoints the session holds, None = the scene's) against
+    CompletePoints run from the device's state before the call, with test_gpu_complete_points.complete_same's comparisons -- records,
+    residuals, inlier bytes and the pose list by bytes, all eight counters, the consequences of the rule, and the second call that
+    changes no byte and admits nothing -- and THE NaN alone.  With `case`, nonfinite_fixtures.completion_routes on the twin's trace of
+    the device's own state: no byte on a bad observation, bad candidates rejected by error and never by depth, untouched tracks
+    untouched, what a completed bad track's rewritten slots hold.
+    -> (stats, points, residuals, bytes, the twin's trace, the state before, the completed bad tracks, the untouched ones with a
+    rejected bad candidate)"""
+    t0 = time.perf_counter()
+    st, pts, res, mask, tr, before = complete_same(ctx, host, sc.ids, sc.kps if kps is None else kps, tracks, nf.THR, max_error, scope, cam=cam)
+    SECONDS["complete"].append(time.perf_counter() - t0)
+    only_the_nan(res, sc.bad, what)
+    assert st["rejected_by_depth"] == 0, (what, st)
+    done = untouched = None
+    if case is not None:
+        posed = np.isin(tracks[1], [int(i) for i, p in zip(*before[3]) if p["valid"]])
+        # (a track created on the plain route over a bad observation carries the extension's byte 1 on it: second form, left out)
+        tight = ~(np.add.reduceat(((before[2] != 0) & sc.bad).astype(np.int64), tracks[0][:-1]) > 0)
+        done, untouched = nf.completion_routes(sc, case, cam, posed, before[:3], (pts, res, mask, st, tr), tight, what, scope)
+    return st, pts, res, mask, tr, before, done, untouched
+
+
+def robust_session(ctx, host, sc, tracks, cam, mh, what, finite=True):
+    """robust triangulation under the OLD images' poses, point refinement, registration of REG, extension by NEW and REG's registered
+    pose with max_hypotheses mh, pose refinement, point refinement: each against its twin -> dict step -> the device's outputs"""
+    first = sc.some([p for p in nf.OLD if p < len(sc.ids)])
+    out = {}
+    out["robust"] = triangulated(ctx, host, sc, tracks, first, cam, True, what + ("robust",))
+    out["refine1"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine1",))
+    new = sc.some([p for p in nf.NEW if p < len(sc.ids)])
+    if nf.REG < len(sc.ids):
+        out["register"] = registered(ctx, host, sc, tracks, cam, what + ("register",))
+        new = _lib.registered_poses(out["register"][1][0], new)
+    out["extend"] = extended(ctx, host, sc, tracks, new, mh, cam, what + ("extend",))
+    out["poses"] = poses_refined(ctx, host, sc, tracks, cam, what + ("poses",))
+    # (with max_hypotheses 0 a bad 3-view track is created on the plain route: after it the sums may be +inf as after the plain call)
+    out["refine2"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine2",), finite_costs=mh > 0 or finite)
+    out["state"] = state(ctx)
+    return out
+
+
+def rebuilt(ctx, sc, cam, mh, session):
+    """the calls of robust_session once more, without the comparisons: the same calls on the same inputs leave the same state --
+    asserted against `session`, the first pass's outputs"""
+    ctx.triangulate_tracks(cam, sc.some([p for p in nf.OLD if p < len(sc.ids)]), *nf.THR, robust=True, max_hypotheses=H)
+    ctx.refine_points()
+    new = sc.some([p for p in nf.NEW if p < len(sc.ids)])
+    if nf.REG < len(sc.ids):
+        ctx.register_images(cam, [int(sc.ids[nf.REG])], **nf.REG_PARAMS)
+        new = _lib.registered_poses(ctx.registrations()[0], new)
+    ctx.extend_points(new, mh)
+    ctx.refine_poses(*nf.POSE_PARAMS, fixed=[int(sc.ids[nf.OLD[0]])])
+    ctx.refine_points()
+    assert same_state(session["state"], state(ctx)), "the second pass of the chain left another state than the first"
+
+
+def planted_and_cured(ctx, host, sc, tracks, cam, what, case):
+    """From the state behind the last point refinement, test_gpu_complete_points.plant()'s method on nonfinite_fixtures.planted_tracks:
+    the keypoints of image PLANT_AT are uploaded with those tracks' observations moved by 40 px, filter_points under the session's
+    thresholds drops them (against its twin, fed the moved keypoints), the original keypoints are uploaded again, and the completion
+    finds them: EVERY bad 8-view track that stands is completed, its bad candidates rejected beside the admitted one.  Then one call
+    with max_error = -0.0 (accepted; nothing fits exactly: no byte moves) and one scoped to REG.  THE CURE: the true keypoints are
+    uploaded in place of the bad ones (the clean scene of the same seed) and the completion admits them: the twin's trace says so for
+    every bad track that stands, no NaN is left in a completed track.  -> (the planted call's outputs, the cure's)"""
+    moved = nf.Scene(sc.ids, nf.moved_keypoints(sc), sc.poses, sc.lst, sc.lengths, sc.bad)
+    ctx.upload_keypoints(int(sc.ids[nf.PLANT_AT]), moved.kps[nf.PLANT_AT])
+    fst, fp, _, fm, ftr = filtered(ctx, host, moved, tracks, cam, what + ("planted filter",))
+    ctx.upload_keypoints(int(sc.ids[nf.PLANT_AT]), sc.kps[nf.PLANT_AT])
+    o = tracks[0]
+    where = np.zeros(len(sc.lengths), bool)
+    where[nf.planted_tracks(sc)] = True
+    badt = np.zeros(len(sc.lengths), bool)
+    badt[sc.bad_tracks()] = True
+    stands = _lib.succeeded(fp) & (tracks[3] != 0)
+    read = where & (ftr["kind"] != ftw.KIND_NOT_ELIGIBLE)
+    assert np.all(ftr["dropped_by_error"][read] >= 1) and not fm[o[:-1][read] + nf.PLANT_AT].any(), (what, fst)
+    zero = completed(ctx, host, sc, tracks, cam, what + ("-0.0",), max_error=-0.0, case=case)
+    assert zero[0]["admitted"] == 0 and zero[0]["candidates"] == zero[0]["rejected_by_error"] > 0 and same_state(zero[5], state(ctx)), (what, zero[0])
+    if nf.REG < len(sc.ids) and int(sc.ids[nf.REG]) in ctx.poses():
+        # (scoped to REG: image 7's candidates alone, the bad ones rejected; what it admits the full call would have admitted as well)
+        reg = int(sc.ids[nf.REG])
+        scoped = completed(ctx, host, sc, tracks, cam, what + ("scoped",), scope=[reg], case=case)
+        rose = (scoped[3] != 0) & (scoped[5][2] == 0)
+        assert np.all(tracks[1][rose] == reg) and scoped[0]["candidates"] == int(((tracks[1] == reg) & (scoped[5][2] == 0) & np.repeat(stands, np.diff(o))).sum())
+    out = completed(ctx, host, sc, tracks, cam, what + ("planted",), case=case)
+    long_bad = badt & where
+    # (on this robust session every bad 8-view track stands, unless the plain route of max_hypotheses 0 created it: second form)
+    assert np.array_equal(out[6][long_bad], stands[long_bad]) and (out[6].any() or not stands[long_bad].any()), (what, out[4][long_bad])
+    assert np.all(out[4]["admitted"][where & stands] >= 1), (what, out[4][where & stands])
+    for pos in sorted(set(nf.BAD_AT + nf.BAD_AT_SHORT)):
+        if pos < len(sc.ids):
+            ctx.upload_keypoints(int(sc.ids[pos]), sc.clean[pos])
+    cure = completed(ctx, host, sc, tracks, cam, what + ("cure",), kps=sc.clean)
+    st, pts, res, mask, tr, before = cure[:6]
+    gained = (mask != 0) & (before[2] == 0)
+    done = np.repeat(tr["kind"] == ctw.KIND_COMPLETED, np.diff(o))
+    assert np.all(sc.bad[gained]) and np.all(np.isfinite(res[gained]) & (res[gained] <= nf.THR[0])), what
+    assert not np.isnan(res[done]).any() and not np.isnan(res[~sc.bad]).any(), what
+    assert not (before[1][gained] <= nf.THR[0]).any(), what
+    if case[0].startswith("nan"):
+        assert np.isnan(before[1][gained]).all(), what
+    # every formerly bad observation of a standing 8-view track sits 0.3 px of noise from its point: admitted (the twin decides; that
+    # it admits them all on these fixtures is tests/test_nonfinite_reference.py::test_the_cure's finding, from tests/complete_ref.py)
+    tight = ~(np.add.reduceat(((before[2] != 0) & sc.bad).astype(np.int64), o[:-1]) > 0)
+    assert st["admitted"] == int(gained.sum()) and st["admitted"] >= int((badt & stands & tight).sum()), (what, st)
+    return out, cure
 
 
 def chain(ctx, host, sc, cam, mh, case):
@@ -181,7 +305,8 @@ def chain(ctx, host, sc, cam, mh, case):
     robust triangulation, point refinement, registration of REG, extension by NEW and REG's registered pose with max_hypotheses mh,
     pose refinement, point refinement; the filter under FILTER_TRIM, then under the tighter FILTER_MIX, and a point refinement; then,
     each behind a robust triangulation under the session's final poses (the state no filter has touched), the filter under
-    FILTER_ANGLE and under FILTER_VIEWS.  -> dict step -> the device's outputs"""
+    FILTER_ANGLE and under FILTER_VIEWS; then the second pass with the completion (module docstring).
+    -> dict step -> the device's outputs"""
     what = (case and case[0], mh)
     tracks = open_scene(ctx, sc)
     first = sc.some([p for p in nf.OLD if p < len(sc.ids)])
@@ -194,16 +319,7 @@ def chain(ctx, host, sc, cam, mh, case):
     # (the filter removes or trims every eligible bad track, the others have no point: every sum is finite behind it, whatever the value)
     out["filter0"] = filtered(ctx, host, sc, tracks, cam, what + ("filter0",), creates_bytes=True)
     out["refine0f"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine0f",))
-    out["robust"] = triangulated(ctx, host, sc, tracks, first, cam, True, what + ("robust",))
-    out["refine1"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine1",))
-    new = sc.some([p for p in nf.NEW if p < len(sc.ids)])
-    if nf.REG < len(sc.ids):
-        out["register"] = registered(ctx, host, sc, tracks, cam, what + ("register",))
-        new = _lib.registered_poses(out["register"][1][0], new)
-    out["extend"] = extended(ctx, host, sc, tracks, new, mh, cam, what + ("extend",))
-    out["poses"] = poses_refined(ctx, host, sc, tracks, cam, what + ("poses",))
-    # (with max_hypotheses 0 a bad 3-view track is created on the plain route: after it the sums may be +inf as after the plain call)
-    out["refine2"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine2",), finite_costs=mh > 0 or finite)
+    out.update(robust_session(ctx, host, sc, tracks, cam, mh, what, finite))
     out["filter_trim"] = filtered(ctx, host, sc, tracks, cam, what + ("trim",), nf.FILTER_TRIM)
     out["filter_mix"] = filtered(ctx, host, sc, tracks, cam, what + ("mix",), nf.FILTER_MIX)
     out["refine3"] = points_refined(ctx, host, sc, tracks, cam, what + ("refine3",))
@@ -211,6 +327,17 @@ def chain(ctx, host, sc, cam, mh, case):
     for name, pair in (("angle", nf.FILTER_ANGLE), ("views", nf.FILTER_VIEWS)):
         triangulated(ctx, host, sc, tracks, last, cam, True, what + ("robust before " + name,))
         out["filter_" + name] = filtered(ctx, host, sc, tracks, cam, what + (name,), pair)
+    # the second pass (module docstring): the completion behind FILTER_TRIM, behind FILTER_TRIM then FILTER_MIX, and planted
+    for name in ("trim", "mix"):
+        rebuilt(ctx, sc, cam, mh, out)
+        for pair in (nf.FILTER_TRIM, nf.FILTER_MIX)[:1 if name == "trim" else 2]:
+            ctx.filter_points(max_error=pair[0], min_angle=pair[1])
+        for got, want in zip(state(ctx)[:3], out["filter_" + name][1:4]):
+            same_bytes(got, want, what + ("the second pass behind " + name,))
+        out["complete_" + name] = completed(ctx, host, sc, tracks, cam, what + ("complete behind " + name,), case=case)
+    if case is not None:
+        rebuilt(ctx, sc, cam, mh, out)
+        out["complete_planted"], out["cure"] = planted_and_cured(ctx, host, sc, tracks, cam, what, case)
     ctx.tracks_end()
     return out
 
@@ -220,7 +347,11 @@ def chain(ctx, host, sc, cam, mh, case):
 def test_the_chain_on_one_session(tctx, host, place, cam):
     """every call of the chain against its twin, with max_hypotheses 8 (the retry list runs) and 0 (ext_mask_kernel and the plain
     route); the routes the fixture is for, on the device's own outputs.  The filter runs five times per chain: on the plain session
-    (ext_mask_kernel as the filter launches it) and under the four pairs of nonfinite_fixtures.FILTER_PAIRS."""
+    (ext_mask_kernel as the filter launches it) and under the four pairs of nonfinite_fixtures.FILTER_PAIRS.  The completion runs
+    on the second pass of every chain: behind FILTER_TRIM, behind FILTER_TRIM and FILTER_MIX, planted, with max_error -0.0, scoped to
+    REG, and on the cured keypoints.  The wall time of the filter steps and of the completion steps is printed."""
+    for k in SECONDS:
+        del SECONDS[k][:]
     for n, case in enumerate(nf.drawn(seed=sorted(PLACEMENTS).index(place) * 2 + sorted(CAMS).index(cam), k=3)):
         sc = PLACEMENTS[place](case)[0]
         for mh in (8, 0):
@@ -243,6 +374,18 @@ def test_the_chain_on_one_session(tctx, host, place, cam):
             assert (trims[0] & badt).any() or (trims[1] & badt).any(), (case[0], mh)      # a bad track's slots were rewritten
             assert (out["filter_trim"][4]["kind"][~badt] == ftw.KIND_UNTOUCHED).any() and out["filter_mix"][0]["trimmed"] > 0
             assert out["filter_angle"][0]["removed_by_angle"] > 0 and out["filter_views"][0]["removed_by_views"] > 0, (case[0], mh)
+            # the completion's routes (tests/test_nonfinite_reference.py, compare_complete), on the twin's traces of the device's own
+            # states: behind the filter a bad track is completed -- its bad slots rewritten -- under one of the two pairs at least,
+            # and one with a rejected bad candidate is left untouched; on the planted route every standing bad 8-view track is
+            # completed (asserted in planted_and_cured) and the cure admits the formerly bad observations
+            behind = [out["complete_trim"], out["complete_mix"]]
+            assert (behind[0][6] | behind[1][6]).any() and (behind[0][7] | behind[1][7]).any(), (case[0], mh, [b[0] for b in behind])
+            reached = dict(behind_trim=int(behind[0][6].sum()), behind_mix=int(behind[1][6].sum()), planted=int(out["complete_planted"][6].sum()),
+                           untouched=[int(b[7].sum()) for b in behind], cured=out["cure"][0]["admitted"])
+            assert reached["planted"] > 0 and reached["cured"] > 0, (case[0], mh, reached)
+            print(place, cam, case[0], mh, "bad tracks completed / left untouched with a rejected bad candidate / observations cured:", reached)
+    print("wall time of this test's filter steps: %d calls, %.3f s; of its completion steps: %d calls, %.3f s" %
+          (len(SECONDS["filter"]), sum(SECONDS["filter"]), len(SECONDS["complete"]), sum(SECONDS["complete"])))
 
 
 @pytest.mark.parametrize("T", [257, 256, 255, 65, 64, 63, 1])
@@ -251,7 +394,34 @@ def test_track_count_prefixes_of_the_lane_placement(tctx, host, T):
     case = nf.drawn(seed=11, k=4)[[257, 256, 255, 65, 64, 63, 1].index(T) % 4]
     sc = nf.lanes(case)[0].prefix(T)
     assert len(sc.bad_tracks()) == sum(t < T for t in nf.LANES)
-    chain(tctx, host, sc, nf.CAM, 8 if T % 2 else 0, case)
+    out = chain(tctx, host, sc, nf.CAM, 8 if T % 2 else 0, case)
+    # the completion step of every prefix: each bad track of it is planted and completed, at whatever lane the prefix ends
+    planted = out["complete_planted"]
+    assert np.all(planted[4]["kind"][sc.bad_tracks()] == ctw.KIND_COMPLETED) and planted[6].sum() == len(sc.bad_tracks()), (T, planted[4][sc.bad_tracks()])
+
+
+@pytest.mark.parametrize("cam", sorted(CAMS))
+@pytest.mark.parametrize("place", ["lanes", "wave"])
+def test_completion_on_the_planted_route(tctx, host, place, cam):
+    """planted_and_cured() behind the robust session (max_hypotheses 8) with values of its own draw (always a signed NaN and an
+    infinity).  lanes: the bad tracks at the lanes 0, 63 | 64, 255 | 256 of cmp_track_kernel are completed, each with its three bad
+    candidates rejected beside the admitted one, and their rewritten slots are THE NaN, +inf or finite as
+    nonfinite_fixtures.bad_slot_class says.  wave: the 64 tracks of the middle wave are completed, each beside one rejected bad
+    candidate: a whole wave of such tracks goes through wave_add_counters, and all eight counters equal the twin's.  Then the cure:
+    the true keypoints uploaded, every formerly bad observation admitted, no NaN left in the session's residuals."""
+    for case in nf.drawn(seed=21 + 2 * ["lanes", "wave"].index(place) + sorted(CAMS).index(cam), k=3):
+        sc = PLACEMENTS[place](case)[0]
+        what = (case[0], place, cam)
+        tracks = open_scene(tctx, sc)
+        robust_session(tctx, host, sc, tracks, CAMS[cam], 8, what)
+        (st, pts, res, mask, tr, before, done, untouched), cure = planted_and_cured(tctx, host, sc, tracks, CAMS[cam], what, case)
+        badt = sc.bad_tracks()
+        n_bad = len(nf.BAD_AT) if place == "lanes" else 1
+        assert np.array_equal(np.nonzero(done)[0], badt) and len(badt) == (len(nf.LANES) if place == "lanes" else 64), (what, tr[badt])
+        assert np.all(tr["candidates"][badt] - tr["admitted"][badt] >= n_bad) and np.all(tr["admitted"][badt] >= 1), (what, tr[badt])
+        assert st["rejected_by_error"] >= n_bad * len(badt) and st["completed"] >= len(nf.planted_tracks(sc)), (what, st)
+        assert cure[0]["admitted"] == n_bad * len(badt) == int(sc.bad.sum()) and not np.isnan(cure[2]).any(), (what, cure[0])
+        tctx.tracks_end()
 
 
 def test_the_clean_neighbours(tctx, host):

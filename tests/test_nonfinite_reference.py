@@ -24,10 +24,18 @@ THE FILTER (msfm_filter_points' twin, FilterPoints) runs at the end of the chain
 state after the last point refinement -- under the session's own thresholds it drops nothing there and would only walk its no-op path
 -- and, on the plain session, behind the first point refinement under the session's thresholds, where it creates the inlier bytes
 (compare_filter, test_the_plain_session_filter).  A trimmed track goes through point_verdict in its `residuals != nullptr` mode, which
-rewrites the slot of every USED observation, the bad ones included: one more store of a NaN."""
+rewrites the slot of every USED observation, the bad ones included: one more store of a NaN.
+
+THE COMPLETION (msfm_complete_points' twin, CompletePoints) runs as a side step of the chain behind the filter under FILTER_MIX and
+FILTER_TRIM, and on the PLANTED route (nf.complete_planted): there one clean observation of every third track and of every bad
+8-view track is moved by 40 px, dropped by the filter under the session's thresholds and found again under the original keypoints.
+Every bad observation in a posed image has byte 0 and is USED: it is a candidate of every completion call, and it must be rejected
+by its error -- `!(err <= max_error)`, the one comparison a NaN passes through -- never by depth, which reads X and the pose alone
+(compare_complete, test_the_cure, test_completion_call_parameters)."""
 import numpy as np
 import pytest
 
+import complete_twin as ctw
 import extend_twin as etw
 import filter_twin as ftw
 import nonfinite_fixtures as nf
@@ -225,19 +233,194 @@ def compare_filter(host, sc, case, cam, a, b, mh, robust, routes=True, mix_trims
             assert ca["removed_by_views"] > 0 and drops > 0, (what, ca)
 
 
+# ---- the completion ---------------------------------------------------------------------------------------------------------------------------
+def completion_steps(out):
+    """(name, the state before the call, first, again) of every completion step of nf.chain's outputs"""
+    steps = [(name, out["filter"][name][:3]) + tuple(out["complete"][name]) for name in nf.COMPLETE_BEHIND]
+    pl = out["complete_planted"]
+    return steps + [("planted", pl["filter"][:3], pl["first"], pl["again"])]
+
+
+def compare_complete(host, sc, gr, case, cam, a, b, mh, robust, routes=True):
+    """The completion steps of the chain outputs `a` (the scene) against those of `b` (the twin scene `gr`): behind FILTER_MIX, behind
+    FILTER_TRIM and on the planted route, each call and its repetition.
+      equivalence   FIRST FORM on every track but the second-form tracks of the last point refinement (compare_filter): records,
+                    inlier bytes, traces and every residual slot but the bad observations' own byte for byte; the six counters and
+                    the two sums where no track is of the second form; the planted route's filter step the same way.
+      rejection     no bad observation gets byte 1; every bad observation of an eligible track is a candidate and is rejected by its
+                    error: the track's rejections by depth are 0 and its rejections by error at least its bad observations;
+                    rejected_by_depth equals the twin scene's (0 on every fixture here).
+      untouched     a track that is not COMPLETED -- untouched or not eligible -- is bit for bit what it was, its bad slots included,
+                    and at least one UNTOUCHED track has a bad candidate: on the planted route a standing bad track outside the
+                    planting (the 3-view tracks of the images placement), elsewhere behind the filter.
+      completed     a completed bad track: every bad slot holds what nf.bad_slot_class says and nothing else; n_views = the bytes,
+                    none of them on a bad observation; every float field of every record finite.  (These three per call:
+                    nf.completion_routes, which tests/test_gpu_nonfinite.py applies to the device's calls.)
+      routes        on the planted route EVERY standing bad 8-view track is completed, with a rejected bad candidate beside the
+                    admitted one, and on the robust session all of them stand; behind the filter at least one of the two pairs
+                    completes a bad track.
+      fixed point   the second call admits nothing and changes no byte, NaN slots included (bytes compared, not values).
+      scope         one call from the planted route's filtered state with the list {REG}: the candidates are the byte-0 elements in
+                    image 7 of the eligible tracks, fewer than without a list, the bad ones among them rejected; equal to the twin
+                    scene's call."""
+    o = sc.tracks[0]
+    T = len(sc.lengths)
+    per_slot = np.repeat(np.arange(T), np.diff(o))
+    loose = loose_tracks("refine2", sc, a, mh, robust)
+    tight, tight_slot = ~loose, ~loose[per_slot]
+    badt = np.zeros(T, bool)
+    badt[sc.bad_tracks()] = True
+    lst = a["poses"][2]
+    posed = np.isin(sc.tracks[1], [i for i, p in ptw.poses_dict(*lst).items() if p is not None])
+    fa, fb = a["complete_planted"]["filter"], b["complete_planted"]["filter"]
+    assert fa[0][tight].tobytes() == fb[0][tight].tobytes() and fa[2][tight_slot].tobytes() == fb[2][tight_slot].tobytes(), case[0]
+    assert fa[4][tight].tobytes() == fb[4][tight].tobytes() and (loose.any() or fa[3] == fb[3]), (case[0], fa[3], fb[3])
+    where = np.zeros(T, bool)
+    where[a["complete_planted"]["where"]] = True
+    moved = where & tight & (fa[4]["kind"] != ftw.KIND_NOT_ELIGIBLE)      # (the filter dropped the moved observation of every track it read)
+    assert np.all(fa[4]["dropped_by_error"][moved] >= 1) and not fa[2][o[:-1][moved] + nf.PLANT_AT].any(), case[0]
+    completed_bad, untouched_bad = {}, {}
+    for (name, before, first, again), (_, _, gfirst, gagain) in zip(completion_steps(a), completion_steps(b)):
+        what = (case[0], name, mh, robust)
+        p0, r0, m0 = before
+        for (pa, sa, ma, ca, ta), (pb, sb, mb, cb, tb) in ((first, gfirst), (again, gagain)):
+            assert not ma[sc.bad & tight_slot].any(), (what, np.nonzero(ma.astype(bool) & sc.bad & tight_slot)[0][:8])
+            assert pa[tight].tobytes() == pb[tight].tobytes(), (what, np.nonzero(pa != pb)[0][:8])
+            assert sa[tight_slot & ~sc.bad].tobytes() == sb[tight_slot & ~sc.bad].tobytes(), what
+            assert ma[tight_slot].tobytes() == mb[tight_slot].tobytes() and ta[tight].tobytes() == tb[tight].tobytes(), what
+            assert ca["rejected_by_depth"] == cb["rejected_by_depth"] == 0, (what, ca, cb)
+            if not loose.any():
+                assert ca == cb, (what, ca, cb)
+            float_fields_finite(pa)
+            assert not np.isnan(sa[~sc.bad]).any() and nan_bits(sa) <= {CANONICAL}, (what, [hex(v) for v in nan_bits(sa)])
+        pa, sa, ma, ca, ta = first
+        completed_bad[name], untouched_bad[name] = nf.completion_routes(sc, case, CAMS[cam], posed, before, first, tight, what)
+        # the fixed point
+        pb, sb, mb, cb, tb = again
+        assert pb.tobytes() == pa.tobytes() and sb.tobytes() == sa.tobytes() and mb.tobytes() == ma.tobytes(), what
+        assert cb["admitted"] == cb["completed"] == 0 and cb["candidates"] == ca["candidates"] - ca["admitted"], (what, ca, cb)
+        assert all(cb[k] == ca[k] for k in ("eligible", "succeeded", "observations_used", "rejected_by_depth")), (what, ca, cb)
+    # one scoped call: the candidates in REG alone
+    reg = int(sc.ids[nf.REG]) if nf.REG < len(sc.ids) else -1
+    if posed[sc.tracks[1] == reg].any():
+        state = fa[:3]
+        full = a["complete_planted"]["first"]
+        got, _ = nf.completed_twice(host, sc, sc.kps, lst, CAMS[cam], state, scope=[reg])
+        want, _ = nf.completed_twice(host, gr, gr.kps, b["poses"][2], CAMS[cam], fb[:3], scope=[reg])
+        eligible = full[4]["kind"] != ctw.KIND_NOT_ELIGIBLE
+        in_reg = (sc.tracks[1] == reg) & (state[2] == 0) & eligible[per_slot]
+        assert got[3]["candidates"] == int(in_reg.sum()) < full[3]["candidates"], (case[0], got[3], full[3])
+        assert np.array_equal(got[4]["candidates"], np.add.reduceat(in_reg.astype(np.int64), o[:-1])), case[0]
+        rose = (got[2] != 0) & (state[2] == 0)
+        assert np.all(sc.tracks[1][rose] == reg) and not got[2][sc.bad & tight_slot].any(), case[0]
+        assert got[3]["rejected_by_error"] >= int((in_reg & sc.bad).sum()) and got[3]["rejected_by_depth"] == 0, (case[0], got[3])
+        assert got[0][tight].tobytes() == want[0][tight].tobytes() and got[2][tight_slot].tobytes() == want[2][tight_slot].tobytes(), case[0]
+        assert got[4][tight].tobytes() == want[4][tight].tobytes() and (loose.any() or got[3] == want[3]), (case[0], got[3], want[3])
+        assert got[1][tight_slot & ~sc.bad].tobytes() == want[1][tight_slot & ~sc.bad].tobytes() and nan_bits(got[1]) <= {CANONICAL}, case[0]
+    if not routes or not (badt & tight).any():
+        return None
+    # the routes
+    stands = _lib.succeeded(fa[0]) & (sc.tracks[3] != 0)
+    long_bad = badt & tight & (np.asarray(sc.lengths) == 8)
+    assert where[long_bad].all() and (stands & long_bad).any(), (case[0], mh, robust)
+    assert not robust or stands[long_bad].all(), (case[0], mh, np.nonzero(long_bad & ~stands)[0])
+    assert np.array_equal(completed_bad["planted"][long_bad], stands[long_bad]), (case[0], mh, robust)   # EVERY standing one
+    assert completed_bad["mix"].any() or completed_bad["trim"].any(), (case[0], mh, robust)
+    outside = badt & tight & ~where & stands
+    if outside.any():
+        assert untouched_bad["planted"][outside].all(), (case[0], mh, robust, np.nonzero(outside & ~untouched_bad["planted"])[0])
+    else:
+        assert untouched_bad["mix"].any() or untouched_bad["trim"].any(), (case[0], mh, robust)
+    return {k: int(v.sum()) for k, v in completed_bad.items()}, {k: int(v.sum()) for k, v in untouched_bad.items()}
+
+
 @pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
 @pytest.mark.parametrize("cam", sorted(CAMS))
 @pytest.mark.parametrize("place", sorted(PLACEMENTS))
 def test_the_chain_equals_the_gross_outlier_scene(host, place, cam, case):
     """robust and plain session, the extension with max_hypotheses 8 and 0: the module docstring says what is compared which way; then
-    the filter steps at the end of every one of these chains (compare_filter)"""
-    sc = PLACEMENTS[place](case)[0]
+    the filter steps at the end of every one of these chains (compare_filter) and the completion steps beside them (compare_complete)"""
+    sc, _, gr = PLACEMENTS[place](case)
     for robust in (True, False):
         for mh in (8, 0):
             a = nf.chain(host, sc, CAMS[cam], mh=mh, robust=robust)
             compare(sc, case, a, gross_chain(host, place, case, cam, mh, robust), mh, robust)
             compare_filter(host, sc, case, CAMS[cam], a, gross_chain(host, place, case, cam, mh, robust), mh, robust,
                            mix_trims_bad=(place, cam) != ("lanes", "cam"))
+            reached = compare_complete(host, sc, gr, case, cam, a, gross_chain(host, place, case, cam, mh, robust), mh, robust)
+            print(place, cam, case[0], "robust" if robust else "plain", mh, "bad tracks completed, untouched with a bad candidate:", reached)
+
+
+@pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
+@pytest.mark.parametrize("cam", sorted(CAMS))
+@pytest.mark.parametrize("place", sorted(PLACEMENTS))
+def test_the_cure(host, place, cam, case):
+    """A bad keypoint that is later replaced by a good one: from the state behind the planted route's completion the TRUE keypoints
+    are uploaded in place of the bad ones (the clean scene of the same seed) and the completion runs again, on the robust and on the
+    plain session (max_hypotheses 8).  What must be admitted comes from tests/complete_ref.py on the cured scene, not from the twin:
+    every formerly bad observation of a standing track whose depth is positive and whose error under the current pose is within
+    max_error -- no such error lies within 1e-6 px of the threshold, the reference module's guard.  The twin's bytes, kinds and view
+    counts equal the reference's on every bad track; an admitted observation's slot goes from a number that fails `<= max_error` (a
+    NaN under a NaN) to a finite one within it; a completed track holds no NaN any more, and NaNs stand only in the bad slots of the
+    tracks that were not completed; every clean track is untouched."""
+    import complete_ref as cr
+    import test_complete_points_reference as xc
+    sc = PLACEMENTS[place](case)[0]
+    clean = PLACEMENTS[place](None)[0]
+    o, img, idx, cons = sc.tracks[:4]
+    kd = clean.kd()
+    badt = sc.bad_tracks()
+    for robust in (True, False):
+        a = nf.chain(host, sc, CAMS[cam], mh=8, robust=robust)
+        lst = a["poses"][2]
+        poses = ptw.poses_dict(*lst)
+        p0, r0, m0 = a["complete_planted"]["first"][:3]
+        pts, res, mask, cnt, tr = ctw.run(host, sc.tracks, sc.ids, clean.kps, lst, CAMS[cam], p0, r0, m0, nf.THR[:2], trace=True)
+        cured = 0
+        for t in badt:
+            b, e = int(o[t]), int(o[t + 1])
+            w = cr.track(img[b:e], idx[b:e], bool(cons[t]), kd, poses, CAMS[cam], p0[t], r0[b:e], m0[b:e], nf.THR[:2], nf.THR[0])
+            what = (case[0], robust, int(t), tr[t], w["kind"], w["mask"])
+            assert w["error_margin"] > xc.GUARD_ERR and w["angle_margin"] > xc.GUARD_ANGLE, what
+            assert tr[t]["kind"] == w["kind"] and np.array_equal(mask[b:e], w["mask"]), what
+            assert (tr[t]["candidates"], tr[t]["admitted"], tr[t]["rejected_by_depth"]) == (w["candidates"], w["admitted"], w["rejected_by_depth"]), what
+            assert pts[t]["status"] == w["status"] and pts[t]["n_views"] == w["n_views"], what
+            if w["kind"] != cr.NOT_ELIGIBLE:
+                assert w["candidates"] >= sc.bad[b:e].sum() and w["rejected_by_depth"] == 0, what   # every formerly bad observation is tested
+            for k in np.nonzero(sc.bad[b:e] & (w["mask"] != 0))[0]:
+                assert m0[b + k] == 0 and not r0[b + k] <= nf.THR[0] and np.isnan(r0[b + k]) == (nf.bad_slot_class(case, CAMS[cam]) == "nan"), (what, r0[b + k])
+                assert np.isfinite(res[b + k]) and 0.0 <= res[b + k] <= nf.THR[0], (what, res[b + k])
+                assert abs(res[b + k] - w["residuals"][k]) <= xc.TOL["residual"], (what, res[b + k], w["residuals"][k])
+                cured += 1
+            if w["kind"] == cr.COMPLETED:
+                assert not np.isnan(res[b:e]).any(), what
+        done = np.repeat(tr["kind"] == ctw.KIND_COMPLETED, np.diff(o))
+        assert not np.isnan(res[~sc.bad | done]).any() and nan_bits(res) <= {CANONICAL}, case[0]
+        rest = np.setdiff1d(np.arange(len(sc.lengths)), badt)
+        assert np.all(tr["kind"][rest] != ctw.KIND_COMPLETED) and pts[rest].tobytes() == p0[rest].tobytes(), case[0]
+        assert cured == cnt["admitted"] and cured >= len(badt), (case[0], robust, cured, cnt)      # (more than one per bad track)
+        float_fields_finite(pts)
+        print(place, cam, case[0], "robust" if robust else "plain", "formerly bad observations admitted:", cured, "of", int(sc.bad.sum()), cnt)
+
+
+def test_completion_call_parameters(host):
+    """max_error as a NaN, +inf, -inf and a negative number: the twin's export refuses them as the entry point does
+    (tests/test_gpu_complete_points.py::test_errors_leave_the_session_alone).  -0.0 is accepted by both -- it is not below zero --
+    and admits only an observation whose error is exactly 0: on the planted route under a bad value, every candidate is rejected by
+    error, nothing is written, and the result is that of +0.0."""
+    case = next(c for c in nf.CASES if c[0] == "nan_signed_xy")
+    sc = nf.lanes(case)[0]
+    a = nf.chain(host, sc, nf.CAM_D)
+    lst, state = a["poses"][2], a["complete_planted"]["filter"][:3]
+    for refused in (np.nan, -np.nan, np.inf, -np.inf, -1.0, np.nextafter(nf.THR[0], np.inf)):
+        with pytest.raises(AssertionError):
+            nf.completed_twice(host, sc, sc.kps, lst, nf.CAM_D, state, max_error=refused)      # host_complete_points returns 3
+    outs = [nf.completed_twice(host, sc, sc.kps, lst, nf.CAM_D, state, max_error=z)[0] for z in (-0.0, 0.0)]
+    for pts, res, mask, cnt, tr in outs:
+        assert cnt["candidates"] == cnt["rejected_by_error"] == a["complete_planted"]["first"][3]["candidates"] > 0 and cnt["admitted"] == 0, cnt
+        assert pts.tobytes() == state[0].tobytes() and res.tobytes() == state[1].tobytes() and mask.tobytes() == state[2].tobytes()
+        assert np.all(tr["kind"] != ctw.KIND_COMPLETED)
+    assert outs[0][3] == outs[1][3] and outs[0][4].tobytes() == outs[1][4].tobytes()
 
 
 @pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)
@@ -521,7 +704,7 @@ def test_the_gross_scene_against_the_references(host, cam, axes):
     """The twin scene (1e6 in the bad coordinates) of the images placement is finite, so the independent numpy references process it:
     every twin of the chain against its reference, fed the same state, with the comparison functions, guards and tolerances of that
     twin's own reference test (tests/test_*_reference.py); the point and pose refinements with those modules' step_tol 1e-4.  Then
-    the filter steps of nf.chain on this scene against tests/filter_ref.py."""
+    the filter steps of nf.chain on this scene against tests/filter_ref.py and its completion steps against tests/complete_ref.py."""
     import extend_ref
     import refine_points_ref
     import refine_poses_ref
@@ -636,7 +819,9 @@ def test_the_gross_scene_against_the_references(host, cam, axes):
     # the filter at the end of the twin scene's chain, under every pair, after the extension with max_hypotheses 8 and 0 (with 0 the bad
     # 3-view tracks are plain records over the 1e6 observation: eligible, the observation FITTING, dropped by error on both sides);
     # the comparison and the tolerances of tests/test_filter_points_reference.py
+    import complete_ref
     import filter_ref
+    import test_complete_points_reference as xc
     import test_filter_points_reference as xf
     rel.clear()
     for mh in (8, 0):
@@ -649,6 +834,15 @@ def test_the_gross_scene_against_the_references(host, cam, axes):
             w, eligible, left, margins = xf.compare(dict(name=(name, mh), tracks=tracks, before=(pp, pr, pm), got=got, want=want))
             print("filter %s, max_hypotheses %d:" % (name, mh), w, eligible, left, margins, got[3])
             assert eligible == len(gr.lengths) and not left and all(w[q] <= xf.TOL[q] for q in xf.TOL), (name, mh, w, left)
+        # the completion steps of the same chain against tests/complete_ref.py, fed the twin's state before each call (on the planted
+        # route: the filter's outputs under the moved keypoints); the comparison and the tolerances of
+        # tests/test_complete_points_reference.py -- DESIGN.md section 22's bounds -- and no track left out by its guards
+        for name, before, first, _ in completion_steps(g):
+            want = complete_ref.run(tracks, kd, ptw.poses_dict(*lst), c_, before[0], before[1], before[2], thr[:2])
+            got = (first[0], bad_slots_apart(first[1], want, xc.TOL["residual"])) + first[2:]
+            w, eligible, left, margins = xc.compare(dict(name=(name, mh), tracks=tracks, before=before, got=got, want=want))
+            print("completion %s, max_hypotheses %d:" % (name, mh), w, eligible, left, margins, got[3])
+            assert eligible >= 48 and got[3]["completed"] > 0 and not left and all(w[q] <= xc.TOL[q] for q in xc.TOL), (name, mh, w, left)
     print("filter: the bad observations' errors, worst difference relative to their size: %.3g over %d slots" % (max(rel, default=0.0), len(rel)))
     assert any(c_[4:]) or len(rel) > 0
 
@@ -664,6 +858,9 @@ def test_track_count_prefixes_on_the_twins(host, T):
             a, b = nf.chain(host, sc, nf.CAM, mh=mh), nf.chain(host, gr, nf.CAM, mh=mh)
             compare(sc, case, a, b, mh, True)
             compare_filter(host, sc, case, nf.CAM, a, b, mh, True, routes=False)     # (one track has no clean neighbour to leave untouched)
+            compare_complete(host, sc, gr, case, "cam", a, b, mh, True, routes=False)
+            pl = a["complete_planted"]                                               # every bad track of the prefix: planted, completed
+            assert np.all(pl["first"][4]["kind"][sc.bad_tracks()] == ctw.KIND_COMPLETED), (T, case[0], mh, pl["first"][4][sc.bad_tracks()])
 
 
 @pytest.mark.parametrize("case", nf.CASES, ids=nf.CASE_IDS)

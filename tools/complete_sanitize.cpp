@@ -9,7 +9,9 @@
 // end.  Prints the counters; exits 1 if nothing was admitted, if an untouched or ineligible track changed, if a completed record moved
 // its X or miscounts its views, if a byte fell, or if the second call changed a byte or admitted anything.
 // A second pass puts the non-finite and huge values of DESIGN.md section 21 into every second candidate's keypoint: every such
-// candidate is rejected, no record field is non-finite, a NaN in a residual slot is THE NaN in such a candidate's slot.
+// candidate is rejected -- by its error: the rejections by depth are those of the clean keypoints --, no record field is non-finite,
+// a NaN in a residual slot is THE NaN in such a candidate's slot, a track that is not completed -- those whose ONLY candidates were
+// replaced among them -- keeps every byte, rejected candidates' slots included.
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
 //       tools/complete_sanitize.cpp -o complete_sanitize && ./complete_sanitize
 #include <cmath>
@@ -159,7 +161,7 @@ int main() {
     const uint32_t values[10] = {0x7fc00000u, 0xffc00000u, 0x7fc00001u, 0x7f800000u, 0xff800000u, 0x7f61b1e6u /* 3e38 */, 0xff61b1e6u,
                                  0x7149f2cau /* 1e30 */, 0x00000001u, 0x80000000u};
     const double calls[2] = {prm.max_error, cmp_max_error};
-    long long replaced_rejected = 0, nan_slots = 0, beside = 0;
+    long long replaced_rejected = 0, nan_slots = 0, beside = 0, only_replaced = 0;
     for (int robust = 0; robust < 2; ++robust) {
         std::vector<msfm_point3d> pts0;
         std::vector<double> res0;
@@ -191,13 +193,32 @@ int main() {
                 std::vector<msfm_point3d> pts = pts0;
                 std::vector<double> res = res0;
                 std::vector<uint8_t> mask = mask0;
+                msfm_cmp::Counts clean_c = {0, 0, 0, 0, 0, 0};   // the same call over the clean keypoints: its rejections by depth
+                msfm_cmp::CompletePoints(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), ptr_clean.data(), table.data(),
+                                         n_img, nullptr, cam, prm, call, true, pts.data(), res.data(), mask.data(), &clean_c);
+                pts = pts0;
+                res = res0;
+                mask = mask0;
                 for (int pass = 0; pass < 2; ++pass) {
                     const std::vector<msfm_point3d> p0 = pts;
                     const std::vector<double> r0 = res;
                     const std::vector<uint8_t> m0 = mask;
                     msfm_cmp::Counts c = {0, 0, 0, 0, 0, 0};
+                    std::vector<msfm_cmp::Trace> trace((size_t)n_tr);
                     msfm_cmp::CompletePoints(offsets.data(), img.data(), idx.data(), cons.data(), 0, n_tr, rank_of.data(), pbad.data(), table.data(), n_img,
-                                             nullptr, cam, prm, call, true, pts.data(), res.data(), mask.data(), &c);
+                                             nullptr, cam, prm, call, true, pts.data(), res.data(), mask.data(), &c, trace.data());
+                    // depth reads X and the pose, never the keypoint; a track that is not completed keeps every byte
+                    bad = bad || c.rejected_by_depth != clean_c.rejected_by_depth || (pass == 0 && c.candidates != clean_c.candidates);
+                    for (int t = 0; t < n_tr; ++t) {
+                        const size_t b = (size_t)offsets[(size_t)t], n = (size_t)offsets[(size_t)t + 1] - b;
+                        const msfm_cmp::Trace& tr = trace[(size_t)t];
+                        if (tr.kind == msfm_cmp::KIND_COMPLETED) continue;
+                        bad = bad || std::memcmp(&pts[(size_t)t], &p0[(size_t)t], sizeof(msfm_point3d)) || std::memcmp(&res[b], &r0[b], n * sizeof(double)) ||
+                              std::memcmp(&mask[b], &m0[b], n);
+                        long long here = 0;
+                        for (size_t k = 0; k < n; ++k) here += replaced[b + k];
+                        if (pass == 0 && tr.kind == msfm_cmp::KIND_UNTOUCHED && here > 0 && here == tr.candidates) only_replaced += 1;
+                    }
                     if (pass == 1) {
                         bad = bad || std::memcmp(pts.data(), p0.data(), pts.size() * sizeof(msfm_point3d)) ||
                               std::memcmp(res.data(), r0.data(), res.size() * sizeof(double)) || std::memcmp(mask.data(), m0.data(), mask.size()) ||
@@ -225,7 +246,7 @@ int main() {
                 }
             }
     }
-    std::printf("admitted %lld in %lld records; replaced candidates rejected %lld (admitted beside them %lld), NaN slots %lld, %s\n", admitted,
-                completed, replaced_rejected, beside, nan_slots, bad ? "BAD" : "ok");
-    return admitted > 0 && completed > 0 && replaced_rejected > 0 && beside > 0 && !bad ? 0 : 1;
+    std::printf("admitted %lld in %lld records; replaced candidates rejected %lld (admitted beside them %lld), NaN slots %lld, untouched tracks "
+                "with replaced candidates alone %lld, %s\n", admitted, completed, replaced_rejected, beside, nan_slots, only_replaced, bad ? "BAD" : "ok");
+    return admitted > 0 && completed > 0 && replaced_rejected > 0 && beside > 0 && nan_slots > 0 && only_replaced > 0 && !bad ? 0 : 1;
 }
