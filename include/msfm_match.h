@@ -772,6 +772,85 @@ int msfm_refine_poses(msfm_ctx* ctx, const msfm_pose_refine_params* params, cons
 int msfm_fetch_poses(msfm_ctx* ctx, int32_t* out_ids, msfm_pose_rt* out_poses, int* n);
 int msfm_fetch_pose_refinements(msfm_ctx* ctx, msfm_pose_refinement* out);
 
+/* ---- camera refinement: Levenberg-Marquardt on focal length, centre and distortion (opt-in) ---------------
+ * The third block of the alternation, the reference's refine_focal_length (CeresBundleOptimizer's shared focal block) and a little
+ * more: msfm_refine_camera moves the session's ONE camera -- the msfm_camera that msfm_triangulate_tracks was given and every later
+ * call reads back -- to the minimum of the SAME pixel cost under FIXED poses and FIXED points: one dense system of at most 6 unknowns
+ * per call, no coupling to any other block.  The arithmetic is csrc/msfm_refine_camera.h, bit-identical to the host twin RefineCamera
+ * (DESIGN.md section 25).
+ *   unknowns     params.mask: MSFM_CAM_FX_FY (fx and fy, the default), MSFM_CAM_F (one scale s: fx <- fx (1 + s), fy <- fy (1 + s);
+ *                exclusive with FX_FY), MSFM_CAM_CX_CY, MSFM_CAM_K1_K2.  p1 and p2 never move.
+ *   contributing an observation of a track whose record has ATTEMPTED | POINT | ERROR_OK | ANGLE_OK, in an image with a valid pose,
+ *                whose inlier byte is 1 after a robust call, with positive depth (`behind` counts those left out by depth alone).
+ *                The set does not depend on the camera and is fixed for the call.
+ *   cost         the sum over the set of |proj(R X + t) - undistort(camera; keypoint)|^2 f^2, f = (fx + fy) / 2: msfm_refine_points'
+ *                and msfm_refine_poses' cost with the camera as the variable.
+ *   LM           28 sums (J^T J, J^T r, the cost; the Jacobian in closed form through the implicit function theorem on the Brown
+ *                model) added in an order fixed by the data -- chunks of 256 observations in the tracks' order, a fixed tree inside
+ *                a chunk, 256 strided partials over the chunks, the same tree -- so that neither the grid nor the CU count reaches a
+ *                bit;  (H + lambda diag H) delta = -g by the 6 x 6 Cholesky of the pose refinement (an unknown that is not selected
+ *                has H_ii = 1, g_i = 0); a pivot that is not > 0, a non-finite delta or camera, fx or fy not > 0 is a rejected step;
+ *                a step is accepted iff its cost is finite and strictly lower; accept: lambda / 10 (floor 1e-12), reject: 10 lambda;
+ *                lambda starts at 1e-3.  The call stops after max_iters evaluated steps, after an accepted step with
+ *                (dfx / fx)^2 + (dfy / fy)^2 + (dcx / f)^2 + (dcy / f)^2 + dk1^2 + dk2^2 <= step_tol^2, or when a rejected step
+ *                raises lambda past 1e4.  There are no box constraints: strict descent and the standing rule are the protection.
+ *   eligible     at least min_observations contributing observations and a finite starting cost; otherwise nothing is attempted.
+ *   standing     the refined camera STANDS iff a step was accepted and it has at least as many contributing observations with
+ *                err <= the triangulation's max_error as the old camera.  It then replaces the session's camera; otherwise not one
+ *                byte of the session's camera, points, residuals or poses changes.
+ *   re-verdict   when it stands, EVERY track with ATTEMPTED | POINT is evaluated again at its unchanged X under the unchanged poses
+ *                and the new camera with the triangulation's code and thresholds: an error for every used observation,
+ *                mean_residual, tri_angle, ERROR_OK, ANGLE_OK, DEPTH_OK over the fitting set, plus MSFM_TRI_RECALIBRATED.  ROBUST,
+ *                REFINED, REPOSED, EXTENDED, FILTERED, COMPLETED, n_views, X and the inlier bytes are kept; the succeeded set may
+ *                shrink or grow (points_lost / points_gained).
+ * max_iters = 0 changes nothing.  The call may be repeated.  It invalidates registrations and pose-refinement records like
+ * msfm_refine_points; points, inlier bytes and poses stay valid.  Every following msfm_refine_points / msfm_refine_poses /
+ * msfm_extend_points / msfm_filter_points / msfm_complete_points / msfm_map_visibility works under the new camera.  A later
+ * msfm_refine_points / msfm_refine_poses / msfm_filter_points / msfm_complete_points CLEARS MSFM_TRI_RECALIBRATED on every record it
+ * rewrites (the filter and the completion too, which keep EXTENDED); msfm_extend_points keeps it on a point it continues, as it keeps
+ * every bit, and a track it creates has none: the bit says that the record is as a camera refinement left it, but for observations
+ * continued into new images.  msfm_register_images takes its own camera: pass
+ * msfm_fetch_camera's.
+ * params NULL = {1e-6, MSFM_CAM_FX_FY, 10, 100}.  Errors: MSFM_E_STATE -- as msfm_refine_points.  MSFM_E_INVALID -- mask 0, a bit
+ * outside the four, FX_FY together with F, max_iters outside 0 .. 100, a non-finite or negative step_tol, min_observations < 6.
+ * MSFM_E_NOIMAGE -- as msfm_refine_points.
+ *   stats        observations: the contributing set; stop: 0 none, 1 step criterion, 2 max_iters, 3 lambda ceiling, 4 fewer than
+ *                min_observations contribute, 5 the starting cost is not finite; refined: 1 iff the camera stands;
+ *                rejected_by_inliers: 1 iff a step was accepted and the camera does not stand; cost_before / cost_after: the cost at
+ *                the old camera and at the camera that stands (0 where nothing was attempted); camera_after = camera_before unless
+ *                it stands.  All but refine_ms are bit-equal to the twin's.
+ * msfm_fetch_camera: the session's current camera; MSFM_E_STATE before a successful triangulation. */
+enum { MSFM_TRI_RECALIBRATED = 2048 };
+enum { MSFM_CAM_FX_FY = 1, MSFM_CAM_F = 2, MSFM_CAM_CX_CY = 4, MSFM_CAM_K1_K2 = 8 };
+typedef struct msfm_camera_refine_params {   /* 24 bytes, no implicit padding */
+    double step_tol;
+    int32_t mask;                    /* MSFM_CAM_* */
+    int32_t max_iters;               /* 0 .. 100 evaluated steps */
+    int32_t min_observations;        /* >= 6 */
+    int32_t reserved;
+} msfm_camera_refine_params;
+typedef struct msfm_camera_refine_stats {   /* 248 bytes, no implicit padding */
+    int64_t observations;            /* the contributing set */
+    int64_t behind;                  /* otherwise fitting observations left out by depth */
+    int64_t iterations;              /* evaluated steps */
+    int64_t accepted_steps;
+    int64_t stop;
+    int64_t refined;                 /* 0 / 1: the refined camera stands */
+    int64_t rejected_by_inliers;     /* 0 / 1: a step was accepted and the refined camera would lose an inlier */
+    int64_t inliers_before;
+    int64_t inliers_after;
+    int64_t points_recalibrated;     /* tracks that went through the re-verdict */
+    int64_t points_lost;             /* ... of which had POINT & ERROR_OK & ANGLE_OK and lost it */
+    int64_t points_gained;           /* ... of which gained it */
+    double cost_before;
+    double cost_after;
+    msfm_camera camera_before;
+    msfm_camera camera_after;
+    double refine_ms;                /* HIP events around all launches of the call */
+} msfm_camera_refine_stats;
+int msfm_refine_camera(msfm_ctx* ctx, const msfm_camera_refine_params* params, msfm_camera_refine_stats* stats);
+int msfm_fetch_camera(msfm_ctx* ctx, msfm_camera* out);
+
 /* ---- map extension: continue and create points under new poses (opt-in) ---------------
  * The step that makes the blocks above an INCREMENTAL reconstruction (the reference's MapBuilder::TryRegisterNextImage after the
  * pose is found: AddObservation, Map::CompletePoint3D, MapBuilder::Triangulate).  msfm_extend_points takes the poses of newly

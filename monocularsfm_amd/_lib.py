@@ -309,6 +309,46 @@ class Camera(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")]
 
 
+# camera refinement (include/msfm_match.h): the record's extra status bit, the unknowns' bits, the 24-byte parameters, the 248-byte stats
+TRI_RECALIBRATED = 2048
+CAM_FX_FY, CAM_F, CAM_CX_CY, CAM_K1_K2 = 1, 2, 4, 8
+_CAM_BITS = {"fx_fy": CAM_FX_FY, "f": CAM_F, "cx_cy": CAM_CX_CY, "k1_k2": CAM_K1_K2}
+
+
+class CameraRefineParams(C.Structure):
+    _fields_ = [("step_tol", C.c_double), ("mask", C.c_int32), ("max_iters", C.c_int32), ("min_observations", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class CameraRefineStats(C.Structure):
+    """msfm_camera_refine_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("observations", "behind", "iterations", "accepted_steps", "stop", "refined", "rejected_by_inliers",
+                                         "inliers_before", "inliers_after", "points_recalibrated", "points_lost", "points_gained")] + \
+               [("cost_before", C.c_double), ("cost_after", C.c_double), ("camera_before", Camera), ("camera_after", Camera),
+                ("refine_ms", C.c_double)]
+
+
+def camera_dict(cam):
+    """A Camera struct -> {"fx": .., "fy": .., "cx": .., "cy": .., "k1": .., "k2": .., "p1": .., "p2": ..}"""
+    return {k: float(getattr(cam, k)) for k, _ in Camera._fields_}
+
+
+def camera_mask(mask):
+    """MSFM_CAM_* bits from an int or from names out of "fx_fy", "f", "cx_cy", "k1_k2" (one name or a sequence of them)."""
+    if isinstance(mask, (int, np.integer)):
+        return int(mask)
+    bits = 0
+    for name in ((mask,) if isinstance(mask, str) else mask):
+        bits |= _CAM_BITS[name]
+    return bits
+
+
+def recalibrated(points):
+    """The records of a POINT3D array that a camera refinement evaluated again under the new camera (MSFM_TRI_RECALIBRATED) and that
+    no refine_points, refine_poses, filter_points or complete_points has rewritten since: those clear the bit on what they rewrite."""
+    return (np.asarray(points)["status"] & TRI_RECALIBRATED) != 0
+
+
 class VerifyParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -425,6 +465,8 @@ def _signatures():
         "msfm_refine_poses": (i, [vp, P(PoseRefineParams), ip, i, P(PoseRefineStats)]),
         "msfm_fetch_poses": (i, [vp, ip, vp, intp]),
         "msfm_fetch_pose_refinements": (i, [vp, vp]),
+        "msfm_refine_camera": (i, [vp, P(CameraRefineParams), P(CameraRefineStats)]),
+        "msfm_fetch_camera": (i, [vp, cam]),
         "msfm_extend_points": (i, [vp, ip, vp, i, P(ExtendParams), P(ExtendStats)]),
         "msfm_filter_points": (i, [vp, P(FilterParams), ip, i, P(FilterStats)]),
         "msfm_complete_points": (i, [vp, P(CompleteParams), ip, i, P(CompleteStats)]),
@@ -958,15 +1000,39 @@ class Context:
         self._chk(self._L.msfm_fetch_pose_refinements(self._h, rec.ctypes.data))
         return rec[:n.value]
 
-    def alternate(self, rounds, fixed=(), point_params=None, pose_params=None):
+    def refine_camera(self, mask=("fx_fy",), max_iters=10, step_tol=1e-6, min_observations=100):
+        """Moves the session's one camera to the minimum of the map's reprojection error under the current poses and points (one
+        6 x 6 Levenberg-Marquardt, msfm_refine_camera).  mask: the unknowns -- names out of "fx_fy" (the default), "f" (one common
+        scale; not with "fx_fy"), "cx_cy", "k1_k2", or the MSFM_CAM_* bits.  The refined camera replaces the session's only where it
+        costs strictly less and loses no inlier; every point's record is then evaluated again (recalibrated(points)).  -> stats dict,
+        camera_before / camera_after as dicts.  camera() returns the current camera: pass it to register_images.  Registrations and
+        pose refinements are invalidated as by refine_points."""
+        prm = CameraRefineParams(float(step_tol), camera_mask(mask), int(max_iters), int(min_observations), 0)
+        st = CameraRefineStats()
+        self._chk(self._L.msfm_refine_camera(self._h, C.byref(prm), C.byref(st)))
+        out = _dict(st)
+        out["camera_before"], out["camera_after"] = camera_dict(st.camera_before), camera_dict(st.camera_after)
+        return out
+
+    def camera(self):
+        """-> the session's current camera as a dict (the form every call takes): what triangulate_tracks was given, or what the last
+        refine_camera that stood left."""
+        cam = Camera()
+        self._chk(self._L.msfm_fetch_camera(self._h, C.byref(cam)))
+        return camera_dict(cam)
+
+    def alternate(self, rounds, fixed=(), point_params=None, pose_params=None, camera_params=None):
         """`rounds` times refine_points(**point_params) then refine_poses(fixed=fixed, **pose_params); stops early after a round that
-        refined neither a point nor a pose.  -> [(point stats, pose stats)] per round run."""
+        refined neither a point nor a pose.  -> [(point stats, pose stats)] per round run.
+        camera_params: a dict (may be empty) runs refine_camera(**camera_params) behind the pose call of every round; the list then
+        holds (point stats, pose stats, camera stats) and the early stop needs a camera that did not stand as well."""
         out = []
         for _ in range(int(rounds)):
             a = self.refine_points(**(point_params or {}))
             b = self.refine_poses(fixed=fixed, **(pose_params or {}))
-            out.append((a, b))
-            if a["refined"] == 0 and b["refined"] == 0:
+            stats = (a, b) if camera_params is None else (a, b, self.refine_camera(**camera_params))
+            out.append(stats)
+            if all(s["refined"] == 0 for s in stats):
                 break
         return out
 
@@ -1037,7 +1103,7 @@ class Context:
         return None, trials, stats
 
     def grow(self, camera, image_ids=None, register_params=None, rounds=1, fixed=(), point_params=None, pose_params=None, max_images=None,
-             window=None):
+             window=None, camera_params=None):
         """One increment of the reconstruction: register_images(camera, image_ids, **register_params) -- image_ids None: every declared
         image without a valid pose in the session -- then extend_points(the registered poses), then alternate(rounds, fixed=...).
         -> (register stats, extend stats or None, alternate's list, the ids that registered).  When no image registers nothing but the
@@ -1045,7 +1111,9 @@ class Context:
         max_images=k (image_ids None): the candidates are next_images(visibility()[0]) -- the unposed images that see enough of the
         map, best-seen first -- tried in batches of k until a batch registers something or the list ends.  window=w: behind
         extend_points one visibility(query=the new ids); alternate holds every posed image fixed that is neither new nor in a new
-        image's local_window(..., size=w).  max_images=1, window=5 is the reference's loop; both None: every call as before."""
+        image's local_window(..., size=w).  max_images=1, window=5 is the reference's loop; both None: every call as before.
+        camera_params: a dict (may be empty) is passed on to alternate, and register_images then runs under self.camera() -- the
+        session's current camera, which an earlier increment may have refined -- in place of `camera`."""
         if image_ids is None and max_images is not None:
             cand = next_images(self.visibility()[0])
             batches = [cand[k:k + int(max_images)] for k in range(0, len(cand), max(int(max_images), 1))]
@@ -1058,7 +1126,7 @@ class Context:
         for batch in batches:
             if not batch:
                 continue
-            reg = self.register_images(camera, batch, **(register_params or {}))
+            reg = self.register_images(camera if camera_params is None else self.camera(), batch, **(register_params or {}))
             new = registered_poses(self.registrations()[0])
             if new:
                 break
@@ -1072,7 +1140,7 @@ class Context:
                 inside.update(local_window(row, records, i, size=window))
             outside = [int(r["image_id"]) for r in records if (r["flags"] & VIS_POSED) and int(r["image_id"]) not in inside]
             fixed = sorted(set(int(i) for i in fixed) | set(outside))
-        alt = self.alternate(rounds, fixed=fixed, point_params=point_params, pose_params=pose_params)
+        alt = self.alternate(rounds, fixed=fixed, point_params=point_params, pose_params=pose_params, camera_params=camera_params)
         return reg, ext, alt, sorted(new)
 
     def filter_points(self, max_error=None, min_angle=None, image_ids=None):
@@ -1111,7 +1179,8 @@ class Context:
         filter_points(**filter_params), repeated until no image registers or max_increments increments have run.  complete_params: a
         dict (may be empty) runs complete_points(**complete_params) behind the filter of every increment; None: no completion.
         grow's max_images=1, window=5 make it the reference's loop in order as well: one image an increment, best-seen first, the new
-        image and its five most covisible neighbours adjusted.
+        image and its five most covisible neighbours adjusted.  grow's camera_params={...} adds refine_camera to every round of the
+        alternation and registers every increment under the session's current camera.
         -> one dict per increment: register, extend, alternate (grow's results), filter (filter_points' stats), registered (the ids),
         and with complete_params "complete" (complete_points' stats)."""
         out = []

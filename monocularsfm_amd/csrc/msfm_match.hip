@@ -46,6 +46,7 @@ using namespace msfm;
 #include "msfm_triangulate_robust.hip.h"
 #include "msfm_refine.hip.h"
 #include "msfm_refine_poses.hip.h"
+#include "msfm_refine_camera.hip.h"
 #include "msfm_extend.hip.h"
 #include "msfm_filter.hip.h"
 #include "msfm_complete.hip.h"
@@ -905,6 +906,22 @@ int msfm_fetch_pose_refinements(msfm_ctx* ctx, msfm_pose_refinement* out) {
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return fetch_pose_refinements_impl(ctx, out);
+    MSFM_API_END
+}
+
+// ---- camera refinement (msfm_refine_camera.hip.h) ----------------------------------------------------------------------------------------
+
+int msfm_refine_camera(msfm_ctx* ctx, const msfm_camera_refine_params* params, msfm_camera_refine_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return refine_camera_impl(ctx, params, stats);
+    MSFM_API_END
+}
+
+int msfm_fetch_camera(msfm_ctx* ctx, msfm_camera* out) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return fetch_camera_impl(ctx, out);
     MSFM_API_END
 }
 

@@ -18,6 +18,7 @@
 #include "../csrc/msfm_triangulate.h"
 #include "../csrc/msfm_refine.h"
 #include "../csrc/msfm_refine_poses.h"
+#include "../csrc/msfm_refine_camera.h"
 #include "../csrc/msfm_extend.h"
 #include "../csrc/msfm_filter.h"
 #include "../csrc/msfm_complete.h"
@@ -775,6 +776,47 @@ int host_refine_poses(const long long* offsets, const int* image_ids, const int*
         costs2[1] += rc.cost_after;
     }
     return 0;
+}
+
+// ---- camera refinement: the host twin of the device kernels (csrc/msfm_refine_camera.h, RefineCamera) ----------------------------------
+// The inputs of host_refine_points (all tracks), mask_bits (MSFM_CAM_*) and min_observations.  `cam` (8 doubles) is read AND rewritten:
+// the refined camera where it stands.  points and residuals are read and rewritten by the re-verdict.  counts12 (may be NULL) RECEIVES
+// observations, behind, iterations, accepted_steps, stop, refined, rejected_by_inliers, inliers_before, inliers_after,
+// points_recalibrated, points_lost, points_gained; costs2 (may be NULL) cost_before and cost_after.  out_trace (may be NULL) receives one
+// msfm_ref::Trace (40 bytes).  Returns 0; 1, 2 as above; 3: a bad parameter.
+int host_refine_camera(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks, const int* ids, int n_images,
+                       const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, double* cam, double max_error,
+                       double min_angle, double step_tol, int mask_bits, int max_iters, int min_observations, msfm_point3d* points,
+                       double* residuals, const unsigned char* mask, long long* counts12, double* costs2, void* out_trace) {
+    static_assert(sizeof(msfm_rc::Slot) == 40 && sizeof(msfm_camera_refine_params) == 24 && sizeof(msfm_camera_refine_stats) == 248, "sizes");
+    TwinScene sc;
+    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
+    if (!msfm_rc::mask_ok(mask_bits) || max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol) ||
+        min_observations < 6)
+        return 3;
+    msfm_rc::Counts rc = {};
+    msfm_rc::RefineCamera(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, sc.rank_of.data(), kxy, sc.table.data(),
+                          mask, &sc.cam, msfm_ref::Verdict{max_error, min_angle},
+                          msfm_rc::Params{step_tol, mask_bits, max_iters, min_observations, 0}, points, residuals, &rc,
+                          static_cast<msfm_ref::Trace*>(out_trace));
+    const double c8[8] = {sc.cam.fx, sc.cam.fy, sc.cam.cx, sc.cam.cy, sc.cam.k1, sc.cam.k2, sc.cam.p1, sc.cam.p2};
+    for (int k = 0; k < 8; ++k) cam[k] = c8[k];
+    if (counts12) {
+        const long long v[12] = {rc.observations, rc.behind, rc.iterations, rc.accepted_steps, rc.stop, rc.refined, rc.rejected_by_inliers,
+                                 rc.inliers_before, rc.inliers_after, rc.points_recalibrated, rc.points_lost, rc.points_gained};
+        for (int k = 0; k < 12; ++k) counts12[k] = v[k];
+    }
+    if (costs2) {
+        costs2[0] = rc.cost_before;
+        costs2[1] = rc.cost_after;
+    }
+    return 0;
+}
+// the 256-element tree and the two levels of the camera refinement's summation over n doubles (tests)
+double host_rc_reduce(const double* v, long long n) {
+    double out[1];
+    msfm_rc::reduce_slots<1>(n, [&](long long s, double* o) { o[0] = v[s]; }, out);
+    return out[0];
 }
 
 // ---- map extension: the host twin of the device kernels (csrc/msfm_extend.h, ExtendPoints) --------------------------------------------
