@@ -7,6 +7,7 @@
 
 #include "Database.h"
 #include "GeometricVerification.h"
+#include "HostTwinMap.h"
 #include "MatchEmission.h"
 #include "YamlConfig.h"
 #include "../csrc/msfm_emat.h"
@@ -604,13 +605,14 @@ int host_tracks_build(const int* ids, const int* rows, int n, int min_pair_match
 }
 
 // ---- track triangulation: the host twin of the device kernels (csrc/msfm_triangulate.h, TriangulateTracks) ---------------------------
-// A finished track result (offsets / image_ids / point_idx / consistent as msfm_fetch_tracks returns them), the declared images `ids`
-// (any order) with kxy[k] = the (x, y) fp32 pairs of ids[k] (may be NULL for an image without a valid pose), the pose list as
-// msfm_triangulate_tracks takes it, cam = fx, fy, cx, cy, k1, k2, p1, p2.  Tracks [first, first + count) are computed and written at
-// their own positions of out_points / out_residuals (so that several threads can share one result).  Returns 0; 1: a pose's image is
-// not declared or given twice; 2: an image id outside [0, MSFM_MAX_IMAGES).
-// What every twin of the reconstruction stage makes of its raw arguments first: the rank of each declared image, the prepared pose of
-// each rank (invalid where the list has none), the rank of each entry of the pose list, and the camera.
+// Every twin of the reconstruction stage (twin_triangulate_tracks .. twin_map_visibility) takes one host_map (HostTwinMap.h): the
+// track result, the declared images with their keypoints, the pose list, the camera, the triangulation's thresholds, the slice and the
+// state.  Each twin's comment names the fields it reads and the ones it rewrites; its own parameters and outputs follow the block.
+// All of them return 0; 1: a pose's image is not declared or given twice; 2: an image id outside [0, MSFM_MAX_IMAGES); 3 and 4 as each
+// twin says.  The host_* exports of the same names, with the block's fields spelt out as raw arguments, stand behind
+// twin_map_visibility.
+// What every twin makes of the block first: the rank of each declared image, the prepared pose of each rank (invalid where the list
+// has none), the rank of each entry of the pose list, and the camera.
 struct TwinScene {
     std::vector<int> rank_of;
     std::vector<msfm_tri::Pose> table;
@@ -620,25 +622,25 @@ struct TwinScene {
     int rank(int id) const { return (id >= 0 && id < MSFM_MAX_IMAGES) ? rank_of[(size_t)id] : -1; }
 };
 // Returns 0, or the twins' codes 2 and 1.
-static int twin_scene(const int* ids, int n_images, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const double* cam, TwinScene* s) {
+static int twin_scene(const host_map& m, TwinScene* s) {
     s->rank_of.assign((size_t)MSFM_MAX_IMAGES, -1);
-    for (int k = 0; k < n_images; ++k) {
-        if (ids[k] < 0 || ids[k] >= MSFM_MAX_IMAGES) return 2;
-        s->rank_of[(size_t)ids[k]] = k;   // (any one-to-one numbering serves the twin: the device's ranks never reach the output)
+    for (int k = 0; k < m.n_images; ++k) {
+        if (m.ids[k] < 0 || m.ids[k] >= MSFM_MAX_IMAGES) return 2;
+        s->rank_of[(size_t)m.ids[k]] = k;   // (any one-to-one numbering serves the twin: the device's ranks never reach the output)
     }
-    s->table.resize((size_t)std::max(n_images, 1));
-    s->list_rank.assign((size_t)std::max(n_poses, 1), 0);
-    std::vector<char> given((size_t)std::max(n_images, 1), 0);
+    s->table.resize((size_t)std::max(m.n_images, 1));
+    s->list_rank.assign((size_t)std::max(m.n_poses, 1), 0);
+    std::vector<char> given((size_t)std::max(m.n_images, 1), 0);
     const msfm_pose_rt none = {};
     for (auto& p : s->table) msfm_tri::prepare_pose(none, &p);
-    for (int k = 0; k < n_poses; ++k) {
-        const int r = s->rank(pose_ids[k]);
+    for (int k = 0; k < m.n_poses; ++k) {
+        const int r = s->rank(m.pose_ids[k]);
         if (r < 0 || given[(size_t)r]) return 1;
         given[(size_t)r] = 1;
         s->list_rank[(size_t)k] = r;
-        msfm_tri::prepare_pose(poses[k], &s->table[(size_t)r]);
+        msfm_tri::prepare_pose(m.poses[k], &s->table[(size_t)r]);
     }
-    s->cam = msfm_emat::Camera{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7]};
+    s->cam = msfm_emat::Camera{m.cam[0], m.cam[1], m.cam[2], m.cam[3], m.cam[4], m.cam[5], m.cam[6], m.cam[7]};
     return 0;
 }
 // A list of ids as one byte per rank; false (the twins' code 4) for an id that is not declared, is given twice or, with `posed`, has
@@ -653,36 +655,31 @@ static bool twin_rank_bytes(const TwinScene& s, const int* ids, int n, bool pose
     return true;
 }
 
-int host_triangulate_tracks(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
-                            const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
-                            int n_poses, const double* cam, double max_error, double min_angle, int min_views, long long first,
-                            long long count, msfm_point3d* out_points, double* out_residuals) {
+// Reads the tracks with `consistent`, the images, the pose list, cam, the three thresholds and the slice; WRITES points and residuals
+// of the slice's tracks (mask and have_mask are not used).
+int twin_triangulate_tracks(const host_map* m) {
     TwinScene sc;
-    if (const int rc = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return rc;
-    const msfm_tri::Params prm = {max_error, min_angle, min_views, 0};
+    if (const int rc = twin_scene(*m, &sc)) return rc;
+    const msfm_tri::Params prm = {m->max_error, m->min_angle, m->min_views, 0};
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are int64");
     static_assert(sizeof(msfm_tri::RobustTrace) == 12 * sizeof(int), "the trace is twelve int32");
-    msfm_tri::TriangulateTracks(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(),
-                                kxy, sc.table.data(), sc.cam, prm, out_points, out_residuals);
+    msfm_tri::TriangulateTracks(m->offsets, m->image_ids, m->point_idx, m->consistent, m->first, m->count, sc.rank_of.data(), m->kxy,
+                                sc.table.data(), sc.cam, prm, m->points, m->residuals);
     return 0;
 }
 
-// The robust twin (TriangulateTracksRobust): the same inputs, max_hypotheses, and the inlier byte per observation.  counts4 (may be
-// NULL): retried, rescued, observations_rejected, hypotheses of the tracks computed by this call are ADDED to it.
-// host_triangulate_tracks_robust_trace: the same, and out_trace (may be NULL) receives msfm_tri::RobustTrace (12 int32) per computed
-// track at the track's own position: the route it took.
-int host_triangulate_tracks_robust_trace(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
-                                         const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
-                                         int n_poses, const double* cam, double max_error, double min_angle, int min_views,
-                                         int max_hypotheses, long long first, long long count, msfm_point3d* out_points,
-                                         double* out_residuals, unsigned char* out_mask, long long* counts4, int* out_trace) {
+// The robust twin (TriangulateTracksRobust): as twin_triangulate_tracks, with max_hypotheses, and it WRITES mask as well, the inlier
+// byte per observation.  counts4 (may be NULL): retried, rescued, observations_rejected, hypotheses of the tracks computed by this call
+// are ADDED to it.  out_trace (may be NULL) receives msfm_tri::RobustTrace (12 int32) per computed track at the track's own position:
+// the route it took.  3: max_hypotheses outside 1 .. 1024.
+int twin_triangulate_tracks_robust(const host_map* m, int max_hypotheses, long long* counts4, int* out_trace) {
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
+    if (const int e = twin_scene(*m, &sc)) return e;
     if (max_hypotheses < 1 || max_hypotheses > 1024) return 3;
-    const msfm_tri::RobustParams prm = {max_error, min_angle, min_views, max_hypotheses};
+    const msfm_tri::RobustParams prm = {m->max_error, m->min_angle, m->min_views, max_hypotheses};
     msfm_tri::RobustCounts rc = {0, 0, 0, 0};
-    msfm_tri::TriangulateTracksRobust(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count,
-                                      sc.rank_of.data(), kxy, sc.table.data(), sc.cam, prm, out_points, out_residuals, out_mask, &rc,
+    msfm_tri::TriangulateTracksRobust(m->offsets, m->image_ids, m->point_idx, m->consistent, m->first, m->count, sc.rank_of.data(), m->kxy,
+                                      sc.table.data(), sc.cam, prm, m->points, m->residuals, m->mask, &rc,
                                       reinterpret_cast<msfm_tri::RobustTrace*>(out_trace));
     if (counts4) {
         counts4[0] += rc.retried;
@@ -692,37 +689,24 @@ int host_triangulate_tracks_robust_trace(const long long* offsets, const int* im
     }
     return 0;
 }
-int host_triangulate_tracks_robust(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
-                                   const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
-                                   int n_poses, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses,
-                                   long long first, long long count, msfm_point3d* out_points, double* out_residuals,
-                                   unsigned char* out_mask, long long* counts4) {
-    return host_triangulate_tracks_robust_trace(offsets, image_ids, point_idx, consistent, ids, n_images, kxy, pose_ids, poses, n_poses, cam,
-                                                max_error, min_angle, min_views, max_hypotheses, first, count, out_points, out_residuals,
-                                                out_mask, counts4, nullptr);
-}
 void host_tri_sample2(long long track, int h, int m, int* idx2) { msfm_tri::sample2(msfm_tri::tri_seed(track), h, m, idx2); }
 
 // ---- point refinement: the host twin of the device kernels (csrc/msfm_refine.h, RefinePoints) ---------------------------------------
-// The inputs of host_triangulate_tracks[_robust] with the thresholds that call ran with (the verdict's), and its OUTPUTS: points and
-// residuals are read and rewritten in place, mask (may be NULL: the points are the plain call's) is read.  Tracks [first, first +
-// count) are refined.  counts5 (may be NULL): eligible, refined, gained_error_ok, rejected_by_verdict, iterations of those tracks are
-// ADDED to it; costs2 (may be NULL): their cost_before and cost_after, summed in track order, are ADDED to it.  out_trace (may be
-// NULL) receives msfm_ref::Trace (40 bytes) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3: max_iters
-// outside 0 .. 100 or a bad step_tol.
-int host_refine_points(const long long* offsets, const int* image_ids, const int* point_idx, const int* ids, int n_images,
-                       const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const double* cam,
-                       double max_error, double min_angle, double step_tol, int max_iters, long long first, long long count,
-                       msfm_point3d* points, double* residuals, const unsigned char* mask, long long* counts5, double* costs2,
-                       void* out_trace) {
+// Reads the tracks (not `consistent`), the images, the pose list, cam, max_error and min_angle (the verdict's: the thresholds the
+// triangulation ran with), the slice and mask (may be NULL: the points are the plain call's); points and residuals of the slice's
+// tracks are read and REWRITTEN in place.  counts5 (may be NULL): eligible, refined, gained_error_ok, rejected_by_verdict, iterations
+// of those tracks are ADDED to it; costs2 (may be NULL): their cost_before and cost_after, summed in track order, are ADDED to it.
+// out_trace (may be NULL) receives msfm_ref::Trace (40 bytes) per computed track at the track's own position.  3: max_iters outside
+// 0 .. 100 or a bad step_tol.
+int twin_refine_points(const host_map* m, double step_tol, int max_iters, long long* counts5, double* costs2, void* out_trace) {
     static_assert(sizeof(msfm_ref::Trace) == 40 && sizeof(msfm_ref::Obs) == 24, "the trace is six int32 and two doubles");
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
+    if (const int e = twin_scene(*m, &sc)) return e;
     if (max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol)) return 3;
     msfm_ref::Counts rc = {0, 0, 0, 0, 0, 0.0, 0.0};
-    msfm_ref::RefinePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, first, count, sc.rank_of.data(), kxy,
-                           sc.table.data(), mask, sc.cam, msfm_ref::Verdict{max_error, min_angle}, msfm_ref::Params{step_tol, max_iters, 0},
-                           points, residuals, &rc, static_cast<msfm_ref::Trace*>(out_trace));
+    msfm_ref::RefinePoints(m->offsets, m->image_ids, m->point_idx, m->first, m->count, sc.rank_of.data(), m->kxy, sc.table.data(), m->mask,
+                           sc.cam, msfm_ref::Verdict{m->max_error, m->min_angle}, msfm_ref::Params{step_tol, max_iters, 0}, m->points,
+                           m->residuals, &rc, static_cast<msfm_ref::Trace*>(out_trace));
     if (counts5) {
         counts5[0] += rc.eligible;
         counts5[1] += rc.refined;
@@ -738,33 +722,31 @@ int host_refine_points(const long long* offsets, const int* image_ids, const int
 }
 
 // ---- pose refinement: the host twin of the device kernels (csrc/msfm_refine_poses.h, RefinePoses) -------------------------------------
-// The inputs of host_refine_points (all tracks: an image's fitting set runs through every track), min_observations and the ids to hold
-// fixed.  `poses` is read AND rewritten: where a refined pose stands its R and t replace the entry.  points and residuals are read and
-// rewritten by the re-verdict.  out_records: one msfm_pose_refinement per entry of the pose list.  counts9 (may be NULL): images,
-// eligible, refined, rejected_by_inliers, iterations, observations, points_reposed, points_lost, points_gained are ADDED to it; costs2
-// (may be NULL): cost_before and cost_after, summed in list order, are ADDED to it.  out_trace (may be NULL) receives msfm_ref::Trace
-// (40 bytes) per entry of the pose list.  Returns 0; 1, 2 as above; 3: a bad parameter; 4: a fixed id that is not declared or given twice.
-int host_refine_poses(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks, const int* ids, int n_images,
-                      const float* const* kxy, const int* pose_ids, msfm_pose_rt* poses, int n_poses, const double* cam, double max_error,
-                      double min_angle, double step_tol, int max_iters, int min_observations, const int* fixed_ids, int n_fixed,
-                      msfm_point3d* points, double* residuals, const unsigned char* mask, msfm_pose_refinement* out_records,
-                      long long* counts9, double* costs2, void* out_trace) {
+// Reads the tracks (not `consistent`; all n_tracks of them, not the slice: an image's fitting set runs through every track), the
+// images, cam, max_error and min_angle (the verdict's) and mask (may be NULL); min_observations and the ids to hold fixed are its own.
+// The entries of `poses` are read AND REWRITTEN: where a refined pose stands its R and t replace the entry.  points and residuals are
+// read and REWRITTEN by the re-verdict.  out_records: one msfm_pose_refinement per entry of the pose list.  counts9 (may be NULL):
+// images, eligible, refined, rejected_by_inliers, iterations, observations, points_reposed, points_lost, points_gained are ADDED to it;
+// costs2 (may be NULL): cost_before and cost_after, summed in list order, are ADDED to it.  out_trace (may be NULL) receives
+// msfm_ref::Trace (40 bytes) per entry of the pose list.  3: a bad parameter; 4: a fixed id that is not declared or given twice.
+int twin_refine_poses(host_map* m, double step_tol, int max_iters, int min_observations, const int* fixed_ids, int n_fixed,
+                      msfm_pose_refinement* out_records, long long* counts9, double* costs2, void* out_trace) {
     static_assert(sizeof(msfm_ref::Trace) == 40 && sizeof(msfm_pose_refinement) == 48, "the trace is six int32 and two doubles");
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
+    if (const int e = twin_scene(*m, &sc)) return e;
     if (max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol) || min_observations < 3 || n_fixed < 0) return 3;
     std::vector<uint8_t> fixed, changed(sc.table.size(), 0);
     if (!twin_rank_bytes(sc, fixed_ids, n_fixed, false, &fixed)) return 4;
     msfm_rp::Counts rc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0};
-    msfm_rp::RefinePoses(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, sc.rank_of.data(), kxy, sc.table.data(),
-                         n_images, mask, sc.cam, msfm_ref::Verdict{max_error, min_angle}, msfm_rp::Params{step_tol, max_iters, min_observations},
-                         sc.list_rank.data(), pose_ids, n_poses, fixed.data(), points, residuals, out_records, changed.data(), &rc,
+    msfm_rp::RefinePoses(m->offsets, m->image_ids, m->point_idx, m->n_tracks, sc.rank_of.data(), m->kxy, sc.table.data(), m->n_images, m->mask,
+                         sc.cam, msfm_ref::Verdict{m->max_error, m->min_angle}, msfm_rp::Params{step_tol, max_iters, min_observations},
+                         sc.list_rank.data(), m->pose_ids, m->n_poses, fixed.data(), m->points, m->residuals, out_records, changed.data(), &rc,
                          static_cast<msfm_ref::Trace*>(out_trace));
-    for (int k = 0; k < n_poses; ++k) {
+    for (int k = 0; k < m->n_poses; ++k) {
         const size_t r = (size_t)sc.list_rank[(size_t)k];
         if (!changed[r]) continue;
-        for (int q = 0; q < 9; ++q) poses[k].R[q] = sc.table[r].R[q];
-        for (int q = 0; q < 3; ++q) poses[k].t[q] = sc.table[r].t[q];
+        for (int q = 0; q < 9; ++q) m->poses[k].R[q] = sc.table[r].R[q];
+        for (int q = 0; q < 3; ++q) m->poses[k].t[q] = sc.table[r].t[q];
     }
     if (counts9) {
         const long long v[9] = {rc.images, rc.eligible, rc.refined, rc.rejected_by_inliers, rc.iterations, rc.observations, rc.points_reposed,
@@ -779,28 +761,26 @@ int host_refine_poses(const long long* offsets, const int* image_ids, const int*
 }
 
 // ---- camera refinement: the host twin of the device kernels (csrc/msfm_refine_camera.h, RefineCamera) ----------------------------------
-// The inputs of host_refine_points (all tracks), mask_bits (MSFM_CAM_*) and min_observations.  `cam` (8 doubles) is read AND rewritten:
-// the refined camera where it stands.  points and residuals are read and rewritten by the re-verdict.  counts12 (may be NULL) RECEIVES
-// observations, behind, iterations, accepted_steps, stop, refined, rejected_by_inliers, inliers_before, inliers_after,
+// Reads the tracks (not `consistent`; all n_tracks of them, not the slice), the images, the pose list, max_error and min_angle (the
+// verdict's) and mask (may be NULL); mask_bits (MSFM_CAM_*) and min_observations are its own.  The block's `cam` is read AND
+// REWRITTEN: the refined camera where it stands.  points and residuals are read and REWRITTEN by the re-verdict.  counts12 (may be
+// NULL) RECEIVES observations, behind, iterations, accepted_steps, stop, refined, rejected_by_inliers, inliers_before, inliers_after,
 // points_recalibrated, points_lost, points_gained; costs2 (may be NULL) cost_before and cost_after.  out_trace (may be NULL) receives one
-// msfm_ref::Trace (40 bytes).  Returns 0; 1, 2 as above; 3: a bad parameter.
-int host_refine_camera(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks, const int* ids, int n_images,
-                       const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, double* cam, double max_error,
-                       double min_angle, double step_tol, int mask_bits, int max_iters, int min_observations, msfm_point3d* points,
-                       double* residuals, const unsigned char* mask, long long* counts12, double* costs2, void* out_trace) {
+// msfm_ref::Trace (40 bytes).  3: a bad parameter.
+int twin_refine_camera(host_map* m, double step_tol, int mask_bits, int max_iters, int min_observations, long long* counts12, double* costs2,
+                       void* out_trace) {
     static_assert(sizeof(msfm_rc::Slot) == 40 && sizeof(msfm_camera_refine_params) == 24 && sizeof(msfm_camera_refine_stats) == 248, "sizes");
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
+    if (const int e = twin_scene(*m, &sc)) return e;
     if (!msfm_rc::mask_ok(mask_bits) || max_iters < 0 || max_iters > 100 || !(step_tol >= 0.0) || !msfm_pose::finite(step_tol) ||
         min_observations < 6)
         return 3;
     msfm_rc::Counts rc = {};
-    msfm_rc::RefineCamera(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, n_tracks, sc.rank_of.data(), kxy, sc.table.data(),
-                          mask, &sc.cam, msfm_ref::Verdict{max_error, min_angle},
-                          msfm_rc::Params{step_tol, mask_bits, max_iters, min_observations, 0}, points, residuals, &rc,
-                          static_cast<msfm_ref::Trace*>(out_trace));
+    msfm_rc::RefineCamera(m->offsets, m->image_ids, m->point_idx, m->n_tracks, sc.rank_of.data(), m->kxy, sc.table.data(), m->mask, &sc.cam,
+                          msfm_ref::Verdict{m->max_error, m->min_angle}, msfm_rc::Params{step_tol, mask_bits, max_iters, min_observations, 0},
+                          m->points, m->residuals, &rc, static_cast<msfm_ref::Trace*>(out_trace));
     const double c8[8] = {sc.cam.fx, sc.cam.fy, sc.cam.cx, sc.cam.cy, sc.cam.k1, sc.cam.k2, sc.cam.p1, sc.cam.p2};
-    for (int k = 0; k < 8; ++k) cam[k] = c8[k];
+    for (int k = 0; k < 8; ++k) m->cam[k] = c8[k];
     if (counts12) {
         const long long v[12] = {rc.observations, rc.behind, rc.iterations, rc.accepted_steps, rc.stop, rc.refined, rc.rejected_by_inliers,
                                  rc.inliers_before, rc.inliers_after, rc.points_recalibrated, rc.points_lost, rc.points_gained};
@@ -820,29 +800,26 @@ double host_rc_reduce(const double* v, long long n) {
 }
 
 // ---- map extension: the host twin of the device kernels (csrc/msfm_extend.h, ExtendPoints) --------------------------------------------
-// The inputs of host_refine_points with `consistent`, the ENLARGED pose list (the session's list with the new images appended or
-// replaced in place, as msfm_extend_points leaves it) and new_ids: the images that gained their valid pose in this call (each must be
-// in the enlarged list with a valid pose).  min_views is the triangulation's; max_hypotheses 0 = plain route for created tracks.
-// points, residuals and mask are read and rewritten in place; have_mask 0: the points are the plain call's and the bytes of the
-// computed tracks are created first.  Tracks [first, first + count) are computed.  counts7 (may be NULL): tracks_touched, continued,
-// observations_added, observations_rejected, created_attempted, created, retried of those tracks are ADDED to it.  out_trace (may be
-// NULL) receives msfm_ext::Trace (four int32) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3:
-// max_hypotheses outside 0 .. 1024; 4: a new id that is not in the enlarged list with a valid pose, or given twice.
-int host_extend_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent, const int* ids,
-                       int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const int* new_ids,
-                       int n_new, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses, long long first,
-                       long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask, long long* counts7,
-                       int* out_trace) {
+// Reads the tracks with `consistent`, the images, cam, the triangulation's three thresholds and the slice.  The block's pose list is
+// the ENLARGED one (the session's list with the new images appended or replaced in place, as msfm_extend_points leaves it); new_ids,
+// its own: the images that gained their valid pose in this call (each must be in the enlarged list with a valid pose); max_hypotheses
+// 0 = plain route for created tracks.  points, residuals and mask of the slice's tracks are read and REWRITTEN in place; have_mask 0:
+// the points are the plain call's and the bytes of the computed tracks are created first.  counts7 (may be NULL): tracks_touched,
+// continued, observations_added, observations_rejected, created_attempted, created, retried of those tracks are ADDED to it.
+// out_trace (may be NULL) receives msfm_ext::Trace (four int32) per computed track at the track's own position.  3: max_hypotheses
+// outside 0 .. 1024; 4: a new id that is not in the enlarged list with a valid pose, or given twice.
+int twin_extend_points(const host_map* m, const int* new_ids, int n_new, int max_hypotheses, long long* counts7, int* out_trace) {
     static_assert(sizeof(msfm_ext::Trace) == 4 * sizeof(int), "the trace is four int32");
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
+    if (const int e = twin_scene(*m, &sc)) return e;
     if (max_hypotheses < 0 || max_hypotheses > 1024) return 3;
     std::vector<uint8_t> gained;
     if (!twin_rank_bytes(sc, new_ids, n_new, true, &gained)) return 4;
     msfm_ext::Counts ec = {0, 0, 0, 0, 0, 0, 0};
-    msfm_ext::ExtendPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(), kxy,
-                           sc.table.data(), gained.data(), sc.cam, msfm_tri::Params{max_error, min_angle, min_views, 0}, max_hypotheses,
-                           have_mask != 0, points, residuals, mask, &ec, reinterpret_cast<msfm_ext::Trace*>(out_trace));
+    msfm_ext::ExtendPoints(m->offsets, m->image_ids, m->point_idx, m->consistent, m->first, m->count, sc.rank_of.data(), m->kxy,
+                           sc.table.data(), gained.data(), sc.cam, msfm_tri::Params{m->max_error, m->min_angle, m->min_views, 0},
+                           max_hypotheses, m->have_mask != 0, m->points, m->residuals, m->mask, &ec,
+                           reinterpret_cast<msfm_ext::Trace*>(out_trace));
     if (counts7) {
         const long long v[7] = {ec.tracks_touched, ec.continued, ec.observations_added, ec.observations_rejected, ec.created_attempted,
                                 ec.created, ec.retried};
@@ -852,31 +829,28 @@ int host_extend_points(const long long* offsets, const int* image_ids, const int
 }
 
 // ---- map filtering: the host twin of the device kernel (csrc/msfm_filter.h, FilterPoints) ----------------------------------------------
-// The inputs of host_extend_points without the new images: the session's CURRENT pose list, the thresholds of the triangulation that
-// made the points (max_error, min_angle), the call's own (flt_max_error, flt_min_angle) and scope_ids: the images the call is limited to
-// (n_scope == 0: every track).  points, residuals and mask are read and rewritten in place; have_mask 0: the bytes of the computed
-// tracks are created first.  Tracks [first, first + count) are computed.  counts7 (may be NULL): eligible, dropped_by_depth,
-// dropped_by_error, trimmed, regained, removed_by_views, removed_by_angle of those tracks are ADDED to it.  out_trace (may be NULL)
-// receives msfm_flt::Trace (four int32) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3: a non-finite or
-// negative threshold or n_scope < 0; 4: a scope id that is not declared or given twice.
-int host_filter_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent, const int* ids,
-                       int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses,
-                       const int* scope_ids, int n_scope, const double* cam, double max_error, double min_angle, double flt_max_error,
-                       double flt_min_angle, long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask,
-                       int have_mask, long long* counts7, int* out_trace) {
+// Reads the tracks with `consistent`, the images, the pose list (the session's CURRENT one), cam, max_error and min_angle (of the
+// triangulation that made the points; min_views is not used) and the slice.  Its own: the call's thresholds (flt_max_error,
+// flt_min_angle) and scope_ids, the images the call is limited to (n_scope == 0: every track).  points, residuals and mask of the
+// slice's tracks are read and REWRITTEN in place; have_mask 0: the bytes of the computed tracks are created first.  counts7 (may be
+// NULL): eligible, dropped_by_depth, dropped_by_error, trimmed, regained, removed_by_views, removed_by_angle of those tracks are ADDED
+// to it.  out_trace (may be NULL) receives msfm_flt::Trace (four int32) per computed track at the track's own position.  3: a
+// non-finite or negative threshold or n_scope < 0; 4: a scope id that is not declared or given twice.
+int twin_filter_points(const host_map* m, const int* scope_ids, int n_scope, double flt_max_error, double flt_min_angle, long long* counts7,
+                       int* out_trace) {
     static_assert(sizeof(msfm_flt::Trace) == 4 * sizeof(int), "the trace is four int32");
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
+    if (const int e = twin_scene(*m, &sc)) return e;
     if (!msfm_pose::finite(flt_max_error) || !msfm_pose::finite(flt_min_angle) || !(flt_max_error >= 0.0) || !(flt_min_angle >= 0.0) ||
         n_scope < 0)
         return 3;
     std::vector<uint8_t> scope;
     if (!twin_rank_bytes(sc, scope_ids, n_scope, false, &scope)) return 4;
     msfm_flt::Counts fc = {0, 0, 0, 0, 0, 0, 0};
-    msfm_flt::FilterPoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(), kxy,
-                           sc.table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, sc.cam, msfm_tri::Params{max_error, min_angle, 2, 0},
-                           msfm_ref::Verdict{flt_max_error, flt_min_angle}, have_mask != 0, points, residuals, mask, &fc,
-                           reinterpret_cast<msfm_flt::Trace*>(out_trace));
+    msfm_flt::FilterPoints(m->offsets, m->image_ids, m->point_idx, m->consistent, m->first, m->count, sc.rank_of.data(), m->kxy,
+                           sc.table.data(), m->n_images, n_scope > 0 ? scope.data() : nullptr, sc.cam,
+                           msfm_tri::Params{m->max_error, m->min_angle, 2, 0}, msfm_ref::Verdict{flt_max_error, flt_min_angle},
+                           m->have_mask != 0, m->points, m->residuals, m->mask, &fc, reinterpret_cast<msfm_flt::Trace*>(out_trace));
     if (counts7) {
         const long long v[7] = {fc.eligible, fc.dropped_by_depth, fc.dropped_by_error, fc.trimmed, fc.regained, fc.removed_by_views,
                                 fc.removed_by_angle};
@@ -886,27 +860,25 @@ int host_filter_points(const long long* offsets, const int* image_ids, const int
 }
 
 // ---- map completion: the host twin of the device kernel (csrc/msfm_complete.h, CompletePoints) ----------------------------------------
-// The inputs of host_filter_points with one threshold of the call's own (cmp_max_error) and scope_ids: the images whose candidates the
-// call is limited to (n_scope == 0: every image).  points, residuals and mask are read and rewritten in place; have_mask 0: the bytes
-// of the computed tracks are created first.  Tracks [first, first + count) are computed.  counts6 (may be NULL): eligible, candidates,
-// admitted, rejected_by_depth, rejected_by_error, completed of those tracks are ADDED to it.  out_trace (may be NULL) receives
-// msfm_cmp::Trace (four int32) per computed track at the track's own position.  Returns 0; 1, 2 as above; 3: a non-finite or negative
+// Reads the tracks with `consistent`, the images, the pose list (the session's CURRENT one), cam, max_error and min_angle (of the
+// triangulation that made the points; min_views is not used) and the slice.  Its own: the call's one threshold (cmp_max_error) and
+// scope_ids, the images whose candidates the call is limited to (n_scope == 0: every image).  points, residuals and mask of the
+// slice's tracks are read and REWRITTEN in place; have_mask 0: the bytes of the computed tracks are created first.  counts6 (may be
+// NULL): eligible, candidates, admitted, rejected_by_depth, rejected_by_error, completed of those tracks are ADDED to it.  out_trace
+// (may be NULL) receives msfm_cmp::Trace (four int32) per computed track at the track's own position.  3: a non-finite or negative
 // threshold, one above max_error, or n_scope < 0; 4: a scope id that is not declared or given twice.
-int host_complete_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
-                         const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses,
-                         const int* scope_ids, int n_scope, const double* cam, double max_error, double min_angle, double cmp_max_error,
-                         long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask,
-                         long long* counts6, int* out_trace) {
+int twin_complete_points(const host_map* m, const int* scope_ids, int n_scope, double cmp_max_error, long long* counts6, int* out_trace) {
     static_assert(sizeof(msfm_cmp::Trace) == 4 * sizeof(int), "the trace is four int32");
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, n_poses, cam, &sc)) return e;
-    if (!msfm_pose::finite(cmp_max_error) || !(cmp_max_error >= 0.0) || cmp_max_error > max_error || n_scope < 0) return 3;
+    if (const int e = twin_scene(*m, &sc)) return e;
+    if (!msfm_pose::finite(cmp_max_error) || !(cmp_max_error >= 0.0) || cmp_max_error > m->max_error || n_scope < 0) return 3;
     std::vector<uint8_t> scope;
     if (!twin_rank_bytes(sc, scope_ids, n_scope, false, &scope)) return 4;
     msfm_cmp::Counts cc = {0, 0, 0, 0, 0, 0};
-    msfm_cmp::CompletePoints(reinterpret_cast<const int64_t*>(offsets), image_ids, point_idx, consistent, first, count, sc.rank_of.data(), kxy,
-                             sc.table.data(), n_images, n_scope > 0 ? scope.data() : nullptr, sc.cam, msfm_tri::Params{max_error, min_angle, 2, 0},
-                             cmp_max_error, have_mask != 0, points, residuals, mask, &cc, reinterpret_cast<msfm_cmp::Trace*>(out_trace));
+    msfm_cmp::CompletePoints(m->offsets, m->image_ids, m->point_idx, m->consistent, m->first, m->count, sc.rank_of.data(), m->kxy,
+                             sc.table.data(), m->n_images, n_scope > 0 ? scope.data() : nullptr, sc.cam,
+                             msfm_tri::Params{m->max_error, m->min_angle, 2, 0}, cmp_max_error, m->have_mask != 0, m->points, m->residuals,
+                             m->mask, &cc, reinterpret_cast<msfm_cmp::Trace*>(out_trace));
     if (counts6) {
         const long long v[6] = {cc.eligible, cc.candidates, cc.admitted, cc.rejected_by_depth, cc.rejected_by_error, cc.completed};
         for (int k = 0; k < 6; ++k) counts6[k] += v[k];
@@ -915,20 +887,21 @@ int host_complete_points(const long long* offsets, const int* image_ids, const i
 }
 
 // ---- map visibility: the host twin of the device kernels (csrc/msfm_visibility.h, MapVisibility) -----------------------------------------
-// A finished track result, the declared images `ids` IN RANK ORDER (the records and the matrix columns follow it), the session's current
-// pose list (n_poses == 0 under basis 0), the query list, the basis (0 tracks, 1 map), points (the records; NULL under basis 0) and mask
-// (the session's inlier bytes or NULL).  out_records: n_images msfm_image_visibility; out_matrix: n_query x n_images uint32 (may be NULL
-// without a query); counts3 (may be NULL): tracks_counted, elements_counted, pair_increments.  Nothing is read and rewritten: the call
-// counts.  Returns 0; 1, 2 as above; 3: an unknown basis or n_query < 0; 4: a query id that is not declared or given twice.
-int host_map_visibility(const long long* offsets, const int* image_ids, const unsigned char* consistent, long long n_tracks, const int* ids,
-                        int n_images, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const int* query_ids, int n_query, int basis,
-                        const msfm_point3d* points, const unsigned char* mask, msfm_image_visibility* out_records, unsigned* out_matrix,
-                        long long* counts3) {
+// Reads the tracks' offsets, image_ids and `consistent` (all n_tracks of them, not the slice), the declared images `ids` IN RANK ORDER
+// (the records and the matrix columns follow it; no pixel is read: kxy, cam and the thresholds are not used) and, under basis 1 only,
+// the pose list (the session's current one), points (the records) and mask (the session's inlier bytes or NULL).  Its own: the query
+// list and the basis (0 tracks, 1 map).  out_records: n_images msfm_image_visibility; out_matrix: n_query x n_images uint32 (may be
+// NULL without a query); counts3 (may be NULL) RECEIVES tracks_counted, elements_counted, pair_increments.  Nothing in the block is
+// rewritten: the call counts.  3: an unknown basis or n_query < 0; 4: a query id that is not declared or given twice.
+int twin_map_visibility(const host_map* m, const int* query_ids, int n_query, int basis, msfm_image_visibility* out_records,
+                        unsigned* out_matrix, long long* counts3) {
     static_assert(sizeof(msfm_image_visibility) == 24 && sizeof(msfm_visibility_params) == 8 && sizeof(msfm_visibility_stats) == 56,
                   "the visibility structs of include/msfm_match.h");
-    const double cam[8] = {1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // (no pixel is read: only the poses' validity)
+    host_map seen = *m;   // (only the poses' validity counts, and only on the map)
+    if (basis != msfm_vis::BASIS_MAP) seen.n_poses = 0;
+    const int n_images = m->n_images;
     TwinScene sc;
-    if (const int e = twin_scene(ids, n_images, pose_ids, poses, basis == msfm_vis::BASIS_MAP ? n_poses : 0, cam, &sc)) return e;
+    if (const int e = twin_scene(seen, &sc)) return e;
     if ((basis != msfm_vis::BASIS_TRACKS && basis != msfm_vis::BASIS_MAP) || n_query < 0) return 3;
     std::vector<uint8_t> queried;
     if (!twin_rank_bytes(sc, query_ids, n_query, false, &queried)) return 4;
@@ -939,12 +912,12 @@ int host_map_visibility(const long long* offsets, const int* image_ids, const un
     for (int k = 0; k < n_query; ++k) row_of[(size_t)sc.rank(query_ids[k])] = k;
     std::vector<uint32_t> image_counters((size_t)msfm_vis::kImageCounters * n, 0);
     msfm_vis::Tally tl = {0, 0, 0};
-    msfm_vis::MapVisibility(reinterpret_cast<const int64_t*>(offsets), image_ids, consistent, n_tracks, sc.rank_of.data(), (int)n, posed.data(),
-                            row_of.data(), n_query, basis, basis == msfm_vis::BASIS_MAP ? points : nullptr,
-                            basis == msfm_vis::BASIS_MAP ? mask : nullptr, image_counters.data(), out_matrix, &tl);
+    msfm_vis::MapVisibility(m->offsets, m->image_ids, m->consistent, m->n_tracks, sc.rank_of.data(), (int)n, posed.data(), row_of.data(),
+                            n_query, basis, basis == msfm_vis::BASIS_MAP ? m->points : nullptr,
+                            basis == msfm_vis::BASIS_MAP ? m->mask : nullptr, image_counters.data(), out_matrix, &tl);
     for (int r = 0; r < n_images; ++r) {
         msfm_image_visibility v = {};
-        v.image_id = ids[r];
+        v.image_id = m->ids[r];
         v.flags = (posed[(size_t)r] ? MSFM_VIS_POSED : 0) | (queried[(size_t)r] ? MSFM_VIS_QUERIED : 0);
         v.n_elements = (int32_t)image_counters[(size_t)msfm_vis::IMG_ELEMENTS * n + (size_t)r];
         v.n_visible = (int32_t)image_counters[(size_t)msfm_vis::IMG_VISIBLE * n + (size_t)r];
@@ -958,6 +931,129 @@ int host_map_visibility(const long long* offsets, const int* image_ids, const un
     }
     return 0;
 }
+// ---- the nine twins under their host_* names, the block's fields as raw arguments -----------------------------------------------------
+// The exports as they were before host_map, for callers built against those lists.  Each fills a block from its arguments and calls
+// the twin above; a field that twin does not read stays 0 or NULL, and nothing is computed here.  tests/*_twin.py call the twins;
+// tests/test_twin_host_abi.py holds each of these against its twin.
+static host_map raw_map(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent, long long n_tracks,
+                        const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses,
+                        const double* cam, double max_error, double min_angle, int min_views, long long first, long long count,
+                        const msfm_point3d* points, double* residuals, const unsigned char* mask, int have_mask) {
+    host_map m = {};
+    m.offsets = reinterpret_cast<const int64_t*>(offsets);
+    m.image_ids = image_ids;
+    m.point_idx = point_idx;
+    m.consistent = consistent;
+    m.n_tracks = n_tracks;
+    m.ids = ids;
+    m.kxy = kxy;
+    m.pose_ids = pose_ids;
+    m.poses = const_cast<msfm_pose_rt*>(poses);
+    m.n_images = n_images;
+    m.n_poses = n_poses;
+    for (int k = 0; k < 8; ++k) m.cam[k] = cam[k];
+    m.max_error = max_error;
+    m.min_angle = min_angle;
+    m.min_views = min_views;
+    m.have_mask = have_mask;
+    m.first = first;
+    m.count = count;
+    m.points = const_cast<msfm_point3d*>(points);
+    m.residuals = residuals;
+    m.mask = const_cast<unsigned char*>(mask);
+    return m;
+}
+int host_triangulate_tracks(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                            const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
+                            int n_poses, const double* cam, double max_error, double min_angle, int min_views, long long first,
+                            long long count, msfm_point3d* out_points, double* out_residuals) {
+    const host_map m = raw_map(offsets, image_ids, point_idx, consistent, 0, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                               min_angle, min_views, first, count, out_points, out_residuals, nullptr, 0);
+    return twin_triangulate_tracks(&m);
+}
+int host_triangulate_tracks_robust_trace(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                                         const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
+                                         int n_poses, const double* cam, double max_error, double min_angle, int min_views,
+                                         int max_hypotheses, long long first, long long count, msfm_point3d* out_points,
+                                         double* out_residuals, unsigned char* out_mask, long long* counts4, int* out_trace) {
+    const host_map m = raw_map(offsets, image_ids, point_idx, consistent, 0, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                               min_angle, min_views, first, count, out_points, out_residuals, out_mask, 0);
+    return twin_triangulate_tracks_robust(&m, max_hypotheses, counts4, out_trace);
+}
+int host_triangulate_tracks_robust(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                                   const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses,
+                                   int n_poses, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses,
+                                   long long first, long long count, msfm_point3d* out_points, double* out_residuals,
+                                   unsigned char* out_mask, long long* counts4) {
+    return host_triangulate_tracks_robust_trace(offsets, image_ids, point_idx, consistent, ids, n_images, kxy, pose_ids, poses, n_poses, cam,
+                                                max_error, min_angle, min_views, max_hypotheses, first, count, out_points, out_residuals,
+                                                out_mask, counts4, nullptr);
+}
+int host_refine_points(const long long* offsets, const int* image_ids, const int* point_idx, const int* ids, int n_images,
+                       const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const double* cam,
+                       double max_error, double min_angle, double step_tol, int max_iters, long long first, long long count,
+                       msfm_point3d* points, double* residuals, const unsigned char* mask, long long* counts5, double* costs2,
+                       void* out_trace) {
+    const host_map m = raw_map(offsets, image_ids, point_idx, nullptr, 0, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                               min_angle, 0, first, count, points, residuals, mask, 0);
+    return twin_refine_points(&m, step_tol, max_iters, counts5, costs2, out_trace);
+}
+int host_refine_poses(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks, const int* ids, int n_images,
+                      const float* const* kxy, const int* pose_ids, msfm_pose_rt* poses, int n_poses, const double* cam, double max_error,
+                      double min_angle, double step_tol, int max_iters, int min_observations, const int* fixed_ids, int n_fixed,
+                      msfm_point3d* points, double* residuals, const unsigned char* mask, msfm_pose_refinement* out_records,
+                      long long* counts9, double* costs2, void* out_trace) {
+    host_map m = raw_map(offsets, image_ids, point_idx, nullptr, n_tracks, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                         min_angle, 0, 0, n_tracks, points, residuals, mask, 0);
+    return twin_refine_poses(&m, step_tol, max_iters, min_observations, fixed_ids, n_fixed, out_records, counts9, costs2, out_trace);
+}
+int host_refine_camera(const long long* offsets, const int* image_ids, const int* point_idx, long long n_tracks, const int* ids, int n_images,
+                       const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, double* cam, double max_error,
+                       double min_angle, double step_tol, int mask_bits, int max_iters, int min_observations, msfm_point3d* points,
+                       double* residuals, const unsigned char* mask, long long* counts12, double* costs2, void* out_trace) {
+    host_map m = raw_map(offsets, image_ids, point_idx, nullptr, n_tracks, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                         min_angle, 0, 0, n_tracks, points, residuals, mask, 0);
+    const int rc = twin_refine_camera(&m, step_tol, mask_bits, max_iters, min_observations, counts12, costs2, out_trace);
+    for (int k = 0; k < 8; ++k) cam[k] = m.cam[k];   // (the refined camera; the given one where the twin refused)
+    return rc;
+}
+int host_extend_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent, const int* ids,
+                       int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const int* new_ids,
+                       int n_new, const double* cam, double max_error, double min_angle, int min_views, int max_hypotheses, long long first,
+                       long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask, long long* counts7,
+                       int* out_trace) {
+    const host_map m = raw_map(offsets, image_ids, point_idx, consistent, 0, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                               min_angle, min_views, first, count, points, residuals, mask, have_mask);
+    return twin_extend_points(&m, new_ids, n_new, max_hypotheses, counts7, out_trace);
+}
+int host_filter_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent, const int* ids,
+                       int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses,
+                       const int* scope_ids, int n_scope, const double* cam, double max_error, double min_angle, double flt_max_error,
+                       double flt_min_angle, long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask,
+                       int have_mask, long long* counts7, int* out_trace) {
+    const host_map m = raw_map(offsets, image_ids, point_idx, consistent, 0, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                               min_angle, 0, first, count, points, residuals, mask, have_mask);
+    return twin_filter_points(&m, scope_ids, n_scope, flt_max_error, flt_min_angle, counts7, out_trace);
+}
+int host_complete_points(const long long* offsets, const int* image_ids, const int* point_idx, const unsigned char* consistent,
+                         const int* ids, int n_images, const float* const* kxy, const int* pose_ids, const msfm_pose_rt* poses, int n_poses,
+                         const int* scope_ids, int n_scope, const double* cam, double max_error, double min_angle, double cmp_max_error,
+                         long long first, long long count, msfm_point3d* points, double* residuals, unsigned char* mask, int have_mask,
+                         long long* counts6, int* out_trace) {
+    const host_map m = raw_map(offsets, image_ids, point_idx, consistent, 0, ids, n_images, kxy, pose_ids, poses, n_poses, cam, max_error,
+                               min_angle, 0, first, count, points, residuals, mask, have_mask);
+    return twin_complete_points(&m, scope_ids, n_scope, cmp_max_error, counts6, out_trace);
+}
+int host_map_visibility(const long long* offsets, const int* image_ids, const unsigned char* consistent, long long n_tracks, const int* ids,
+                        int n_images, const int* pose_ids, const msfm_pose_rt* poses, int n_poses, const int* query_ids, int n_query, int basis,
+                        const msfm_point3d* points, const unsigned char* mask, msfm_image_visibility* out_records, unsigned* out_matrix,
+                        long long* counts3) {
+    const double cam[8] = {1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // (no pixel is read: only the poses' validity)
+    const host_map m = raw_map(offsets, image_ids, nullptr, consistent, n_tracks, ids, n_images, nullptr, pose_ids, poses, n_poses, cam, 0.0, 0.0,
+                               0, 0, n_tracks, points, nullptr, mask, 0);
+    return twin_map_visibility(&m, query_ids, n_query, basis, out_records, out_matrix, counts3);
+}
+
 // msfm_vis::vis_route: out4 = route (0: ROUTE_LDS asked for and no fit), lds_bytes, matrix_in_lds, wgs_per_cu
 void host_vis_route(int want, long long n, long long n_query, long long T, long long O, int* out4) {
     const msfm_vis::Route r = msfm_vis::vis_route(want, n, n_query, T, O);

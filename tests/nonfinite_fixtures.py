@@ -10,8 +10,6 @@ The layout of every chain scene: tracks of 8 views through the images 0 .. 7 and
 A bad 8-view track carries the bad value in an OLD image (4), a NEW one (1) and REG (7): the consensus rejects the first, the
 continuation the second, the registration meets the third.  A bad 3-view track carries it in image 1: not attempted at the
 triangulation (one posed view), created by the extension from the views 0, 1, 2, of which 0 and 2 (2.4 degrees apart) agree."""
-import ctypes as C
-
 import numpy as np
 
 import complete_twin as ctw
@@ -22,6 +20,7 @@ import refine_poses_twin as ptw
 import registration_twin as regtw
 import robust_triangulation_twin as robtw
 import triangulation_twin as tw
+import twin_host
 from monocularsfm_amd import _lib
 from refine_points_fixtures import tracks_of
 from test_gpu_robust_triangulation import ring_job
@@ -352,18 +351,7 @@ def chain(host, sc, cam=CAM, thr=THR, H=8, mh=8, robust=True, trace=True):
     return out
 
 
-def load_host():
-    L = ftw.load_host()                  # (etw.load_host()'s exports and host_filter_points)
-    vp = C.c_void_p                      # host_complete_points as complete_twin.load_host declares it
-    L.host_complete_points.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, ctw.DP, C.c_double, C.c_double, C.c_double,
-                                       C.c_longlong, C.c_longlong, vp, vp, vp, C.c_int, vp, vp]
-    L.host_complete_points.restype = C.c_int
-    R = regtw.load_host()
-    for name in ("host_register_counts", "host_register_images", "host_register_sample3", "host_p3p", "host_register_refine"):
-        f = getattr(R, name)
-        g = getattr(L, name)
-        g.argtypes, g.restype = f.argtypes, f.restype
-    return L
+load_host = twin_host.load
 
 
 def registration_bad(sc, reg):

@@ -1,17 +1,12 @@
 """ctypes driver of the two-view geometry's host twin (host/GeometricVerification.cpp, TwoViewGeometry, and the pieces of
 csrc/msfm_pose.h, through libmsfm_host.so), and the twin's records over the unverified lists of a context, pair by pair on a thread
 pool as tests/verify_twin.py runs the masks."""
-import ctypes as C
-import os
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "monocularsfm_amd", "host")
-FP, DP, UP = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_ubyte)
-WORKERS = 16
+import twin_host
+from twin_host import DP, FP, UP, WORKERS
 
 # msfm_two_view_record (include/msfm_match.h): 144 bytes, no implicit padding
 RECORD = np.dtype([("valid", "<i4"), ("reserved", "<i4"), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_kept", "<i4"),
@@ -21,20 +16,7 @@ assert RECORD.itemsize == 144
 DEFAULTS = (100, 2.0, 4.0)   # min_num_inliers, tri_max_error (px), tri_min_angle (degrees): the reference's
 
 
-def load_host():
-    subprocess.check_call(["make", "-C", HOST, "-s", "libmsfm_host.so"])
-    L = C.CDLL(os.path.join(HOST, "libmsfm_host.so"))
-    L.host_pose_decompose.argtypes = [DP, DP]
-    L.host_pose_triangulate.argtypes = [DP, C.c_double, C.c_double, C.c_double, C.c_double, DP]
-    L.host_pose_evaluate.argtypes = [DP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, DP]
-    L.host_pose_acos.argtypes = [DP, C.c_int, DP]
-    L.host_initial_candidate.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]
-    L.host_pose_record.argtypes = [DP, DP, DP, DP, DP, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p]
-    L.host_two_view_geometry.argtypes = [FP, FP, C.c_int, DP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
-                                         C.c_ulonglong, UP, C.c_void_p]
-    L.host_essential_ransac.argtypes = [FP, FP, C.c_int, DP, C.c_double, C.c_double, C.c_int, C.c_ulonglong, UP]
-    L.host_emat_undistort.argtypes = [DP, DP, C.c_int, DP]
-    return L
+load_host = twin_host.load
 
 
 def _dp(a):

@@ -2,39 +2,18 @@
 offsets, track ids, flags and residuals the device must give for a triangulated track result, computed in slices of the image list on
 a thread pool.  Test infrastructure only."""
 import ctypes as C
-import os
-import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "monocularsfm_amd", "host")
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-DP = C.POINTER(C.c_double)
-WORKERS = 16
-
-from monocularsfm_amd._lib import POINT3D, REGISTRATION  # noqa: E402
+import twin_host
+from monocularsfm_amd._lib import POINT3D, REGISTRATION
+from twin_host import DP, WORKERS
 
 assert REGISTRATION.itemsize == 128
 DEFAULTS = dict(max_error=4.0, confidence=0.9999, max_iters=1024, min_inliers=15, refine_iters=10)   # Registrant.h:22-26
 ROUND = 64
-
-
-def load_host():
-    subprocess.check_call(["make", "-C", HOST, "-s", "libmsfm_host.so"])
-    L = C.CDLL(os.path.join(HOST, "libmsfm_host.so"))
-    vp = C.c_void_p
-    L.host_register_counts.argtypes = [vp, vp, C.c_longlong, vp, vp, C.c_int, vp]
-    L.host_register_images.argtypes = [vp, vp, vp, C.c_longlong, vp, vp, C.c_int, vp, DP, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
-                                       vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.host_register_sample3.argtypes = [C.c_int, C.c_int, C.c_int, vp]
-    L.host_register_sample3.restype = None
-    L.host_p3p.argtypes = [DP, DP, DP, DP]
-    L.host_register_refine.argtypes = [DP, DP, DP, DP, DP, C.c_int, C.c_int, DP, DP]
-    return L
+load_host = twin_host.load
 
 
 def sample3(host, image_id, it, n):

@@ -3,8 +3,7 @@ residuals, inlier bytes, pose list, camera, triangulation thresholds and route) 
 twins and references that the stage tests compare the device with.  The glue -- initialize, grow, alternate, reconstruct -- is not
 written again: the class borrows the functions of _lib.Context, so the Python under test is the same code on both sides.
 
-Every twin driver's load_host() declares the argtypes of its own exports on its own handle; each stage goes through the handle of its
-own module.  Test infrastructure only."""
+Every stage goes through the one handle of tests/twin_host.py.  Test infrastructure only."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -20,21 +19,13 @@ import registration_twin
 import robust_triangulation_twin
 import tracks_ref
 import triangulation_twin
+import twin_host
 import verify_twin
 import visibility_twin
 from monocularsfm_amd import _lib
 from oracle import c_oracle
 
-_MODULES = dict(tri=triangulation_twin, robust=robust_triangulation_twin, register=registration_twin, extend=extend_twin,
-                points=refine_points_twin, poses=refine_poses_twin, camera=refine_camera_twin, filter=filter_twin,
-                complete=complete_twin, visibility=visibility_twin, pose=pose_twin, verify=verify_twin)
-_HOSTS = {}
-
-
-def host(name):
-    if name not in _HOSTS:
-        _HOSTS[name] = _MODULES[name].load_host()
-    return _HOSTS[name]
+host = twin_host.load
 
 
 def _state_error(what):
@@ -112,10 +103,10 @@ class TwinContext:
         pairs_l = [(int(a), int(b)) for a, b in pairs]
         if self._two_view is None:
             self._records = None
-            out = verify_twin.run(host("verify"), (offs, qt, d), pairs_l, kps, 1, self._verify_cam, False, 0.7, threshold, confidence,
+            out = verify_twin.run(host(), (offs, qt, d), pairs_l, kps, 1, self._verify_cam, False, 0.7, threshold, confidence,
                                   int(max_iters), int(seed))["lists"]
         else:
-            h = host("pose")
+            h = host()
 
             def one(p):
                 i, j = pairs_l[p]
@@ -194,9 +185,9 @@ class TwinContext:
         thr = (float(max_error), float(min_angle), int(min_views))
         extra = {}
         if robust:
-            pts, res, mask, extra = robust_triangulation_twin.run(host("robust"), *self._common(), lst, cam, thr + (int(max_hypotheses),))
+            pts, res, mask, extra = robust_triangulation_twin.run(host(), *self._common(), lst, cam, thr + (int(max_hypotheses),))
         else:
-            pts, res = triangulation_twin.run(host("tri"), *self._common(), lst, cam, thr)
+            pts, res = triangulation_twin.run(host(), *self._common(), lst, cam, thr)
             mask = None
         self._clear_map()
         self._points, self._residuals, self._mask, self._pose_list, self._cam, self._thr = pts, res, mask, lst, cam, thr
@@ -228,7 +219,7 @@ class TwinContext:
     def register_images(self, camera, image_ids, max_error=4.0, confidence=0.9999, max_iters=1024, min_inliers=15, refine_iters=10):
         self._need_map()
         ids = [int(i) for i in np.asarray(image_ids).reshape(-1)]
-        got = registration_twin.run(host("register"), self._tracks, self._points, ids, self._kps, refine_camera_twin.camera8(camera),
+        got = registration_twin.run(host(), self._tracks, self._points, ids, self._kps, refine_camera_twin.camera8(camera),
                                     max_error=max_error, confidence=confidence, max_iters=max_iters, min_inliers=min_inliers,
                                     refine_iters=refine_iters)
         self._registrations = got
@@ -246,7 +237,7 @@ class TwinContext:
         self._need_map()
         if max_hypotheses is None:
             max_hypotheses = getattr(self, "_tri_route", 0)
-        pts, res, mask, counts, lst = extend_twin.run(host("extend"), *self._common(), self._pose_list, _lib.pose_table(poses), self._cam,
+        pts, res, mask, counts, lst = extend_twin.run(host(), *self._common(), self._pose_list, _lib.pose_table(poses), self._cam,
                                                       self._points, self._residuals, self._mask, self._thr, int(max_hypotheses))
         self._points, self._residuals, self._mask, self._pose_list = pts, res, mask, lst
         self._changed()
@@ -254,7 +245,7 @@ class TwinContext:
 
     def refine_points(self, max_iters=10, step_tol=1e-10):
         self._need_map()
-        pts, res, counts = refine_points_twin.run(host("points"), *self._common(), self._pose_list, self._cam, self._points, self._residuals,
+        pts, res, counts = refine_points_twin.run(host(), *self._common(), self._pose_list, self._cam, self._points, self._residuals,
                                                   self._mask, self._thr[:2], (int(max_iters), float(step_tol)))
         self._points, self._residuals = pts.copy(), res.copy()
         self._changed()
@@ -262,7 +253,7 @@ class TwinContext:
 
     def refine_poses(self, max_iters=10, step_tol=1e-6, min_observations=15, fixed=()):
         self._need_map()
-        pts, res, lst, rec, counts = refine_poses_twin.run(host("poses"), *self._common(), self._pose_list, self._cam, self._points,
+        pts, res, lst, rec, counts = refine_poses_twin.run(host(), *self._common(), self._pose_list, self._cam, self._points,
                                                            self._residuals, self._mask, self._thr[:2],
                                                            (int(max_iters), float(step_tol), int(min_observations)), [int(i) for i in fixed])
         self._points, self._residuals, self._pose_list = pts.copy(), res.copy(), (lst[0].copy(), lst[1].copy())
@@ -278,7 +269,7 @@ class TwinContext:
     def refine_camera(self, mask=("fx_fy",), max_iters=10, step_tol=1e-6, min_observations=100):
         self._need_map()
         before = self.camera()
-        pts, res, cam, counts = refine_camera_twin.run(host("camera"), *self._common(), self._pose_list, self._cam, self._points,
+        pts, res, cam, counts = refine_camera_twin.run(host(), *self._common(), self._pose_list, self._cam, self._points,
                                                        self._residuals, self._mask, self._thr[:2],
                                                        (int(max_iters), float(step_tol), int(min_observations)), _lib.camera_mask(mask))
         self._points, self._residuals, self._cam = pts.copy(), res.copy(), tuple(cam)
@@ -288,7 +279,7 @@ class TwinContext:
     def filter_points(self, max_error=None, min_angle=None, image_ids=None):
         self._need_map()
         params = (float(max_error), float(min_angle)) if max_error is not None and min_angle is not None else None
-        pts, res, mask, counts = filter_twin.run(host("filter"), *self._common(), self._pose_list, self._cam, self._points, self._residuals,
+        pts, res, mask, counts = filter_twin.run(host(), *self._common(), self._pose_list, self._cam, self._points, self._residuals,
                                                  self._mask, self._thr[:2], params, list(image_ids) if image_ids is not None else ())
         self._points, self._residuals, self._mask = pts, res, mask
         self._changed()
@@ -296,7 +287,7 @@ class TwinContext:
 
     def complete_points(self, max_error=None, image_ids=None):
         self._need_map()
-        pts, res, mask, counts = complete_twin.run(host("complete"), *self._common(), self._pose_list, self._cam, self._points,
+        pts, res, mask, counts = complete_twin.run(host(), *self._common(), self._pose_list, self._cam, self._points,
                                                    self._residuals, self._mask, self._thr[:2], max_error,
                                                    list(image_ids) if image_ids is not None else ())
         self._points, self._residuals, self._mask = pts, res, mask
@@ -309,7 +300,7 @@ class TwinContext:
         if basis == "map":
             self._need_map()
         on_map = basis == "map"
-        rec, mat, counts = visibility_twin.run(host("visibility"), self._tracks, self._session["ids"], self._pose_list if on_map else None,
+        rec, mat, counts = visibility_twin.run(host(), self._tracks, self._session["ids"], self._pose_list if on_map else None,
                                                self._points if on_map else None, self._mask if on_map else None,
                                                [int(i) for i in query], basis)
         flags = rec["flags"]

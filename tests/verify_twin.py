@@ -7,27 +7,14 @@ nE, nH) and the predicted verification_stats() (solved, rounds) from host_staged
 hypotheses and the largest of their round counts; under the selection with model 0 the homography's alone (F is not staged), with
 model 1 the essential matrix's and the homography's together."""
 import ctypes as C
-import os
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "monocularsfm_amd", "host")
-FP, DP, UP, IP = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)
-WORKERS = 16   # a fixed pool: the machine's CPU count says nothing about the CPUs this process may use
+import twin_host
+from twin_host import DP, FP, IP, UP, WORKERS  # noqa: F401
 
-
-def load_host():
-    subprocess.check_call(["make", "-C", HOST, "-s", "libmsfm_host.so"])
-    L = C.CDLL(os.path.join(HOST, "libmsfm_host.so"))
-    L.host_essential_ransac.argtypes = [FP, FP, C.c_int, DP, C.c_double, C.c_double, C.c_int, C.c_ulonglong, UP]
-    L.host_homography_ransac.argtypes = [FP, FP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_ulonglong, UP]
-    L.host_two_view_select.argtypes = [FP, FP, C.c_int, C.c_int, DP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_ulonglong, UP, IP]
-    L.host_staged_schedule.argtypes = [C.c_int, FP, FP, C.c_int, DP, C.c_double, C.c_double, C.c_int, C.c_ulonglong,
-                                       C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
-    return L
+load_host = twin_host.load
 
 
 def _schedule(host, model, a, b, n, cam, threshold, confidence, max_iters, seed):
