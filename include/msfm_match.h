@@ -384,6 +384,44 @@ typedef struct msfm_two_view_record {   /* 144 bytes, no implicit padding */
 } msfm_two_view_record;
 int msfm_set_two_view_geometry(msfm_ctx* ctx, int enable, const msfm_two_view_params* params);
 int msfm_fetch_two_view_geometry(msfm_ctx* ctx, msfm_two_view_record* out);
+
+/* ---- two-view pose refinement ---------------------------------------------------------------------
+ * Off by default; needs the two-view geometry.  When on, the pose of every valid record with n_kept >= min_matches is polished over
+ * ALL the pair's kept matches: Levenberg-Marquardt on the Sampson error (pixels through (fx + fy) / 2) in five unknowns, three of
+ * the rotation (R <- C(a) R, Cayley) and two of the translation direction (|t| = 1 is kept), one 5 x 5 system per pair.  The
+ * record's statistics are then computed again under the refined pose, and the refined record replaces the record iff a step was
+ * accepted and neither n_positive_depth nor n_triangulated is lower than before; otherwise not one byte of the record changes.
+ * n_kept, the match lists, the statistics and the selection records never change.  The arithmetic is csrc/msfm_pose_refine.h,
+ * bit-identical to the host twin RefineTwoView.  The layout of msfm_two_view_record does not change: what the refinement did is in
+ * a record of its own per pair, all zero for a pair that is not eligible (an invalid record, or n_kept < min_matches):
+ *   status       MSFM_TVR_ELIGIBLE | MSFM_TVR_STEP_ACCEPTED (the loop accepted a step) | MSFM_TVR_REFINED (the record was replaced)
+ *   stop         why the loop ended: 1 the step fell below step_tol, 2 max_iters steps were evaluated, 3 the damping passed its ceiling
+ *   steps, accepted   evaluated steps, and those of them that lowered the cost
+ *   n_positive_depth_before, n_triangulated_before   the counts of the record that went in
+ *   cost_before, cost_after   the sum of squared Sampson residuals in px^2 at the record's pose and at the pose that stands
+ *                             (cost_after = cost_before when the record was not replaced)
+ * msfm_set_two_view_refinement: enable 0 / 1; params NULL = {10, 15, 1e-6}.  MSFM_E_INVALID for max_iters < 1, min_matches < 5, a
+ * negative or non-finite step_tol, and when enabled while the two-view geometry is off; MSFM_E_STATE while a streaming series is
+ * open.  msfm_set_two_view_geometry(0) while this is on is MSFM_E_INVALID: switch this off first.
+ * msfm_fetch_two_view_refinements: one record per pair of the last msfm_match_pairs_verified call, or of the chunk the last
+ * msfm_match_pairs_next returned; out may be NULL.  MSFM_E_STATE if that call / chunk ran without the refinement. */
+#define MSFM_TVR_ELIGIBLE 1
+#define MSFM_TVR_STEP_ACCEPTED 2
+#define MSFM_TVR_REFINED 4
+typedef struct msfm_two_view_refine_params {   /* 16 bytes */
+    int32_t max_iters;           /* evaluated steps per pair at most: 10 */
+    int32_t min_matches;         /* kept matches a pair needs: 15 */
+    double step_tol;             /* the loop ends when |delta|^2 <= step_tol^2: 1e-6 */
+} msfm_two_view_refine_params;
+typedef struct msfm_two_view_refinement {   /* 40 bytes, no implicit padding */
+    int32_t status;
+    int32_t stop;
+    int32_t steps, accepted;
+    int32_t n_positive_depth_before, n_triangulated_before;
+    double cost_before, cost_after;
+} msfm_two_view_refinement;
+int msfm_set_two_view_refinement(msfm_ctx* ctx, int enable, const msfm_two_view_refine_params* params);
+int msfm_fetch_two_view_refinements(msfm_ctx* ctx, msfm_two_view_refinement* out);
 int msfm_match_pairs_verified(msfm_ctx* ctx, const int32_t* pairs, int n_pairs,
                               const msfm_match_params* params, const msfm_verify_params* verify,
                               int64_t* out_offsets);

@@ -32,6 +32,22 @@ TWO_VIEW_RECORD = np.dtype([("valid", "<i4"), ("reserved", "<i4"), ("R", "<f8", 
                             ("median_tri_angle", "<f8"), ("mean_tri_angle", "<f8"), ("mean_residual", "<f8")])
 
 
+class TwoViewRefineParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("min_matches", C.c_int32), ("step_tol", C.c_double)]
+
+
+# msfm_two_view_refinement (include/msfm_match.h): 40 bytes, no implicit padding; its status bits
+TWO_VIEW_REFINEMENT = np.dtype([("status", "<i4"), ("stop", "<i4"), ("steps", "<i4"), ("accepted", "<i4"),
+                                ("n_positive_depth_before", "<i4"), ("n_triangulated_before", "<i4"), ("cost_before", "<f8"),
+                                ("cost_after", "<f8")])
+TVR_ELIGIBLE, TVR_STEP_ACCEPTED, TVR_REFINED = 1, 2, 4
+
+
+def two_view_refined(refinements):
+    """The pairs whose two-view record was replaced by its refined one: a bool mask over a TWO_VIEW_REFINEMENT array."""
+    return (np.asarray(refinements)["status"] & TVR_REFINED) != 0
+
+
 class TrackParams(C.Structure):
     _fields_ = [("min_pair_matches", C.c_int32), ("add_only", C.c_int32)]
 
@@ -448,6 +464,8 @@ def _signatures():
         "msfm_fetch_model_selection": (i, [vp, ip, ip, ip]),
         "msfm_set_two_view_geometry": (i, [vp, i, P(TwoViewParams)]),
         "msfm_fetch_two_view_geometry": (i, [vp, vp]),
+        "msfm_set_two_view_refinement": (i, [vp, i, P(TwoViewRefineParams)]),
+        "msfm_fetch_two_view_refinements": (i, [vp, vp]),
         # feature tracks and the reconstruction stage
         "msfm_tracks_begin": (i, [vp, ip, i, P(TrackParams)]),
         "msfm_tracks_add": (i, [vp, ip, i, i64p, ip]),
@@ -751,6 +769,8 @@ class Context:
                     item["model_selection"] = self.model_selection(n)
                 if verified and self._two_view_ran():
                     item["two_view_geometry"] = self.two_view_geometry(n)
+                    if self._two_view_refinement_ran():
+                        item["two_view_refinements"] = self.two_view_refinements(n)
                 yield item
         finally:
             # a consumer that breaks out of the loop (GeneratorExit) or whose body raises must not leave the series open: the store
@@ -845,6 +865,27 @@ class Context:
 
     def _two_view_ran(self):
         return self._L.msfm_fetch_two_view_geometry(self._h, None) == OK
+
+    def set_two_view_refinement(self, enable=True, max_iters=10, step_tol=1e-6, min_matches=15):
+        """The two-view pose refinement behind the two-view geometry (include/msfm_match.h): the pose of every valid record with at
+        least min_matches kept matches is polished by LM on the Sampson error over all its kept matches, and the refined record
+        replaces the record iff a step was accepted and neither count of the record drops.  The lists do not change.  E_INVALID for
+        max_iters < 1, min_matches < 5, a negative / non-finite step_tol or while the two-view geometry is off; E_STATE while a
+        series is open."""
+        prm = TwoViewRefineParams(int(max_iters), int(min_matches), float(step_tol))
+        self._chk(self._L.msfm_set_two_view_refinement(self._h, int(bool(enable)), C.byref(prm)))
+
+    def two_view_refinements(self, n_pairs):
+        """Per pair of the last match_pairs_verified call (or of the last verified stream chunk): a structured array of dtype
+        TWO_VIEW_REFINEMENT (two_view_refined gives the mask of the replaced records).  E_STATE if that call ran without the
+        refinement."""
+        n = int(n_pairs)
+        out = np.zeros(max(n, 1), TWO_VIEW_REFINEMENT)
+        self._chk(self._L.msfm_fetch_two_view_refinements(self._h, out.ctypes.data))
+        return out[:n]
+
+    def _two_view_refinement_ran(self):
+        return self._L.msfm_fetch_two_view_refinements(self._h, None) == OK
 
     # ---- feature tracks (include/msfm_match.h) ----
     def tracks_begin(self, ids, min_pair_matches=0, add_only=False):

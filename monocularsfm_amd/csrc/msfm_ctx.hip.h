@@ -589,7 +589,8 @@ struct Scratch {
     // the two-view geometry (msfm_verify_pose.hip.h): a record per pair, the kept-index and angle slots of the staged lists' size, the E
     // winners saved from the homography's rounds under the selection; h_tv: the records on the host, read at the end of the sub-batch
     DevBuf d_tv_records, d_tv_idx, d_tv_angles, d_tv_best_it;
-    PinnedBuf h_tv;
+    DevBuf d_tvr_records;             // the two-view refinement (msfm_verify_pose_refine.hip.h): a msfm_two_view_refinement per pair
+    PinnedBuf h_tv;                   // the records [P], then (refinement on) the refinement records [P]
     DevBuf d_tk_pairs;                // feature tracks (msfm_tracks.hip.h): the sub-batch's (id1, id2) per pair, for the fold
     PinnedBuf h_tk_pairs;             //   and its page-locked staging, rewritten only after the set's stream has been waited for
     msfm_profile prof = {};           // this sub-batch's share; joins the call's profile when the sub-batch is accepted
@@ -605,7 +606,7 @@ struct Scratch {
                           &d_vpairs, &d_vpf, &d_vitems, &d_lists, &d_colmask, &d_gtot, &d_grow0, &d_cnt, &d_mrow, &d_summary, &d_overflow,
                           &d_totals, &d_vf_pairs,
                           &d_vf_x1, &d_vf_y1, &d_vf_x2, &d_vf_y2, &d_vf_hyp, &d_vf_best_it, &d_vf_best_count, &d_vf_flags, &d_st2_qt,
-                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_tv_records, &d_tv_idx, &d_tv_angles, &d_tv_best_it, &d_tk_pairs, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2, &d_wg_end};
+                          &d_st2_d, &d_counts2, &d_ve_x1, &d_ve_y1, &d_ve_x2, &d_ve_y2, &d_staged_state, &d_staged_stats, &d_vs_records, &d_tv_records, &d_tv_idx, &d_tv_angles, &d_tv_best_it, &d_tvr_records, &d_tk_pairs, &d_cmp_s0, &d_cmp_s1, &d_summary_a, &d_items16, &d_cand_val, &d_cmp_n2, &d_wg_end};
         for (DevBuf* b : bufs) fn(*b, arg);
     }
     long long device_bytes() {
@@ -786,6 +787,11 @@ struct msfm_ctx {
     msfm_two_view_params tv_params = {100, 0, 2.0, 4.0};
     std::vector<msfm_two_view_record> tv_records;
     bool tv_valid = false;
+    // two-view pose refinement (msfm_set_two_view_refinement): every valid record is polished; tvr_records / tvr_valid: as tv_records / tv_valid
+    bool tv_refine = false;
+    msfm_two_view_refine_params tvr_params = {10, 15, 1e-6};
+    std::vector<msfm_two_view_refinement> tvr_records;
+    bool tvr_valid = false;
     TrackSession tracks;              // feature tracks (msfm_tracks_begin .. msfm_tracks_end)
 };
 

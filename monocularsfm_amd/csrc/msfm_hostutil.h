@@ -190,11 +190,13 @@ inline long long msfm_pair_two_view_bytes(int n1, int n2) {
 //   route 0, brute force: three 4-byte row partials per padded row, three per 128-row block and column.
 // (A mixed sub-batch -- byte pairs next to float pairs -- allocates by route 1's sizes for all of them: this is the cut, not a cap.)
 // two_view: the call computes two-view geometry records (msfm_pair_two_view_bytes on top, whatever the route).
+// two_view_refine: it also refines them (msfm_set_two_view_refinement): the pair's msfm_two_view_refinement, 40 B.
 inline long long msfm_pair_scratch_bytes(int n1, int n2, int n1pad, int n2pad, int blocks128, int blocks512, int route,
-                                         bool two_view = false) {
+                                         bool two_view = false, bool two_view_refine = false) {
     if (n1 <= 0 || n2 <= 0) return 0;
     const long long slots = (long long)n1pad + n2pad;
-    const long long common = (route == 3 ? 24LL : 36LL) * slots + 24LL * n1 + 1024 + (two_view ? msfm_pair_two_view_bytes(n1, n2) : 0);
+    const long long common = (route == 3 ? 24LL : 36LL) * slots + 24LL * n1 + 1024 + (two_view ? msfm_pair_two_view_bytes(n1, n2) : 0) +
+                             (two_view_refine ? 40LL : 0);
     if (route == 0) return common + 12LL * n1pad + 12LL * (long long)blocks128 * n2pad;
     const long long partials = 8LL * n1pad + (route == 3 ? 4LL : 8LL) * (long long)blocks512 * n2pad;
     if (route == 2) return common + partials + 128LL * ((long long)n1 + n2) + 16384;

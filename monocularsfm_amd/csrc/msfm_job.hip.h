@@ -56,6 +56,7 @@ struct MatchJob {
     bool streaming = false;
     bool select = false;   // the two-view model selection runs (msfm_verify_select.hip.h): verified, selection on, model 0 or 1
     bool pose = false;     // the two-view geometry runs (msfm_verify_pose.hip.h): verified, switched on (model 1, by msfm_set_two_view_geometry)
+    bool refine = false;   // the two-view pose refinement runs behind it (msfm_verify_pose_refine.hip.h): pose, and msfm_set_two_view_refinement
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     int kSets = kInFlight;
     long long kScratchBytes = 1;
@@ -84,6 +85,9 @@ struct MatchJob {
         c->sel_records.assign(select && !stream_mode ? 3 * (size_t)n : 0, 0);
         pose = vp && c->two_view && c->verify_model == MSFM_VERIFY_ESSENTIAL;
         c->tv_records.assign(pose && !stream_mode ? (size_t)n : 0, msfm_two_view_record{});
+        c->tvr_valid = false;
+        refine = pose && c->tv_refine;
+        c->tvr_records.assign(refine && !stream_mode ? (size_t)n : 0, msfm_two_view_refinement{});
         if (vp) {
             verify_store = *vp;
             verify = &verify_store;
@@ -206,7 +210,7 @@ struct MatchJob {
                 return fail(ctx, MSFM_E_STATE, "geometric verification needs msfm_upload_keypoints for image " +
                                                    std::to_string(ia.nk < ia.n ? pairs[2 * end] : pairs[2 * end + 1]));
             const int route = msfm_scratch_route(knobs, prune.prune, prune.ratio, pp.use != 0, ia.is_u8, ib.is_u8);
-            const long long need = pd.valid ? msfm_pair_scratch_bytes(pd.n1, pd.n2, pd.n1pad, pd.n2pad, pd.a_blocks, pd.a_blocks256, route, pose) : 0;
+            const long long need = pd.valid ? msfm_pair_scratch_bytes(pd.n1, pd.n2, pd.n1pad, pd.n2pad, pd.a_blocks, pd.a_blocks256, route, pose, refine) : 0;
             const long long c = pd.valid ? (long long)pd.n1 * pd.n2 : 0;
             if (end > begin && est + need > kScratchBytes) break;
             if (end > begin && !marks.empty() && cost_begin + cost + c / 2 > mark) break;
@@ -282,11 +286,14 @@ struct MatchJob {
         rc = queue_tail_copies(ctx, P, select ? &SC.d_vs_records : nullptr);
         if (rc != MSFM_OK) return rc;
         if (pose) {   // the records leave by a copy of their own (export_tail_kernel once more): the tail above stays what it is
-            HIPCHK(ctx, SC.h_tv.ensure(P * sizeof(msfm_two_view_record) + 64, 0));
+            const size_t rec_bytes = P * sizeof(msfm_two_view_record);
+            HIPCHK(ctx, SC.h_tv.ensure(rec_bytes + (refine ? P * sizeof(msfm_two_view_refinement) : 0) + 64, 0));
             char* h = nullptr;
             HIPCHK(ctx, hipHostGetDevicePointer((void**)&h, SC.h_tv.p, 0));
             ExportSegs segs = {};
-            segs.s[0] = ExportSeg{SC.d_tv_records.as<char>(), h, (unsigned)(P * sizeof(msfm_two_view_record))};
+            segs.s[0] = ExportSeg{SC.d_tv_records.as<char>(), h, (unsigned)rec_bytes};
+            if (refine)   // (the refinement records: a second segment, behind the records)
+                segs.s[1] = ExportSeg{SC.d_tvr_records.as<char>(), h + rec_bytes, (unsigned)(P * sizeof(msfm_two_view_refinement))};
             hipLaunchKernelGGL(export_tail_kernel, dim3(32), dim3(256), 0, SC.stream, segs);
             HIPCHK(ctx, hipGetLastError());
         }
@@ -408,6 +415,16 @@ struct MatchJob {
                                (const SelectRecord*)(select ? SC.d_vs_records.as<SelectRecord>() : nullptr), prm, f, ctx->tv_params, (int)P,
                                SC.d_tv_idx.as<int>(), SC.d_tv_angles.as<double>(), SC.d_tv_records.as<msfm_two_view_record>());
             HIPCHK(ctx, hipGetLastError());
+            if (refine) {   // directly behind it, on the same stream: the records are polished where they lie
+                HIPCHK(ctx, SC.d_tvr_records.ensure(P * sizeof(msfm_two_view_refinement)));
+                const unsigned rgrid = (unsigned)std::min<size_t>(P, (size_t)kTvrGroupsPerCU * (size_t)std::max(1, ctx->cu_count));
+                hipLaunchKernelGGL(tv_refine_kernel, dim3(rgrid), dim3(kTvrThreads), 0, SC.stream, dp, (const double*)SC.d_ve_x1.as<double>(),
+                                   (const double*)SC.d_ve_y1.as<double>(), (const double*)SC.d_ve_x2.as<double>(),
+                                   (const double*)SC.d_ve_y2.as<double>(), (const int*)SC.d_tv_idx.as<int>(), f, ctx->tv_params,
+                                   ctx->tvr_params, (int)P, SC.d_tv_angles.as<double>(), SC.d_tv_records.as<msfm_two_view_record>(),
+                                   SC.d_tvr_records.as<msfm_two_view_refinement>());
+                HIPCHK(ctx, hipGetLastError());
+            }
         }
         HIPCHK(ctx, hipEventRecord(v1, SC.stream));
         return MSFM_OK;
@@ -511,6 +528,11 @@ struct MatchJob {
             else w.sel.clear();
             if (pose) w.tv.assign(SC.h_tv.as<msfm_two_view_record>(), SC.h_tv.as<msfm_two_view_record>() + P);
             else w.tv.clear();
+            w.tvr.clear();
+            if (refine) {   // (behind the records: issue)
+                const msfm_two_view_refinement* h_tvr = reinterpret_cast<const msfm_two_view_refinement*>(SC.h_tv.as<msfm_two_view_record>() + P);
+                w.tvr.assign(h_tvr, h_tvr + P);
+            }
             for (size_t p = 0; p < P; ++p) SC.prof.order_sensitive_rows += sens[p];
             ctx->res_count += (size_t)total;   // (matches of the job so far)
         } else {
@@ -552,6 +574,8 @@ struct MatchJob {
             }
             if (select) std::memcpy(ctx->sel_records.data() + 3 * (size_t)w.begin, sens + P, P * 12);
             if (pose) std::memcpy(ctx->tv_records.data() + (size_t)w.begin, SC.h_tv.p, P * sizeof(msfm_two_view_record));
+            if (refine)
+                std::memcpy(ctx->tvr_records.data() + (size_t)w.begin, SC.h_tv.as<msfm_two_view_record>() + P, P * sizeof(msfm_two_view_refinement));
         }
         SC.prof.descriptor_pairs += b.desc_pairs;
         SC.prof.dist_algo_bytes += b.algo_bytes;

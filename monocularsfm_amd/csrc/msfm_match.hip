@@ -17,6 +17,7 @@
 #include "msfm_verify_h.hip.h"
 #include "msfm_verify_select.hip.h"
 #include "msfm_verify_pose.hip.h"
+#include "msfm_verify_pose_refine.hip.h"
 #include "msfm_retrieval.hip.h"
 
 #include <sys/mman.h>
@@ -309,6 +310,7 @@ struct SubBatch {
     std::vector<int32_t> sens;    //   order-certificate counts, until the caller asks for the next chunk
     std::vector<int32_t> sel;     //   and the model selection's records {model, nE, nH} per pair (msfm_fetch_model_selection)
     std::vector<msfm_two_view_record> tv;   //   and the two-view geometry's (msfm_fetch_two_view_geometry)
+    std::vector<msfm_two_view_refinement> tvr;   //   and the two-view refinement's (msfm_fetch_two_view_refinements)
 };
 
 void add_profile(msfm_profile& to, const msfm_profile& d) {
@@ -405,6 +407,7 @@ static int match_pairs_impl(msfm_ctx* ctx, const int32_t* pairs, int n_pairs, co
     ctx->have_results = true;   // what the blocking form hands out: set here and nowhere else
     ctx->sel_valid = job.select;
     ctx->tv_valid = job.pose;
+    ctx->tvr_valid = job.refine;
     return MSFM_OK;
 }
 
@@ -491,6 +494,8 @@ int msfm_set_two_view_geometry(msfm_ctx* ctx, int enable, const msfm_two_view_pa
         return fail(ctx, MSFM_E_INVALID, "two-view parameters must be finite and not negative");
     if (enable && ctx->verify_model != MSFM_VERIFY_ESSENTIAL)
         return fail(ctx, MSFM_E_INVALID, "the two-view geometry needs the essential-matrix model (msfm_set_verification_model)");
+    if (!enable && ctx->tv_refine)
+        return fail(ctx, MSFM_E_INVALID, "the two-view refinement is on and needs the two-view geometry: switch it off first");
     p.reserved = 0;
     ctx->two_view = enable != 0;
     ctx->tv_params = p;
@@ -503,6 +508,33 @@ int msfm_fetch_two_view_geometry(msfm_ctx* ctx, msfm_two_view_record* out) {
     if (!ctx) return MSFM_E_INVALID;
     if (!ctx->tv_valid) return fail(ctx, MSFM_E_STATE, "the last verified call / chunk ran without the two-view geometry");
     if (out && !ctx->tv_records.empty()) std::memcpy(out, ctx->tv_records.data(), ctx->tv_records.size() * sizeof(msfm_two_view_record));
+    return MSFM_OK;
+    MSFM_API_END
+}
+
+int msfm_set_two_view_refinement(msfm_ctx* ctx, int enable, const msfm_two_view_refine_params* params) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (ctx->series_open) return fail(ctx, MSFM_E_STATE, "a streaming series is open");
+    if (enable != 0 && enable != 1) return fail(ctx, MSFM_E_INVALID, "enable must be 0 or 1");
+    msfm_two_view_refine_params p = msfm_tvr::default_params();
+    if (params) p = *params;
+    if (p.max_iters < 1 || p.min_matches < 5 || !std::isfinite(p.step_tol) || p.step_tol < 0.0)
+        return fail(ctx, MSFM_E_INVALID, "two-view refinement: max_iters >= 1, min_matches >= 5, step_tol finite and not negative");
+    if (enable && !ctx->two_view)
+        return fail(ctx, MSFM_E_INVALID, "the two-view refinement needs the two-view geometry (msfm_set_two_view_geometry)");
+    ctx->tv_refine = enable != 0;
+    ctx->tvr_params = p;
+    return MSFM_OK;
+    MSFM_API_END
+}
+
+int msfm_fetch_two_view_refinements(msfm_ctx* ctx, msfm_two_view_refinement* out) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    if (!ctx->tvr_valid) return fail(ctx, MSFM_E_STATE, "the last verified call / chunk ran without the two-view refinement");
+    if (out && !ctx->tvr_records.empty())
+        std::memcpy(out, ctx->tvr_records.data(), ctx->tvr_records.size() * sizeof(msfm_two_view_refinement));
     return MSFM_OK;
     MSFM_API_END
 }
@@ -546,7 +578,7 @@ static int next_impl(msfm_ctx* ctx, msfm_chunk* out) {
     if (!ctx->series_open) return fail(ctx, MSFM_E_STATE, "msfm_match_pairs_next without msfm_match_pairs_begin");
     MatchJob& job = *ctx->job;
     *out = msfm_chunk{};
-    ctx->sel_valid = ctx->tv_valid = false;   // (the chunk before is gone; a step that fails hands out nothing)
+    ctx->sel_valid = ctx->tv_valid = ctx->tvr_valid = false;   // (the chunk before is gone; a step that fails hands out nothing)
     const SubBatch* w = nullptr;   // the chunk; none: the series is complete, n_pairs == 0
     int slot = 0;
     if (job.more()) {
@@ -559,6 +591,8 @@ static int next_impl(msfm_ctx* ctx, msfm_chunk* out) {
     ctx->sel_valid = job.select;
     ctx->tv_records = w ? w->tv : std::vector<msfm_two_view_record>();
     ctx->tv_valid = job.pose;
+    ctx->tvr_records = w ? w->tvr : std::vector<msfm_two_view_refinement>();
+    ctx->tvr_valid = job.refine;
     if (!w) return job.finish();
     const Scratch& sc = ctx->sc[slot];
     out->first_pair = w->begin;

@@ -310,6 +310,39 @@ MSFM_UNROLL
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
+// The statistics of the n kept matches under the pose P = R[9] | t[3] on the host, literally the definition above (tv_pose_kernel's
+// steps 5 and 6): n_positive_depth counts the matches evaluate puts in front of both cameras, the two sums are in the stated order,
+// lo / hi are the two middle angles of the sorted list.  The ONE host copy: two_view_record and the refinement's twin
+// (msfm_pose_refine.h) both call it.
+struct HostStatistics {
+    int n_positive_depth, n_triangulated;
+    double sum_residual, sum_angle, lo, hi;
+};
+inline HostStatistics host_statistics(const double* P, const double* x1, const double* y1, const double* x2, const double* y2, int n, double f,
+                                      double tri_max_error) {
+    std::vector<double> angles((size_t)n), part_r((size_t)kLanes, 0.0), part_a((size_t)kLanes, 0.0);
+    int n_pos = 0, n_tri = 0;
+    for (int i = 0; i < n; ++i) {   // (lane i % kLanes meets its matches in ascending order)
+        bool depth;
+        double err, ang;
+        evaluate(P, f, x1[i], y1[i], x2[i], y2[i], &depth, &err, &ang);
+        angles[(size_t)i] = ang;
+        n_pos += depth ? 1 : 0;
+        if (depth && err < tri_max_error) {
+            n_tri += 1;
+            part_r[(size_t)(i % kLanes)] = part_r[(size_t)(i % kLanes)] + err;
+            part_a[(size_t)(i % kLanes)] = part_a[(size_t)(i % kLanes)] + ang;
+        }
+    }
+    for (int s = kLanes / 2; s >= 1; s /= 2)
+        for (int l = 0; l < s; ++l) {
+            part_r[(size_t)l] = part_r[(size_t)l] + part_r[(size_t)(l + s)];
+            part_a[(size_t)l] = part_a[(size_t)l] + part_a[(size_t)(l + s)];
+        }
+    std::sort(angles.begin(), angles.end());
+    return HostStatistics{n_pos, n_tri, part_r[0], part_a[0], angles[(size_t)((n - 1) / 2)], angles[(size_t)(n / 2)]};
+}
+
 // The whole record of one pair on the host, literally the definition above: E the winner, (x1, y1) <-> (x2, y2) the n kept
 // matches in list order, f = (fx + fy) / 2.  `winner` (may be NULL): the candidate index, -1 for an invalid record.
 inline void two_view_record(const double E[9], const double* x1, const double* y1, const double* x2, const double* y2, int n, double f,
@@ -326,26 +359,8 @@ inline void two_view_record(const double E[9], const double* x1, const double* y
         if (count[c] > count[w]) w = c;
     if (count[w] == 0) return;
     const double* P = cand + 12 * w;
-    std::vector<double> angles((size_t)n), part_r((size_t)kLanes, 0.0), part_a((size_t)kLanes, 0.0);
-    int n_tri = 0;
-    for (int i = 0; i < n; ++i) {   // (lane i % kLanes meets its matches in ascending order)
-        bool depth;
-        double err, ang;
-        evaluate(P, f, x1[i], y1[i], x2[i], y2[i], &depth, &err, &ang);
-        angles[(size_t)i] = ang;
-        if (depth && err < prm.tri_max_error) {
-            n_tri += 1;
-            part_r[(size_t)(i % kLanes)] = part_r[(size_t)(i % kLanes)] + err;
-            part_a[(size_t)(i % kLanes)] = part_a[(size_t)(i % kLanes)] + ang;
-        }
-    }
-    for (int s = kLanes / 2; s >= 1; s /= 2)
-        for (int l = 0; l < s; ++l) {
-            part_r[(size_t)l] = part_r[(size_t)l] + part_r[(size_t)(l + s)];
-            part_a[(size_t)l] = part_a[(size_t)l] + part_a[(size_t)(l + s)];
-        }
-    std::sort(angles.begin(), angles.end());
-    finish_record<1>(P, n, count[w], n_tri, part_r[0], part_a[0], angles[(size_t)((n - 1) / 2)], angles[(size_t)(n / 2)], prm, r);
+    const HostStatistics st = host_statistics(P, x1, y1, x2, y2, n, f, prm.tri_max_error);
+    finish_record<1>(P, n, count[w], st.n_triangulated, st.sum_residual, st.sum_angle, st.lo, st.hi, prm, r);
     if (winner) *winner = w;
 }
 #endif

@@ -18,6 +18,7 @@
 //      msfm_pose.h's stated order (per-thread partial sums strided by kLanes, then the fixed tree in LDS);
 //   6  the exact median: an MSB-first radix selection (8 bits a pass, LDS histogram) over the fp64 bit patterns of the slot's
 //      non-negative angles -- once for an odd nE, twice (both middle ranks) for an even one.
+//   (5 and 6 are tv_statistics below: tv_refine_kernel, msfm_verify_pose_refine.hip.h, calls the same function under its final pose.)
 // SELECTION ALWAYS, no LDS sort: the slot has just been written by the same CU (L2 / L1 resident), nE spans 5 .. ~8000 and a pair of
 // 350 kept matches reads its slot in 2 loads per thread and pass; one path for every size, 10.1 KiB of LDS (10 328 B) whatever nE is, so the
 // LDS never limits the residency (the registers do: DESIGN.md 13).
@@ -61,6 +62,48 @@ __device__ __forceinline__ double tv_select(const double* a, int n, int k, int* 
         __syncthreads();
     }
     return __longlong_as_double((long long)prefix);
+}
+
+// Steps 5 and 6 of tv_pose_kernel, shared with tv_refine_kernel (msfm_verify_pose_refine.hip.h): under the pose P = R[9] | t[3] every
+// thread of the workgroup strides over the pair's kept list (x1 .. angles: the pair's slots), the angle of every kept match goes to the
+// angle slot, the two sums are reduced in msfm_pose.h's stated order into part_r[0] / part_a[0], *n_tri counts the triangulated matches
+// and, with kCountDepth, *n_pos those in front of both cameras (one LDS atomic per thread that has any: both must be 0 and visible on
+// entry); lo / hi: the two middle angles by the radix selection.  Every thread returns behind a barrier with the same values.
+template <bool kCountDepth>
+__device__ __forceinline__ void tv_statistics(const double* P, double focal, double tri_max_error, const double* x1, const double* y1,
+                                              const double* x2, const double* y2, const int* idx, double* angles, int nk, double* part_r_s,
+                                              double* part_a_s, int* hist, unsigned long long* s_sel, int* n_tri_s, int* n_pos_s, int tid,
+                                              double* lo_out, double* hi_out) {
+    double part_r = 0.0, part_a = 0.0;
+    int n_tri = 0, n_pos = 0;
+    for (int j = tid; j < nk; j += kTvThreads) {
+        const int i = idx[j];
+        bool depth;
+        double err, ang;
+        msfm_pose::evaluate(P, focal, x1[i], y1[i], x2[i], y2[i], &depth, &err, &ang);
+        angles[j] = ang;
+        if (kCountDepth) n_pos += depth ? 1 : 0;
+        if (depth && err < tri_max_error) {
+            n_tri += 1;
+            part_r = part_r + err;
+            part_a = part_a + ang;
+        }
+    }
+    part_r_s[tid] = part_r;
+    part_a_s[tid] = part_a;
+    if (n_tri) atomicAdd(n_tri_s, n_tri);
+    if (kCountDepth && n_pos) atomicAdd(n_pos_s, n_pos);
+    __syncthreads();   // (also: the angle slot is visible to the workgroup)
+    for (int s = kTvThreads / 2; s >= 1; s >>= 1) {
+        if (tid < s) {
+            part_r_s[tid] = part_r_s[tid] + part_r_s[tid + s];
+            part_a_s[tid] = part_a_s[tid] + part_a_s[tid + s];
+        }
+        __syncthreads();
+    }
+    const double hi = tv_select(angles, nk, nk / 2, hist, s_sel, tid);
+    *lo_out = (nk & 1) ? hi : tv_select(angles, nk, (nk - 1) / 2, hist, s_sel, tid);
+    *hi_out = hi;
 }
 
 // counts: the staged counts; best_it: the E winners; sel: the selection's records or NULL; idx / angles: slots of the staged lists'
@@ -155,36 +198,11 @@ __global__ __launch_bounds__(kTvThreads) void tv_pose_kernel(
             if (tid == 0) msfm_pose::clear_record(&records[p]);
             continue;
         }
-        // 5: the per-match quantities under the winner, the sums in the stated order
+        // 5 and 6: the per-match quantities under the winner, the two sums, the median (tv_statistics)
         const double* P = s_cand + 12 * w;
-        double part_r = 0.0, part_a = 0.0;
-        int n_tri = 0;
-        for (int j = tid; j < nk; j += kTvThreads) {
-            const int i = idx[base + j];
-            bool depth;
-            double err, ang;
-            msfm_pose::evaluate(P, focal, x1[base + i], y1[base + i], x2[base + i], y2[base + i], &depth, &err, &ang);
-            angles[base + j] = ang;
-            if (depth && err < tp.tri_max_error) {
-                n_tri += 1;
-                part_r = part_r + err;
-                part_a = part_a + ang;
-            }
-        }
-        s_part_r[tid] = part_r;
-        s_part_a[tid] = part_a;
-        if (n_tri) atomicAdd(&s_ntri, n_tri);
-        __syncthreads();   // (also: the angle slot is visible to the workgroup)
-        for (int s = kTvThreads / 2; s >= 1; s >>= 1) {
-            if (tid < s) {
-                s_part_r[tid] = s_part_r[tid] + s_part_r[tid + s];
-                s_part_a[tid] = s_part_a[tid] + s_part_a[tid + s];
-            }
-            __syncthreads();
-        }
-        // 6: the median
-        const double hi = tv_select(angles + base, nk, nk / 2, s_hist, s_sel, tid);
-        const double lo = (nk & 1) ? hi : tv_select(angles + base, nk, (nk - 1) / 2, s_hist, s_sel, tid);
+        double lo, hi;
+        tv_statistics<false>(P, focal, tp.tri_max_error, x1 + base, y1 + base, x2 + base, y2 + base, idx + base, angles + base, nk, s_part_r,
+                             s_part_a, s_hist, s_sel, &s_ntri, nullptr, tid, &lo, &hi);
         if (tid == 0) msfm_pose::finish_record<1>(P, nk, n_front, s_ntri, s_part_r[0], s_part_a[0], lo, hi, tp, &records[p]);
     }
 }

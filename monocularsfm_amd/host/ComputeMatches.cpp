@@ -254,6 +254,34 @@ int main(int argc, char** argv) {
                   << std::endl;
         return EXIT_FAILURE;
     }
+    // SIFTmatch.two_view_refine : 0 (default) | 1 (the pose of every record of the two_view_geometries table is polished over all the
+    // pair's kept matches, LM on the Sampson error; two_view_refine_max_iters / _step_tol / _min_matches; include/msfm_match.h)
+    int two_view_refine = 0;
+    msfm_two_view_refine_params two_view_refine_params = {10, 15, 1e-6};
+    int two_view_refine_max_iters = two_view_refine_params.max_iters, two_view_refine_min_matches = two_view_refine_params.min_matches;
+    fs.Get("SIFTmatch.two_view_refine", &two_view_refine);
+    fs.Get("SIFTmatch.two_view_refine_max_iters", &two_view_refine_max_iters);
+    fs.Get("SIFTmatch.two_view_refine_step_tol", &two_view_refine_params.step_tol);
+    fs.Get("SIFTmatch.two_view_refine_min_matches", &two_view_refine_min_matches);
+    two_view_refine_params.max_iters = two_view_refine_max_iters;
+    two_view_refine_params.min_matches = two_view_refine_min_matches;
+    if (!(two_view_refine == 0 || two_view_refine == 1)) {
+        std::cerr << "ComputeMatches: SIFTmatch.two_view_refine must be 0 or 1" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (two_view_refine == 1 && two_view_geometry != 1) {
+        std::cerr << "ComputeMatches: SIFTmatch.two_view_refine : 1 refines the two-view records; it needs SIFTmatch.two_view_geometry : 1"
+                  << std::endl;
+        return EXIT_FAILURE;
+    }
+    // (the optional keys are checked only when the feature is on: a configuration that carries them with it off runs as before)
+    if (two_view_refine == 1 && (two_view_refine_max_iters < 1 || two_view_refine_min_matches < 5 ||
+                                 !(std::isfinite(two_view_refine_params.step_tol) && two_view_refine_params.step_tol >= 0))) {
+        std::cerr << "ComputeMatches: SIFTmatch.two_view_refine_max_iters must be >= 1, two_view_refine_min_matches >= 5, "
+                     "two_view_refine_step_tol finite and not negative"
+                  << std::endl;
+        return EXIT_FAILURE;
+    }
 
     const char* honour = std::getenv("MSFM_HONOUR_YAML_MATCH_PARAMS");
     const bool use_yaml = honour && honour[0] == '1';
@@ -285,6 +313,7 @@ int main(int argc, char** argv) {
     matcher->SetVerificationModel(verification_model, camera);
     matcher->SetModelSelection(model_selection == 1, h_ratio);
     matcher->SetTwoViewGeometry(two_view_geometry == 1, two_view_params);
+    matcher->SetTwoViewRefinement(two_view_refine == 1, two_view_refine_params);
     matcher->SetTracks(tracks == 1, tracks_min_num_matches, tracks_min_length, tracks_max_length, tracks_keep_inconsistent == 1);
     matcher->SetTriangulation(triangulation == 1, camera, triangulation_ids, triangulation_poses, triangulation_params);
 

@@ -157,6 +157,9 @@ void FeatureMatcher::OpenDatabaseAndDevice() {
             if (status[g] == MSFM_OK && model_selection_) status[g] = msfm_set_model_selection(c, 1, h_ratio_);
             if (status[g] == MSFM_OK && two_view_geometry_ && geometric_verification_ && !verification_on_host_)
                 status[g] = msfm_set_two_view_geometry(c, 1, &two_view_params_);
+            if (status[g] == MSFM_OK && two_view_refine_ && two_view_geometry_ && geometric_verification_ && !verification_on_host_ &&
+                verification_model_ == MSFM_VERIFY_ESSENTIAL)
+                status[g] = msfm_set_two_view_refinement(c, 1, &two_view_refine_params_);
             // An ordinal listed k times (the tests' way to run the fan-out on a one-GPU box): every context would size its scratch
             // for a quarter of the device's free memory on its own -- four of them on one MI355X ran out of memory at config-4 scale.
             // They share the default budget instead (MSFM_SCRATCH_MIB still overrides: it is read at msfm_create, this only applies without it).
@@ -614,7 +617,14 @@ void FeatureMatcher::MatchImagePairGroups(const std::vector<std::vector<std::pai
                                 b[i] = Point2f{kb[(size_t)qt[2 * i + 1]].x, kb[(size_t)qt[2 * i + 1]].y};
                             }
                             msfm_two_view_record rec;
-                            TwoViewGeometry(a, b, camera_, two_view_params_, &rec);
+                            const std::vector<unsigned char> mask = TwoViewGeometry(a, b, camera_, two_view_params_, &rec);
+                            if (two_view_refine_ && rec.valid) {   // (the kept list: the mask's matches, in list order)
+                                std::vector<double> k[4];
+                                KeptNormalised(a, b, mask, camera_, k);
+                                msfm_two_view_refinement done;
+                                RefineTwoView(k[0].data(), k[1].data(), k[2].data(), k[3].data(), (int)k[0].size(), camera_, two_view_params_,
+                                              two_view_refine_params_, &rec, &done);
+                            }
                             std::memcpy(out->geometry.data() + p * kRec, &rec, kRec);
                         }
                         if (two_view) {

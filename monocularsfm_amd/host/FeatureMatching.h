@@ -56,6 +56,13 @@ public:
         two_view_geometry_ = on;
         two_view_params_ = params;
     }
+    // SIFTmatch.two_view_refine (+ two_view_refine_max_iters / _step_tol / _min_matches), with two_view_geometry only: the records are
+    // refined before they are written (msfm_set_two_view_refinement on every device context, or RefineTwoView in the host twin); the
+    // table keeps its schema.  Call before RunMatching.
+    void SetTwoViewRefinement(bool on, const msfm_two_view_refine_params& params) {
+        two_view_refine_ = on;
+        two_view_refine_params_ = params;
+    }
     // SIFTmatch.tracks (+ tracks_min_num_matches / _min_length / _max_length / _keep_inconsistent): the run's kept matches joined
     // into multi-view tracks (include/msfm_match.h "feature tracks") and written into the `tracks` table, rebuilt whole at the end of
     // the run.  Every device context opens a session over all images in front of the run's matching; rows the run computes are
@@ -99,6 +106,8 @@ protected:
     bool cross_check_;
     bool geometric_verification_ = true;
     bool verification_on_host_ = false;  // MSFM_GEOMETRIC_VERIFICATION=host
+    bool two_view_refine_ = false;                       // SetTwoViewRefinement
+    msfm_two_view_refine_params two_view_refine_params_ = {10, 15, 1e-6};
     bool two_view_geometry_ = false;                     // SetTwoViewGeometry
     msfm_two_view_params two_view_params_ = {100, 0, 2.0, 4.0};
     int verification_model_ = MSFM_VERIFY_FUNDAMENTAL;   // SetVerificationModel

@@ -9,6 +9,7 @@
 #include "../csrc/msfm_hmat.h"
 #include "../csrc/msfm_hostutil.h"
 #include "../csrc/msfm_pose.h"
+#include "../csrc/msfm_pose_refine.h"
 
 namespace MonocularSfM {
 
@@ -146,6 +147,25 @@ std::vector<unsigned char> TwoViewGeometry(const std::vector<Point2f>& pts1, con
     msfm_pose::two_view_record(E, k[0].data(), k[1].data(), k[2].data(), k[3].data(), (int)k[0].size(),
                                (camera.fx + camera.fy) * 0.5, params, record);
     return mask;
+}
+
+void KeptNormalised(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2, const std::vector<unsigned char>& mask,
+                    const CameraIntrinsics& camera, std::vector<double> kept[4]) {
+    const msfm_emat::Camera cam{camera.fx, camera.fy, camera.cx, camera.cy, camera.k1, camera.k2, camera.p1, camera.p2};
+    for (int c = 0; c < 4; ++c) kept[c].clear();
+    for (size_t i = 0; i < mask.size(); ++i) {
+        if (!mask[i]) continue;
+        double v[4];
+        msfm_emat::undistort(cam, (double)pts1[i].x, (double)pts1[i].y, &v[0], &v[1]);
+        msfm_emat::undistort(cam, (double)pts2[i].x, (double)pts2[i].y, &v[2], &v[3]);
+        for (int c = 0; c < 4; ++c) kept[c].push_back(v[c]);
+    }
+}
+
+void RefineTwoView(const double* x1, const double* y1, const double* x2, const double* y2, int n, const CameraIntrinsics& camera,
+                   const msfm_two_view_params& params, const msfm_two_view_refine_params& refine, msfm_two_view_record* record,
+                   msfm_two_view_refinement* refinement) {
+    msfm_tvr::refine_record(x1, y1, x2, y2, n, (camera.fx + camera.fy) * 0.5, params, refine, record, refinement);
 }
 
 // The sequential loop of msfm_fmat::replay_adaptive<4> over lazily scored hypotheses: hypothesis it is sampled, checked, solved

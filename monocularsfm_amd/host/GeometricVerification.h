@@ -64,6 +64,17 @@ std::vector<unsigned char> TwoViewGeometry(const std::vector<Point2f>& pts1, con
                                            msfm_two_view_record* record, double threshold = 3.0, double confidence = 0.99,
                                            int max_iters = 1000, unsigned long long seed = 0x5eed5eedULL);
 
+// The two-view pose refinement (msfm_set_two_view_refinement, csrc/msfm_pose_refine.h) behind TwoViewGeometry: (the kept matches'
+// normalised undistorted coordinates in list order, the record, the parameters) -> (the record, polished by LM on the Sampson error
+// where the refined one stands and untouched otherwise; what the refinement did).  n must be the record's n_kept.  Host twin of
+// tv_refine_kernel (csrc/msfm_verify_pose_refine.hip.h): the same bits.
+void RefineTwoView(const double* x1, const double* y1, const double* x2, const double* y2, int n, const CameraIntrinsics& camera,
+                   const msfm_two_view_params& params, const msfm_two_view_refine_params& refine, msfm_two_view_record* record,
+                   msfm_two_view_refinement* refinement);
+// what RefineTwoView takes after TwoViewGeometry: x1 | y1 | x2 | y2 of the matches whose mask byte is set, undistorted with `camera`
+void KeptNormalised(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2, const std::vector<unsigned char>& mask,
+                    const CameraIntrinsics& camera, std::vector<double> kept[4]);
+
 // FeatureUtils::GetAlignedPointsFromMatches + FilterMatches, with the model of SIFTmatch.verification_model
 // (msfm_match.h: MSFM_VERIFY_FUNDAMENTAL as the reference, MSFM_VERIFY_ESSENTIAL with `camera`, MSFM_VERIFY_HOMOGRAPHY) and the
 // reference's constants.  model_selection (SIFTmatch.model_selection, models 0 and 1 only): TwoViewSelectMask with h_ratio;

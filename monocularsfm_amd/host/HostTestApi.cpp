@@ -15,6 +15,7 @@
 #include "../csrc/msfm_hmat.h"
 #include "../csrc/msfm_hostutil.h"
 #include "../csrc/msfm_pose.h"
+#include "../csrc/msfm_pose_refine.h"
 #include "../csrc/msfm_tracks.h"
 #include "../csrc/msfm_triangulate.h"
 #include "../csrc/msfm_refine.h"
@@ -565,6 +566,48 @@ int host_two_view_geometry(const float* p1, const float* p2, int n, const double
     const std::vector<unsigned char> m = TwoViewGeometry(a, b, c, prm, record, threshold, confidence, max_iters, seed);
     for (size_t i = 0; i < m.size(); ++i) mask[i] = m[i];
     return (int)m.size();
+}
+
+// RefineTwoView on the kept matches in normalised coordinates (n each, list order) under the focal length f: *record is read and
+// rewritten iff the refined record stands, *refinement is always filled
+void host_refine_two_view(const double* x1, const double* y1, const double* x2, const double* y2, int n, double f, int min_num_inliers,
+                          double tri_max_error, double tri_min_angle, int max_iters, int min_matches, double step_tol,
+                          msfm_two_view_record* record, msfm_two_view_refinement* refinement) {
+    const CameraIntrinsics c{f, f, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const msfm_two_view_params prm = {min_num_inliers, 0, tri_max_error, tri_min_angle};
+    const msfm_two_view_refine_params rp = {max_iters, min_matches, step_tol};
+    RefineTwoView(x1, y1, x2, y2, n, c, prm, rp, record, refinement);
+}
+
+// the pieces of csrc/msfm_pose_refine.h at the pose (R, t): the residuals r[n], with J != NULL the Jacobian J[n x 5] too
+void host_tvr_residuals(const double* R, const double* t, double f, const double* x1, const double* y1, const double* x2, const double* y2,
+                        int n, double* r, double* J) {
+    msfm_tvr::State s;
+    for (int k = 0; k < 9; ++k) s.R[k] = R[k];
+    for (int k = 0; k < 3; ++k) s.t[k] = t[k];
+    double E[9], D[5][9];
+    msfm_tvr::linear_model(s, E, D);
+    for (int i = 0; i < n; ++i) {
+        if (J) r[i] = msfm_tvr::jacobian(E, D, f, x1[i], y1[i], x2[i], y2[i], J + 5 * i);
+        else r[i] = msfm_tvr::residual(E, f, x1[i], y1[i], x2[i], y2[i]);
+    }
+}
+
+// (R, t) moved by delta = (a, b): msfm_tvr::apply_step; returns 0 when the new pose is not finite
+int host_tvr_update(const double* R, const double* t, const double* delta, double* Rn, double* tn) {
+    msfm_tvr::State s, sn;
+    for (int k = 0; k < 9; ++k) s.R[k] = R[k];
+    for (int k = 0; k < 3; ++k) s.t[k] = t[k];
+    const bool ok = msfm_tvr::apply_step(s, delta, &sn);
+    for (int k = 0; k < 9; ++k) Rn[k] = sn.R[k];
+    for (int k = 0; k < 3; ++k) tn[k] = sn.t[k];
+    return ok ? 1 : 0;
+}
+
+// msfm_pair_scratch_bytes with its two defaulted arguments spelled out
+long long host_pair_scratch_bytes_refine(int n1, int n2, int n1pad, int n2pad, int blocks128, int blocks512, int route, int two_view,
+                                         int two_view_refine) {
+    return msfm_pair_scratch_bytes(n1, n2, n1pad, n2pad, blocks128, blocks512, route, two_view != 0, two_view_refine != 0);
 }
 
 // ---- feature tracks: the host twin of the device session (csrc/msfm_tracks.h) ------------------------------------------------------
