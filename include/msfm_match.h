@@ -1135,6 +1135,92 @@ typedef struct msfm_visibility_stats {   /* 56 bytes, no implicit padding */
 int msfm_map_visibility(msfm_ctx* ctx, const msfm_visibility_params* params, const int32_t* query_ids, int n_query,
                         msfm_image_visibility* out_images, uint32_t* out_covisible, msfm_visibility_stats* stats);
 
+/* ---- map alignment: a robust similarity to known camera positions, and the edit that applies one (opt-in) ---------------
+ * A map lives in the gauge of its initial pair: the first image at the identity, a baseline of length 1, an arbitrary orientation.
+ * Captures with position priors (a rig, an INS, an earlier reconstruction) want it in the priors' frame and units, the step every SfM
+ * tool has (COLMAP's model_aligner, OpenSfM's align).  msfm_estimate_alignment finds the similarity from the session's camera centres
+ * to the caller's positions; msfm_transform_map moves every pose and every point by a similarity, that one or any other (a
+ * normalisation).  The arithmetic is csrc/msfm_align.h, bit-identical to the host twins EstimateAlignment / TransformMap (DESIGN.md
+ * section 28).
+ *   similarity   world' = s Q X + d: s > 0, Q row-major and a proper rotation.
+ *   priors       positions[3 k ..] is the position of image_ids[k].  A listed image without a valid pose in the session is reported as
+ *                not used and is no error: callers pass the priors of all images.  m: the usable ones, in list order.  ATTEMPTED iff
+ *                m >= 3.
+ *   fit          Umeyama's closed form over pairs (camera centre, position): one 3 x 3 decomposition.  Valid iff every number is finite,
+ *                the centres are not all one point, s > 0 and the second singular value is above 1e-6 of the first (centres on a line
+ *                leave the rotation about it free).
+ *   error        of a prior: |position - (s Q centre + d)|, in the prior's units; an inlier iff error <= max_error.
+ *   robust       hypotheses it = 0 .. : the fit of three distinct priors from the counter stream keyed by `it`, counted by its
+ *                inliers among all m; the sequential adaptive rule (w^3, confidence) over at most max_hypotheses hypotheses, scored in
+ *                rounds of 256; the winner is the lowest iteration among the largest count (MODEL).  Then at most four refits over the
+ *                current inlier set, each standing (REFIT) iff it is valid and has at least as many inliers.  SUCCEEDED iff the final
+ *                model has at least max(3, min_inliers) inliers.
+ *   least squares max_hypotheses == 0 (and params NULL): one fit of all m priors (LEAST_SQUARES); every usable prior is reported as an
+ *                inlier, max_error is not read.
+ *   record       hypotheses: those the stopping rule evaluated (at most max_hypotheses); refits: those that stood; rms over the
+ *                inliers.  A failed estimate is MSFM_OK with SUCCEEDED clear, an all-zero similarity and error -1.0 on every prior.
+ *   per prior    out_per_prior[k] (may be NULL), in list order: MSFM_ALN_USED, MSFM_ALN_INLIER and the error under the final model
+ *                (-1.0 when not used or when the estimate failed).
+ * msfm_estimate_alignment is READ-ONLY like msfm_map_visibility: not one byte of the session changes and no validity flag drops; it may
+ * run between msfm_register_images and msfm_fetch_registrations.  Errors: MSFM_E_STATE -- as msfm_refine_points.  MSFM_E_INVALID -- n < 0
+ * or a NULL list with n > 0, NULL out, an id that is not declared in the session or given twice, a non-finite position, max_hypotheses
+ * outside 0 .. 4096, a robust call whose max_error is not finite and positive, confidence outside (0, 1).
+ *
+ * msfm_transform_map EDITS the map.  Every valid pose becomes R' = R Q^T, t' = s t - R' d (the camera frame is scaled by s: depths
+ * scale, projections do not change; R is not re-orthogonalised).  Every record with ATTEMPTED | POINT gets X' = s (Q X) + d and is
+ * evaluated again at X' under the new poses with the session's camera and thresholds, as msfm_refine_camera's re-verdict does: the
+ * residual slots of its used observations, mean_residual, tri_angle and the three verdict bits are rewritten, n_views and the inlier
+ * bytes are kept; status = ATTEMPTED | POINT | those bits | the record's ROBUST .. COMPLETED bits | MSFM_TRI_ALIGNED.  A non-finite X'
+ * (only an overflow gives one) leaves ATTEMPTED | those kept bits | ALIGNED, every other field 0 and every residual slot of the track
+ * -1.0: the shape msfm_filter_points gives a removed point; it counts in points_lost.  The identity leaves every X and every pose bit
+ * for bit.  MSFM_TRI_ALIGNED needs no rule in any other call: every call that rewrites a record builds its status from an explicit
+ * mask of the bits it keeps and thereby clears it (as it clears MSFM_TRI_RECALIBRATED, which this call clears too).
+ * The call invalidates registrations and pose-refinement records as every edit does -- they hold poses of the old frame -- and replaces
+ * the session's pose list; points, inlier bytes and camera stay valid.  Errors, after each of which the session is exactly what it
+ * was: MSFM_E_STATE -- as msfm_refine_points.  MSFM_E_INVALID -- NULL similarity, s not finite and positive, d not finite,
+ * max |Q Q^T - I| > 1e-9 or det Q <= 0, a new pose that would not be finite.  MSFM_E_NOIMAGE -- as msfm_refine_points. */
+enum { MSFM_TRI_ALIGNED = 4096 };
+enum { MSFM_ALN_ATTEMPTED = 1, MSFM_ALN_MODEL = 2, MSFM_ALN_SUCCEEDED = 4, MSFM_ALN_REFIT = 8, MSFM_ALN_LEAST_SQUARES = 16 };   /* status */
+enum { MSFM_ALN_USED = 1, MSFM_ALN_INLIER = 2 };                                                                                /* per prior */
+typedef struct msfm_similarity {   /* 104 bytes, no implicit padding */
+    double s;
+    double Q[9];                     /* row-major */
+    double d[3];
+} msfm_similarity;
+typedef struct msfm_alignment_params {   /* 24 bytes, no implicit padding */
+    double max_error;                /* the prior's units; not read when max_hypotheses == 0 */
+    double confidence;               /* 0.9999 */
+    int32_t max_hypotheses;          /* 1024; 0 .. 4096, 0 = least squares */
+    int32_t min_inliers;             /* 3 */
+} msfm_alignment_params;
+typedef struct msfm_alignment {   /* 144 bytes, no implicit padding */
+    int32_t status;                  /* MSFM_ALN_* */
+    int32_t n_listed;                /* n */
+    int32_t n_used;                  /* m: listed images with a valid pose */
+    int32_t n_inliers;
+    int32_t hypotheses;              /* evaluated by the stopping rule */
+    int32_t refits;                  /* that stood */
+    msfm_similarity similarity;      /* all zero unless SUCCEEDED */
+    double rms;                      /* over the inliers */
+    double estimate_ms;              /* HIP events around the launch */
+} msfm_alignment;
+typedef struct msfm_alignment_residual {   /* 16 bytes, no implicit padding */
+    int32_t flags;                   /* MSFM_ALN_USED | MSFM_ALN_INLIER */
+    int32_t reserved;
+    double error;                    /* -1.0 when not used */
+} msfm_alignment_residual;
+typedef struct msfm_transform_stats {   /* 48 bytes, no implicit padding */
+    int64_t poses_transformed;       /* valid poses of the session's list */
+    int64_t points_transformed;      /* records with ATTEMPTED | POINT */
+    int64_t points_lost;             /* ... that had POINT & ERROR_OK & ANGLE_OK and no longer have it */
+    int64_t points_gained;           /* ... that did not have it and now do */
+    int64_t succeeded;               /* POINT & ERROR_OK & ANGLE_OK over all tracks after the call */
+    double transform_ms;             /* HIP events around all launches of the call */
+} msfm_transform_stats;
+int msfm_estimate_alignment(msfm_ctx* ctx, const int32_t* image_ids, const double* positions, int n, const msfm_alignment_params* params,
+                            msfm_alignment* out, msfm_alignment_residual* out_per_prior);
+int msfm_transform_map(msfm_ctx* ctx, const msfm_similarity* similarity, msfm_transform_stats* stats);
+
 /* ---- image registration: absolute pose from the triangulated tracks (opt-in) ---------------
  * The reference's MapBuilder::TryRegisterNextImage -> Registrant::Register (src/Reconstruction/Registrant.cpp) for every listed
  * image at once: the 2D-3D correspondences an image has with the points of the last msfm_triangulate_tracks, P3P RANSAC, a

@@ -251,6 +251,62 @@ def initial_second_images(row, records, image_id):
     return _by_count(r["image_id"][keep], row[keep])
 
 
+# map alignment (include/msfm_match.h): the record's extra status bit, the estimate's status bits, the per-prior flags, the 104-byte
+# similarity, the 24-byte parameters, the 144-byte record, the 16-byte per-prior record, the 48-byte stats
+TRI_ALIGNED = 4096
+ALN_ATTEMPTED, ALN_MODEL, ALN_SUCCEEDED, ALN_REFIT, ALN_LEAST_SQUARES = 1, 2, 4, 8, 16
+ALN_USED, ALN_INLIER = 1, 2
+ALIGNMENT_RESIDUAL = np.dtype([("flags", "<i4"), ("reserved", "<i4"), ("error", "<f8")])
+
+
+class Similarity(C.Structure):
+    """msfm_similarity: world' = s Q X + d, Q row-major."""
+    _fields_ = [("s", C.c_double), ("Q", C.c_double * 9), ("d", C.c_double * 3)]
+
+
+class AlignmentParams(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("confidence", C.c_double), ("max_hypotheses", C.c_int32), ("min_inliers", C.c_int32)]
+
+
+class Alignment(C.Structure):
+    """msfm_alignment (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("status", "n_listed", "n_used", "n_inliers", "hypotheses", "refits")] + \
+               [("similarity", Similarity), ("rms", C.c_double), ("estimate_ms", C.c_double)]
+
+
+class TransformStats(C.Structure):
+    """msfm_transform_stats (include/msfm_match.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("poses_transformed", "points_transformed", "points_lost", "points_gained", "succeeded")] + \
+               [("transform_ms", C.c_double)]
+
+
+def similarity_struct(s, Q, d):
+    """(s, Q 3 x 3, d 3) -> Similarity"""
+    return Similarity(float(s), (C.c_double * 9)(*np.asarray(Q, np.float64).reshape(9)), (C.c_double * 3)(*np.asarray(d, np.float64).reshape(3)))
+
+
+def alignment_dict(a):
+    """An Alignment struct -> dict: its integers, rms, estimate_ms, and the similarity as s (float), Q (3 x 3), d (3)."""
+    out = {k: getattr(a, k) for k, _ in Alignment._fields_ if k != "similarity"}
+    out.update(s=float(a.similarity.s), Q=np.array(a.similarity.Q, np.float64).reshape(3, 3), d=np.array(a.similarity.d, np.float64))
+    return out
+
+
+def prior_table(positions):
+    """{image id: (x, y, z)} -> (ids int32 by ascending id, positions float64 [n, 3])"""
+    ids = np.asarray(sorted(int(i) for i in positions), np.int32)
+    pos = np.zeros((max(len(ids), 1), 3), np.float64)
+    for k, i in enumerate(ids):
+        pos[k] = np.asarray(positions[int(i)], np.float64).reshape(3)
+    return ids, pos[:len(ids)]
+
+
+def aligned(points):
+    """The records of a POINT3D array that the last transform_map moved (MSFM_TRI_ALIGNED) and that no later call has rewritten: every
+    call that rewrites a record clears the bit."""
+    return (np.asarray(points)["status"] & TRI_ALIGNED) != 0
+
+
 def succeeded(points):
     """The reference's is_succeed per record of a POINT3D array: POINT & ERROR_OK & ANGLE_OK."""
     want = TRI_POINT | TRI_ERROR_OK | TRI_ANGLE_OK
@@ -489,6 +545,8 @@ def _signatures():
         "msfm_filter_points": (i, [vp, P(FilterParams), ip, i, P(FilterStats)]),
         "msfm_complete_points": (i, [vp, P(CompleteParams), ip, i, P(CompleteStats)]),
         "msfm_map_visibility": (i, [vp, P(VisibilityParams), ip, i, vp, vp, P(VisibilityStats)]),
+        "msfm_estimate_alignment": (i, [vp, ip, P(C.c_double), i, P(AlignmentParams), P(Alignment), vp]),
+        "msfm_transform_map": (i, [vp, P(Similarity), P(TransformStats)]),
         "msfm_register_images": (i, [vp, cam, ip, i, P(RegisterParams), P(RegisterStats)]),
         "msfm_fetch_registrations": (i, [vp, vp, vp, vp, vp, vp]),
     }
@@ -1111,6 +1169,44 @@ class Context:
         self._chk(self._L.msfm_map_visibility(self._h, C.byref(prm), _ip(q) if len(q) else None, len(q), rec.ctypes.data,
                                               mat.ctypes.data if mat.size else None, C.byref(st)))
         return rec[:n], mat, _dict(st)
+
+    # ---- map alignment (include/msfm_match.h) ----
+    def estimate_alignment(self, positions, max_error=None, confidence=0.9999, max_hypotheses=1024, min_inliers=3):
+        """The similarity world' = s Q X + d that takes the session's camera centres to known positions (msfm_estimate_alignment),
+        read-only.  positions: {image id: (x, y, z)}; an image without a valid pose in the session is reported as not used.
+        max_error, in the positions' units: a prior is an inlier iff its error is at most that, and the estimate is robust (three-prior
+        hypotheses, at most max_hypotheses of them under `confidence`, then refits over the inliers).  max_error=None: one least-squares
+        fit of all usable priors.  Subtract a local origin from large coordinates (UTM) first.
+        -> (dict: status (ALN_* bits), n_listed, n_used, n_inliers, hypotheses, refits, s, Q, d, rms, estimate_ms;
+            ALIGNMENT_RESIDUAL array, one per prior by ascending image id: flags (ALN_USED | ALN_INLIER), error).  A failed estimate
+        has ALN_SUCCEEDED clear and s = 0."""
+        ids, pos = prior_table(positions)
+        robust = max_error is not None
+        prm = AlignmentParams(float(max_error) if robust else 0.0, float(confidence), int(max_hypotheses) if robust else 0, int(min_inliers))
+        out = Alignment()
+        rec = np.zeros(max(len(ids), 1), ALIGNMENT_RESIDUAL)
+        self._chk(self._L.msfm_estimate_alignment(self._h, _ip(ids) if len(ids) else None,
+                                                  pos.ctypes.data_as(C.POINTER(C.c_double)) if len(ids) else None, len(ids), C.byref(prm),
+                                                  C.byref(out), rec.ctypes.data))
+        return alignment_dict(out), rec[:len(ids)]
+
+    def transform_map(self, s, Q, d):
+        """Moves the whole map by the similarity world' = s Q X + d (msfm_transform_map): every valid pose becomes R Q^T, s t - R' d,
+        every point s Q X + d, and every point's record is evaluated again under the new poses (aligned(points)); projections do not
+        change.  Any valid similarity is taken: estimate_alignment's or the caller's own.  -> stats dict.  pose_list(), points3d(),
+        point_inliers() and camera() work after it; registrations and pose refinements are invalidated."""
+        g = similarity_struct(s, Q, d)
+        st = TransformStats()
+        self._chk(self._L.msfm_transform_map(self._h, C.byref(g), C.byref(st)))
+        return _dict(st)
+
+    def align(self, positions, **estimate_kwargs):
+        """estimate_alignment(positions, **estimate_kwargs), then transform_map(its similarity) iff it succeeded.
+        -> (alignment dict, per-prior records, transform stats or None)."""
+        a, rec = self.estimate_alignment(positions, **estimate_kwargs)
+        if not a["status"] & ALN_SUCCEEDED:
+            return a, rec, None
+        return a, rec, self.transform_map(a["s"], a["Q"], a["d"])
 
     def initialize(self, camera, two_view, max_trials=100, min_points=100, **triangulate_kwargs):
         """The reference's TryInitialize order over the finished tracks: first images by their number of track elements

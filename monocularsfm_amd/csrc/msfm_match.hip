@@ -52,6 +52,7 @@ using namespace msfm;
 #include "msfm_filter.hip.h"
 #include "msfm_complete.hip.h"
 #include "msfm_visibility.hip.h"
+#include "msfm_align.hip.h"
 #include "msfm_register.hip.h"
 
 // =========================================================================================
@@ -995,6 +996,23 @@ int msfm_map_visibility(msfm_ctx* ctx, const msfm_visibility_params* params, con
     MSFM_API_BEGIN(ctx)
     if (!ctx) return MSFM_E_INVALID;
     return visibility_impl(ctx, params, query_ids, n_query, out_images, out_covisible, stats);
+    MSFM_API_END
+}
+
+// ---- map alignment (msfm_align.hip.h) ----------------------------------------------------------------------------------------------------
+
+int msfm_estimate_alignment(msfm_ctx* ctx, const int32_t* image_ids, const double* positions, int n, const msfm_alignment_params* params,
+                            msfm_alignment* out, msfm_alignment_residual* out_per_prior) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return estimate_alignment_impl(ctx, image_ids, positions, n, params, out, out_per_prior);
+    MSFM_API_END
+}
+
+int msfm_transform_map(msfm_ctx* ctx, const msfm_similarity* similarity, msfm_transform_stats* stats) {
+    MSFM_API_BEGIN(ctx)
+    if (!ctx) return MSFM_E_INVALID;
+    return transform_map_impl(ctx, similarity, stats);
     MSFM_API_END
 }
 

@@ -25,6 +25,7 @@
 #include "../csrc/msfm_filter.h"
 #include "../csrc/msfm_complete.h"
 #include "../csrc/msfm_visibility.h"
+#include "../csrc/msfm_align.h"
 #include "../csrc/msfm_register.h"
 
 using namespace MonocularSfM;
@@ -653,7 +654,7 @@ int host_tracks_build(const int* ids, const int* rows, int n, int min_pair_match
 // state.  Each twin's comment names the fields it reads and the ones it rewrites; its own parameters and outputs follow the block.
 // All of them return 0; 1: a pose's image is not declared or given twice; 2: an image id outside [0, MSFM_MAX_IMAGES); 3 and 4 as each
 // twin says.  The host_* exports of the same names, with the block's fields spelt out as raw arguments, stand behind
-// twin_map_visibility.
+// twin_map_visibility and the two twins of the map alignment (which have no host_* form).
 // What every twin makes of the block first: the rank of each declared image, the prepared pose of each rank (invalid where the list
 // has none), the rank of each entry of the pose list, and the camera.
 struct TwinScene {
@@ -974,6 +975,75 @@ int twin_map_visibility(const host_map* m, const int* query_ids, int n_query, in
     }
     return 0;
 }
+// ---- map alignment: the host twins of the device kernels (csrc/msfm_align.h, EstimateAlignment / TransformMap) ----------------------------
+// twin_estimate_alignment reads the images and the pose list (the session's current one) and nothing else of the block, and rewrites
+// nothing.  Its own: the n priors (prior_ids, positions: 3 doubles per id), max_error, confidence, max_hypotheses (0: least squares),
+// min_inliers.  out: one msfm_alignment (estimate_ms 0); out_per_prior (may be NULL): n msfm_alignment_residual.  3: a bad parameter;
+// 4: a prior's id that is not declared or given twice; 5: a non-finite position.
+int twin_estimate_alignment(const host_map* m, const int* prior_ids, const double* positions, int n, double max_error, double confidence,
+                            int max_hypotheses, int min_inliers, msfm_alignment* out, msfm_alignment_residual* out_per_prior) {
+    static_assert(sizeof(msfm_similarity) == 104 && sizeof(msfm_alignment_params) == 24 && sizeof(msfm_alignment) == 144 &&
+                      sizeof(msfm_alignment_residual) == 16 && sizeof(msfm_transform_stats) == 48 && sizeof(msfm_aln::Prior) == 48,
+                  "the alignment structs of include/msfm_match.h");
+    TwinScene sc;
+    if (const int e = twin_scene(*m, &sc)) return e;
+    if (n < 0 || max_hypotheses < 0 || max_hypotheses > msfm_aln::kMaxHypotheses || !(confidence > 0.0 && confidence < 1.0) ||
+        (max_hypotheses > 0 && !(msfm_pose::finite(max_error) && max_error > 0.0)))
+        return 3;
+    std::vector<uint8_t> listed;
+    if (!twin_rank_bytes(sc, prior_ids, n, false, &listed)) return 4;
+    for (long long k = 0; k < 3LL * n; ++k)
+        if (!msfm_pose::finite(positions[k])) return 5;
+    std::vector<msfm_aln::Prior> priors;
+    std::vector<int> at;
+    for (int k = 0; k < n; ++k) {
+        const msfm_tri::Pose& p = sc.table[(size_t)sc.rank(prior_ids[k])];
+        if (!p.valid) continue;
+        priors.push_back(msfm_aln::Prior{{p.O[0], p.O[1], p.O[2]}, {positions[3 * k], positions[3 * k + 1], positions[3 * k + 2]}});
+        at.push_back(k);
+    }
+    const int used = (int)priors.size();
+    std::vector<msfm_alignment_residual> rec((size_t)std::max(used, 1));
+    msfm_aln::EstimateAlignment(priors.data(), used, msfm_aln::Params{max_error, confidence, max_hypotheses, min_inliers}, out, rec.data());
+    out->n_listed = n;
+    if (out_per_prior) {
+        for (int k = 0; k < n; ++k) out_per_prior[k] = msfm_alignment_residual{0, 0, -1.0};
+        for (int j = 0; j < used; ++j) out_per_prior[at[(size_t)j]] = rec[(size_t)j];
+    }
+    return 0;
+}
+
+// twin_transform_map reads the tracks (not `consistent`; all n_tracks of them, not the slice), the images, cam, max_error and min_angle
+// (the verdict's) and mask (may be NULL).  The entries of `poses` are read AND REWRITTEN, as are points and residuals.  counts5 (may be
+// NULL) RECEIVES poses_transformed, points_transformed, points_lost, points_gained, succeeded.  3: a similarity msfm_transform_map does
+// not take, or a new pose that would not be finite -- nothing is written then.
+int twin_transform_map(host_map* m, const msfm_similarity* g, long long* counts5) {
+    TwinScene sc;
+    if (const int e = twin_scene(*m, &sc)) return e;
+    if (!g || !msfm_aln::similarity_ok(*g)) return 3;
+    long long moved = 0;
+    if (!msfm_aln::TransformPoses(*g, m->poses, m->n_poses, m->poses, &moved)) return 3;
+    if (const int e = twin_scene(*m, &sc)) return e;   // the table of the new poses
+    msfm_aln::TransformCounts tc = {};
+    msfm_aln::TransformMap(m->offsets, m->image_ids, m->point_idx, m->n_tracks, sc.rank_of.data(), m->kxy, sc.table.data(), m->mask, sc.cam,
+                           msfm_ref::Verdict{m->max_error, m->min_angle}, *g, m->points, m->residuals, &tc);
+    if (counts5) {
+        const long long v[5] = {moved, tc.points_transformed, tc.points_lost, tc.points_gained, tc.succeeded};
+        for (int k = 0; k < 5; ++k) counts5[k] = v[k];
+    }
+    return 0;
+}
+// the fit of n priors (6 doubles each: centre, position) in the header's summation order, no sampling: 1 valid, 0 not (tests)
+int host_aln_fit(const double* priors6, int n, msfm_similarity* out) {
+    std::vector<int> counts(1);
+    const msfm_aln::HostPriors pv{reinterpret_cast<const msfm_aln::Prior*>(priors6), n, counts.data(), nullptr};
+    msfm_aln::clear_similarity(out);
+    msfm_similarity g;
+    if (!msfm_aln::fit_set(pv, [](const msfm_aln::Prior&) { return true; }, &g)) return 0;
+    *out = g;
+    return 1;
+}
+
 // ---- the nine twins under their host_* names, the block's fields as raw arguments -----------------------------------------------------
 // The exports as they were before host_map, for callers built against those lists.  Each fills a block from its arguments and calls
 // the twin above; a field that twin does not read stays 0 or NULL, and nothing is computed here.  tests/*_twin.py call the twins;
